@@ -3,6 +3,7 @@
 800x800 renders of the depth-8 SH9 shell tree (BASELINE.json configs[2]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--forward-only] [--route plain|camera]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -14,9 +15,14 @@ the tree and renders its own camera (weak scaling: per-GPU work fixed); the pixe
 backward runs, and the gradient is all-reduced (row chunks on a side stream, svox_t_amd/parallel.py) and
 WAITED FOR before the next step starts -- the arrangement of a trainer that updates the features after every
 batch (svox_t/renderer.py:60-77 under an optimizer); the gradient-accumulation arrangement, in which the
-all-reduce hides under the next step, is timed afterwards and reported beside it.
+all-reduce hides under the next step, is timed afterwards and reported beside it (--full).
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `roofline` prices the bytes
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs if --dump-outputs DIR is given (see dump_outputs) and prints the headline: metric, value, unit,
+higher_is_better, dtype, ms_per_step and the per-step intervals behind them.  Everything else is measured with
+--full only: the device-side counts, the other routes and tolerance modes, BASELINE.json's other configs, the N > 1
+accumulation arrangement and exchange probe, and the line's `counters`, `touched`, `compulsory_bytes`, `roofline`,
+`limits` and `cpu_baseline`.  With --full, `roofline` prices the bytes
 THIS implementation cannot avoid moving to and from memory for the dominant kernel group (what
 the algorithm as run reads and writes once: rays, pixels, sample records, the distinct feature
 rows and tree words touched, the memset, the atomic requests, the row compaction -- counted on
@@ -71,6 +77,31 @@ PREWARM_MIN_S, PREWARM_MAX_S, PREWARM_WINDOW, PREWARM_TOL, PREWARM_BATCH = 1.0, 
 # routes measured after it)
 PREWARM_TREND_S, PREWARM_TREND_TOL = 0.4, 0.01
 STALL_FACTOR = 4.0
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: the files' size in all, headers included
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each array as <path>/<name>.npy, float32.  Smallest first, an array that does not fit an equal
+    share of what is left of `budget` keeps a fixed sample of its rows (row indices drawn with seed 0, in ascending
+    order), so that two builds run with the same arguments can be compared file for file.  Returns {name: rows kept}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = budget - 128 * len(arrays)                 # (a .npy header is 128 bytes for these shapes)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    kept = {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach().float()
+        rows = t.shape[0]
+        row_bytes = 4 * max(1, t.numel() // max(rows, 1))
+        keep = min(rows, left // (len(items) - i) // row_bytes)
+        if keep < rows:
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        kept[name] = keep
+    return kept
 
 
 def _median(xs):
@@ -251,7 +282,17 @@ def main(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: rehearse launch, rendezvous, pixel gather, gradient exchange, timing and the JSON line on CPU "
                          "tensors over gloo with a stand-in for the renderer (tests/test_bench_launch.py); the number means nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline (off: set up, warm up, time the K steps, "
+                         "print the headline): the device-side counts and the roofline, limits and compulsory bytes priced "
+                         "from them, the other routes, the tolerance mode, BASELINE.json's other configs, the CPU baseline, "
+                         "and with N > 1 the accumulation arrangement and the exchange probe; the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/pixels.npy and (with a backward) "
+                         "DIR/grad_features.npy, float32, at most 64 MB in all (a fixed seeded sample of rows beyond that)")
     args = ap.parse_args(argv)
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs writes the renderer's outputs; a --dry-run has none")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args, sys.argv[1:] if argv is None else argv)       # (before anything touches the GPU)
@@ -325,25 +366,27 @@ def main(argv=None):
             return renderer.render_persp(features, c2w, width=W, height=H, fx=fx, fast=args.fast).view(Q, -1)
         return renderer(features, rays, image_shape=(H, W), fast=args.fast)
 
-    # ---- one-off device-side counts (before the timed region) -------------------------------
-    rs_hint = _rays_spec_from_rays(rays, (H, W))
-    rs_hint.need_grad = False
-    spec = tree._spec(features)
-    cnt = _C.count_forward(spec, rs_hint, opt).cpu().tolist()
-    touched = _C.count_touched(spec, rs_hint, opt)
-    atomic_requests = merged_rows = rays_with_samples = None
-    if not args.forward_only:
-        with _C.bwd_counters(dev) as ctr:
+    # ---- one-off device-side counts (before the timed region; --full) -------------------------------
+    cnt = touched = atomic_requests = merged_rows = None
+    if args.full:
+        rs_hint = _rays_spec_from_rays(rays, (H, W))
+        rs_hint.need_grad = False
+        spec = tree._spec(features)
+        cnt = _C.count_forward(spec, rs_hint, opt).cpu().tolist()
+        touched = _C.count_touched(spec, rs_hint, opt)
+        if not args.forward_only:
+            with _C.bwd_counters(dev) as ctr:
+                features.grad = None
+                render(args.route).backward(gout)
+                torch.cuda.synchronize()
+            atomic_requests, merged_rows = ctr.read()
             features.grad = None
-            render(args.route).backward(gout)
-            torch.cuda.synchronize()
-        atomic_requests, merged_rows = ctr.read()
-        features.grad = None
     # N > 1: which gradient exchange?  RCCL's own all-reduce (ring / tree over its channels) or the direct form priced in
     # NOTEBOOK.md 7 (reduce-scatter + all-gather as two rounds of simultaneous point-to-point transfers, one per xGMI link)?
     # Measured here on a gradient-sized buffer, both checked against each other; the faster one is what the step uses.
+    # (A plain run with the default exchange has nothing to choose: the probe is then a --full record.)
     exchange = None
-    if dist is not None and not args.forward_only:
+    if dist is not None and not args.forward_only and (args.full or args.exchange != "all_reduce"):
         probe = torch.ones((M, K), dtype=torch.float32, device=dev)
         timings = {}
         for mode in (("all_reduce", "direct") if args.exchange == "auto" else (args.exchange,)):
@@ -427,9 +470,10 @@ def main(argv=None):
         return fwd, bwd
 
     _TEST_STALL_MS = [float(os.environ.get("BENCH_TEST_STALL_MS", "0") or 0)]      # (tests/test_gpu_bench_contract.py)
+    last_out = [None]          # what the last step of the last timed() returned (--dump-outputs)
 
     def timed(n, **kw):
-        """Mean seconds per step of n steps, bracketed by barrier + synchronize, max over ranks."""
+        """Seconds of n steps, bracketed by barrier + synchronize, max over ranks."""
         if reducer is not None:
             reducer.wait()
         torch.cuda.synchronize()
@@ -442,7 +486,10 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 time.sleep(_TEST_STALL_MS[0] * 1e-3)
                 _TEST_STALL_MS[0] = 0.0
-            step(i if kw.get("events") else None, **{k: v for k, v in kw.items() if k != "events"})
+            out = step(i if kw.get("events") else None, **{k: v for k, v in kw.items() if k != "events"})
+            if i == n - 1:
+                last_out[0] = out
+            del out                           # (no step's output outlives it but the last one, as before)
         if reducer is not None:
             reducer.wait()                    # the last gradient is reduced inside the timed region
         torch.cuda.synchronize()
@@ -530,6 +577,14 @@ def main(argv=None):
                    "first_run": {"ms_per_step": round(elapsed * 1e3 / args.steps, 4),
                                  "forward": [round(x, 4) for x in f1], "backward": [round(x, 4) for x in b1]}}
         elapsed = timed(args.steps, events=True)
+    # what the caller of the timed path received from its last step (N > 1: this rank's pixels, the reduced gradient),
+    # written before anything else runs on the device
+    if args.dump_outputs and rank == 0:
+        outs = {"pixels": last_out[0]}
+        if not args.forward_only:
+            outs["grad_features"] = features.grad
+        dump_outputs(args.dump_outputs, outs)
+    last_out[0] = None
     gc.enable()
     if hasattr(_C, "freeze_pools"):
         _C.freeze_pools(False)
@@ -544,7 +599,7 @@ def main(argv=None):
     # N > 1: the gradient-accumulation arrangement (one gradient in flight under the next step) beside the
     # timed every-step-update one, same process, same number of steps
     accumulation = None
-    if dist is not None and not args.forward_only:
+    if args.full and dist is not None and not args.forward_only:
         for _ in range(3):
             step(accumulate=True)
         el = timed(args.steps, accumulate=True)
@@ -561,7 +616,7 @@ def main(argv=None):
             "camera": "VolumeRenderer.render_persp (svox_t/renderer.py:310-366 -> volume_render_image, rt_kernel.cu:1153-1238): "
                       "the kernels generate the pinhole rays themselves, no ray tensors are read"}
     other = []
-    if world == 1 and not args.no_plain:
+    if args.full and world == 1 and not args.no_plain:
         for oroute in ("hinted", "plain", "camera"):
             if oroute == args.route:
                 continue
@@ -596,7 +651,7 @@ def main(argv=None):
     # the opt-in tolerance modes, for the record (same process, after the timed region; `value` above is the exact mode)
     tolerance = None
     wide = fmt == "RGBA" and K in (8, 16, 32)
-    if world == 1 and not args.no_plain and wide and not _C.NATIVE_MATH:
+    if args.full and world == 1 and not args.no_plain and wide and not _C.NATIVE_MATH:
         # rows of 8 / 16 / 32 floats: bit-exact stepping, shading with v_exp_f32 / v_rcp_f32 (forward and backward)
         dt, routes = timed_with("NATIVE_MATH", True)
         tolerance = {"setting": "SVOXT_NATIVE_MATH=1", "value": round(Q / dt / 1e6, 3), "unit": "Mrays/s",
@@ -606,7 +661,7 @@ def main(argv=None):
                              "instead of the bit-exact expf replica and a double-precision divide: outputs within 1e-5 "
                              "relative (+1e-6), gradients within 1e-5 of the tight scale, tested at this size "
                              "(tests/test_gpu_query_and_misc.py::test_config4_native_math_tolerance_mode_full_size)"}
-    elif world == 1 and not args.no_plain and not args.forward_only and _C.BWD_EXACT:
+    elif args.full and world == 1 and not args.no_plain and not args.forward_only and _C.BWD_EXACT:
         # round 1's headline arithmetic: the backward that takes accum from the forward's output instead of
         # adding it up like the reference's first pass
         dt, _ = timed_with("BWD_EXACT", False)
@@ -618,11 +673,11 @@ def main(argv=None):
                              "`value` above is the exact backward"}
     single_march = tolerance
 
-    # BASELINE.json's other single-GPU configs, measured briefly in the SAME process (the default headline run only), so
-    # that whoever times this command -- the driver -- holds a number for them too and not just the builder's profiles
+    # BASELINE.json's other single-GPU configs, measured briefly in the SAME process (the headline workload with --full only),
+    # so that whoever runs the full benchmark holds a number for them too and not just the builder's profiles
     # (VERDICT r04 "missing" 5).  Each: the hinted route, >= 0.25 s of untimed steps, then 20 steps between synchronizes.
     other_configs = None
-    if world == 1 and args.workload == "d8_sh9_800" and not (args.no_plain or args.no_other_configs or args.forward_only or args.fast):
+    if args.full and world == 1 and args.workload == "d8_sh9_800" and not (args.no_plain or args.no_other_configs or args.forward_only or args.fast):
         def short(label, rend, feat, ry, shape, go, fwd_only, fast, q):
             def one():
                 if fwd_only:
@@ -681,149 +736,6 @@ def main(argv=None):
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         value = world * Q / (elapsed / args.steps) / 1e6
-        ref_fwd, ref_bwd = reference_equivalent_bytes(cnt, Q, M, K, C)
-        A = cnt[4]
-        stride = K if (K <= 8 or K % 16 == 0) else (K + 15) // 16 * 16
-        tree_bytes = 4 * touched.get("grid_cells", 0) + 8 * touched.get("node_pairs", 0) + \
-            4 * (touched.get("child_words", 0) + touched.get("data_words", 0))
-        recording = not args.forward_only
-        fwd_parts = {
-            "rays": 36 * Q, "pixels_written": 4 * (C + 1) * Q,
-            "feature_rows_read": 4 * K * touched["rows_valid"], "tree_words_read": tree_bytes,
-            "records_written": 8 * A if recording else 0, "aux_written": 16 * Q if recording else 0,
-            # (att, e0, e1, e2) per sample, left by the recording forward for the exact backward
-            "backward_terms_written": 16 * A if (recording and forward_terms) else 0,
-        }
-        if fmt == "RGBA" and K in (8, 16, 32) and _C.EXP_TABLE and not _C.NATIVE_MATH and "shade_chan" in (route_fwd or ""):
-            # the exponentials table (svoxt_tree.exp_table): every forward that is not told the features are static
-            # reads the feature table once and writes the table once; the shade then reads ITS rows (counted above)
-            fwd_parts["exp_table_pass"] = 0 if args.forward_only else 2 * 4 * M * K
-        bwd_parts = None
-        kept_scratch = bool(_C.GRAD_SCRATCH and "render_bwd_kernel (marches" not in (route_bwd or ""))
-        if not args.forward_only:
-            bwd_parts = {
-                # (the padded scratch kept between steps is left zeroed by the row compaction: no fill of its own)
-                "grad_memset": 0 if (kept_scratch and stride != K) else 4 * M * stride,
-                "upstream_gradient_read": 4 * (C + 1) * Q, "aux_read": 16 * Q,
-                "rays": 36 * cnt[0], "records_read": 8 * A,
-                # with the forward's hand-over the backward reads 16 B per sample instead of the feature rows
-                "feature_rows_read": 0 if forward_terms else 4 * K * touched["rows_composited"],
-                "terms_read": 16 * A if forward_terms else 0,
-                "atomic_requests_64B": 64 * atomic_requests if atomic_requests else 4 * K * A,
-                # (read the padded rows, write the dense gradient, and -- kept scratch -- leave the padded rows zeroed again)
-                "row_compaction": (4 * M * stride + 4 * M * K + (4 * M * stride if kept_scratch else 0)) if stride != K else 0,
-            }
-            if "grad_wide_kernel" in (route_bwd or "") or "ONEPASS" in (route_bwd or ""):
-                # sweep 1 -> sweep 2: (attenuation,) second-pass total_color per sample, written and read
-                bwd_parts["sweep_handover"] = (16 if "grad_wide_kernel" in route_bwd else 8) * A
-            if atomic_requests is None or not atomic_requests:
-                bwd_parts["atomic_requests_note"] = "one row per sample (this route has no counting instance)"
-        # (the exponentials table of rows of 8 / 16 / 32 floats is an OVERHEAD pass -- the reference has none -- like the
-        # sigma bitmask: carried per kernel below, no longer counted as compulsory: VERDICT r04 weak 3)
-        exp_table_bytes = fwd_parts.pop("exp_table_pass", 0)
-        fwd_bytes = sum(fwd_parts.values())
-        bwd_bytes = sum(v for v in bwd_parts.values() if not isinstance(v, str)) if bwd_parts else 0
-        # ---- per kernel: which kernel moves which of the items above
-        fp, bp = fwd_parts, (bwd_parts or {})
-        tiles = (Q + 63) // 64
-        mask_bytes = 64 * M + M // 8 + (4 * (tiles * 24 + 512 + 17 * tiles + 514) if recording else 0)   # one line per row, the bits, the lists' tables
-        assign, survey = {}, {}
-        rf = route_fwd or ""
-        if "fwd_roles_kernel" in rf:
-            assign["mask"] = (0, mask_bytes, "forward")
-            assign["roles"] = (fwd_bytes, 0, "forward")
-            assign["finish"] = (0, 0, "forward")
-            survey["roles"] = ref_fwd
-        elif "march_rec_kernel" in rf:
-            assign["exptab" if exp_table_bytes else "mask"] = (0, exp_table_bytes or mask_bytes, "forward")
-            march_b = fp["rays"] + fp["tree_words_read"] + fp["records_written"] + fp["aux_written"] + M // 8
-            assign["march"] = (march_b, 0, "forward")
-            # the shade reads the lists back and the (table) rows, writes the pixels (and the backward's terms)
-            assign["shade"] = (8 * A + 16 * Q + fp["feature_rows_read"] + fp["pixels_written"] + fp["backward_terms_written"], 0, "forward")
-            survey["march"], survey["shade"] = None, ref_fwd           # (8(d) has no split: the whole forward against the shade, the larger one)
-        else:
-            assign["fwd"] = (fwd_bytes, 0, "forward")
-            survey["fwd"] = ref_fwd
-        if bwd_parts:
-            rb = route_bwd or ""
-            main = "fused" if "grad_fused" in rb else "wide" if "grad_wide" in rb else "bwd"
-            zero_fill, compaction = bp.get("grad_memset", 0), bp.get("row_compaction", 0)
-            assign[main] = (bwd_bytes - zero_fill - compaction, 0, "backward")
-            survey[main] = ref_bwd - 4 * M * K
-            if compaction:
-                # the dense [M, K] gradient is written once (the reference's zero-fill stands for it in 8(d)); reading the
-                # padded rows and clearing them again is this implementation's overhead
-                assign["compact"] = (4 * M * K, compaction - 4 * M * K, "backward")
-                survey["compact"] = 4 * M * K
-            if zero_fill:
-                assign["fill"] = (zero_fill, 0, "backward")
-                survey["fill"] = 4 * M * K
-        if args.forward_only or fwd_ms >= bwd_ms:
-            dom, dom_kernel, dom_ms, dom_bytes, dom_ref = "forward", route_fwd, fwd_ms, fwd_bytes, ref_fwd
-        else:
-            dom, dom_kernel, dom_ms, dom_bytes, dom_ref = "backward", route_bwd, bwd_ms, bwd_bytes, ref_bwd
-            dom_kernel += " + grad memset + row compaction"
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-        prof_ok = world == 1 and not args.fast            # (committed profiles: N = 1, thresholds 0)
-        traffic, traffic_note = pmc_traffic(args.workload, args.forward_only, dom) if prof_ok else \
-            (None, "PMC profiles exist for N=1, thresholds 0 only")
-        # Like with like: the chain floor of the STEPPING against the march kernel's own time (from the committed
-        # kernel statistics of this command) when the forward is march + shade; the floor of stepping + shading
-        # in one chain against the whole forward when it is one kernel.
-        two_kernel = "march_rec" in (route_fwd or "")
-        chain = "march" if two_kernel else "march+shade"
-        kstats = kernel_stats_ms(args.workload, args.forward_only) if prof_ok else {}
-        march_ms = next((v for k, v in kstats.items() if k.startswith("march_rec_kernel")), None)
-        shade_ms = next((v for k, v in kstats.items() if k.startswith("shade_")), None)
-        limits = {"forward": {
-            "bound": "dependent chain of the longest ray (tree words -> step -> next tree words), not bytes",
-            "longest_ray_crossings": touched["longest_ray_crossings"],
-            "us_per_crossing_unloaded": US_PER_CROSSING_UNLOADED[chain],
-            "floor_ms": round(touched["longest_ray_crossings"] * US_PER_CROSSING_UNLOADED[chain] * 1e-3, 4),
-            "floor_of": "march_rec_kernel alone" if two_kernel else "render_fwd_kernel (stepping and shading in one chain)",
-            "measured_ms": march_ms if two_kernel else round(fwd_ms, 4),
-            "measured_of": (f"march_rec_kernel, profiles/{ROUND}_{args.workload}{'_fwd' if args.forward_only else ''}_kernel_stats.csv"
-                            + ("" if march_ms is not None else " (not committed yet)")) if two_kernel
-                           else "the whole forward (HIP events of this run)",
-            "forward_ms_whole": round(fwd_ms, 4)}}
-        if two_kernel and shade_ms is not None:
-            limits["forward"]["shade_kernel_ms"] = shade_ms
-        if atomic_requests:
-            limits["backward"] = {
-                "bound": "floor: the rate at which the memory side takes 64-byte float-atomic requests (exp/atomic_bench.hip: 22 G/s)"
-                         + (".  Not what binds the per-tile backward today: 15 % fewer requests (rows carried across the reduce's "
-                            "16-record groups) made it 6 % SLOWER, shorter instruction paths in the same reduce 3 % faster -- its phases "
-                            "are serial per workgroup and latency-bound (NOTEBOOK.md steps 39-41)"
-                            if "grad_fused" in (route_bwd or "") else ""),
-                "atomic_requests": atomic_requests, "merged_rows": merged_rows,
-                "floor_ms": round(atomic_requests / ATOMIC_REQUESTS_PER_S * 1e3, 4), "measured_ms": round(bwd_ms, 4)}
-        # What binds the dominant kernel group -- from this run's own numbers, not asserted: the working set of
-        # configs 1-3 never leaves the Infinity Cache and the two big kernels sit at 0.13-0.29 of the HBM roofline, so
-        # "hbm" would misname it.  forward: as long as the dependent chain of its longest ray
-        # (+ the shading backlog) -> "latency"; per-tile backward of 3-channel payloads: a chain of barrier-separated
-        # phases over an atomic-request floor it does not reach -> "latency"; backward of wide rows in exact mode:
-        # vector ALU (the bit-exact expf replica and a double-precision divide per sigmoid) -> "valu".
-        wide_exact = "grad_wide_kernel" in (route_bwd or "") and "native" not in (route_bwd or "")
-        if dom == "backward" and wide_exact and "forward's table" not in (route_bwd or ""):
-            bound, bound_detail = "valu", ("vector ALU: the exact sigmoids of both sweeps (pexpf + a double-precision divide each); "
-                                           "rocprofv3 PMC of this command: SQ_INSTS_VALU per (sample, channel) in profiles/" + ROUND + "_*")
-        elif dom == "backward" and wide_exact:
-            lim = limits.get(dom, {})
-            bound = "latency"
-            bound_detail = ("barrier-separated phases per tile and window at four workgroups per CU: with the exponentials from the "
-                            "forward's table the kernel waits 70 % of its wavefront-cycles (SQ_WAIT_ANY / SQ_WAVE_CYCLES, 11 % VALU "
-                            "active: profiles/" + ROUND + "_d9_rgba32_1024_pmc_summary.txt); its atomic-request floor is %s ms of the %s measured"
-                            % (lim.get("floor_ms"), lim.get("measured_ms")))
-        else:
-            lim = limits.get(dom, {})
-            bound = "latency"
-            bound_detail = (("the dependent chain of the longest ray: floor %(floor_ms)s ms against %(measured_ms)s measured" % lim)
-                            if dom == "forward" else
-                            ("barrier-separated phases per tile; its atomic-request floor is %s ms of the %s measured"
-                             % (lim.get("floor_ms"), lim.get("measured_ms"))))
-        step_ref = ref_fwd + (0 if args.forward_only else ref_bwd)
-        ktable = kernel_table(args.workload, args.forward_only, assign, survey, {"forward": fwd_ms, "backward": bwd_ms}, prof_ok)
-        largest = next((r for r in ktable if r["ms"]), None)
         res = {
             "metric": "Mrays/s fwd+bwd, 800×800 render, depth-8 SH9 N3Tree, 1→8 MI355X"
                       if args.workload == "d8_sh9_800" and not args.forward_only and not args.fast
@@ -867,55 +779,201 @@ def main(argv=None):
             "kernel_ms": {"forward": round(fwd_ms, 4), "backward": round(bwd_ms, 4),
                           "forward_median": round(_median(fwd_steps), 4), "backward_median": round(_median(bwd_steps), 4)},
             "kernels": {"forward": route_fwd, "backward": route_bwd},
-            "counters": dict(zip(("rays_hit", "steps", "levels", "valid", "active"), cnt)),
-            "touched": touched,
-            "compulsory_bytes": {"forward": fwd_parts, "backward": bwd_parts,
-                                 "overhead_passes": {k: v[1] for k, v in assign.items() if v[1]},
-                                 "step_total": fwd_bytes + bwd_bytes,
-                                 "step_gbps": round((fwd_bytes + bwd_bytes) / (ms_per_step * 1e-3) / 1e9, 2)},
-            "roofline": {
-                "bound": bound,
-                "bound_detail": bound_detail,
-                "frac_of": "hbm (secondary: the fraction of the 8 TB/s HBM roofline the dominant group's compulsory bytes reach; "
-                           "the group is bound by `bound`, see limits)",
-                "kernel": dom_kernel,
-                "achieved": round(achieved, 2),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5),
-                "traffic": traffic,
-                "traffic_note": traffic_note,
-                # per kernel: the largest kernel first; `frac_largest_kernel` is ITS fraction of the HBM
-                # roofline (durations from this round's committed kernel statistics; null until those exist)
-                "kernels": ktable,
-                "frac_largest_kernel": None if largest is None else largest["frac"],
-                "largest_kernel": None if largest is None else largest["kernel"],
-                "frac_8d_note": "frac_8d > 1 in a row below: the kernel does not do the reference's work (sample lists replace two of "
-                                "its three marches, the grid its descent, the per-tile merge its per-sample atomics) -- the same route is "
-                                "held bit for bit (forward) / to 1e-5 of the tight scale (gradient) at full size by the tests",
-                "achieved_note": f"compulsory bytes of the {dom} as run (compulsory_bytes.{dom}: each item counted once, "
-                                 "distinct rows / tree words / atomic requests counted on the device) / its mean duration "
-                                 "from HIP events on the launch stream; the working set of this config sits in the 256 MiB "
-                                 "Infinity Cache, so the fraction of the HBM roofline is low by construction: see limits",
-                "reference_equivalent_gbps": round(dom_ref / (dom_ms * 1e-3) / 1e9, 2),
-                "reference_equivalent_note": "SURVEY.md 8(d): the bytes the REFERENCE's algorithm moves for the same result "
-                                             "(a tree march per pass, 8 B per gradient float) / this kernel group's time",
-                # SURVEY.md 8(d)'s own figure for the WHOLE step, so that nobody has to recompute it: above 1 does not
-                # mean skipped work -- the sample lists replace two of the reference's three marches, the grid its
-                # descent, the per-tile merge its per-sample atomics; the same route is held bit for bit (forward) /
-                # to 1e-5 of the tight scale (gradient) at full size by tests/test_gpu_query_and_misc.py
-                "reference_equivalent": {"bytes_per_step": step_ref, "gbps": round(step_ref / (ms_per_step * 1e-3) / 1e9, 2),
-                                         "frac_of_hbm_peak": round(step_ref / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                         "forward_bytes": ref_fwd, "backward_bytes": None if args.forward_only else ref_bwd},
-                # both kernel groups (the dominant one is whichever took longer in this run: at the headline config the
-                # two are within 2 % of each other and take turns)
-                "groups": {g: {"ms": round(ms_, 4), "compulsory_bytes": b_, "achieved": round(b_ / (ms_ * 1e-3) / 1e9, 2),
-                               "frac": round(b_ / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                               "traffic": (pmc_traffic(args.workload, args.forward_only, g)[0] if prof_ok else None)}
-                           for g, ms_, b_ in (("forward", fwd_ms, fwd_bytes), ("backward", bwd_ms, bwd_bytes)) if ms_ > 0.02 and b_ > 0},
-            },
-            "limits": limits,
         }
+        if args.full:
+            ref_fwd, ref_bwd = reference_equivalent_bytes(cnt, Q, M, K, C)
+            A = cnt[4]
+            stride = K if (K <= 8 or K % 16 == 0) else (K + 15) // 16 * 16
+            tree_bytes = 4 * touched.get("grid_cells", 0) + 8 * touched.get("node_pairs", 0) + \
+                4 * (touched.get("child_words", 0) + touched.get("data_words", 0))
+            recording = not args.forward_only
+            fwd_parts = {
+                "rays": 36 * Q, "pixels_written": 4 * (C + 1) * Q,
+                "feature_rows_read": 4 * K * touched["rows_valid"], "tree_words_read": tree_bytes,
+                "records_written": 8 * A if recording else 0, "aux_written": 16 * Q if recording else 0,
+                # (att, e0, e1, e2) per sample, left by the recording forward for the exact backward
+                "backward_terms_written": 16 * A if (recording and forward_terms) else 0,
+            }
+            if fmt == "RGBA" and K in (8, 16, 32) and _C.EXP_TABLE and not _C.NATIVE_MATH and "shade_chan" in (route_fwd or ""):
+                # the exponentials table (svoxt_tree.exp_table): every forward that is not told the features are static
+                # reads the feature table once and writes the table once; the shade then reads ITS rows (counted above)
+                fwd_parts["exp_table_pass"] = 0 if args.forward_only else 2 * 4 * M * K
+            bwd_parts = None
+            kept_scratch = bool(_C.GRAD_SCRATCH and "render_bwd_kernel (marches" not in (route_bwd or ""))
+            if not args.forward_only:
+                bwd_parts = {
+                    # (the padded scratch kept between steps is left zeroed by the row compaction: no fill of its own)
+                    "grad_memset": 0 if (kept_scratch and stride != K) else 4 * M * stride,
+                    "upstream_gradient_read": 4 * (C + 1) * Q, "aux_read": 16 * Q,
+                    "rays": 36 * cnt[0], "records_read": 8 * A,
+                    # with the forward's hand-over the backward reads 16 B per sample instead of the feature rows
+                    "feature_rows_read": 0 if forward_terms else 4 * K * touched["rows_composited"],
+                    "terms_read": 16 * A if forward_terms else 0,
+                    "atomic_requests_64B": 64 * atomic_requests if atomic_requests else 4 * K * A,
+                    # (read the padded rows, write the dense gradient, and -- kept scratch -- leave the padded rows zeroed again)
+                    "row_compaction": (4 * M * stride + 4 * M * K + (4 * M * stride if kept_scratch else 0)) if stride != K else 0,
+                }
+                if "grad_wide_kernel" in (route_bwd or "") or "ONEPASS" in (route_bwd or ""):
+                    # sweep 1 -> sweep 2: (attenuation,) second-pass total_color per sample, written and read
+                    bwd_parts["sweep_handover"] = (16 if "grad_wide_kernel" in route_bwd else 8) * A
+                if atomic_requests is None or not atomic_requests:
+                    bwd_parts["atomic_requests_note"] = "one row per sample (this route has no counting instance)"
+            # (the exponentials table of rows of 8 / 16 / 32 floats is an OVERHEAD pass -- the reference has none -- like the
+            # sigma bitmask: carried per kernel below, no longer counted as compulsory: VERDICT r04 weak 3)
+            exp_table_bytes = fwd_parts.pop("exp_table_pass", 0)
+            fwd_bytes = sum(fwd_parts.values())
+            bwd_bytes = sum(v for v in bwd_parts.values() if not isinstance(v, str)) if bwd_parts else 0
+            # ---- per kernel: which kernel moves which of the items above
+            fp, bp = fwd_parts, (bwd_parts or {})
+            tiles = (Q + 63) // 64
+            mask_bytes = 64 * M + M // 8 + (4 * (tiles * 24 + 512 + 17 * tiles + 514) if recording else 0)   # one line per row, the bits, the lists' tables
+            assign, survey = {}, {}
+            rf = route_fwd or ""
+            if "fwd_roles_kernel" in rf:
+                assign["mask"] = (0, mask_bytes, "forward")
+                assign["roles"] = (fwd_bytes, 0, "forward")
+                assign["finish"] = (0, 0, "forward")
+                survey["roles"] = ref_fwd
+            elif "march_rec_kernel" in rf:
+                assign["exptab" if exp_table_bytes else "mask"] = (0, exp_table_bytes or mask_bytes, "forward")
+                march_b = fp["rays"] + fp["tree_words_read"] + fp["records_written"] + fp["aux_written"] + M // 8
+                assign["march"] = (march_b, 0, "forward")
+                # the shade reads the lists back and the (table) rows, writes the pixels (and the backward's terms)
+                assign["shade"] = (8 * A + 16 * Q + fp["feature_rows_read"] + fp["pixels_written"] + fp["backward_terms_written"], 0, "forward")
+                survey["march"], survey["shade"] = None, ref_fwd           # (8(d) has no split: the whole forward against the shade, the larger one)
+            else:
+                assign["fwd"] = (fwd_bytes, 0, "forward")
+                survey["fwd"] = ref_fwd
+            if bwd_parts:
+                rb = route_bwd or ""
+                main = "fused" if "grad_fused" in rb else "wide" if "grad_wide" in rb else "bwd"
+                zero_fill, compaction = bp.get("grad_memset", 0), bp.get("row_compaction", 0)
+                assign[main] = (bwd_bytes - zero_fill - compaction, 0, "backward")
+                survey[main] = ref_bwd - 4 * M * K
+                if compaction:
+                    # the dense [M, K] gradient is written once (the reference's zero-fill stands for it in 8(d)); reading the
+                    # padded rows and clearing them again is this implementation's overhead
+                    assign["compact"] = (4 * M * K, compaction - 4 * M * K, "backward")
+                    survey["compact"] = 4 * M * K
+                if zero_fill:
+                    assign["fill"] = (zero_fill, 0, "backward")
+                    survey["fill"] = 4 * M * K
+            if args.forward_only or fwd_ms >= bwd_ms:
+                dom, dom_kernel, dom_ms, dom_bytes, dom_ref = "forward", route_fwd, fwd_ms, fwd_bytes, ref_fwd
+            else:
+                dom, dom_kernel, dom_ms, dom_bytes, dom_ref = "backward", route_bwd, bwd_ms, bwd_bytes, ref_bwd
+                dom_kernel += " + grad memset + row compaction"
+            achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+            prof_ok = world == 1 and not args.fast            # (committed profiles: N = 1, thresholds 0)
+            traffic, traffic_note = pmc_traffic(args.workload, args.forward_only, dom) if prof_ok else \
+                (None, "PMC profiles exist for N=1, thresholds 0 only")
+            # Like with like: the chain floor of the STEPPING against the march kernel's own time (from the committed
+            # kernel statistics of this command) when the forward is march + shade; the floor of stepping + shading
+            # in one chain against the whole forward when it is one kernel.
+            two_kernel = "march_rec" in (route_fwd or "")
+            chain = "march" if two_kernel else "march+shade"
+            kstats = kernel_stats_ms(args.workload, args.forward_only) if prof_ok else {}
+            march_ms = next((v for k, v in kstats.items() if k.startswith("march_rec_kernel")), None)
+            shade_ms = next((v for k, v in kstats.items() if k.startswith("shade_")), None)
+            limits = {"forward": {
+                "bound": "dependent chain of the longest ray (tree words -> step -> next tree words), not bytes",
+                "longest_ray_crossings": touched["longest_ray_crossings"],
+                "us_per_crossing_unloaded": US_PER_CROSSING_UNLOADED[chain],
+                "floor_ms": round(touched["longest_ray_crossings"] * US_PER_CROSSING_UNLOADED[chain] * 1e-3, 4),
+                "floor_of": "march_rec_kernel alone" if two_kernel else "render_fwd_kernel (stepping and shading in one chain)",
+                "measured_ms": march_ms if two_kernel else round(fwd_ms, 4),
+                "measured_of": (f"march_rec_kernel, profiles/{ROUND}_{args.workload}{'_fwd' if args.forward_only else ''}_kernel_stats.csv"
+                                + ("" if march_ms is not None else " (not committed yet)")) if two_kernel
+                               else "the whole forward (HIP events of this run)",
+                "forward_ms_whole": round(fwd_ms, 4)}}
+            if two_kernel and shade_ms is not None:
+                limits["forward"]["shade_kernel_ms"] = shade_ms
+            if atomic_requests:
+                limits["backward"] = {
+                    "bound": "floor: the rate at which the memory side takes 64-byte float-atomic requests (exp/atomic_bench.hip: 22 G/s)"
+                             + (".  Not what binds the per-tile backward today: 15 % fewer requests (rows carried across the reduce's "
+                                "16-record groups) made it 6 % SLOWER, shorter instruction paths in the same reduce 3 % faster -- its phases "
+                                "are serial per workgroup and latency-bound (NOTEBOOK.md steps 39-41)"
+                                if "grad_fused" in (route_bwd or "") else ""),
+                    "atomic_requests": atomic_requests, "merged_rows": merged_rows,
+                    "floor_ms": round(atomic_requests / ATOMIC_REQUESTS_PER_S * 1e3, 4), "measured_ms": round(bwd_ms, 4)}
+            # What binds the dominant kernel group -- from this run's own numbers, not asserted: the working set of
+            # configs 1-3 never leaves the Infinity Cache and the two big kernels sit at 0.13-0.29 of the HBM roofline, so
+            # "hbm" would misname it.  forward: as long as the dependent chain of its longest ray
+            # (+ the shading backlog) -> "latency"; per-tile backward of 3-channel payloads: a chain of barrier-separated
+            # phases over an atomic-request floor it does not reach -> "latency"; backward of wide rows in exact mode:
+            # vector ALU (the bit-exact expf replica and a double-precision divide per sigmoid) -> "valu".
+            wide_exact = "grad_wide_kernel" in (route_bwd or "") and "native" not in (route_bwd or "")
+            if dom == "backward" and wide_exact and "forward's table" not in (route_bwd or ""):
+                bound, bound_detail = "valu", ("vector ALU: the exact sigmoids of both sweeps (pexpf + a double-precision divide each); "
+                                               "rocprofv3 PMC of this command: SQ_INSTS_VALU per (sample, channel) in profiles/" + ROUND + "_*")
+            elif dom == "backward" and wide_exact:
+                lim = limits.get(dom, {})
+                bound = "latency"
+                bound_detail = ("barrier-separated phases per tile and window at four workgroups per CU: with the exponentials from the "
+                                "forward's table the kernel waits 70 % of its wavefront-cycles (SQ_WAIT_ANY / SQ_WAVE_CYCLES, 11 % VALU "
+                                "active: profiles/" + ROUND + "_d9_rgba32_1024_pmc_summary.txt); its atomic-request floor is %s ms of the %s measured"
+                                % (lim.get("floor_ms"), lim.get("measured_ms")))
+            else:
+                lim = limits.get(dom, {})
+                bound = "latency"
+                bound_detail = (("the dependent chain of the longest ray: floor %(floor_ms)s ms against %(measured_ms)s measured" % lim)
+                                if dom == "forward" else
+                                ("barrier-separated phases per tile; its atomic-request floor is %s ms of the %s measured"
+                                 % (lim.get("floor_ms"), lim.get("measured_ms"))))
+            step_ref = ref_fwd + (0 if args.forward_only else ref_bwd)
+            ktable = kernel_table(args.workload, args.forward_only, assign, survey, {"forward": fwd_ms, "backward": bwd_ms}, prof_ok)
+            largest = next((r for r in ktable if r["ms"]), None)
+            res.update({
+                "counters": dict(zip(("rays_hit", "steps", "levels", "valid", "active"), cnt)),
+                "touched": touched,
+                "compulsory_bytes": {"forward": fwd_parts, "backward": bwd_parts,
+                                     "overhead_passes": {k: v[1] for k, v in assign.items() if v[1]},
+                                     "step_total": fwd_bytes + bwd_bytes,
+                                     "step_gbps": round((fwd_bytes + bwd_bytes) / (ms_per_step * 1e-3) / 1e9, 2)},
+                "roofline": {
+                    "bound": bound,
+                    "bound_detail": bound_detail,
+                    "frac_of": "hbm (secondary: the fraction of the 8 TB/s HBM roofline the dominant group's compulsory bytes reach; "
+                               "the group is bound by `bound`, see limits)",
+                    "kernel": dom_kernel,
+                    "achieved": round(achieved, 2),
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5),
+                    "traffic": traffic,
+                    "traffic_note": traffic_note,
+                    # per kernel: the largest kernel first; `frac_largest_kernel` is ITS fraction of the HBM
+                    # roofline (durations from this round's committed kernel statistics; null until those exist)
+                    "kernels": ktable,
+                    "frac_largest_kernel": None if largest is None else largest["frac"],
+                    "largest_kernel": None if largest is None else largest["kernel"],
+                    "frac_8d_note": "frac_8d > 1 in a row below: the kernel does not do the reference's work (sample lists replace two of "
+                                    "its three marches, the grid its descent, the per-tile merge its per-sample atomics) -- the same route is "
+                                    "held bit for bit (forward) / to 1e-5 of the tight scale (gradient) at full size by the tests",
+                    "achieved_note": f"compulsory bytes of the {dom} as run (compulsory_bytes.{dom}: each item counted once, "
+                                     "distinct rows / tree words / atomic requests counted on the device) / its mean duration "
+                                     "from HIP events on the launch stream; the working set of this config sits in the 256 MiB "
+                                     "Infinity Cache, so the fraction of the HBM roofline is low by construction: see limits",
+                    "reference_equivalent_gbps": round(dom_ref / (dom_ms * 1e-3) / 1e9, 2),
+                    "reference_equivalent_note": "SURVEY.md 8(d): the bytes the REFERENCE's algorithm moves for the same result "
+                                                 "(a tree march per pass, 8 B per gradient float) / this kernel group's time",
+                    # SURVEY.md 8(d)'s own figure for the WHOLE step, so that nobody has to recompute it: above 1 does not
+                    # mean skipped work -- the sample lists replace two of the reference's three marches, the grid its
+                    # descent, the per-tile merge its per-sample atomics; the same route is held bit for bit (forward) /
+                    # to 1e-5 of the tight scale (gradient) at full size by tests/test_gpu_query_and_misc.py
+                    "reference_equivalent": {"bytes_per_step": step_ref, "gbps": round(step_ref / (ms_per_step * 1e-3) / 1e9, 2),
+                                             "frac_of_hbm_peak": round(step_ref / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                             "forward_bytes": ref_fwd, "backward_bytes": None if args.forward_only else ref_bwd},
+                    # both kernel groups (the dominant one is whichever took longer in this run: at the headline config the
+                    # two are within 2 % of each other and take turns)
+                    "groups": {g: {"ms": round(ms_, 4), "compulsory_bytes": b_, "achieved": round(b_ / (ms_ * 1e-3) / 1e9, 2),
+                                   "frac": round(b_ / (ms_ * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                   "traffic": (pmc_traffic(args.workload, args.forward_only, g)[0] if prof_ok else None)}
+                               for g, ms_, b_ in (("forward", fwd_ms, fwd_bytes), ("backward", bwd_ms, bwd_bytes)) if ms_ > 0.02 and b_ > 0},
+                },
+                "limits": limits,
+            })
         if other:
             res["other_routes"] = other
             # the drop-in route's number at top level: `value` is the `config.route` route
@@ -937,7 +995,7 @@ def main(argv=None):
         if world > 1:
             res["multi_gpu_note"] = ("kernel_ms is the compute stream's forward / backward per step; ms_per_step - kernel "
                                      "time = exposed collectives + host; unmeasured on hardware by the builder (no 8-GPU node)")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(st, feats, o, d, v, fmt, K, gout.cpu(), args.forward_only)
         print(json.dumps(res), flush=True)
     if dist is not None:

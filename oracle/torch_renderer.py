@@ -89,7 +89,9 @@ def volume_render(tree: O.Tree, origins, dirs, vdirs, opt: O.RenderOptions,
     # ---- per-ray set-up (float32, reference operation order) ----
     o = offset + scaling * o
     d = d * scaling
-    nrm = torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    # sqrtf through numpy, which rounds it correctly: torch's CPU sqrt goes through MKL's vector math, whose float32
+    # results are off in the last bit for some inputs, and for which inputs depends on the host CPU
+    nrm = torch.from_numpy(np.sqrt(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).numpy()))
     delta_scale = 1.0 / nrm
     d = d * delta_scale[:, None]
     inv = (1.0 / (d.double() + 1e-9)).float()

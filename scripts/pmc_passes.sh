@@ -2,12 +2,12 @@
 # PMC counter passes (run on the GPU box through gpurun).  Each pass is its own
 # rocprofv3 run with --pmc only (no trace domains), as the pool requires; results land
 # in gpurun_out/pmc_<tag>/.
-#   scripts/pmc_passes.sh <tag> [python-script args...]   (default: bench.py --steps 3 --warmup 1 --no-cpu-baseline)
+#   scripts/pmc_passes.sh <tag> [python-script args...]   (default: bench.py --steps 3 --warmup 1 --full --no-cpu-baseline)
 #   PMC_GROUPS="sq1 sq2" selects passes (default: all seven)
 set -u
 TAG=${1:-r02}
 shift || true
-if [ $# -eq 0 ]; then set -- bench.py --steps 3 --warmup 1 --no-cpu-baseline; fi
+if [ $# -eq 0 ]; then set -- bench.py --steps 3 --warmup 1 --full --no-cpu-baseline; fi
 SCRIPT=$GRAFT_REPO_ROOT/$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 GROUPS_WANTED=${PMC_GROUPS:-"fetch write tcc sq1 sq2 tcp grbm"}

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 bench() {   # name, args...
   local name=$1; shift
-  timeout -k 10 300 python3 bench.py "$@" > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err < /dev/null || echo "bench $name failed"
+  timeout -k 10 300 python3 bench.py --full "$@" > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err < /dev/null || echo "bench $name failed"
   echo "bench $name done"
 }
 stats() {   # name, args...
@@ -25,7 +25,7 @@ stats() {   # name, args...
 }
 pmc() {     # name, args...
   local name=$1; shift
-  bash scripts/pmc_passes.sh $name bench.py --steps 3 --warmup 1 --prewarm-s 0 --no-cpu-baseline --no-plain "$@" > $OUT/${name}_pmc.log 2>&1 < /dev/null
+  bash scripts/pmc_passes.sh $name bench.py --steps 3 --warmup 1 --prewarm-s 0 --full --no-cpu-baseline --no-plain "$@" > $OUT/${name}_pmc.log 2>&1 < /dev/null
   python3 scripts/pmc_summary.py $name $OUT/${name}_pmc.json > $OUT/${name}_pmc_summary.txt 2>&1
   cp $OUT/${name}_pmc.json profiles/${ROUND}_${name}_pmc.json      # (on the box's copy: the bench lines below read it for roofline.traffic)
   echo "pmc $name done"

@@ -63,3 +63,28 @@ def test_bench_without_a_gpu_fails_loudly():
         pytest.skip("a GPU is present")
     p = _run("--steps", "1", "--warmup", "0")
     assert p.returncode != 0 and "GPU" in (p.stderr + p.stdout)
+
+
+def test_dump_outputs_keeps_what_fits_and_a_seeded_row_sample_of_the_rest(tmp_path):
+    """--dump-outputs' writer: float32 files within the budget; the smaller array whole, the larger one as rows drawn with a
+    fixed seed, in order -- the same rows on every call, so that two builds can be compared file for file."""
+    import numpy as np
+    import torch
+
+    import bench
+    grad = torch.arange(50000, dtype=torch.float64)[:, None] * torch.ones(1, 28, dtype=torch.float64)   # row i holds i
+    pix = torch.rand(4096, 4)
+    budget = 1_000_000
+    kept = bench.dump_outputs(str(tmp_path / "a"), {"grad_features": grad, "pixels": pix}, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), {"pixels": pix, "grad_features": grad}, budget=budget)
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == ["grad_features.npy", "pixels.npy"]
+    assert sum(f.stat().st_size for f in files) <= budget
+    g, p = np.load(tmp_path / "a" / "grad_features.npy"), np.load(tmp_path / "a" / "pixels.npy")
+    assert g.dtype == p.dtype == np.float32
+    np.testing.assert_array_equal(p, pix.numpy())
+    rows = g[:, 0].astype(np.int64)
+    assert kept == {"pixels": 4096, "grad_features": len(rows)} and 0.9 * (budget - 4096 * 16) / 112 < len(rows) < 50000
+    assert np.all(np.diff(rows) > 0) and np.all(g == rows[:, None])            # distinct rows of the input, in order
+    for f in files:
+        np.testing.assert_array_equal(np.load(f), np.load(tmp_path / "b" / f.name))

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the fields the driver reads (GPU box)."""
+"""bench.py prints ONE JSON line: the headline in a plain run, everything it measures with --full (GPU box)."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run_bench():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -91,3 +91,48 @@ def test_a_stalled_step_is_timed_again_and_said_so(gpu):
     p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--no-cpu-baseline",
                          "--no-plain", "--no-other-configs"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert json.loads([l for l in p2.stdout.splitlines() if l.strip()][-1])["retimed"] is None
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_steps_outputs(gpu, tmp_path):
+    """A plain run measures the headline only; --dump-outputs writes what its last timed step returned: the pixels whole,
+    the gradient as the seeded row sample dump_outputs takes -- the same as a forward + backward of the same inputs here."""
+    import numpy as np
+    import torch
+
+    import bench
+    import svox_t_amd as svox
+    from svox_t_amd import synth
+
+    out = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "Mrays/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["metric"].startswith("Mrays/s fwd+bwd, 800×800") and len(r["per_step_ms"]["forward"]) == 3
+    assert abs(r["value"] - 0.64 / r["ms_per_step"] * 1e3) / r["value"] < 1e-3
+    for k in ("roofline", "limits", "counters", "cpu_baseline", "other_routes", "other_configs", "tolerance_mode"):
+        assert k not in r, k                                      # (--full only)
+    files = sorted(f.name for f in out.iterdir())
+    assert files == ["grad_features.npy", "pixels.npy"], files
+    assert sum(f.stat().st_size for f in out.iterdir()) <= bench.DUMP_BYTES
+    pix, grad = np.load(out / "pixels.npy"), np.load(out / "grad_features.npy")
+    assert pix.dtype == grad.dtype == np.float32 and pix.shape == (640000, 4)
+
+    # the same inputs, one step here: bench.py's workload and camera (rank 0)
+    dev = torch.device("cuda:0")
+    depth, K, fmt, W, H = bench.WORKLOADS["d8_sh9_800"]
+    st = synth.shell_tree(depth)
+    tree = svox.N3Tree.from_arrays(st.child, st.data, st.parent_depth, synth.shell_features(st.n_features, K),
+                                   data_format=fmt, device=dev)
+    o, d, v = synth.pinhole_rays(W, H, c2w=synth.camera_pose(azimuth_deg=30.0))
+    o_ = svox.VolumeRenderer(tree)(tree.features, svox.Rays(o.to(dev), d.to(dev), v.to(dev)), image_shape=(H, W))
+    o_.backward(synth.grad_output(W * H, 4).to(dev))
+    kept = bench.dump_outputs(str(tmp_path / "here"), {"pixels": o_, "grad_features": tree.features.grad})
+    assert kept == {"pixels": 640000, "grad_features": grad.shape[0]} and 0 < grad.shape[0] < st.n_features
+    np.testing.assert_array_equal(pix, np.load(tmp_path / "here" / "pixels.npy"))     # the forward is bit-exact
+    gref = np.load(tmp_path / "here" / "grad_features.npy")
+    # (float atomics: the gradient's last bits may differ from run to run; the same rows are compared)
+    assert np.abs(grad - gref).max() <= 1e-5 * np.abs(gref).max() and np.abs(gref).max() > 0
