@@ -12,6 +12,8 @@
  *   svoxt_render_depth        <- render_depth             svox_t/csrc/svox.cpp:63,134   (rt_kernel.cu:1506-1523)
  *   svoxt_query_fwd           <- query_vertical           svox_t/csrc/svox.cpp:45,119   (svox_kernel.cu:274-324)
  *   svoxt_query_bwd           <- query_vertical_backward  svox_t/csrc/svox.cpp:46,120   (svox_kernel.cu:380-402)
+ *   svoxt_p2v_fwd             <- p2v                      svox_t/csrc/svox.cpp:52,125   (p2v_kernel.cu:240-261)
+ *   svoxt_p2v_bwd             <- p2v_backward             svox_t/csrc/svox.cpp:53,126   (p2v_kernel.cu:263-285)
  *   svoxt_tree / svoxt_rays / svoxt_options
  *                             <- TreeSpec / RaysSpec / RenderOptions
  *                                                         svox_t/csrc/include/data_spec.hpp:52-145
@@ -705,6 +707,44 @@ int svoxt_warp_vertices_bwd(const float* matrices, int32_t n_joints, const float
                             const float* grad_vertices, const float* grad_matrix_out,
                             float* grad_points, float* grad_matrices, float* grad_skinning_weights,
                             void* stream);
+
+/* ---- Point-to-voxel splat: voxelize (p2v.py:33-54, p2v_kernel.cu:104-286) --------------------------
+ *
+ * voxels[x][y][z] (device [n, n, n, 1]) = sum over the points p whose window holds (x, y, z) and with
+ * r = |xyz_p - (i * voxel_size + volume_corner)| <= conv_radius of
+ * expf(-r*r / (2*kernel_radius*kernel_radius)) * point_features[p][F-1], voxel_size = volume_size / (n - 1):
+ * the reference's float expressions, so the same (point, voxel) pairs.  Unlike the reference the sum is
+ * bit-identical from run to run (no float atomics: points sorted by 4x4x4 tile, one wavefront per tile and
+ * chunk of candidates, bins in fixed order and ascending point index within a bin).  Non-finite points
+ * contribute nothing.
+ *
+ * points: device [P, 3]; point_features: device [P, F], F >= 1; volume_corner / volume_size: HOST float[3]
+ * (size > 0); n_voxels in [2, 1024]; kernel_radius > 0; conv_radius finite and >= 0; P in [0, 2^31).
+ * Every argument is checked before any HIP call (SVOXT_ERR_INVALID).  order (device int32 [P], optional):
+ * receives the permutation the forward sorted the points into, for svoxt_p2v_bwd.  workspace: device,
+ * svoxt_p2v_workspace_bytes(P, n_voxels, volume_corner, volume_size, conv_radius) bytes, the same arguments as the
+ * forward's (-1: invalid arguments, or too many work items: tiles + P x apron bins / 1024 reaches 2^32 -- e.g. P near
+ * 2^31 with conv_radius over ~21 voxels; then the forward returns SVOXT_ERR_UNSUPPORTED).  Size: ~40 bytes a point
+ * plus ~256 bytes per 1 024 candidates (P x apron bins; 27 bins up to conv_radius = 3 voxels, 125 below 7) plus
+ * 12 bytes a tile -- 51 MiB for 1 M points at n = 256 and 2 voxels, 98 GiB for 2^31 - 1 points at 3 voxels.
+ * No host read, no synchronisation. */
+int64_t svoxt_p2v_workspace_bytes(int64_t P, int32_t n_voxels, const float* volume_corner, const float* volume_size,
+                                  float conv_radius);
+int svoxt_p2v_fwd(const float* points, const float* point_features, int64_t P, int32_t F,
+                  const float* volume_corner, const float* volume_size, int32_t n_voxels,
+                  float kernel_radius, float conv_radius, float* voxels, int32_t* order,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
+/* p2v_backward: grad_output device [n, n, n, 1].  points_grad [P, 3] and point_features_grad [P, F]
+ * (device, each optional: NULL = not computed) get every element written once, no atomics.  The
+ * reference's per-point loop (x -> y -> z) with its expressions and its order of addition per point;
+ * the feature gradient goes to column F-1, the column the forward reads (the reference writes column 0,
+ * p2v_kernel.cu:203), the other columns are 0.  Non-finite points get zero gradient.  order: the
+ * forward's permutation (optional; the walk order only, results do not depend on it). */
+int svoxt_p2v_bwd(const float* grad_output, const float* points, const float* point_features, int64_t P,
+                  int32_t F, const float* volume_corner, const float* volume_size, int32_t n_voxels,
+                  float kernel_radius, float conv_radius, const int32_t* order, float* points_grad,
+                  float* point_features_grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,9 @@ EXPORTS = {
     "svoxt_motion_workspace_bytes": (ctypes.c_int64, [_i64, _i32]),
     "svoxt_motion_feature_render_fwd": (ctypes.c_int, [_P(_CTree), _P(_CMotion), _P(_CRays), _P(_COptions), _vp, _vp, _i64, _vp]),
     "svoxt_motion_feature_render_bwd": (ctypes.c_int, [_P(_CTree), _P(_CMotion), _P(_CRays), _P(_COptions), _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_p2v_workspace_bytes": (_i64, [_i64, _i32, _vp, _vp, ctypes.c_float]),
+    "svoxt_p2v_fwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_p2v_bwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -339,6 +339,91 @@ def build_octree(points: torch.Tensor, offset: torch.Tensor, scaling: torch.Tens
     return child, data, parent_depth, n
 
 
+def _p2v_args(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius, conv_radius):
+    """The checks of p2v / p2v_backward (the reference's check_indices, p2v_kernel.cu:241, and more: its kernels
+    take anything).  Corner and size come to the library as host floats: reading a CUDA tensor here is a sync."""
+    for name, x in (("points", points), ("point_features", point_features)):
+        _check_input(x, name)
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise RuntimeError(f"{name} must be a 2-D float32 tensor")
+    if points.shape[1] != 3:
+        raise RuntimeError("points must be [P, 3]")
+    if point_features.shape[0] != points.shape[0] or point_features.shape[1] < 1:
+        raise RuntimeError("point_features must be [P, F] with the rows of points and F >= 1")
+    if point_features.device != points.device:
+        raise RuntimeError("points and point_features must be on the same device")
+    geo = []
+    for name, v in (("volume_corner", volume_corner), ("volume_size", volume_size)):
+        if isinstance(v, torch.Tensor):
+            if v.is_floating_point() is False or v.numel() != 3:
+                raise RuntimeError(f"{name} must hold 3 floating-point numbers")
+            v = v.detach().reshape(3).to("cpu", torch.float32).tolist()
+        else:
+            v = [float(c) for c in v]
+            if len(v) != 3:
+                raise RuntimeError(f"{name} must hold 3 numbers")
+        geo.append((ctypes.c_float * 3)(*v))
+    return geo[0], geo[1], int(n_voxels), float(kernel_radius), float(conv_radius)
+
+
+def p2v_order(points: torch.Tensor, point_features: torch.Tensor, volume_corner, volume_size, n_voxels: int,
+              kernel_radius: float, conv_radius: float):
+    """p2v and the permutation its sort put the points in (int32 [P]; p2v_backward walks the points in that order)."""
+    corner, size, n, kr, cr = _p2v_args(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius,
+                                        conv_radius)
+    dev = points.device
+    P, F = points.shape[0], point_features.shape[1]
+    nbytes = _lib.svoxt_p2v_workspace_bytes(P, n, corner, size, cr)
+    if nbytes < 0:                                 # the library names what is wrong, before it touches the GPU
+        _call("svoxt_p2v_fwd", None, None, P, F, corner, size, n, kr, cr, None, None, None, 0, None)
+    with _on(dev):
+        voxels = torch.empty((n, n, n, 1), dtype=torch.float32, device=dev)
+        order = torch.empty((P,), dtype=torch.int32, device=dev)
+        ws = torch.empty((nbytes if P > 0 else 0,), dtype=torch.uint8, device=dev)
+        _call("svoxt_p2v_fwd", _ptr(points), _ptr(point_features), P, F, corner, size, n, kr, cr, _ptr(voxels),
+              _ptr(order), _ptr(ws), nbytes, _stream(dev))
+    return voxels, order
+
+
+def p2v(points: torch.Tensor, point_features: torch.Tensor, volume_corner, volume_size, n_voxels: int,
+        kernel_radius: float, conv_radius: float) -> torch.Tensor:
+    """p2v_kernel.cu:240-261: the Gaussian splat of point_features[:, F-1] into a float32 [n, n, n, 1] volume.
+
+    Same (point, voxel) pairs as the reference; unlike it the result is bit-identical from run to run, non-finite
+    points contribute nothing, inputs are float32 only and bad arguments raise RuntimeError."""
+    return p2v_order(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius, conv_radius)[0]
+
+
+def p2v_backward(grad_output: torch.Tensor, points: torch.Tensor, point_features: torch.Tensor, volume_corner,
+                 volume_size, n_voxels: int, kernel_radius: float, conv_radius: float, order=None,
+                 need_points_grad: bool = True, need_features_grad: bool = True):
+    """p2v_kernel.cu:263-285.  Returns [points_grad [P, 3], point_features_grad [P, F]] (None for one not asked for).
+
+    The reference writes the feature gradient to column 0 although the forward reads column F-1 (:203 vs :147);
+    here column F-1 gets it and the other columns are 0 -- for F = 1 the two agree.  No atomics: each element is
+    written once, the sums per point in the reference's order.  `order`: the forward's permutation (speed only)."""
+    corner, size, n, kr, cr = _p2v_args(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius,
+                                        conv_radius)
+    if not isinstance(grad_output, torch.Tensor):
+        raise RuntimeError("grad_output must be a tensor")
+    grad_output = grad_output.contiguous()         # autograd hands sum().backward() an expanded, stride-0 gradient
+    _check_input(grad_output, "grad_output")
+    if grad_output.dtype != torch.float32 or tuple(grad_output.shape) != (n, n, n, 1):
+        raise RuntimeError(f"grad_output must be float32 [{n}, {n}, {n}, 1]")
+    if grad_output.device != points.device:
+        raise RuntimeError("grad_output must be on the points' device")
+    if order is not None and (order.dtype != torch.int32 or order.shape != (points.shape[0],) or order.device != points.device):
+        raise RuntimeError("order must be the forward's int32 [P] permutation")
+    dev = points.device
+    P, F = points.shape[0], point_features.shape[1]
+    with _on(dev):
+        pg = torch.empty((P, 3), dtype=torch.float32, device=dev) if need_points_grad else None
+        fg = torch.empty((P, F), dtype=torch.float32, device=dev) if need_features_grad else None
+        _call("svoxt_p2v_bwd", _ptr(grad_output), _ptr(points), _ptr(point_features), P, F, corner, size, n, kr, cr,
+              _ptr(order), _ptr(pg), _ptr(fg), _stream(dev))
+    return [pg, fg]
+
+
 # ---------------------------------------------------------------------------
 # Entry points of svox_t.csrc that are outside this project's hot path
 # (SURVEY.md section 2).  They exist so a caller gets a clear error, not an
@@ -354,6 +439,5 @@ def _out_of_scope(name):
     return fn
 
 
-for _n in ("assign_vertical", "p2v", "p2v_backward",
-           "calc_corners", "grid_weight_render", "quantize_median_cut"):
+for _n in ("assign_vertical", "calc_corners", "grid_weight_render", "quantize_median_cut"):
     globals()[_n] = _out_of_scope(_n)

@@ -25,4 +25,9 @@ TreeDev to_dev(const svoxt_tree* t);
 RaysDev to_dev(const svoxt_rays* r, const svoxt_tree* t, const svoxt_sample_lists* l = nullptr);
 Opts to_dev(const svoxt_options* o);
 
+// Exclusive scan of n uint32 counters into starts (not in place), two launches on `st` (svoxt_order.hip);
+// chunk_sums holds exclusive_scan_chunks(n) words.  Returns SVOXT_OK / SVOXT_ERR_HIP.
+size_t exclusive_scan_chunks(size_t n);
+int exclusive_scan(const uint32_t* counts, size_t n, uint32_t* chunk_sums, uint32_t* starts, hipStream_t st, const char* fn);
+
 }  // namespace svoxt

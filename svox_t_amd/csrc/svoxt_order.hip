@@ -270,6 +270,17 @@ image_probe_merge_kernel(int32_t* __restrict__ res, int32_t ticket) {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// the scan above for other callers (svoxt_p2v.hip): no second copy of its kernels in the library
+size_t exclusive_scan_chunks(size_t n) { return (n + kScanChunk - 1) / kScanChunk; }
+
+int exclusive_scan(const uint32_t* counts, size_t n, uint32_t* chunk_sums, uint32_t* starts, hipStream_t st, const char* fn) {
+    const unsigned chunks = (unsigned)exclusive_scan_chunks(n);
+    if (chunks == 0) return SVOXT_OK;
+    hipLaunchKernelGGL(scan_chunk_sums_kernel, dim3(chunks), dim3(kScanThreads), 0, st, counts, n, chunk_sums);
+    hipLaunchKernelGGL(scan_chunks_kernel, dim3(chunks), dim3(kScanThreads), 0, st, counts, n, chunk_sums, starts);
+    return check_launch(fn);
+}
+
 }  // namespace svoxt
 
 using namespace svoxt;
