@@ -26,272 +26,171 @@ bool launch_bwd_xform(const TreeDev& tr, const RaysDev& rays, const Opts& opt, i
                       const float* grad_out, float* grad, int gstride, RecLists L, const uint4* aux,
                       const float* fwd_out, hipStream_t st) {
     if (opt.format != FMT_SH || C != 3) return false;
-    const unsigned nb = nblocks(rays.Q);
-#define SVOXT_BWD_XF(BB)                                                                                      \
-    hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, REPLAY, true>), dim3(nb), dim3(kBlock), 0, st, \
-                       tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out);                         \
-    return true;
-    switch (opt.basis_dim) {
-        case 1: SVOXT_BWD_XF(1)
-        case 4: SVOXT_BWD_XF(4)
-        case 9: SVOXT_BWD_XF(9)
-        case 16: SVOXT_BWD_XF(16)
-        case 25: SVOXT_BWD_XF(25)
-    }
-#undef SVOXT_BWD_XF
-    return false;
+    return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+        hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, REPLAY, true>), dim3(nblocks(rays.Q)), dim3(kBlock), 0, st,
+                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out);
+        return true;
+    });
 }
 
 bool launch_lobes_bwd_tiles(const TreeDev& tr, const RaysDev& rays, const Opts& opt, const float* grad_out, float* grad,
                             int gstride, RecLists L, const uint4* aux, hipStream_t st, int terms_state) {
     if (L.terms == nullptr || terms_state != 3 || !lobes_payload(opt, tr.K) || g_bwd_counters != nullptr) return false;
     const unsigned nb = nblocks(rays.Q);
-#define SVOXT_LOBES_BWD(BB)                                                                                         \
-    {                                                                                                               \
-        hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, false, true, false, true>), dim3(nb), dim3(kBlock), \
-                           0, st, tr, rays, opt, grad_out, grad, gstride, L, aux, (const float*)nullptr, (float4*)nullptr); \
-        hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 3, true>), dim3(nb), dim3(512), 0, st,       \
-                           tr, rays, opt, grad_out, L, aux, (const float*)nullptr, grad, gstride);                  \
-        return true;                                                                                                \
-    }
-    switch (opt.basis_dim) {
-        case 1: SVOXT_LOBES_BWD(1)
-        case 4: SVOXT_LOBES_BWD(4)
-        case 9: SVOXT_LOBES_BWD(9)
-        case 16: SVOXT_LOBES_BWD(16)
-        case 25: SVOXT_LOBES_BWD(25)
-    }
-#undef SVOXT_LOBES_BWD
-    return false;
+    return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+        hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, false, true, false, true>), dim3(nb), dim3(kBlock), 0, st,
+                           tr, rays, opt, grad_out, grad, gstride, L, aux, nullptr, nullptr);
+        hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 3, true>), dim3(nb), dim3(512), 0, st,
+                           tr, rays, opt, grad_out, L, aux, nullptr, grad, gstride);
+        return true;
+    });
 }
 
-// two-kernel backward: SH 1/4/9 (also with view rotations) and RGBA with 3 channels
-// (K <= 32) on N = 2 trees
+// The grad_wide_kernel instance for rows of KK floats (nullptr: none -- a checked run of the fast-math form)
+template <int KK>
+auto wide_instance(bool check, bool count, bool native, bool etab) -> decltype(&grad_wide_kernel<KK>) {
+    if (check) return native ? nullptr : grad_wide_kernel<KK, false, false, true>;
+    if (count) return grad_wide_kernel<KK, false, true>;
+    if (native) return grad_wide_kernel<KK, true>;
+    return etab ? grad_wide_kernel<KK, false, false, false, true> : grad_wide_kernel<KK, false>;
+}
+
+// The grad_fused_kernel instance of the one-kernel per-tile backward (nullptr: none).  handover: the forward's
+// hand-over in L.terms, terms_state 2 (lane-major) or 3 (position-major); 0: none.
+template <int F, int BB>
+auto fused_instance(bool check, bool count, bool fwd_out, int handover) -> decltype(&grad_fused_kernel<F, BB, true>) {
+    if (check) {
+        // the checked instance of the route that would run: the default route (the forward's position-major
+        // hand-over) for every payload, the other routes for SH9
+        if (handover == 3 && !fwd_out) return grad_fused_kernel<F, BB, true, false, 3, false, true>;
+        if constexpr (F == FMT_SH && BB == 9) {
+            if (fwd_out) return grad_fused_kernel<F, BB, false, false, 0, false, true>;
+            return handover == 2 ? grad_fused_kernel<F, BB, true, false, 2, false, true>
+                                 : grad_fused_kernel<F, BB, true, false, 0, false, true>;
+        }
+        return nullptr;
+    }
+    if constexpr (BB > 9) {
+        // (SH16 / SH25: only over a hand-over, without counters -- see launch_bwd_gather)
+        return handover == 2 ? grad_fused_kernel<F, BB, true, false, 2> : grad_fused_kernel<F, BB, true, false, 3>;
+    } else {
+        if (count) return fwd_out ? grad_fused_kernel<F, BB, false, true> : grad_fused_kernel<F, BB, true, true>;
+        if (fwd_out) return grad_fused_kernel<F, BB, false>;
+        if (handover == 2) return grad_fused_kernel<F, BB, true, false, 2>;
+        if (handover == 3) return grad_fused_kernel<F, BB, true, false, 3>;
+        return grad_fused_kernel<F, BB, true>;     // (no hand-over from the forward: both sweeps gather the rows)
+    }
+}
+
+// The per-tile backward over sample lists on N = 2 trees: the two-kernel form (list walk into coef + grad_merge_kernel)
+// for SH 1/4/9 (also with view rotations) and RGBA with 3 channels (K <= 32), or the one-kernel form (grad_fused_kernel,
+// grad_wide_kernel) for those, for SH16 / SH25 and for RGBA-style rows of 8 / 16 / 32 floats
 bool launch_bwd_gather(const TreeDev& tr, const RaysDev& rays, const Opts& opt, int C,
                        const float* grad_out, float* grad, int gstride, RecLists L, const uint4* aux,
                        const float* fwd_out, float4* coef, bool xf, hipStream_t st, int terms_state = 0,
                        bool native = false) {
     const unsigned nb = nblocks(rays.Q);
+    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(g_bwd_counters);
+    unsigned long long* chkw = reinterpret_cast<unsigned long long*>(g_bwd_check);
+    unsigned long long* words = chkw != nullptr ? chkw : ctr;          // (for the checked / counting instances)
+    // The one-kernel per-tile forms launch the tails of overflowed rays first (a tail-only launch of the per-ray kernel);
+    // where no per-tile instance serves the call then, it returns false after that launch.
+    auto tails = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, nullptr);
+    };
     if (C > 3) {
         // RGBA-style rows of 8 / 16 / 32 floats: the exact per-tile form only (one kernel, a float per
         // list slot in L.terms); tails of overflowed rays first, as for the 3-channel fused kernel
-        if (opt.format != FMT_RGBA || coef != nullptr || xf || fwd_out != nullptr || L.terms == nullptr) return false;
-#define SVOXT_WIDE(KK)                                                                                        \
-    {                                                                                                         \
-        hipLaunchKernelGGL((render_bwd_kernel<FMT_RGBA, KK - 1, 0, true, true, false, true>), dim3(nb), dim3(kBlock), 0, st, \
-                           tr, rays, opt, grad_out, grad, gstride, L, aux, (const float*)nullptr, (float4*)nullptr); \
-        unsigned long long* ctr = reinterpret_cast<unsigned long long*>(g_bwd_counters);                      \
-        unsigned long long* chkw = reinterpret_cast<unsigned long long*>(g_bwd_check);                        \
-        if (chkw != nullptr && !native)                                                                       \
-            hipLaunchKernelGGL((grad_wide_kernel<KK, false, false, true>), dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, \
-                               grad, gstride, chkw);                                                          \
-        else if (chkw != nullptr)                                                                             \
-            return false;                                                                                     \
-        else if (ctr != nullptr)                                                                              \
-            hipLaunchKernelGGL((grad_wide_kernel<KK, false, true>), dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, \
-                               grad, gstride, ctr);                                                           \
-        else if (native)                                                                                      \
-            hipLaunchKernelGGL((grad_wide_kernel<KK, true>), dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, \
-                               grad, gstride, (unsigned long long*)nullptr);                                  \
-        else if (tr.etab != nullptr)                                                                          \
-            hipLaunchKernelGGL((grad_wide_kernel<KK, false, false, false, true>), dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, \
-                               grad, gstride, (unsigned long long*)nullptr);                                  \
-        else                                                                                                  \
-            hipLaunchKernelGGL((grad_wide_kernel<KK, false>), dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, \
-                               grad, gstride, (unsigned long long*)nullptr);                                  \
-        return true;                                                                                          \
-    }
-        if (C == 7 && tr.K == 8) SVOXT_WIDE(8)
-        if (C == 15 && tr.K == 16) SVOXT_WIDE(16)
-        if (C == 31 && tr.K == 32) SVOXT_WIDE(32)
-#undef SVOXT_WIDE
-        return false;
+        if (opt.format != FMT_RGBA || coef != nullptr || xf || fwd_out != nullptr || L.terms == nullptr || C + 1 != tr.K)
+            return false;
+        return with_int(ChanRows{}, tr.K, [&](auto KK) {
+            tails(render_bwd_kernel<FMT_RGBA, KK - 1, 0, true, true, false, true>);
+            const auto k = wide_instance<KK>(chkw != nullptr, ctr != nullptr, native, tr.etab != nullptr);
+            if (k == nullptr) return false;
+            hipLaunchKernelGGL(k, dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, grad, gstride, words);
+            return true;
+        });
     }
     if (C != 3) return false;
     // a caller that hands over a coef buffer asks for the two-kernel form; without one (coef_bytes < 0)
     // the per-tile route runs if it can run as ONE kernel.  (The choice is the caller's alone: the
-    // Python layer reads SVOXT_BWD_FUSED, the library reads no environment for this.)
+    // library reads no environment for it.)
     const bool fused = coef == nullptr;
-    if (fused && xf && (fwd_out != nullptr || opt.format != FMT_SH || opt.basis_dim > 9)) return false;   // (the exact one-kernel form only)
-    // four wavefronts per tile and tables of 1024 (measured: one wavefront per tile 0.41 ms,
-    // two 0.33, four 0.30 before step 15; tables of 512 / 256 cost more passes than they buy)
-#define SVOXT_GATHER(F, BB)                                                                                   \
-    if (fused) {   /* tails of overflowed rays (a tail-only launch), then list walk and merge in one kernel */ \
-        hipLaunchKernelGGL((render_bwd_kernel<F, 3, BB, true, true, false, true>), dim3(nb), dim3(kBlock), 0, st, \
-                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, (float4*)nullptr);   \
-        unsigned long long* ctr = reinterpret_cast<unsigned long long*>(g_bwd_counters);                      \
-        unsigned long long* chkw = reinterpret_cast<unsigned long long*>(g_bwd_check);                        \
-        if (chkw != nullptr) {   /* the checked instance of the route that would run: the default route (the forward's      \
-                                    position-major hand-over) for every payload, the other routes for SH9 */  \
-            if (L.terms != nullptr && terms_state == 3 && fwd_out == nullptr)                                 \
-                hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, false, 3, false, true>), dim3(nb), dim3(512), 0, st, \
-                                   tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, chkw);            \
-            else if constexpr (F == FMT_SH && BB == 9) {                                                      \
-                if (fwd_out != nullptr)                                                                       \
-                    hipLaunchKernelGGL((grad_fused_kernel<F, BB, false, false, 0, false, true>), dim3(nb), dim3(512), 0, st, \
-                                       tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, chkw);        \
-                else if (L.terms != nullptr && terms_state == 2)                                              \
-                    hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, false, 2, false, true>), dim3(nb), dim3(512), 0, st, \
-                                       tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, chkw);        \
-                else                                                                                          \
-                    hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, false, 0, false, true>), dim3(nb), dim3(512), 0, st, \
-                                       tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, chkw); \
-            } else return false;                                                                              \
-            return true;                                                                                      \
-        }                                                                                                     \
-        if (fwd_out != nullptr && ctr == nullptr)                                                             \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, false>), dim3(nb), dim3(512), 0, st,                 \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                 \
-        else if (ctr == nullptr && L.terms != nullptr && terms_state == 2)                                    \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, false, 2>), dim3(nb), dim3(512), 0, st,        \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                      \
-        else if (ctr == nullptr && L.terms != nullptr && terms_state == 3)                                    \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, false, 3>), dim3(nb), dim3(512), 0, st,        \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                      \
-        else if (ctr == nullptr)   /* (no hand-over from the forward: both sweeps gather the rows) */         \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, true>), dim3(nb), dim3(512), 0, st,                  \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                 \
-        else if (fwd_out != nullptr)                                                                          \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, false, true>), dim3(nb), dim3(512), 0, st,           \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, ctr);            \
-        else                                                                                                  \
-            hipLaunchKernelGGL((grad_fused_kernel<F, BB, true, true>), dim3(nb), dim3(512), 0, st,            \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, ctr);            \
-        return true;                                                                                          \
-    }                                                                                                         \
-    hipLaunchKernelGGL((render_bwd_kernel<F, 3, BB, true, true, false, true>), dim3(nb), dim3(kBlock), 0, st, \
-                       tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, coef);                   \
-    hipLaunchKernelGGL((grad_merge_kernel<F, BB, 1024, 1024, 4>), dim3(nb), dim3(256), 0, st, tr, rays,      \
-                       grad_out, L, coef, aux, grad, gstride);                                                \
-    return true;
-#define SVOXT_GATHER_XF(BB)                                                                                       \
-    hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, true, true>), dim3(nb), dim3(kBlock), 0, st, \
-                       tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, coef);                       \
-    hipLaunchKernelGGL((grad_merge_kernel<FMT_SH, BB, 1024, 512, 4, true>), dim3(nb), dim3(256), 0, st, tr, rays, \
-                       grad_out, L, coef, aux, grad, gstride);                                                    \
-    return true;
-    // (r04) view rotations as ONE kernel: the rays whose list overflowed whole by the per-ray kernel, every other ray by
-    // grad_fused_kernel<..., XF> (no checked / counting instance: svoxt_set_bwd_check and _counters do not see this route)
-#define SVOXT_FUSED_XF(BB)                                                                                        \
-    {                                                                                                             \
-        hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, true>), dim3(nb), dim3(kBlock), 0, st,   \
-                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, reinterpret_cast<float4*>(kOnlyOverflowed)); \
-        if (L.terms != nullptr && terms_state == 3)   /* the forward's hand-over: exponentials of each record's own basis */ \
-            hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 3, false, false, true>), dim3(nb), dim3(512), 0, st, \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                          \
-        else                                                                                                      \
-            hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 0, false, false, true>), dim3(nb), dim3(512), 0, st, \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                          \
-        return true;                                                                                              \
-    }
+    // the two-kernel form: list walk (coefficients into coef), then merge.  Four wavefronts per tile and tables of
+    // 1024 (measured: one wavefront per tile 0.41 ms, two 0.33, four 0.30 before step 15; tables of 512 / 256 cost
+    // more passes than they buy)
+    auto two_kernels = [&](auto F, auto BB, auto XF) {
+        hipLaunchKernelGGL((render_bwd_kernel<F, 3, BB, true, true, XF, true>), dim3(nb), dim3(kBlock), 0, st,
+                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, coef);
+        hipLaunchKernelGGL((grad_merge_kernel<F, BB, 1024, XF ? 512 : 1024, 4, XF>), dim3(nb), dim3(256), 0, st,
+                           tr, rays, grad_out, L, coef, aux, grad, gstride);
+        return true;
+    };
+    // the one-kernel form: tails, then list walk and merge in one kernel
+    auto one_kernel = [&](auto F, auto BB) {
+        tails(render_bwd_kernel<F, 3, BB, true, true, false, true>);
+        const int handover = L.terms != nullptr && (terms_state == 2 || terms_state == 3) ? terms_state : 0;
+        const auto k = fused_instance<F, BB>(chkw != nullptr, ctr != nullptr, fwd_out != nullptr, handover);
+        if (k == nullptr) return false;
+        hipLaunchKernelGGL(k, dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, words);
+        return true;
+    };
     if (xf) {
-        if (opt.format != FMT_SH) return false;
-        if (fused) {
-            switch (opt.basis_dim) {
-                case 1: SVOXT_FUSED_XF(1)
-                case 4: SVOXT_FUSED_XF(4)
-                case 9: SVOXT_FUSED_XF(9)
-            }
-            return false;
-        }
-        switch (opt.basis_dim) {
-            case 1: SVOXT_GATHER_XF(1)
-            case 4: SVOXT_GATHER_XF(4)
-            case 9: SVOXT_GATHER_XF(9)
-        }
-        return false;
+        if (opt.format != FMT_SH || (fused && fwd_out != nullptr)) return false;   // (the exact one-kernel form only)
+        return with_int(XfRolesBases{}, opt.basis_dim, [&](auto BB) {
+            if (!fused) return two_kernels(Int<FMT_SH>{}, BB, std::true_type{});
+            // (r04) view rotations as ONE kernel: the rays whose list overflowed whole by the per-ray kernel, every other
+            // ray by grad_fused_kernel<..., XF> (no checked / counting instance: svoxt_set_bwd_check and _counters do not
+            // see this route); over the forward's hand-over (exponentials of each record's own basis) where it left one
+            hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, true>), dim3(nb), dim3(kBlock), 0, st,
+                               tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, reinterpret_cast<float4*>(kOnlyOverflowed));
+            const auto k = L.terms != nullptr && terms_state == 3 ? grad_fused_kernel<FMT_SH, BB, true, false, 3, false, false, true>
+                                                                  : grad_fused_kernel<FMT_SH, BB, true, false, 0, false, false, true>;
+            hipLaunchKernelGGL(k, dim3(nb), dim3(512), 0, st, tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, nullptr);
+            return true;
+        });
     }
-#undef SVOXT_FUSED_XF
-    if (opt.format == FMT_RGBA) { SVOXT_GATHER(FMT_RGBA, 0) }
-    // SH16 / SH25 (rows of 49 / 76 floats, r03): the one-kernel per-tile form only, and only over the hand-over a
-    // recording forward left (terms_state 2 / 3): the kernel then never holds a feature row
-#define SVOXT_GATHER_WIDE(BB)                                                                                 \
-    {                                                                                                         \
-        if (!fused || g_bwd_counters != nullptr || fwd_out != nullptr || L.terms == nullptr ||                \
-            (terms_state != 2 && terms_state != 3)) return false;                                             \
-        hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, true, true, false, true>), dim3(nb), dim3(kBlock), 0, st, \
-                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, (float4*)nullptr);        \
-        unsigned long long* chkw = reinterpret_cast<unsigned long long*>(g_bwd_check);                        \
-        if (chkw != nullptr && terms_state == 2)                                                              \
-            return false;                                                                                     \
-        else if (chkw != nullptr)                                                                             \
-            hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 3, false, true>), dim3(nb), dim3(512), 0, st, \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride, chkw);                \
-        else if (terms_state == 2)                                                                            \
-            hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 2>), dim3(nb), dim3(512), 0, st,   \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                      \
-        else                                                                                                  \
-            hipLaunchKernelGGL((grad_fused_kernel<FMT_SH, BB, true, false, 3>), dim3(nb), dim3(512), 0, st,   \
-                               tr, rays, opt, grad_out, L, aux, fwd_out, grad, gstride);                      \
-        return true;                                                                                          \
-    }
-    if (opt.format == FMT_SH) {
-        switch (opt.basis_dim) {
-            case 1: SVOXT_GATHER(FMT_SH, 1)
-            case 4: SVOXT_GATHER(FMT_SH, 4)
-            case 9: SVOXT_GATHER(FMT_SH, 9)
-            case 16: SVOXT_GATHER_WIDE(16)
-            case 25: SVOXT_GATHER_WIDE(25)
+    if (opt.format == FMT_RGBA)
+        return fused ? one_kernel(Int<FMT_RGBA>{}, Int<0>{}) : two_kernels(Int<FMT_RGBA>{}, Int<0>{}, std::false_type{});
+    if (opt.format != FMT_SH) return false;
+    return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+        if constexpr (BB > 9) {
+            // SH16 / SH25 (rows of 49 / 76 floats, r03): the one-kernel per-tile form only, and only over the hand-over a
+            // recording forward left (terms_state 2 / 3): the kernel then never holds a feature row
+            if (!fused || ctr != nullptr || fwd_out != nullptr || L.terms == nullptr || (terms_state != 2 && terms_state != 3))
+                return false;
+            return one_kernel(Int<FMT_SH>{}, BB);
+        } else {
+            return fused ? one_kernel(Int<FMT_SH>{}, BB) : two_kernels(Int<FMT_SH>{}, BB, std::false_type{});
         }
-    }
-#undef SVOXT_GATHER_WIDE
-#undef SVOXT_GATHER
-#undef SVOXT_GATHER_XF
-    return false;
+    });
 }
 
 template <bool N2, bool REPLAY>
 bool launch_bwd_special(const TreeDev& tr, const RaysDev& rays, const Opts& opt, int C,
                         const float* grad_out, float* grad, int gstride, RecLists L, const uint4* aux,
                         const float* fwd_out, hipStream_t st) {
-    const unsigned nb = nblocks(rays.Q);
-#define SVOXT_BWD(F, CC, BB)                                                                      \
-    hipLaunchKernelGGL((render_bwd_kernel<F, CC, BB, N2, REPLAY>), dim3(nb), dim3(kBlock), 0, st, \
-                       tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out);             \
-    return true;
-#define SVOXT_BWD1(CC)                                                                                          \
-    hipLaunchKernelGGL((render_bwd_kernel<FMT_RGBA, CC, 0, N2, true, false, false, true>), dim3(nb), dim3(kBlock), \
-                       0, st, tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out);                         \
-    return true;
-    if (opt.format == FMT_RGBA) {
-        if (C == 3) { SVOXT_BWD(FMT_RGBA, 3, 0) }
-        if constexpr (REPLAY) {
-            // lists + a float per slot + the exact form asked for: one sigmoid pass instead of two
-            if (L.terms != nullptr && fwd_out == nullptr) {
-                if (C == 7) { SVOXT_BWD1(7) }
-                if (C == 15) { SVOXT_BWD1(15) }
-                if (C == 31) { SVOXT_BWD1(31) }
+    auto bwd = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(rays.Q)), dim3(kBlock), 0, st,
+                           tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out, nullptr);
+        return true;
+    };
+    if (opt.format == FMT_RGBA)
+        return with_int(RgbaWidths{}, C, [&](auto CC) {
+            if constexpr (REPLAY && CC > 3) {
+                // lists + a float per slot + the exact form asked for: one sigmoid pass instead of two
+                if (L.terms != nullptr && fwd_out == nullptr) return bwd(render_bwd_kernel<FMT_RGBA, CC, 0, N2, true, false, false, true>);
             }
-        }
-        if (C == 7) { SVOXT_BWD(FMT_RGBA, 7, 0) }
-        if (C == 15) { SVOXT_BWD(FMT_RGBA, 15, 0) }
-        if (C == 31) { SVOXT_BWD(FMT_RGBA, 31, 0) }
-    } else if (opt.format == FMT_SH && C == 3) {
-        switch (opt.basis_dim) {
-            case 1: SVOXT_BWD(FMT_SH, 3, 1)
-            case 4: SVOXT_BWD(FMT_SH, 3, 4)
-            case 9: SVOXT_BWD(FMT_SH, 3, 9)
-            case 16: SVOXT_BWD(FMT_SH, 3, 16)
-            case 25: SVOXT_BWD(FMT_SH, 3, 25)
-        }
-    } else if constexpr (!REPLAY) {
-#define SVOXT_BWD_LOBES(BB)                                                                                        \
-    hipLaunchKernelGGL((render_bwd_kernel<FMT_SH, 3, BB, N2, false, false, false, false, true>), dim3(nb), dim3(kBlock), \
-                       0, st, tr, rays, opt, grad_out, grad, gstride, L, aux, fwd_out);                            \
-    return true;
-        if ((opt.format == FMT_SG || opt.format == FMT_ASG) && C == 3 && tr.K == 3 * opt.basis_dim + 1) {
-            switch (opt.basis_dim) {
-                case 1: SVOXT_BWD_LOBES(1)
-                case 4: SVOXT_BWD_LOBES(4)
-                case 9: SVOXT_BWD_LOBES(9)
-                case 16: SVOXT_BWD_LOBES(16)
-                case 25: SVOXT_BWD_LOBES(25)
-            }
-        }
-#undef SVOXT_BWD_LOBES
+            return bwd(render_bwd_kernel<FMT_RGBA, CC, 0, N2, REPLAY>);
+        });
+    if (opt.format == FMT_SH)
+        return C == 3 && with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) { return bwd(render_bwd_kernel<FMT_SH, 3, BB, N2, REPLAY>); });
+    if constexpr (!REPLAY) {
+        if (C == 3 && lobes_payload(opt, tr.K))
+            return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+                return bwd(render_bwd_kernel<FMT_SH, 3, BB, N2, false, false, false, false, true>);
+            });
     }
-#undef SVOXT_BWD
-#undef SVOXT_BWD1
     return false;
 }
 
@@ -380,12 +279,15 @@ int bwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_optio
                                          fwd_out, have_coef ? reinterpret_cast<float4*>(lists->coef) : nullptr, false, st,
                                          (lists->terms_state == 2 || lists->terms_state == 3) ? lists->terms_state : 1,
                                          (lists->flags & SVOXT_LISTS_NATIVE_MATH) != 0);
-            if (!done) done = n2 ? launch_bwd_special<true, true>(tr, rd, od, C, grad_out, grad_features, gs, l1, laux, fwd_out, st)
-                      : launch_bwd_special<false, true>(tr, rd, od, C, grad_out, grad_features, gs, l1, laux, fwd_out, st);
+            if (!done)
+                done = with_bool(n2, [&](auto N2) {
+                    return launch_bwd_special<N2, true>(tr, rd, od, C, grad_out, grad_features, gs, l1, laux, fwd_out, st);
+                });
             if (!done) return fail(SVOXT_ERR_UNSUPPORTED, "%s: no specialised kernel for this payload", fn);
         } else {
-            done = n2 ? launch_bwd_special<true, false>(tr, rd, od, C, grad_out, grad_features, gs, wl, nullptr, nullptr, st)
-                      : launch_bwd_special<false, false>(tr, rd, od, C, grad_out, grad_features, gs, wl, nullptr, nullptr, st);
+            done = with_bool(n2, [&](auto N2) {
+                return launch_bwd_special<N2, false>(tr, rd, od, C, grad_out, grad_features, gs, wl, nullptr, nullptr, st);
+            });
         }
     } else if (lists != nullptr) {
         return fail(SVOXT_ERR_UNSUPPORTED, "%s: sample lists need a specialised payload", fn);
@@ -393,14 +295,12 @@ int bwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_optio
     if (!done) {
         const unsigned nb = nblocks(rays->Q);
         const size_t lds = (size_t)(kBlock / 64) * 64 * (tree->K | 1) * sizeof(float) + kBlock * sizeof(int32_t);
-        if (C > 0 && lds <= 65536) {      // shaped atomics through LDS staging (default dynamic-LDS limit: 64 KiB)
-            if (n2) hipLaunchKernelGGL((render_bwd_generic_staged_kernel<true>), dim3(nb), dim3(kBlock), lds, st, tr, rd, od, C, grad_out, grad_features, gs);
-            else hipLaunchKernelGGL((render_bwd_generic_staged_kernel<false>), dim3(nb), dim3(kBlock), lds, st, tr, rd, od, C, grad_out, grad_features, gs);
-        } else {
-            // C == 0 (opacity: one value per sample, nothing to shape) or rows too wide to stage
-            if (n2) hipLaunchKernelGGL((render_bwd_generic_kernel<true>), dim3(nb), dim3(kBlock), 0, st, tr, rd, od, C, grad_out, grad_features, gs);
-            else hipLaunchKernelGGL((render_bwd_generic_kernel<false>), dim3(nb), dim3(kBlock), 0, st, tr, rd, od, C, grad_out, grad_features, gs);
-        }
+        // shaped atomics through LDS staging (default dynamic-LDS limit: 64 KiB); unstaged for C == 0 (opacity: one value
+        // per sample, nothing to shape) or rows too wide to stage
+        const bool staged = C > 0 && lds <= 65536;
+        const auto k = staged ? (n2 ? render_bwd_generic_staged_kernel<true> : render_bwd_generic_staged_kernel<false>)
+                              : (n2 ? render_bwd_generic_kernel<true> : render_bwd_generic_kernel<false>);
+        hipLaunchKernelGGL(k, dim3(nb), dim3(kBlock), staged ? lds : 0, st, tr, rd, od, C, grad_out, grad_features, gs);
     }
     return check_launch(fn);
 }

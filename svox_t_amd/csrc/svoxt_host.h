@@ -2,10 +2,44 @@
 // libsvoxt_hip.so (not part of the public C ABI).
 #pragma once
 
+#include <type_traits>
+
 #include "../../include/svoxt.h"
 #include "svoxt_device.h"
 
 namespace svoxt {
+
+// A set of compile-time ints: the payload sizes below, and the instances a launch dispatches over.
+template <int... Vs>
+struct IntSet {
+    static constexpr bool has(int v) { return ((v == Vs) || ...); }
+};
+
+// Compile-time dispatch of the launches.  with_int(IntSet<Vs...>{}, v, f) calls f(std::integral_constant<int, V>{}) for
+// the V among Vs equal to v and returns its result, or false where none is: the instances are exactly f's for Vs.
+// with_bool(b, f) calls f(std::true_type{}) or f(std::false_type{}) and returns its result.
+template <int... Vs, class F>
+bool with_int(IntSet<Vs...>, int v, F&& f) {
+    bool r = false;
+    (void)((v == Vs && (r = f(std::integral_constant<int, Vs>{}), true)) || ...);
+    return r;
+}
+template <class F>
+auto with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int V>
+using Int = std::integral_constant<int, V>;     // a compile-time int argument of a dispatch lambda, e.g. Int<FMT_SH>{}
+
+// The payload sizes with specialised kernels: SH bases of degree 0 .. 4 (and as many SG / ASG lobes), RGBA-style rows of
+// 8 / 16 / 32 floats (channels on lanes, the exponentials table), and the SH bases whose view-rotation forms run as one
+// launch (fwd_roles_kernel<..., XF>, grad_fused_kernel<..., XF>).
+using SpecialBases = IntSet<1, 4, 9, 16, 25>;
+using ChanRows = IntSet<8, 16, 32>;
+using XfRolesBases = IntSet<1, 4, 9>;
+inline bool special_basis(int basis_dim) { return SpecialBases::has(basis_dim); }
+inline bool chan_rows(int K) { return ChanRows::has(K); }
+inline bool xf_roles_basis(int basis_dim) { return XfRolesBases::has(basis_dim); }
 
 // Records the text svoxt_last_error() returns on this thread and hands back `code`.
 int set_error(int code, const char* fmt, const char* a = "", const char* b = "");

@@ -114,8 +114,7 @@ int check_opts(const svoxt_options* o, const svoxt_tree* t, const char* fn, bool
     if (!needs_basis || o->format == SVOXT_FORMAT_RGBA) return SVOXT_OK;
     if (o->basis_dim < 1 || o->basis_dim > 25)
         return fail(SVOXT_ERR_INVALID, "%s: basis_dim must be in [1, 25]", fn);
-    if (o->format == SVOXT_FORMAT_SH && o->basis_dim != 1 && o->basis_dim != 4 && o->basis_dim != 9 &&
-        o->basis_dim != 16 && o->basis_dim != 25)
+    if (o->format == SVOXT_FORMAT_SH && !special_basis(o->basis_dim))
         return fail(SVOXT_ERR_INVALID, "%s: SH basis_dim must be 1, 4, 9, 16 or 25", fn);
     if (o->min_comp < 0 || o->max_comp >= o->basis_dim)
         return fail(SVOXT_ERR_INVALID, "%s: min_comp / max_comp outside [0, basis_dim)", fn);
@@ -140,7 +139,7 @@ TreeDev to_dev(const svoxt_tree* t) {
     d.accel_g = use_accel ? (t->accel_log2 & ~SVOXT_ACCEL_BRICKS) : 0;
     d.accel_bricks = use_accel && (t->accel_log2 & SVOXT_ACCEL_BRICKS) != 0;
     // the exponentials table serves RGBA-style rows of 8 / 16 / 32 floats only
-    d.etab = (t->exp_table != nullptr && (t->K == 8 || t->K == 16 || t->K == 32)) ? t->exp_table : nullptr;
+    d.etab = (t->exp_table != nullptr && chan_rows(t->K)) ? t->exp_table : nullptr;
     return d;
 }
 
@@ -183,26 +182,16 @@ Opts to_dev(const svoxt_options* o) {
 
 namespace {
 
-
 // specialised kernels with per-leaf view rotations: SH payloads on N = 2 trees
 template <bool REC>
 bool launch_fwd_xform(const TreeDev& tr, const RaysDev& rays, const Opts& opt, int C, float* out,
                       RecLists L, uint4* aux, hipStream_t st) {
     if (opt.format != FMT_SH || C != 3) return false;
-    const unsigned nb = nblocks(rays.Q);
-#define SVOXT_FWD_XF(BB)                                                                                    \
-    hipLaunchKernelGGL((render_fwd_kernel<FMT_SH, 3, BB, true, REC, true>), dim3(nb), dim3(kBlock), 0, st,  \
-                       tr, rays, opt, out, L, aux);                                                    \
-    return true;
-    switch (opt.basis_dim) {
-        case 1: SVOXT_FWD_XF(1)
-        case 4: SVOXT_FWD_XF(4)
-        case 9: SVOXT_FWD_XF(9)
-        case 16: SVOXT_FWD_XF(16)
-        case 25: SVOXT_FWD_XF(25)
-    }
-#undef SVOXT_FWD_XF
-    return false;
+    return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+        hipLaunchKernelGGL((render_fwd_kernel<FMT_SH, 3, BB, true, REC, true>), dim3(nblocks(rays.Q)), dim3(kBlock), 0, st,
+                           tr, rays, opt, out, L, aux);
+        return true;
+    });
 }
 
 #ifndef SVOXT_ROLES_BAND_ROWS
@@ -235,104 +224,76 @@ inline RolesLaunch roles_launch(unsigned nb, int tiles_per_row) {
     return r;
 }
 
+// March and shade as ONE launch (an instance of fwd_roles_kernel), then the fallback shade of what that launch left
+// unshaded + the tails of overflowed rays: one small launch (the matching instance of fwd_finish_kernel).
+template <class Roles, class Finish>
+bool launch_roles(Roles roles, Finish finish, const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out,
+                  RecLists L, uint4* aux, hipStream_t st, const uint32_t* sigma_mask, int32_t* tile_state, int tflags) {
+    const unsigned nb = nblocks(rays.Q);
+    // n_march: a multiple of 8 (see fwd_roles_kernel); grid: + the shading workgroups (the active ones: one per tile)
+    const RolesLaunch rl = roles_launch(nb, rays.tiles_per_row);
+    hipLaunchKernelGGL(roles, dim3(rl.grid), dim3(512), 0, st, tr, rays, opt, L, aux, out, sigma_mask, tile_state,
+                       rl.n_march, (int)nb, tflags, rl.map);
+    hipLaunchKernelGGL(finish, dim3(finish_grid(nb)), dim3(512), 0, st, tr, rays, opt, L, aux, out, tile_state, (int)nb);
+    return true;
+}
+
+// march_rec_kernel: through the acceleration grid where the tree has one, over the sigma bitmask where one is at hand
+// and no stop rule applies while marching
+template <bool N2, bool STOP>
+void launch_march(const TreeDev& tr, const RaysDev& rays, const Opts& opt, RecLists L, uint4* aux,
+                  const uint32_t* sigma_mask, hipStream_t st) {
+    const bool acc = N2 && tr.accel != nullptr;
+    const bool mask = !STOP && sigma_mask != nullptr;
+    const auto march = mask ? (acc ? march_rec_kernel<N2, false, 1, true> : march_rec_kernel<N2, false, 0, true>)
+                            : (acc ? march_rec_kernel<N2, STOP, 1> : march_rec_kernel<N2, STOP, 0>);
+    hipLaunchKernelGGL(march, dim3(nblocks(rays.Q)), dim3(kBlock), 0, st, tr, rays, opt, L, aux,
+                       mask ? sigma_mask : nullptr);
+}
+
 // ... with sample lists: the recording forward as march + tile shade + tail launch, leaving the backward's hand-over
 // (position-major: terms_state 3), and the per-tile backward over it -- the exact one-kernel form only.
 template <bool N2>
 bool launch_lobes_fwd_record(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out, RecLists L, uint4* aux,
-                             hipStream_t st, const uint32_t* sigma_mask, int32_t* tile_state, int tflags = 0) {
+                             hipStream_t st, const uint32_t* sigma_mask, int32_t* tile_state, int tflags) {
     if (L.terms == nullptr || !lobes_payload(opt, tr.K)) return false;
     const unsigned nb = nblocks(rays.Q);
-    const bool acc = N2 && tr.accel != nullptr;
-    if constexpr (N2) {
-        // march and shade in one launch (fwd_roles_kernel<..., LOBES>) where SH takes it too: up to 16 lobes, grid at hand
-        if (tile_state != nullptr && sigma_mask != nullptr && acc && opt.basis_dim <= 16 && nb < (1u << 30)) {
-            const RolesLaunch rl = roles_launch(nb, rays.tiles_per_row);
-            const int n_march = rl.n_march;
-            const unsigned grid = rl.grid;
-            const RolesMap rmap = rl.map;
-#define SVOXT_LOBES_ROLES(BB)                                                                                       \
-    {                                                                                                               \
-        hipLaunchKernelGGL((fwd_roles_kernel<FMT_SH, BB, 1, true, true>), dim3(grid), dim3(512), 0, st,             \
-                           tr, rays, opt, L, aux, out, sigma_mask, tile_state, n_march, (int)nb, tflags, rmap);     \
-        hipLaunchKernelGGL((fwd_finish_kernel<FMT_SH, BB, true, true>), dim3(finish_grid(nb)), dim3(512), 0, st,    \
-                           tr, rays, opt, L, aux, out, tile_state, (int)nb);                                        \
-        return true;                                                                                                \
-    }
-            switch (opt.basis_dim) {
-                case 1: SVOXT_LOBES_ROLES(1)
-                case 4: SVOXT_LOBES_ROLES(4)
-                case 9: SVOXT_LOBES_ROLES(9)
-                case 16: SVOXT_LOBES_ROLES(16)
-            }
-#undef SVOXT_LOBES_ROLES
-        }
-    }
-    if (sigma_mask != nullptr) {
-        if (acc) hipLaunchKernelGGL((march_rec_kernel<N2, false, 1, true>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, sigma_mask);
-        else hipLaunchKernelGGL((march_rec_kernel<N2, false, 0, true>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, sigma_mask);
-    } else {
-        if (acc) hipLaunchKernelGGL((march_rec_kernel<N2, false, 1>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, (const uint32_t*)nullptr);
-        else hipLaunchKernelGGL((march_rec_kernel<N2, false, 0>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, (const uint32_t*)nullptr);
-    }
-#define SVOXT_LOBES_FWD(BB)                                                                                         \
-    {                                                                                                               \
-        hipLaunchKernelGGL((shade_tile_kernel<FMT_SH, BB, false, false, true, true>), dim3(nb), dim3(512), 0, st,   \
-                           tr, rays, opt, L, aux, out, (const int32_t*)nullptr);                                    \
-        hipLaunchKernelGGL((render_fwd_kernel<FMT_SH, 3, BB, N2, false, false, true, true>), dim3(nb), dim3(kBlock), \
-                           0, st, tr, rays, opt, out, L, aux);                                                      \
-        return true;                                                                                                \
-    }
-    switch (opt.basis_dim) {
-        case 1: SVOXT_LOBES_FWD(1)
-        case 4: SVOXT_LOBES_FWD(4)
-        case 9: SVOXT_LOBES_FWD(9)
-        case 16: SVOXT_LOBES_FWD(16)
-        case 25: SVOXT_LOBES_FWD(25)
-    }
-#undef SVOXT_LOBES_FWD
-    return false;
+    // march and shade in one launch (fwd_roles_kernel<..., LOBES>) where SH takes it too: up to 16 lobes, grid at hand
+    if (N2 && tile_state != nullptr && sigma_mask != nullptr && tr.accel != nullptr && nb < (1u << 30) &&
+        with_int(IntSet<1, 4, 9, 16>{}, opt.basis_dim, [&](auto BB) {
+            return launch_roles(fwd_roles_kernel<FMT_SH, BB, 1, true, true>, fwd_finish_kernel<FMT_SH, BB, true, true>,
+                                tr, rays, opt, out, L, aux, st, sigma_mask, tile_state, tflags);
+        }))
+        return true;
+    launch_march<N2, false>(tr, rays, opt, L, aux, sigma_mask, st);
+    return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+        hipLaunchKernelGGL((shade_tile_kernel<FMT_SH, BB, false, false, true, true>), dim3(nb), dim3(512), 0, st,
+                           tr, rays, opt, L, aux, out, nullptr);
+        hipLaunchKernelGGL((render_fwd_kernel<FMT_SH, 3, BB, N2, false, false, true, true>), dim3(nb), dim3(kBlock), 0, st,
+                           tr, rays, opt, out, L, aux);
+        return true;
+    });
 }
 
 template <bool N2, bool REC>
 bool launch_fwd_special(const TreeDev& tr, const RaysDev& rays, const Opts& opt, int C, float* out,
                         RecLists L, uint4* aux, hipStream_t st) {
-    const unsigned nb = nblocks(rays.Q);
-#define SVOXT_FWD(F, CC, BB)                                                                   \
-    hipLaunchKernelGGL((render_fwd_kernel<F, CC, BB, N2, REC>), dim3(nb), dim3(kBlock), 0, st, \
-                       tr, rays, opt, out, L, aux);                                       \
-    return true;
-    if (opt.format == FMT_RGBA) {
-        if (C == 3) { SVOXT_FWD(FMT_RGBA, 3, 0) }
-        if (C == 7) { SVOXT_FWD(FMT_RGBA, 7, 0) }
-        if (C == 15) { SVOXT_FWD(FMT_RGBA, 15, 0) }
-        if (C == 31) { SVOXT_FWD(FMT_RGBA, 31, 0) }
-    } else if (opt.format == FMT_SH && C == 3) {
-        switch (opt.basis_dim) {
-            case 1: SVOXT_FWD(FMT_SH, 3, 1)
-            case 4: SVOXT_FWD(FMT_SH, 3, 4)
-            case 9: SVOXT_FWD(FMT_SH, 3, 9)
-            case 16: SVOXT_FWD(FMT_SH, 3, 16)
-            case 25: SVOXT_FWD(FMT_SH, 3, 25)
-        }
-    } else if constexpr (!REC) {
+    auto fwd = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(rays.Q)), dim3(kBlock), 0, st, tr, rays, opt, out, L, aux);
+        return true;
+    };
+    if (opt.format == FMT_RGBA)
+        return with_int(RgbaWidths{}, C, [&](auto CC) { return fwd(render_fwd_kernel<FMT_RGBA, CC, 0, N2, REC>); });
+    if (opt.format == FMT_SH)
+        return C == 3 && with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) { return fwd(render_fwd_kernel<FMT_SH, 3, BB, N2, REC>); });
+    if constexpr (!REC) {
         // SG / ASG payloads with 1 / 4 / 9 / 16 / 25 lobes and three channels (r03; they used to take the generic
         // kernels): a ray's basis values are formed once (precalc_lobes) and used like an SH basis
-#define SVOXT_FWD_LOBES(BB)                                                                                     \
-    hipLaunchKernelGGL((render_fwd_kernel<FMT_SH, 3, BB, N2, false, false, false, true>), dim3(nb), dim3(kBlock), \
-                       0, st, tr, rays, opt, out, L, aux);                                                      \
-    return true;
-        if ((opt.format == FMT_SG || opt.format == FMT_ASG) && C == 3 && tr.K == 3 * opt.basis_dim + 1) {
-            switch (opt.basis_dim) {
-                case 1: SVOXT_FWD_LOBES(1)
-                case 4: SVOXT_FWD_LOBES(4)
-                case 9: SVOXT_FWD_LOBES(9)
-                case 16: SVOXT_FWD_LOBES(16)
-                case 25: SVOXT_FWD_LOBES(25)
-            }
-        }
-#undef SVOXT_FWD_LOBES
+        if (C == 3 && lobes_payload(opt, tr.K))
+            return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) {
+                return fwd(render_fwd_kernel<FMT_SH, 3, BB, N2, false, false, false, true>);
+            });
     }
-#undef SVOXT_FWD
     return false;
 }
 
@@ -348,95 +309,53 @@ bool launch_fwd_special(const TreeDev& tr, const RaysDev& rays, const Opts& opt,
 bool fwd_split_enabled(const svoxt_tree* t, const svoxt_options* o, bool with_terms, int32_t list_flags) {
     if (list_flags & SVOXT_LISTS_FWD_ONE_KERNEL) return false;
     if (list_flags & SVOXT_LISTS_FWD_TWO_KERNELS) return true;
-    if (o->format == SVOXT_FORMAT_RGBA && (t->K == 8 || t->K == 16 || t->K == 32)) return true;
+    if (o->format == SVOXT_FORMAT_RGBA && chan_rows(t->K)) return true;
     return with_terms && t->xform == nullptr && t->weight_accum == nullptr;
 }
 
 bool fwd_split_payload(const svoxt_tree* t, const svoxt_options* o, int C) {
     if (t->weight_accum != nullptr) return false;
-    if (o->format == SVOXT_FORMAT_RGBA && (t->K == 8 || t->K == 16 || t->K == 32)) return true;   // channel lanes
+    if (o->format == SVOXT_FORMAT_RGBA && chan_rows(t->K)) return true;   // channel lanes
     if (C != 3) return false;
     if (o->format == SVOXT_FORMAT_RGBA) return t->K == 4;
-    if (o->format != SVOXT_FORMAT_SH || t->K != 3 * o->basis_dim + 1) return false;
-    return o->basis_dim == 1 || o->basis_dim == 4 || o->basis_dim == 9 || o->basis_dim == 16 || o->basis_dim == 25;
+    return o->format == SVOXT_FORMAT_SH && t->K == 3 * o->basis_dim + 1 && special_basis(o->basis_dim);
 }
 
 // The shade (+ tail) launches of one range of tiles.
 template <bool N2, bool STOP>
 bool launch_shade(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out, RecLists L, uint4* aux,
                   bool xf, bool fast, unsigned nb, hipStream_t st) {
-#define SVOXT_SPLIT(F, BB, X)                                                                                 \
-    {                                                                                                         \
-        if (!STOP && L.terms != nullptr)                                                                      \
-            hipLaunchKernelGGL((shade_tile_kernel<F, BB, X, STOP, !STOP>), dim3(nb), dim3(512), 0, st,        \
-                               tr, rays, opt, L, aux, out);                                                   \
-        else                                                                                                  \
-        hipLaunchKernelGGL((shade_tile_kernel<F, BB, X, STOP>), dim3(nb), dim3(512), 0, st, tr, rays, opt,    \
-                           L, aux, out);                                                                 \
-        hipLaunchKernelGGL((render_fwd_kernel<F, 3, BB, N2, false, X, true>), dim3(nb), dim3(kBlock), 0, st,  \
-                           tr, rays, opt, out, L, aux);                                      \
-        return true;                                                                                          \
-    }
     if (opt.format == FMT_RGBA && tr.K != 4) {
         // rows of 8 / 16 / 32 floats: channels on lanes, 64 / K rays per wavefront, 4 wavefronts per workgroup
-#define SVOXT_CHAN(KK)                                                                                        \
-        {                                                                                                     \
-            const unsigned nbc = (unsigned)(((int64_t)nb * 64 / (64 / KK) + 3) / 4);                          \
-            /* (r05) lists for a backward (!STOP) under a stop threshold: the instance that applies the rule, told to  \
-               keep the overflow flags (the march did not stop: the backward's tail still needs them) */             \
-            const bool stop_rt = !STOP && opt.stop_thresh > 0.f;                                               \
-            if (stop_rt) {                                                                                     \
-                if (fast) hipLaunchKernelGGL((shade_chan_kernel<KK, true, true>), dim3(nbc), dim3(256), 0, st, \
-                                             tr, rays, opt, L, aux, out, 1);                                   \
-                else if (tr.etab != nullptr)                                                                   \
-                    hipLaunchKernelGGL((shade_chan_kernel<KK, true, false, true>), dim3(nbc), dim3(256), 0, st, \
-                                       tr, rays, opt, L, aux, out, 1);                                         \
-                else hipLaunchKernelGGL((shade_chan_kernel<KK, true, false>), dim3(nbc), dim3(256), 0, st,     \
-                                        tr, rays, opt, L, aux, out, 1);                                        \
-            } else                                                                                             \
-            if (fast) hipLaunchKernelGGL((shade_chan_kernel<KK, STOP, true>), dim3(nbc), dim3(256), 0, st,    \
-                                         tr, rays, opt, L, aux, out, 0);                                 \
-            else if (tr.etab != nullptr)                                                                      \
-                hipLaunchKernelGGL((shade_chan_kernel<KK, STOP, false, true>), dim3(nbc), dim3(256), 0, st,   \
-                                   tr, rays, opt, L, aux, out, 0);                                       \
-            else hipLaunchKernelGGL((shade_chan_kernel<KK, STOP, false>), dim3(nbc), dim3(256), 0, st,        \
-                                    tr, rays, opt, L, aux, out, 0);                                      \
-            if (fast) hipLaunchKernelGGL((tail_chan_kernel<KK, N2, true>), dim3(nb), dim3(256), 0, st,        \
-                                         tr, rays, opt, aux, out, L);                                         \
-            else hipLaunchKernelGGL((tail_chan_kernel<KK, N2, false>), dim3(nb), dim3(256), 0, st,            \
-                                    tr, rays, opt, aux, out, L);                                              \
-            return true;                                                                                      \
-        }
-        switch (tr.K) {
-            case 8: SVOXT_CHAN(8)
-            case 16: SVOXT_CHAN(16)
-            case 32: SVOXT_CHAN(32)
-        }
-#undef SVOXT_CHAN
-        return false;
+        return with_int(ChanRows{}, tr.K, [&](auto KK) {
+            const unsigned nbc = (unsigned)(((int64_t)nb * 64 / (64 / KK) + 3) / 4);
+            // (r05) lists for a backward (!STOP) under a stop threshold: the instance that applies the rule, told to
+            // keep the overflow flags (the march did not stop: the backward's tail still needs them)
+            const bool keep_over = !STOP && opt.stop_thresh > 0.f;
+            const auto shade = with_bool(STOP || keep_over, [&](auto S) {
+                return fast ? shade_chan_kernel<KK, S, true>
+                            : tr.etab != nullptr ? shade_chan_kernel<KK, S, false, true> : shade_chan_kernel<KK, S, false>;
+            });
+            hipLaunchKernelGGL(shade, dim3(nbc), dim3(256), 0, st, tr, rays, opt, L, aux, out, keep_over ? 1 : 0);
+            hipLaunchKernelGGL((fast ? tail_chan_kernel<KK, N2, true> : tail_chan_kernel<KK, N2, false>), dim3(nb), dim3(256), 0,
+                               st, tr, rays, opt, aux, out, L);
+            return true;
+        });
     }
-    if (opt.format == FMT_RGBA) SVOXT_SPLIT(FMT_RGBA, 0, false)
-    if constexpr (N2) {
-        if (xf) {
-            switch (opt.basis_dim) {
-                case 1: SVOXT_SPLIT(FMT_SH, 1, true)
-                case 4: SVOXT_SPLIT(FMT_SH, 4, true)
-                case 9: SVOXT_SPLIT(FMT_SH, 9, true)
-                case 16: SVOXT_SPLIT(FMT_SH, 16, true)
-                case 25: SVOXT_SPLIT(FMT_SH, 25, true)
-            }
-            return false;
-        }
-    }
-    switch (opt.basis_dim) {
-        case 1: SVOXT_SPLIT(FMT_SH, 1, false)
-        case 4: SVOXT_SPLIT(FMT_SH, 4, false)
-        case 9: SVOXT_SPLIT(FMT_SH, 9, false)
-        case 16: SVOXT_SPLIT(FMT_SH, 16, false)
-        case 25: SVOXT_SPLIT(FMT_SH, 25, false)
-    }
-#undef SVOXT_SPLIT
-    return false;
+    // the tile shade (leaving the backward's hand-over where the lists have room for it) + the tail launch
+    auto split = [&](auto F, auto BB, auto XF) {
+        const auto shade = !STOP && L.terms != nullptr ? shade_tile_kernel<F, BB, XF, STOP, !STOP>
+                                                       : shade_tile_kernel<F, BB, XF, STOP>;
+        hipLaunchKernelGGL(shade, dim3(nb), dim3(512), 0, st, tr, rays, opt, L, aux, out, nullptr);
+        hipLaunchKernelGGL((render_fwd_kernel<F, 3, BB, N2, false, XF, true>), dim3(nb), dim3(kBlock), 0, st,
+                           tr, rays, opt, out, L, aux);
+        return true;
+    };
+    if (opt.format == FMT_RGBA) return split(Int<FMT_RGBA>{}, Int<0>{}, std::false_type{});
+    return with_bool(N2 && xf, [&](auto XF) {
+        if constexpr (XF && !N2) return false;
+        else return with_int(SpecialBases{}, opt.basis_dim, [&](auto BB) { return split(Int<FMT_SH>{}, BB, XF); });
+    });
 }
 
 // (Measured r02 and removed in r03: the tiles cut into 2..7 ranges pipelined over two streams, so that
@@ -447,91 +366,36 @@ bool launch_shade(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float
 template <bool N2, bool STOP>
 bool launch_fwd_roles(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out, RecLists L, uint4* aux,
                       hipStream_t st, const uint32_t* sigma_mask, int32_t* tile_state, int tflags, bool xf) {
-    if constexpr (!N2 || STOP) {
-        return false;
-    } else {
-        const unsigned nb = nblocks(rays.Q);
-        if (nb >= (1u << 30)) return false;
-        const RolesLaunch rl = roles_launch(nb, rays.tiles_per_row);
-        const int n_march = rl.n_march;                                 // a multiple of 8: see fwd_roles_kernel
-        const unsigned grid = rl.grid;                                  // + the shading workgroups (the active ones: one per tile)
-        const RolesMap rmap = rl.map;
-        // (r05: only with the acceleration grid -- the default for every N = 2 tree of 64 nodes and more; without one the
-        // march and the shade stay two launches: the 18 grid-less instances of this kernel had no default caller)
-        if (tr.accel == nullptr) return false;
-        const bool wt = L.terms != nullptr;
-#define SVOXT_ROLES(F, BB)                                                                                        \
-        {                                                                                                         \
-            if (wt) hipLaunchKernelGGL((fwd_roles_kernel<F, BB, 1, true>), dim3(grid), dim3(512), 0, st,          \
-                                       tr, rays, opt, L, aux, out, sigma_mask, tile_state, n_march, (int)nb, tflags, rmap); \
-            else hipLaunchKernelGGL((fwd_roles_kernel<F, BB, 1, false>), dim3(grid), dim3(512), 0, st,            \
-                                    tr, rays, opt, L, aux, out, sigma_mask, tile_state, n_march, (int)nb, tflags, rmap); \
-            /* the fallback shade of what the launch left unshaded + the tails of overflowed rays: one small launch */ \
-            if (wt) hipLaunchKernelGGL((fwd_finish_kernel<F, BB, true>), dim3(finish_grid(nb)), dim3(512), 0, st, \
-                                       tr, rays, opt, L, aux, out, tile_state, (int)nb);                          \
-            else hipLaunchKernelGGL((fwd_finish_kernel<F, BB, false>), dim3(finish_grid(nb)), dim3(512), 0, st,   \
-                                    tr, rays, opt, L, aux, out, tile_state, (int)nb);                             \
-            return true;                                                                                          \
-        }
-        if (xf) {
-            // (r04) per-leaf view rotations: SH 1 / 4 / 9 without hand-over (the lists' backward is grad_fused_kernel<..., XF>)
-            if (opt.format != FMT_SH || opt.basis_dim > 9) return false;
-#define SVOXT_ROLES_XF1(BB, AA, WW)                                                                               \
-                hipLaunchKernelGGL((fwd_roles_kernel<FMT_SH, BB, AA, WW, false, true>), dim3(grid), dim3(512), 0, st, \
-                                   tr, rays, opt, L, aux, out, sigma_mask, tile_state, n_march, (int)nb, tflags, rmap);
-#define SVOXT_ROLES_XF(BB)                                                                                        \
-            {                                                                                                     \
-                if (wt) SVOXT_ROLES_XF1(BB, 1, true) else SVOXT_ROLES_XF1(BB, 1, false)                           \
-                if (wt) hipLaunchKernelGGL((fwd_finish_kernel<FMT_SH, BB, true, false, true>), dim3(finish_grid(nb)), dim3(512), 0, st, \
-                                           tr, rays, opt, L, aux, out, tile_state, (int)nb);                      \
-                else hipLaunchKernelGGL((fwd_finish_kernel<FMT_SH, BB, false, false, true>), dim3(finish_grid(nb)), dim3(512), 0, st, \
-                                        tr, rays, opt, L, aux, out, tile_state, (int)nb);                         \
-                return true;                                                                                      \
-            }
-            switch (opt.basis_dim) {
-                case 1: SVOXT_ROLES_XF(1)
-                case 4: SVOXT_ROLES_XF(4)
-                case 9: SVOXT_ROLES_XF(9)
-            }
-#undef SVOXT_ROLES_XF
-#undef SVOXT_ROLES_XF1
-            return false;
-        }
-        if (opt.format == FMT_RGBA && tr.K == 4) SVOXT_ROLES(FMT_RGBA, 0)
-        if (opt.format == FMT_SH) {
-            switch (opt.basis_dim) {
-                case 1: SVOXT_ROLES(FMT_SH, 1)
-                case 4: SVOXT_ROLES(FMT_SH, 4)
-                case 9: SVOXT_ROLES(FMT_SH, 9)
-                case 16: SVOXT_ROLES(FMT_SH, 16)      // (r03: 0.833 -> 0.805 ms forward+backward; SH25, at 129 registers, loses: 1.139 -> 1.194)
-            }
-        }
-#undef SVOXT_ROLES
-        return false;
-    }
+    // (r05: only with the acceleration grid -- the default for every N = 2 tree of 64 nodes and more; without one the
+    // march and the shade stay two launches: the 18 grid-less instances of this kernel had no default caller)
+    if (!N2 || STOP || nblocks(rays.Q) >= (1u << 30) || tr.accel == nullptr) return false;
+    auto roles = [&](auto F, auto BB, auto XF) {
+        return with_bool(L.terms != nullptr, [&](auto WT) {
+            return launch_roles(fwd_roles_kernel<F, BB, 1, WT, false, XF>, fwd_finish_kernel<F, BB, WT, false, XF>,
+                                tr, rays, opt, out, L, aux, st, sigma_mask, tile_state, tflags);
+        });
+    };
+    // (r04) per-leaf view rotations: SH 1 / 4 / 9 without hand-over (the lists' backward is grad_fused_kernel<..., XF>)
+    if (xf)
+        return opt.format == FMT_SH &&
+               with_int(XfRolesBases{}, opt.basis_dim, [&](auto BB) { return roles(Int<FMT_SH>{}, BB, std::true_type{}); });
+    if (opt.format == FMT_RGBA) return tr.K == 4 && roles(Int<FMT_RGBA>{}, Int<0>{}, std::false_type{});
+    // (SH16 r03: 0.833 -> 0.805 ms forward+backward; SH25, at 129 registers, loses: 1.139 -> 1.194)
+    return opt.format == FMT_SH &&
+           with_int(IntSet<1, 4, 9, 16>{}, opt.basis_dim, [&](auto BB) { return roles(Int<FMT_SH>{}, BB, std::false_type{}); });
 }
 
+// The forward as march + shade into the lists L: march and shade as one launch where the lists have tile states, else
+// march_rec_kernel and launch_shade.  (sigma_mask and tile_state serve the form without the stop rule only.)
 template <bool N2, bool STOP>
-bool launch_fwd_split(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out,
-                      RecLists L, uint4* aux, bool xf, bool fast, hipStream_t st,
-                      const uint32_t* sigma_mask = nullptr, int32_t* tile_state = nullptr, int tflags = 0) {
-    const unsigned nb = nblocks(rays.Q);
+bool launch_fwd_split(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float* out, RecLists L, uint4* aux,
+                      bool xf, bool fast, hipStream_t st, const uint32_t* sigma_mask, int32_t* tile_state, int tflags) {
     if (xf && !N2) return false;
-    const bool acc = N2 && tr.accel != nullptr;
-    if (tile_state != nullptr && sigma_mask != nullptr && !STOP &&
+    if (tile_state != nullptr && sigma_mask != nullptr &&
         launch_fwd_roles<N2, STOP>(tr, rays, opt, out, L, aux, st, sigma_mask, tile_state, tflags, xf))
         return true;
-    if constexpr (!STOP) {
-        if (sigma_mask != nullptr) {
-            if (acc) hipLaunchKernelGGL((march_rec_kernel<N2, false, 1, true>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, sigma_mask);
-            else hipLaunchKernelGGL((march_rec_kernel<N2, false, 0, true>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, sigma_mask);
-        }
-    }
-    if (STOP || sigma_mask == nullptr) {
-        if (acc) hipLaunchKernelGGL((march_rec_kernel<N2, STOP, 1>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, (const uint32_t*)nullptr);
-        else hipLaunchKernelGGL((march_rec_kernel<N2, STOP, 0>), dim3(nb), dim3(kBlock), 0, st, tr, rays, opt, L, aux, (const uint32_t*)nullptr);
-    }
-    return launch_shade<N2, STOP>(tr, rays, opt, out, L, aux, xf, fast, nb, st);
+    launch_march<N2, STOP>(tr, rays, opt, L, aux, sigma_mask, st);
+    return launch_shade<N2, STOP>(tr, rays, opt, out, L, aux, xf, fast, nblocks(rays.Q), st);
 }
 
 }  // namespace
@@ -631,17 +495,21 @@ static int fwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svox
     const int32_t lflags = flags | (lists != nullptr ? lists->flags : 0) | (scratch != nullptr ? scratch->flags : 0);
     const bool fast = (lflags & SVOXT_LISTS_NATIVE_MATH) != 0;
     const bool want_terms = lists != nullptr && lists->terms != nullptr && C == 3;
+    const int tflags = (lflags >> 8) & 15;
+    // (tile states: march and shade as ONE launch; pooled lists only -- their fill clears the states too)
+    auto states = [&](const svoxt_sample_lists* l) -> int32_t* {
+        return (l->blocktab != nullptr && !(lflags & SVOXT_LISTS_FWD_NO_OVERLAP)) ? reinterpret_cast<int32_t*>(l->tile_state) : nullptr;
+    };
     if (lists != nullptr && lobes_payload(od, tree->K)) {
         // SG / ASG with sample lists: only as march + tile shade that leaves the backward's hand-over (svoxt_can_record)
         if (!want_terms || !full_comp(opt) || uses_xform(tree, opt) || tree->weight_accum != nullptr)
             return fail(SVOXT_ERR_UNSUPPORTED, "%s: SG / ASG payloads record sample lists only with lists.terms (the exact per-tile backward's hand-over), all components, no transformation_matrices, no weight accumulation", fn);
         const uint32_t* smask = (tree->sigma_mask != nullptr && tree->sigma_mask_thresh == 0.f)      // (lists: every sigma > 0)
                                     ? reinterpret_cast<const uint32_t*>(tree->sigma_mask) : nullptr;
-        uint4* aux = reinterpret_cast<uint4*>(lists->aux);
-        int32_t* states = (lists->blocktab != nullptr && !(lflags & SVOXT_LISTS_FWD_NO_OVERLAP))
-                              ? reinterpret_cast<int32_t*>(lists->tile_state) : nullptr;
-        done = n2 ? launch_lobes_fwd_record<true>(tr, rd, od, out, lists_dev(lists, rays->Q), aux, st, smask, states, (lflags >> 8) & 15)
-                  : launch_lobes_fwd_record<false>(tr, rd, od, out, lists_dev(lists, rays->Q), aux, st, smask, nullptr);
+        done = with_bool(n2, [&](auto N2) {
+            return launch_lobes_fwd_record<N2>(tr, rd, od, out, lists_dev(lists, rays->Q), reinterpret_cast<uint4*>(lists->aux),
+                                               st, smask, states(lists), tflags);
+        });
         if (!done) return fail(SVOXT_ERR_UNSUPPORTED, "%s: no recording kernel for this SG / ASG payload", fn);
         return check_launch(fn);
     }
@@ -652,69 +520,54 @@ static int fwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svox
         // backward hold every sample with sigma > 0: their march wants the mask of threshold 0
         const uint32_t* smask = (tree->sigma_mask != nullptr && tree->sigma_mask_thresh == (lists != nullptr ? 0.f : opt->sigma_thresh))
                                     ? reinterpret_cast<const uint32_t*>(tree->sigma_mask) : nullptr;
-        // (tile states: march and shade as ONE launch; pooled lists only -- their fill clears the states too)
-        auto states = [&](const svoxt_sample_lists* l) -> int32_t* {
-            return (l->blocktab != nullptr && !(lflags & SVOXT_LISTS_FWD_NO_OVERLAP)) ? reinterpret_cast<int32_t*>(l->tile_state) : nullptr;
+        auto split = [&](auto STOP, RecLists L, uint4* aux, int32_t* tile_state) {
+            return with_bool(n2, [&](auto N2) {
+                return launch_fwd_split<N2, STOP>(tr, rd, od, out, L, aux, xf, fast, st, smask, tile_state, tflags);
+            });
         };
-        if (lists != nullptr) {
-            uint4* aux = reinterpret_cast<uint4*>(lists->aux);
-            done = n2 ? launch_fwd_split<true, false>(tr, rd, od, out, lists_dev(lists, rays->Q), aux, xf, fast, st, smask, states(lists), (lflags >> 8) & 15)
-                      : launch_fwd_split<false, false>(tr, rd, od, out, lists_dev(lists, rays->Q), aux, xf, fast, st, smask);
-        } else if (scratch != nullptr && smask != nullptr &&
-                   (opt->stop_thresh == 0.f || (opt->format == SVOXT_FORMAT_RGBA && (tree->K == 8 || tree->K == 16 || tree->K == 32)))) {
-            // With stop_thresh = 0 the stop rule ends a ray only once its transmittance is exactly 0; every
-            // later sample then has weight 0 * (1 - att) = 0 and the final rescale is by 1 / (1 - 0): the
-            // outputs are the same without it, and the march needs no sigma value -- the bitmask will do.
+        if (lists != nullptr || scratch != nullptr) {
+            const svoxt_sample_lists* l = lists != nullptr ? lists : scratch;
+            // Caller-owned lists as scratch (dense or pooled) serve no backward: the stop rule applies while marching,
+            // unless the march can run over the bitmask.  With stop_thresh = 0 the stop rule ends a ray only once its
+            // transmittance is exactly 0; every later sample then has weight 0 * (1 - att) = 0 and the final rescale is
+            // by 1 / (1 - 0): the outputs are the same without it, and the march needs no sigma value -- the bitmask will do.
             // (r05) Rows of 8 / 16 / 32 floats take this route under a stop threshold too: the rule is then applied
             // by the SHADE (shade_chan_kernel's STOP instance; the march lists the whole ray), which keeps the
             // bitmask and the exponentials table -- depth 9 / K = 32 at 1024 x 1024, fast=True forward: 1.05 -> 0.8x ms;
             // 3-channel payloads stay with the march that stops (800 x 800 / depth 8: 0.173 ms against 0.204).
-            if ((rc = lists_begin(scratch, rays->Q, st, fn))) return rc;
-            uint4* aux = reinterpret_cast<uint4*>(scratch->aux);
-            done = n2 ? launch_fwd_split<true, false>(tr, rd, od, out, lists_dev(scratch, rays->Q), aux, xf, fast, st, smask, states(scratch), (lflags >> 8) & 15)
-                      : launch_fwd_split<false, false>(tr, rd, od, out, lists_dev(scratch, rays->Q), aux, xf, fast, st, smask);
-        } else if (scratch != nullptr) {      // caller-owned lists as scratch (dense or pooled): the stop rule applies
-            if ((rc = lists_begin(scratch, rays->Q, st, fn))) return rc;
-            uint4* aux = reinterpret_cast<uint4*>(scratch->aux);
-            done = n2 ? launch_fwd_split<true, true>(tr, rd, od, out, lists_dev(scratch, rays->Q), aux, xf, fast, st)
-                      : launch_fwd_split<false, true>(tr, rd, od, out, lists_dev(scratch, rays->Q), aux, xf, fast, st);
+            const bool stop = lists == nullptr &&
+                              !(smask != nullptr && (opt->stop_thresh == 0.f || (opt->format == SVOXT_FORMAT_RGBA && chan_rows(tree->K))));
+            if (lists == nullptr && (rc = lists_begin(scratch, rays->Q, st, fn))) return rc;
+            done = with_bool(stop, [&](auto STOP) {
+                return split(STOP, lists_dev(l, rays->Q), reinterpret_cast<uint4*>(l->aux), states(l));
+            });
         } else if (workspace != nullptr && rec_capacity(workspace_bytes - rec_rays(rays->Q) * 16, rays->Q) >= kRecBlock) {
             const int64_t S = rec_capacity(workspace_bytes - rec_rays(rays->Q) * 16, rays->Q);
             uint4* aux = reinterpret_cast<uint4*>(workspace);                       // aux first: rec stays 64-byte aligned
-            const RecLists L = dense_lists(reinterpret_cast<char*>(workspace) + rec_rays(rays->Q) * 16, S, rays->Q);
-            done = n2 ? launch_fwd_split<true, true>(tr, rd, od, out, L, aux, xf, fast, st)
-                      : launch_fwd_split<false, true>(tr, rd, od, out, L, aux, xf, fast, st);
+            done = split(std::true_type{}, dense_lists(reinterpret_cast<char*>(workspace) + rec_rays(rays->Q) * 16, S, rays->Q),
+                         aux, nullptr);
         }
         if (done) return check_launch(fn);
     }
     // (r05) Scratch lists this forward will not use (no two-kernel forward for the payload, or the tree accumulates weights):
     // their block counters are still left "nothing taken", so that a caller who sizes its pool by them reads a defined state.
     if (scratch != nullptr && (rc = lists_begin(scratch, rays->Q, st, fn))) return rc;
+    const RecLists L = lists != nullptr ? lists_dev(lists, rays->Q) : RecLists{};
+    uint4* aux = lists != nullptr ? reinterpret_cast<uint4*>(lists->aux) : nullptr;
     if (uses_xform(tree, opt)) {
         // per-leaf view rotations re-evaluate the basis per sample: specialised for SH
         // payloads on N = 2 trees, the generic kernel otherwise
-        if (full_comp(opt) && xform_special(tree, opt)) {
-            if (lists != nullptr)
-                done = launch_fwd_xform<true>(tr, rd, od, C, out, lists_dev(lists, rays->Q),
-                                              reinterpret_cast<uint4*>(lists->aux), st);
-            else
-                done = launch_fwd_xform<false>(tr, rd, od, C, out, RecLists{}, nullptr, st);
-        }
+        if (full_comp(opt) && xform_special(tree, opt))
+            done = with_bool(lists != nullptr, [&](auto REC) { return launch_fwd_xform<REC>(tr, rd, od, C, out, L, aux, st); });
     } else if (full_comp(opt)) {
-        if (lists != nullptr) {
-            uint4* aux = reinterpret_cast<uint4*>(lists->aux);
-            done = n2 ? launch_fwd_special<true, true>(tr, rd, od, C, out, lists_dev(lists, rays->Q), aux, st)
-                      : launch_fwd_special<false, true>(tr, rd, od, C, out, lists_dev(lists, rays->Q), aux, st);
-        } else {
-            done = n2 ? launch_fwd_special<true, false>(tr, rd, od, C, out, RecLists{}, nullptr, st)
-                      : launch_fwd_special<false, false>(tr, rd, od, C, out, RecLists{}, nullptr, st);
-        }
+        done = with_bool(n2, [&](auto N2) {
+            return with_bool(lists != nullptr, [&](auto REC) { return launch_fwd_special<N2, REC>(tr, rd, od, C, out, L, aux, st); });
+        });
     }
     if (!done) {
         if (lists != nullptr) return fail(SVOXT_ERR_UNSUPPORTED, "%s: sample lists need a specialised payload", fn);
-        const unsigned nb = nblocks(rays->Q);
-        if (n2) hipLaunchKernelGGL((render_fwd_generic_kernel<true>), dim3(nb), dim3(kBlock), 0, st, tr, rd, od, C, out);
-        else hipLaunchKernelGGL((render_fwd_generic_kernel<false>), dim3(nb), dim3(kBlock), 0, st, tr, rd, od, C, out);
+        hipLaunchKernelGGL(n2 ? render_fwd_generic_kernel<true> : render_fwd_generic_kernel<false>, dim3(nblocks(rays->Q)),
+                           dim3(kBlock), 0, st, tr, rd, od, C, out);
     }
     return check_launch(fn);
 }
@@ -783,7 +636,7 @@ int svoxt_exp_table_build(const svoxt_tree* tree, float sigma_thresh, void* mask
     const char* fn = "svoxt_exp_table_build";
     int rc;
     if ((rc = check_tree(tree, fn))) return rc;
-    if (tree->K != 8 && tree->K != 16 && tree->K != 32)
+    if (!chan_rows(tree->K))
         return fail(SVOXT_ERR_UNSUPPORTED, "%s: the table serves RGBA-style rows of 8, 16 or 32 floats", fn);
     if (tree->M == 0) return SVOXT_OK;
     if (table == nullptr || ((uintptr_t)table & 15u) != 0 || ((uintptr_t)tree->features & 15u) != 0)
@@ -793,9 +646,10 @@ int svoxt_exp_table_build(const svoxt_tree* tree, float sigma_thresh, void* mask
     const dim3 grid((unsigned)((threads + 255) / 256));
     hipStream_t st = (hipStream_t)stream;
     uint8_t* mb = reinterpret_cast<uint8_t*>(mask);
-    if (tree->K == 8) hipLaunchKernelGGL((svoxt::exp_table_kernel<8>), grid, dim3(256), 0, st, tree->features, tree->M, sigma_thresh, mb, table);
-    else if (tree->K == 16) hipLaunchKernelGGL((svoxt::exp_table_kernel<16>), grid, dim3(256), 0, st, tree->features, tree->M, sigma_thresh, mb, table);
-    else hipLaunchKernelGGL((svoxt::exp_table_kernel<32>), grid, dim3(256), 0, st, tree->features, tree->M, sigma_thresh, mb, table);
+    with_int(ChanRows{}, tree->K, [&](auto KK) {
+        hipLaunchKernelGGL((svoxt::exp_table_kernel<KK>), grid, dim3(256), 0, st, tree->features, tree->M, sigma_thresh, mb, table);
+        return true;
+    });
     return check_launch(fn);
 }
 
@@ -803,7 +657,7 @@ int svoxt_fwd_fills_terms(const svoxt_tree* tree, const svoxt_options* opt, int3
     if (tree == nullptr || opt == nullptr || !svoxt_can_record(tree, opt)) return 0;
     const int C = svoxt_out_data_dim(opt, tree->K) - 1;
     if (uses_xform(tree, opt))      // (r04) view rotations: only the two-kernel / one-launch forward of SH 1 / 4 / 9 leaves a hand-over
-        return (C == 3 && tree->N == 2 && opt->format == SVOXT_FORMAT_SH && opt->basis_dim <= 9 && (list_flags & SVOXT_LISTS_FWD_TWO_KERNELS) &&
+        return (C == 3 && tree->N == 2 && opt->format == SVOXT_FORMAT_SH && xf_roles_basis(opt->basis_dim) && (list_flags & SVOXT_LISTS_FWD_TWO_KERNELS) &&
                 full_comp(opt) && fwd_split_payload(tree, opt, C) && xform_special(tree, opt)) ? 3 : 0;
     if (C != 3) return 0;
     if (lobes_payload(to_dev(opt), tree->K)) return 3;
@@ -816,10 +670,8 @@ int svoxt_can_record(const svoxt_tree* tree, const svoxt_options* opt) {
     if (!full_comp(opt)) return 0;        // (r05: any thresholds)
     if (uses_xform(tree, opt)) return xform_special(tree, opt) ? 1 : 0;
     const int C = svoxt_out_data_dim(opt, tree->K) - 1;
-    if (opt->format == SVOXT_FORMAT_RGBA) return (C == 3 || C == 7 || C == 15 || C == 31) ? 1 : 0;
-    if (opt->format == SVOXT_FORMAT_SH && C == 3 && tree->K == 3 * opt->basis_dim + 1)
-        return (opt->basis_dim == 1 || opt->basis_dim == 4 || opt->basis_dim == 9 || opt->basis_dim == 16 ||
-                opt->basis_dim == 25) ? 1 : 0;
+    if (opt->format == SVOXT_FORMAT_RGBA) return RgbaWidths::has(C) ? 1 : 0;
+    if (opt->format == SVOXT_FORMAT_SH && C == 3 && tree->K == 3 * opt->basis_dim + 1) return special_basis(opt->basis_dim) ? 1 : 0;
     // SG / ASG (r03): 2 = lists can be recorded, but only together with the exact per-tile backward's hand-over
     // (lists.terms; svoxt_fwd_fills_terms says 3) on N = 2 trees without weight accumulation -- they serve that backward alone
     if (C == 3 && lobes_payload(to_dev(opt), tree->K) && tree->N == 2 && tree->weight_accum == nullptr) return 2;
@@ -872,8 +724,8 @@ int svoxt_opacity_render_fwd(const svoxt_tree* tree, const svoxt_rays* rays,
     if (out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: out is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = nblocks(rays->Q);
-    if (tree->N == 2) hipLaunchKernelGGL((opacity_fwd_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), out);
-    else hipLaunchKernelGGL((opacity_fwd_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), out);
+    hipLaunchKernelGGL(tree->N == 2 ? opacity_fwd_kernel<true> : opacity_fwd_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), to_dev(rays, tree), to_dev(opt), out, RecLists{}, nullptr);
     return check_launch(fn);
 }
 
@@ -897,8 +749,8 @@ int svoxt_opacity_render_fwd_record(const svoxt_tree* tree, const svoxt_rays* ra
     if ((rc = lists_begin(lists, rays->Q, st, fn))) return rc;
     const RecLists L = lists_dev(lists, rays->Q);
     uint4* aux = reinterpret_cast<uint4*>(lists->aux);
-    if (tree->N == 2) hipLaunchKernelGGL((opacity_fwd_kernel<true, true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree, lists), to_dev(opt), out, L, aux);
-    else hipLaunchKernelGGL((opacity_fwd_kernel<false, true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree, lists), to_dev(opt), out, L, aux);
+    hipLaunchKernelGGL((tree->N == 2 ? opacity_fwd_kernel<true, true> : opacity_fwd_kernel<false, true>), dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), to_dev(rays, tree, lists), to_dev(opt), out, L, aux);
     return check_launch(fn);
 }
 
@@ -923,8 +775,8 @@ int svoxt_opacity_render_bwd_replay(const svoxt_tree* tree, const svoxt_rays* ra
     const RaysDev rd = to_dev(rays, tree, lists);
     const RecLists L = lists_dev(lists, rays->Q);
     uint4* aux = reinterpret_cast<uint4*>(lists->aux);
-    if (tree->N == 2) hipLaunchKernelGGL((opacity_walk_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), rd, to_dev(opt), grad_out, grad_features, gs, L, aux);
-    else hipLaunchKernelGGL((opacity_walk_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), rd, to_dev(opt), grad_out, grad_features, gs, L, aux);
+    hipLaunchKernelGGL(tree->N == 2 ? opacity_walk_kernel<true> : opacity_walk_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), rd, to_dev(opt), grad_out, grad_features, gs, L, aux);
     hipLaunchKernelGGL((opacity_merge_kernel<1024, 4>), dim3(nb), dim3(256), 0, st, rd, L, aux, grad_features, gs, (int)tree->K - 1);
     return check_launch(fn);
 }
@@ -939,8 +791,8 @@ int svoxt_render_depth(const svoxt_tree* tree, const svoxt_rays* rays,
     if (depth == nullptr) return fail(SVOXT_ERR_INVALID, "%s: depth is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = nblocks(rays->Q);
-    if (tree->N == 2) hipLaunchKernelGGL((depth_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), depth);
-    else hipLaunchKernelGGL((depth_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), depth);
+    hipLaunchKernelGGL(tree->N == 2 ? depth_kernel<true> : depth_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), to_dev(rays, tree), to_dev(opt), depth);
     return check_launch(fn);
 }
 
@@ -956,8 +808,8 @@ int svoxt_query_fwd(const svoxt_tree* tree, const float* points, int64_t Q,
         return fail(SVOXT_ERR_INVALID, "%s: points / values / node_ids / data_ids is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = nblocks(Q);
-    if (tree->N == 2) hipLaunchKernelGGL((query_fwd_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), points, Q, values, node_ids, data_ids, hit_mask);
-    else hipLaunchKernelGGL((query_fwd_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), points, Q, values, node_ids, data_ids, hit_mask);
+    hipLaunchKernelGGL(tree->N == 2 ? query_fwd_kernel<true> : query_fwd_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), points, Q, values, node_ids, data_ids, hit_mask);
     return check_launch(fn);
 }
 
@@ -976,8 +828,8 @@ int svoxt_query_bwd(const svoxt_tree* tree, const float* points, int64_t Q,
     if (Q == 0 || tree->M == 0) return SVOXT_OK;
     if (points == nullptr || grad_out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: points / grad_out is NULL", fn);
     const unsigned nb = nblocks(Q);
-    if (tree->N == 2) hipLaunchKernelGGL((query_bwd_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), points, Q, grad_out, grad_features);
-    else hipLaunchKernelGGL((query_bwd_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), points, Q, grad_out, grad_features);
+    hipLaunchKernelGGL(tree->N == 2 ? query_bwd_kernel<true> : query_bwd_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), points, Q, grad_out, grad_features);
     return check_launch(fn);
 }
 
@@ -994,8 +846,8 @@ int svoxt_count_fwd(const svoxt_tree* tree, const svoxt_rays* rays,
     unsigned long long* c = reinterpret_cast<unsigned long long*>(counters);
     TreeDev tr = to_dev(tree);
     tr.accel = nullptr;   // the counters are the reference's: levels of the plain root descent
-    if (tree->N == 2) hipLaunchKernelGGL((count_fwd_kernel<true>), dim3(nb), dim3(kBlock), 0, st, tr, to_dev(rays, tree), to_dev(opt), c);
-    else hipLaunchKernelGGL((count_fwd_kernel<false>), dim3(nb), dim3(kBlock), 0, st, tr, to_dev(rays, tree), to_dev(opt), c);
+    hipLaunchKernelGGL(tree->N == 2 ? count_fwd_kernel<true> : count_fwd_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       tr, to_dev(rays, tree), to_dev(opt), c);
     return check_launch(fn);
 }
 
@@ -1012,8 +864,8 @@ int svoxt_count_touched(const svoxt_tree* tree, const svoxt_rays* rays, const sv
     const unsigned nb = nblocks(rays->Q);
     const uint32_t n_slots = (uint32_t)(tree->n_internal * tree->N * tree->N * tree->N);
     unsigned long long* lg = reinterpret_cast<unsigned long long*>(longest);
-    if (tree->N == 2) hipLaunchKernelGGL((count_touched_kernel<true>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), row_mask, tree_mask, n_slots, lg);
-    else hipLaunchKernelGGL((count_touched_kernel<false>), dim3(nb), dim3(kBlock), 0, st, to_dev(tree), to_dev(rays, tree), to_dev(opt), row_mask, tree_mask, n_slots, lg);
+    hipLaunchKernelGGL(tree->N == 2 ? count_touched_kernel<true> : count_touched_kernel<false>, dim3(nb), dim3(kBlock), 0, st,
+                       to_dev(tree), to_dev(rays, tree), to_dev(opt), row_mask, tree_mask, n_slots, lg);
     return check_launch(fn);
 }
 

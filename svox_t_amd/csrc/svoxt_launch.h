@@ -49,8 +49,8 @@ inline int64_t rec_capacity(int64_t bytes, int64_t Q) {       // records per ray
     return S > 4096 ? 4096 : S;
 }
 
-// Specialised payloads: (format, C, BD) with all components selected.
-struct Payload { int fmt, C, BD; };
+// the channel counts of the specialised RGBA kernels (rows of 4 / 8 / 16 / 32 floats)
+using RgbaWidths = IntSet<3, 7, 15, 31>;
 
 // transformation_matrices only matter for view-dependent formats (for RGBA the
 // reference's per-sample basis re-evaluation is a no-op, rt_kernel.cu:181-183)
@@ -64,15 +64,13 @@ inline bool full_comp(const svoxt_options* o) {
 
 // can the specialised kernels serve this tree / options pair with its view rotations?
 inline bool xform_special(const svoxt_tree* t, const svoxt_options* o) {
-    return t->N == 2 && o->format == SVOXT_FORMAT_SH && t->K == 3 * o->basis_dim + 1 &&
-           (o->basis_dim == 1 || o->basis_dim == 4 || o->basis_dim == 9 || o->basis_dim == 16 || o->basis_dim == 25);
+    return t->N == 2 && o->format == SVOXT_FORMAT_SH && t->K == 3 * o->basis_dim + 1 && special_basis(o->basis_dim);
 }
 
 // SG / ASG payloads with an SH-sized lobe count and three channels (r03): a ray's basis values are formed once
 // (precalc_lobes) and used like an SH basis by the <LOBES> instances of the FMT_SH kernels.
 inline bool lobes_payload(const Opts& opt, int K) {
-    return (opt.format == FMT_SG || opt.format == FMT_ASG) && K == 3 * opt.basis_dim + 1 &&
-           (opt.basis_dim == 1 || opt.basis_dim == 4 || opt.basis_dim == 9 || opt.basis_dim == 16 || opt.basis_dim == 25);
+    return (opt.format == FMT_SG || opt.format == FMT_ASG) && K == 3 * opt.basis_dim + 1 && special_basis(opt.basis_dim);
 }
 
 // volume_render_backward / opacity_render_backward behind the C ABI's entry points (svoxt_bwd.hip)

@@ -406,16 +406,9 @@ MotionDev to_dev(const svoxt_motion* m) {
 
 unsigned blocks_of(int64_t Q, int block) { return (unsigned)((Q + block - 1) / block); }
 
+// the padded feature width FMAX of the kernels' instances (with_int(FmaxWidths{}, fmax_of(F), ...))
 int fmax_of(int F) { return F <= 4 ? 4 : F <= 8 ? 8 : F <= 16 ? 16 : 32; }
-
-// run BODY with the compile-time FMAX matching the runtime feature width
-#define SVOXT_MOTION_DISPATCH(F, BODY)                         \
-    switch (fmax_of(F)) {                                      \
-        case 4: { constexpr int FMAX = 4; BODY } break;        \
-        case 8: { constexpr int FMAX = 8; BODY } break;        \
-        case 16: { constexpr int FMAX = 16; BODY } break;      \
-        default: { constexpr int FMAX = 32; BODY } break;      \
-    }
+using FmaxWidths = IntSet<4, 8, 16, 32>;
 
 }  // namespace
 
@@ -433,12 +426,8 @@ int svoxt_motion_render(const svoxt_tree* tree, const svoxt_rays* rays, const sv
         return set_error(SVOXT_ERR_INVALID, "%s: an output pointer is NULL", fn);
     const TreeDev tr = to_dev(tree);
     const unsigned nb = blocks_of(rays->Q, kMotionBlock);
-    if (tree->N == 2)
-        hipLaunchKernelGGL((motion_render_kernel<true>), dim3(nb), dim3(kMotionBlock), 0, (hipStream_t)stream,
-                           tr, to_dev(rays, tree), to_dev(opt), (int)tree->extra_rows, out, depth, hit_point, data_idx);
-    else
-        hipLaunchKernelGGL((motion_render_kernel<false>), dim3(nb), dim3(kMotionBlock), 0, (hipStream_t)stream,
-                           tr, to_dev(rays, tree), to_dev(opt), (int)tree->extra_rows, out, depth, hit_point, data_idx);
+    hipLaunchKernelGGL(tree->N == 2 ? motion_render_kernel<true> : motion_render_kernel<false>, dim3(nb), dim3(kMotionBlock), 0,
+                       (hipStream_t)stream, tr, to_dev(rays, tree), to_dev(opt), (int)tree->extra_rows, out, depth, hit_point, data_idx);
     return check_launch(fn);
 }
 
@@ -475,14 +464,13 @@ int svoxt_motion_feature_render_fwd(const svoxt_tree* tree, const svoxt_motion* 
     const Opts od = to_dev(opt);
     const int F = motion->feature_dim;
     const unsigned nb = blocks_of(rays->Q, kMotionBlock);
-    SVOXT_MOTION_DISPATCH(F,
+    with_int(FmaxWidths{}, fmax_of(F), [&](auto FMAX) {
         if (tree->M > 0)
             hipLaunchKernelGGL((motion_blend_kernel<FMAX, 1>), dim3(blocks_of(tree->M, 256)), dim3(256), 0, st, mo, tree->M, blended);
-        if (tree->N == 2)
-            hipLaunchKernelGGL((motion_feature_fwd_kernel<true, FMAX>), dim3(nb), dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, out);
-        else
-            hipLaunchKernelGGL((motion_feature_fwd_kernel<false, FMAX>), dim3(nb), dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, out);
-    )
+        hipLaunchKernelGGL((tree->N == 2 ? motion_feature_fwd_kernel<true, FMAX> : motion_feature_fwd_kernel<false, FMAX>), dim3(nb),
+                           dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, out);
+        return true;
+    });
     return check_launch(fn);
 }
 
@@ -512,17 +500,14 @@ int svoxt_motion_feature_render_bwd(const svoxt_tree* tree, const svoxt_motion* 
     const unsigned nb = blocks_of(rays->Q, kMotionBlock);
     const unsigned nbm = blocks_of(tree->M, 256);
     const bool lds = jbytes <= 65536;
-    SVOXT_MOTION_DISPATCH(F,
+    with_int(FmaxWidths{}, fmax_of(F), [&](auto FMAX) {
         hipLaunchKernelGGL((motion_blend_kernel<FMAX, 2>), dim3(nbm), dim3(256), 0, st, mo, tree->M, blended);
-        if (tree->N == 2)
-            hipLaunchKernelGGL((motion_feature_bwd_kernel<true, FMAX>), dim3(nb), dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, grad_out, grad_blended);
-        else
-            hipLaunchKernelGGL((motion_feature_bwd_kernel<false, FMAX>), dim3(nb), dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, grad_out, grad_blended);
-        if (lds)
-            hipLaunchKernelGGL((motion_reduce_kernel<FMAX, true>), dim3(nbm), dim3(256), jbytes, st, mo, tree->M, grad_blended, grad_joint_features);
-        else
-            hipLaunchKernelGGL((motion_reduce_kernel<FMAX, false>), dim3(nbm), dim3(256), 0, st, mo, tree->M, grad_blended, grad_joint_features);
-    )
+        hipLaunchKernelGGL((tree->N == 2 ? motion_feature_bwd_kernel<true, FMAX> : motion_feature_bwd_kernel<false, FMAX>), dim3(nb),
+                           dim3(kMotionBlock), 0, st, tr, F, blended, rd, od, grad_out, grad_blended);
+        hipLaunchKernelGGL((lds ? motion_reduce_kernel<FMAX, true> : motion_reduce_kernel<FMAX, false>), dim3(nbm), dim3(256),
+                           lds ? jbytes : 0, st, mo, tree->M, grad_blended, grad_joint_features);
+        return true;
+    });
     return check_launch(fn);
 }
 

@@ -20,9 +20,7 @@ namespace {
 
 constexpr int64_t kAlign = 256;
 inline int64_t up(int64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-inline bool wide_rows(const svoxt_tree* t, const svoxt_options* o) {
-    return o->format == SVOXT_FORMAT_RGBA && (t->K == 8 || t->K == 16 || t->K == 32);
-}
+inline bool wide_rows(const svoxt_tree* t, const svoxt_options* o) { return o->format == SVOXT_FORMAT_RGBA && chan_rows(t->K); }
 inline bool sh_like(const svoxt_options* o) {
     return o->format == SVOXT_FORMAT_SH || o->format == SVOXT_FORMAT_SG || o->format == SVOXT_FORMAT_ASG;
 }
@@ -33,7 +31,7 @@ inline bool is_tiled(const svoxt_rays* r) {
 // per-leaf view rotations whose recording forward runs march and shade as one launch (SH 1 / 4 / 9)
 inline bool xf_roles(const svoxt_tree* t, const svoxt_options* o) {
     return t->xform != nullptr && t->N == 2 && t->weight_accum == nullptr && o->format == SVOXT_FORMAT_SH &&
-           (o->basis_dim == 1 || o->basis_dim == 4 || o->basis_dim == 9) && t->K == 3 * o->basis_dim + 1;
+           xf_roles_basis(o->basis_dim) && t->K == 3 * o->basis_dim + 1;
 }
 inline char* at(void* ws, int64_t off) { return static_cast<char*>(ws) + off; }
 
@@ -44,12 +42,12 @@ struct PadLayout { int Kp, real, dummy, w; };
 inline bool pad_layout(const svoxt_tree* t, const svoxt_options* o, PadLayout* p) {
     const int K = t->K, bd = o->basis_dim;
     if (o->format == SVOXT_FORMAT_RGBA) {
-        if (K < 2 || K > 32 || K == 4 || K == 8 || K == 16 || K == 32) return false;
+        if (K < 2 || K > 32 || K == 4 || chan_rows(K)) return false;
         const int Kp = K < 4 ? 4 : K < 8 ? 8 : K < 16 ? 16 : 32;
         *p = PadLayout{Kp, K - 1, Kp - K, 1};
         return true;
     }
-    if (!(bd == 1 || bd == 4 || bd == 9 || bd == 16 || bd == 25) || (K - 1) % bd != 0 || o->min_comp != 0 || o->max_comp != bd - 1) return false;
+    if (!special_basis(bd) || (K - 1) % bd != 0 || o->min_comp != 0 || o->max_comp != bd - 1) return false;
     const int C = (K - 1) / bd;
     if (C < 1 || C >= 3) return false;
     *p = PadLayout{3 * bd + 1, C * bd, (3 - C) * bd, bd};
