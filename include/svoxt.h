@@ -746,6 +746,50 @@ int svoxt_p2v_bwd(const float* grad_output, const float* points, const float* po
                   float kernel_radius, float conv_radius, const int32_t* order, float* points_grad,
                   float* point_features_grad, void* stream);
 
+/* ---- Pruning: N3Tree.prune (the halves the reference keeps as tensor ops: merge, svox.py:352-389, and
+ * shrink_to_fit, :600-642) ------------------------------------------------------------------------------
+ *
+ * From the tree tables (child device int32 [>= n_internal, N, N, N], data the same extent, parent_depth device int32
+ * [>= n_internal, 2]), the number M of feature rows and a decision per slot of child -- keep (device uint8, non-zero =
+ * kept) or weights (device float32; kept iff weights >= threshold, so a NaN weight drops the slot); exactly one of the
+ * two, entries at slots that are not leaves are ignored -- the tables of the pruned tree:
+ *   1. a leaf (child == 0) that is not kept becomes empty: data = empty_index.  (A leaf is empty when its data word,
+ *      read as unsigned, is >= M; a kept empty leaf keeps its word.)
+ *   2. collapse != 0: a node other than the root is removed iff no kept, non-empty leaf lies below it; its parent slot
+ *      becomes an empty leaf (child 0, data empty_index).  collapse == 0: every node stays.
+ *   3. the nodes that stay keep their order and are numbered 0, 1, 2, ...; child words are new_id(child) - new_id(node),
+ *      parent_depth[:, 0] is new_id(parent) * N^3 + slot (the root's row is copied), parent_depth[:, 1] is copied,
+ *      data at slots that are not leaves is empty_index.
+ *   4. compact_features != 0: a feature row stays iff a kept non-empty leaf names it; the rows that stay keep their
+ *      order, data is renumbered, row_map (device int64 [new_M]) lists the old row of every new one.
+ *      compact_features == 0: data words are left as they are, new_M = M, row_map is not written.
+ * Integer work, no order dependence: the outputs are a function of the inputs, identical from run to run.
+ *
+ * svoxt_prune_count marks and scans; counts (device int64[3]) receives the nodes that stay, the rows that stay and the
+ * leaves dropped in step 1.  The host reads it -- the one host read -- allocates child_out / data_out [new_n_internal,
+ * N, N, N], parent_depth_out [new_n_internal, 2] and row_map, and calls svoxt_prune_emit with the same inputs and the
+ * workspace unchanged; every row of the outputs is written.  workspace: svoxt_prune_workspace_bytes(n_internal, M)
+ * device bytes (8 bytes per node and per feature row; -1 for extents outside [1, 2^31) / [0, 2^31)).
+ * Every argument is checked before any HIP call (SVOXT_ERR_INVALID): N in [2, 16], n_internal * N^3 < 2^31,
+ * empty_index >= M as an unsigned number, no NULL where a pointer is required. */
+int64_t svoxt_prune_workspace_bytes(int64_t n_internal, int64_t M);
+int svoxt_prune_count(const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n_internal,
+                      int32_t N, int64_t M, const uint8_t* keep, const float* weights, float threshold,
+                      int32_t collapse, int32_t compact_features, void* workspace, int64_t workspace_bytes,
+                      int64_t* counts, void* stream);
+int svoxt_prune_emit(const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n_internal,
+                     int32_t N, int64_t M, const uint8_t* keep, const float* weights, float threshold,
+                     int32_t compact_features, const void* workspace, int64_t workspace_bytes,
+                     int64_t new_n_internal, int64_t new_M, int32_t empty_index, int32_t* child_out,
+                     int32_t* data_out, int32_t* parent_depth_out, int64_t* row_map, void* stream);
+
+/* dst[i, :] = src[row_map[i], :] for i < n: the feature table (and whatever else is kept per row: optimizer state)
+ * behind a prune.  src device float32 [src_rows, cols], dst [n, cols], row_map device int64 [n]; an entry outside
+ * [0, src_rows) leaves its row of dst unwritten.  16 bytes a thread when cols is a multiple of 4 and both tables are
+ * 16-byte aligned. */
+int svoxt_prune_gather_rows(const float* src, int64_t src_rows, const int64_t* row_map, float* dst, int64_t n,
+                            int32_t cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

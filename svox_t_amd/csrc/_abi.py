@@ -150,6 +150,11 @@ EXPORTS = {
     "svoxt_p2v_workspace_bytes": (_i64, [_i64, _i32, _vp, _vp, ctypes.c_float]),
     "svoxt_p2v_fwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_p2v_bwd": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "svoxt_prune_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_prune_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, ctypes.c_float, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "svoxt_prune_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i64, _i32,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_prune_gather_rows": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -1,6 +1,6 @@
 """The operators of `svox_t.csrc` around the render path: point query (svox_kernel.cu:45-94, 240-324), the roofline
 counters, the motion variants (rt_kernel.cu:698-1061), point skinning (svox_kernel.cu:123-211), octree construction
-(svox.py:160-161, 488-560) -- marshalling only, one C-ABI call each (two for the builder)."""
+(svox.py:160-161, 488-560), pruning -- marshalling only, one C-ABI call each (two for the builder and for prune)."""
 from __future__ import annotations
 
 import ctypes
@@ -337,6 +337,98 @@ def build_octree(points: torch.Tensor, offset: torch.Tensor, scaling: torch.Tens
               _ptr(ws), nbytes, _ptr(child), _ptr(data), _ptr(parent_depth), n, int(empty_index),
               _stream(dev))
     return child, data, parent_depth, n
+
+
+def prune_tree(child: torch.Tensor, data: torch.Tensor, parent_depth: torch.Tensor, n_internal: int, M: int,
+               keep: torch.Tensor = None, weights: torch.Tensor = None, threshold: float = None, collapse: bool = True,
+               compact_features: bool = True, reserve: int = 0, empty_index: int = 1410065408, return_dropped: bool = False):
+    """The tables of a pruned tree in one pipeline (not an entry of the reference's extension, which has merge and
+    shrink_to_fit as tensor ops: svox.py:352-389, 600-642; include/svoxt.h, svoxt_prune_count has the four steps).
+
+    keep: bool / uint8 with the shape of child, or weights: float32 of that shape with `threshold` (kept iff
+    weights >= threshold; NaN drops).  Returns (child [n' + reserve, N, N, N], data [n' + reserve, N, N, N, 1],
+    parent_depth [n' + reserve, 2], n', row_map): new tensors, the `reserve` rows behind the tree initialised like unused
+    rows of an N3Tree; row_map int64 [M'] = the old row of every new feature row (None without compact_features);
+    with return_dropped a sixth value, the number of leaves that held a feature row and were not kept.
+    One host read (the counts that size the outputs)."""
+    for nm, x in (("child", child), ("data", data), ("parent_depth", parent_depth)):
+        _check_input(x, nm)
+        if x.dtype != torch.int32:
+            raise RuntimeError(f"{nm} must be int32")
+        if x.device != child.device:
+            raise RuntimeError(f"{nm} must be on the device of child")
+    if child.dim() != 4 or child.shape[1] < 2 or child.shape[1] > 16 or child.shape[2] != child.shape[1] \
+            or child.shape[3] != child.shape[1]:
+        raise RuntimeError("child must be int32 [cap, N, N, N] with N in [2, 16]")
+    cap, N = child.shape[0], child.shape[1]
+    if data.numel() != child.numel() or data.shape[0] != cap:
+        raise RuntimeError("data must be int32 [cap, N, N, N, 1] matching child")
+    if parent_depth.dim() != 2 or tuple(parent_depth.shape) != (cap, 2):
+        raise RuntimeError("parent_depth must be int32 [cap, 2]")
+    n, M, reserve = int(n_internal), int(M), int(reserve)
+    if n < 1 or n > cap:
+        raise RuntimeError("n_internal must be in [1, cap]")
+    if M < 0 or reserve < 0:
+        raise RuntimeError("M and reserve must be >= 0")
+    if (keep is None) == (weights is None):
+        raise RuntimeError("exactly one of keep / weights must be given")
+    if keep is not None:
+        _check_input(keep, "keep")
+        if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != tuple(child.shape):
+            raise RuntimeError("keep must be a bool or uint8 tensor with the shape of child")
+        if threshold is not None:
+            raise RuntimeError("threshold goes with weights, not with keep")
+        decision, thr = keep, 0.0
+    else:
+        _check_input(weights, "weights")
+        if weights.dtype != torch.float32 or tuple(weights.shape) != tuple(child.shape):
+            raise RuntimeError("weights must be a float32 tensor with the shape of child")
+        if threshold is None or float(threshold) != float(threshold):
+            raise RuntimeError("weights needs a threshold (not NaN)")
+        decision, thr = weights, float(threshold)
+    if decision.device != child.device:
+        raise RuntimeError("keep / weights must be on the device of child")
+    dev = child.device
+    kp, wp = (_ptr(keep), None) if keep is not None else (None, _ptr(weights))
+    with _on(dev):
+        nbytes = _lib.svoxt_prune_workspace_bytes(n, M)
+        if nbytes < 0:
+            raise RuntimeError("prune_tree: n_internal and M must be below 2^31")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((3,), dtype=torch.int64, device=dev)
+        _call("svoxt_prune_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, kp, wp, thr, int(bool(collapse)),
+              int(bool(compact_features)), _ptr(ws), nbytes, _ptr(counts), _stream(dev))
+        new_n, new_M, dropped = (int(v) for v in counts.tolist())      # the one host read: sizes the outputs
+        rows = new_n + reserve
+        child_out = torch.empty((rows, N, N, N), dtype=torch.int32, device=dev)
+        data_out = torch.empty((rows, N, N, N, 1), dtype=torch.int32, device=dev)
+        pd_out = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+        if reserve > 0:
+            child_out[new_n:].zero_()
+            data_out[new_n:].fill_(int(empty_index))
+            pd_out[new_n:].zero_()
+        row_map = torch.empty((new_M,), dtype=torch.int64, device=dev) if compact_features else None
+        _call("svoxt_prune_emit", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, kp, wp, thr, int(bool(compact_features)),
+              _ptr(ws), nbytes, new_n, new_M, int(empty_index), _ptr(child_out), _ptr(data_out), _ptr(pd_out), _ptr(row_map),
+              _stream(dev))
+    res = (child_out, data_out, pd_out, new_n, row_map)
+    return res + (dropped,) if return_dropped else res
+
+
+def gather_rows(src: torch.Tensor, row_map: torch.Tensor) -> torch.Tensor:
+    """src[row_map] for a float32 [M, K] table and prune_tree's row_map (svoxt_prune_gather_rows: 16 bytes a thread)."""
+    _check_input(src, "src")
+    _check_input(row_map, "row_map")
+    if src.dtype != torch.float32 or src.dim() != 2 or src.shape[1] < 1:
+        raise RuntimeError("src must be float32 [M, K]")
+    if row_map.dtype != torch.int64 or row_map.dim() != 1 or row_map.device != src.device:
+        raise RuntimeError("row_map must be int64 [M'] on the device of src")
+    dev = src.device
+    with _on(dev):
+        dst = torch.empty((row_map.shape[0], src.shape[1]), dtype=torch.float32, device=dev)
+        _call("svoxt_prune_gather_rows", _ptr(src), src.shape[0], _ptr(row_map), _ptr(dst), row_map.shape[0], src.shape[1],
+              _stream(dev))
+    return dst
 
 
 def _p2v_args(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius, conv_radius):

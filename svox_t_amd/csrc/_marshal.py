@@ -118,6 +118,9 @@ def _pack_tree(tree: TreeSpec) -> _CTree:
             _check_input(t, nm)
     if tree.features.dtype != torch.float32 or tree.features.dim() != 2:
         raise RuntimeError("features must be a float32 [M, K] tensor")
+    if tree.features.shape[0] == 0:
+        # (what N3Tree.prune leaves when nothing was kept: no kernel here has been shown to run on a NULL table)
+        raise RuntimeError("features has no rows: a tree without a feature row cannot be rendered or queried")
     if tree.child.dtype != torch.int32 or tree.child.dim() != 4:
         raise RuntimeError("child must be an int32 [n, N, N, N] tensor")
     if tree.data.dtype != torch.int32 or tree.data.numel() != tree.child.numel():

@@ -14,6 +14,7 @@ Layout (identical to the reference so trees interchange):
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
 
 import torch
 from torch import autograd, nn
@@ -24,6 +25,14 @@ _C = _get_c_extension()
 
 # int(1e10) as int32: the fill value of `data` in the reference (svox.py:124).
 EMPTY_INDEX = 1410065408
+
+
+class PruneResult(NamedTuple):
+    """What N3Tree.prune did."""
+    n_internal: int
+    nodes_removed: int
+    leaves_dropped: int            # leaves that held a feature row and were not kept
+    row_map: Optional[torch.Tensor]
 
 
 class _QueryVerticalFunction(autograd.Function):
@@ -266,6 +275,64 @@ class N3Tree(nn.Module):
         self.child = torch.cat((self.child, torch.zeros((cap_needed, N, N, N), dtype=torch.int32, device=dev)))
         self.parent_depth = torch.cat((self.parent_depth,
                                        torch.zeros((cap_needed, 2), dtype=torch.int32, device=dev)))
+
+    # ------------------------------------------------------------------ prune
+    def prune(self, keep=None, *, weights=None, threshold=None, collapse=True, compact_features=True, reserve=0):
+        """Drop leaves, collapse what is left empty, compact the tree (one HIP pipeline, csrc/svoxt_prune.hip; the
+        reference has the halves as tensor ops, both stale in this fork: merge, svox.py:352-389, and shrink_to_fit,
+        :600-642, which never touches `features`).
+
+        The decision is per slot of `child`, entries at slots that are not leaves are ignored: `keep`, bool / uint8
+        with the shape of `child`, or `weights` (float32 of that shape: what `accumulate_weights()` gives as
+        `accum.value`) with `threshold` -- a slot is kept iff weights >= threshold, so a NaN weight drops it.
+          1. every leaf that is not kept becomes empty (data = EMPTY_INDEX);
+          2. `collapse`: every node but the root below which no kept, non-empty leaf is left is removed, its parent
+             slot becomes an empty leaf;
+          3. the nodes that remain keep their order and are renumbered, `reserve` free rows behind them;
+          4. `compact_features`: the feature rows no remaining leaf names are removed, the others keep their order.
+        Without `collapse` the geometry of every remaining leaf is unchanged, and dropping only leaves that contribute
+        nothing (sigma <= 0, or empty) leaves every render bit for bit what it was.  With `collapse` empty space is
+        described by fewer, larger leaves: the march takes other steps through it (a step is a leaf crossing plus
+        `step_size`), so renders change within step-size effects -- the price of a smaller tree, as with the
+        reference's merge.
+
+        Replaces `child`, `data`, `parent_depth` and, with `compact_features`, `self.features` by a NEW
+        nn.Parameter(features[row_map]): an optimizer that holds the old parameter has to be rebuilt, its state sliced
+        with the result's `row_map` (the reference's warning on shrink_to_fit, svox.py:606-607).  A tree left without a
+        feature row (nothing kept) is refused by the renderer and the point query (RuntimeError) until it has rows again.  GPU only.
+        :return: PruneResult(n_internal, nodes_removed, leaves_dropped, row_map); row_map int64 [M'] = the old row of
+                 every new feature row, None without `compact_features`"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if not self.data.is_cuda:
+            raise RuntimeError("prune: only the GPU (HIP) path exists; move the tree to a GPU")
+        with torch.no_grad():
+            before = self.filled
+            child, data, parent_depth, n, row_map, dropped = _C.prune_tree(
+                self.child, self.data, self.parent_depth, before, self.features.shape[0], keep, weights, threshold,
+                collapse, compact_features, reserve, EMPTY_INDEX, return_dropped=True)
+            _C.invalidate_caches(self.child)         # the old tables' acceleration grid goes now, not with the tensor
+            self.child, self.data, self.parent_depth = child, data, parent_depth
+            if row_map is not None:
+                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
+                                             requires_grad=self.features.requires_grad)
+            self._n_internal.fill_(n)
+            self.filled = n
+            self._invalidate()
+        return PruneResult(n, before - n, dropped, row_map)
+
+    def shrink_to_fit(self):
+        """Trim the topology buffers to the nodes in use (the reference's name, svox.py:600; its node
+        defragmentation is what prune() does).  Returns True iff anything changed."""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if self.capacity == self.filled:
+            return False
+        n = self.filled
+        self.child, self.data = self.child[:n].clone(), self.data[:n].clone()
+        self.parent_depth = self.parent_depth[:n].clone()
+        self._invalidate()
+        return True
 
     # ------------------------------------------------------------- properties
     @property
