@@ -790,6 +790,36 @@ int svoxt_prune_emit(const int32_t* child, const int32_t* data, const int32_t* p
 int svoxt_prune_gather_rows(const float* src, int64_t src_rows, const int64_t* row_map, float* dst, int64_t n,
                             int32_t cols, void* stream);
 
+/* ---- Dense-grid weights: grid_weights (the reference's grid_weight_render, rt_kernel.cu:1240-1344, 1454-1478) ----
+ *
+ * Marches rays through a dense density volume sigma (device float32 [R, R, R], cell (u, v, w) at (u R + v) R + w) and
+ * keeps per cell the largest compositing weight any ray gave it (weight) and the number of samples taken in it (hits),
+ * both device float32 [R, R, R].  One ray: the preamble of the render calls (camera ray and NDC warp as in
+ * svoxt_rays / options.ndc_*, p' = offset + scaling p, unit direction, slab test), then while t < tmax: the point
+ * origin + t dir, clamped to [0, 1 - 1e-6], times R gives the cell and the cell-local point; delta_t = the cell's
+ * chord / R + step_size; if sigma[cell] > sigma_thresh: att = exp(-delta_t delta_scale sigma), w = T (1 - att),
+ * T *= att, weight[cell] = max(weight[cell], w), hits[cell] += 1; t += delta_t.  There is no early stop and stop_thresh
+ * is not read: of the options only step_size, sigma_thresh and ndc_* are.
+ *
+ * The maximum is taken on the weight's bit pattern as a signed integer (a negative weight -- possible only with a
+ * negative sigma_thresh -- never raises a cell) and the count in integers, converted to float once (exact to 2^24 a
+ * cell, where the reference's float adds agree; at most 2^32 - 1 samples a cell and call): neither depends on the order
+ * the rays arrive in, so the outputs are bit-identical from run to run.
+ *
+ * Rays: camera mode (rays->c2w != NULL): n_views >= 1 cameras, c2w_stride (12: [V, 3, 4], 16: [V, 4, 4]) floats apart,
+ * sharing fx, fy, image_width and image_height (any size >= 1; walked in 8 x 8 pixel tiles), rays->Q = image_width *
+ * image_height; the result is over all n_views * Q rays, one launch.  Ray-batch mode (c2w NULL): origins / dirs device
+ * [Q, 3] (vdirs and order are not read), n_views = 1, c2w_stride ignored.
+ * offset / scaling: device float32 [3], as svoxt_tree's.  flags: 0 or SVOXT_GRIDW_ACCUMULATE.
+ * Every argument is checked before any HIP call (SVOXT_ERR_INVALID): R >= 1 with R^3 < 2^31, step_size finite and > 0
+ * (so that every march ends), n_views * tiles < 2^31, no NULL where a pointer is required.  No workspace, no host read,
+ * no synchronisation.  While the call's kernels run, hits holds integers: it is a float volume again when they end. */
+#define SVOXT_GRIDW_ACCUMULATE 1  /* weight / hits hold an earlier call's result (non-negative integers in hits) and are
+                                     updated -- max and count compose across calls; else they are zeroed first */
+int svoxt_grid_weights(const float* sigma, int32_t R, const svoxt_rays* rays, int32_t n_views, int32_t c2w_stride,
+                       const svoxt_options* opt, const float* offset, const float* scaling, int32_t flags,
+                       float* weight, float* hits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

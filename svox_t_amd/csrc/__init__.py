@@ -1175,4 +1175,4 @@ from ._extras import (assign_vertical, build_octree, bwd_check, bwd_counters, ca
                       count_forward, count_touched, grid_weight_render, motion_feature_render,
                       motion_feature_render_backward, motion_render, p2v, p2v_backward, p2v_order, quantize_median_cut,
                       query_vertical, query_vertical_backward, refine_leaves, warp_vertices, warp_vertices_backward)
-from ._extras import gather_rows, prune_tree  # noqa: E402,F401
+from ._extras import gather_rows, grid_weights, prune_tree  # noqa: E402,F401

@@ -7,8 +7,8 @@ import ctypes
 
 import torch
 
-from ._abi import _CMotion, _CTree, _lib
-from ._marshal import (RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _numel, _pack_opts, _pack_rays,
+from ._abi import _CMotion, _CRays, _CTree, _lib
+from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _numel, _pack_opts, _pack_rays,
                        _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
 
 def _check_indices(indices):
@@ -516,20 +516,113 @@ def p2v_backward(grad_output: torch.Tensor, points: torch.Tensor, point_features
     return [pg, fg]
 
 
+GRIDW_ACCUMULATE = 1          # SVOXT_GRIDW_ACCUMULATE (include/svoxt.h)
+
+
+def grid_weights(sigma: torch.Tensor, cams_or_rays, opt: RenderOptions, offset: torch.Tensor, scaling: torch.Tensor,
+                 out=None):
+    """The reference's grid_weight_render (rt_kernel.cu:1240-1344, 1454-1478) over many views: per cell of the dense
+    float32 volume sigma [R, R, R] (or [R, R, R, 1]) the largest compositing weight any ray gave it and the number of
+    samples taken in it.  Returns (weight, hits), float32 with the shape of sigma.
+
+    cams_or_rays: a CameraSpec whose c2w is [V, 3, 4] / [V, 4, 4] (or one [3, 4] / [4, 4] matrix) -- V cameras
+    sharing fx, fy, width, height, all marched by one launch -- or a RaysSpec (origins, dirs [Q, 3]; vdirs is not
+    read).  Of opt, step_size, sigma_thresh and ndc_* are read.  out = (weight, hits): updated instead of zeroed
+    (max and count compose across calls).
+    The checks of shapes and values come before the device checks, and all of them before any GPU work."""
+    if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32:
+        raise RuntimeError("sigma must be a float32 tensor")
+    if sigma.dim() not in (3, 4) or sigma.shape[0] < 1 or sigma.shape[1] != sigma.shape[0] or sigma.shape[2] != sigma.shape[0] \
+            or (sigma.dim() == 4 and sigma.shape[3] != 1):
+        raise RuntimeError("sigma must be a cubic volume [R, R, R] or [R, R, R, 1] with R >= 1")
+    R = sigma.shape[0]
+    if R ** 3 >= 1 << 31:
+        raise RuntimeError("sigma is too large: R^3 must be below 2^31")
+    step = float(opt.step_size)
+    if not (step > 0.0) or step == float("inf"):
+        raise RuntimeError("step_size must be finite and > 0")
+    for name, x in (("offset", offset), ("scaling", scaling)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != 3:
+            raise RuntimeError(f"{name} must be float32 [3]")
+    if isinstance(cams_or_rays, CameraSpec):
+        c2w = cams_or_rays.c2w
+        if not isinstance(c2w, torch.Tensor) or c2w.dtype != torch.float32 or c2w.dim() not in (2, 3) \
+                or tuple(c2w.shape[-2:]) not in ((3, 4), (4, 4)):
+            raise RuntimeError("cameras must be float32 [V, 3, 4] or [V, 4, 4]")
+        V = c2w.shape[0] if c2w.dim() == 3 else 1
+        if V < 1:
+            raise RuntimeError("cameras holds no view")
+        w, h = int(cams_or_rays.width), int(cams_or_rays.height)
+        if w < 1 or h < 1:
+            raise RuntimeError("camera width / height must be positive")
+        cr = _CRays()
+        cr.Q, cr.image_width, cr.image_height = w * h, w, h
+        cr.fx, cr.fy = float(cams_or_rays.fx), float(cams_or_rays.fy)
+        stride, tensors = 4 * c2w.shape[-2], [("cameras", c2w)]
+    elif isinstance(cams_or_rays, RaysSpec):
+        o, d = cams_or_rays.origins, cams_or_rays.dirs
+        for name, x in (("origins", o), ("dirs", d)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3:
+                raise RuntimeError(f"{name} must be float32 [Q, 3]")
+        if o.shape[0] != d.shape[0]:
+            raise RuntimeError("origins and dirs must have the same number of rays")
+        c2w, V, stride = None, 1, 0
+        cr = _CRays()
+        cr.Q = o.shape[0]
+        tensors = [("origins", o), ("dirs", d)]
+    else:
+        raise RuntimeError("grid_weights needs a CameraSpec or a RaysSpec")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise RuntimeError("out must be (weight, hits)")
+        for name, x in zip(("out weight", "out hits"), out):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != tuple(sigma.shape):
+                raise RuntimeError(f"{name} must be float32 with the shape of sigma")
+        if out[0] is out[1] or out[0].data_ptr() == out[1].data_ptr():
+            raise RuntimeError("out weight and out hits must be two tensors")
+        tensors += [("out weight", out[0]), ("out hits", out[1])]
+    for name, x in [("sigma", sigma), ("offset", offset), ("scaling", scaling)] + tensors:
+        _check_input(x, name)
+        if x.device != sigma.device:
+            raise RuntimeError(f"{name} must be on the device of sigma")
+    dev = sigma.device
+    if c2w is not None:
+        cr.c2w = c2w.data_ptr()
+    else:
+        cr.origins, cr.dirs = _ptr(o), _ptr(d)
+    co = _pack_opts(opt)
+    flags = GRIDW_ACCUMULATE if out is not None else 0
+    with _on(dev):
+        if out is not None:
+            weight, hits = out
+        else:
+            weight = torch.empty(sigma.shape, dtype=torch.float32, device=dev)     # zeroed by the call
+            hits = torch.empty(sigma.shape, dtype=torch.float32, device=dev)
+        _call("svoxt_grid_weights", sigma.data_ptr(), R, ctypes.byref(cr), V, stride, ctypes.byref(co), offset.data_ptr(),
+              scaling.data_ptr(), flags, weight.data_ptr(), hits.data_ptr(), _stream(dev))
+    return weight, hits
+
+
 # ---------------------------------------------------------------------------
 # Entry points of svox_t.csrc that are outside this project's hot path
 # (SURVEY.md section 2).  They exist so a caller gets a clear error, not an
 # AttributeError.
 # ---------------------------------------------------------------------------
 
-def _out_of_scope(name):
+def _out_of_scope(name, instead=None):
     def fn(*_a, **_k):
         raise NotImplementedError(
-            f"svox_t_amd.csrc.{name}: outside the accelerated hot path "
-            "(volume_render / opacity / depth / query / construct_tree); see SURVEY.md section 2")
+            f"svox_t_amd.csrc.{name}: " + (instead or
+            "outside the accelerated hot path "
+            "(volume_render / opacity / depth / query / construct_tree); see SURVEY.md section 2"))
     fn.__name__ = name
     return fn
 
 
-for _n in ("assign_vertical", "calc_corners", "grid_weight_render", "quantize_median_cut"):
+for _n in ("assign_vertical", "calc_corners", "quantize_median_cut"):
     globals()[_n] = _out_of_scope(_n)
+# the reference's one-camera form of grid_weights; the name is kept a stub (INTEGRATION.md)
+grid_weight_render = _out_of_scope(
+    "grid_weight_render", "served under another name: grid_weight_render(data, cam, opt, offset, scaling) is "
+    "grid_weights(data, cameras=cam.c2w[None], ...) -- svox_t_amd.grid_weights, or svox_t_amd.csrc.grid_weights(data, cam, "
+    "opt, offset, scaling), which returns the reference's (weight, hits); see INTEGRATION.md")
