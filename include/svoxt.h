@@ -14,6 +14,7 @@
  *   svoxt_query_bwd           <- query_vertical_backward  svox_t/csrc/svox.cpp:46,120   (svox_kernel.cu:380-402)
  *   svoxt_p2v_fwd             <- p2v                      svox_t/csrc/svox.cpp:52,125   (p2v_kernel.cu:240-261)
  *   svoxt_p2v_bwd             <- p2v_backward             svox_t/csrc/svox.cpp:53,126   (p2v_kernel.cu:263-285)
+ *   svoxt_quantize_median_cut <- quantize_median_cut      svox_t/csrc/svox.cpp:71,144   (quantizer.cpp:130-157)
  *   svoxt_tree / svoxt_rays / svoxt_options
  *                             <- TreeSpec / RaysSpec / RenderOptions
  *                                                         svox_t/csrc/include/data_spec.hpp:52-145
@@ -819,6 +820,34 @@ int svoxt_prune_gather_rows(const float* src, int64_t src_rows, const int64_t* r
 int svoxt_grid_weights(const float* sigma, int32_t R, const svoxt_rays* rays, int32_t n_views, int32_t c2w_stride,
                        const svoxt_options* opt, const float* offset, const float* scaling, int32_t flags,
                        float* weight, float* hits, void* stream);
+
+/* ---- Palette quantisation: quantize_median_cut (the reference's CPU recursion, svox_t/csrc/quantizer.cpp:48-157) ------
+ *
+ * Median cut of the rows of data (device float32 [M, K]) into at most 2^order segments, level by level: all rows start
+ * as one segment; for `order` levels every segment of more than one row is cut in two, a segment of <= 1 rows is closed
+ * and keeps its place.  A cut: the split column is the first one with the largest float32 (max - min); the segment is
+ * ordered by (value in that column, row index), -0.0 equal to +0.0; unweighted (weights NULL) the cut is at
+ * l + (r - l) / 2, weighted (weights device float32 [M]) at the first position whose inclusive float64 prefix sum of
+ * weights is > 0.5 x the segment's total, r if none is; an empty child is a segment like any other.  After the last
+ * level the segments, left to right, are the colours 0, 1, ... (the reference's depth-first emission order):
+ * color_id_map (device int32 [M]) receives every row's colour, colors (device float32 [2^order, K]) the (weighted)
+ * mean of every segment's rows, summed in float64 in a fixed order and rounded once.  Differences from the reference:
+ * the row of an empty segment (and every row past the last segment) is zero, not 0 / 0; a non-empty segment whose
+ * weights sum to zero takes the plain mean; ties are broken by row index where nth_element / sort leave them open.
+ * NaN in data is not checked: the result is then unspecified.  No float atomics: bit-identical from run to run.
+ *
+ * Checked before any HIP call (SVOXT_ERR_INVALID): order in [0, 16], K >= 1, 2^order <= M < 2^31, no NULL where a
+ * pointer is required.  workspace: device, svoxt_quantize_workspace_bytes(M, K, order, weighted) bytes (-1 for
+ * arguments outside those limits): ~20 bytes a row (28 weighted) plus 8 K + 24 bytes a colour.  One stream, no host
+ * read, no synchronisation. */
+int64_t svoxt_quantize_workspace_bytes(int64_t M, int32_t K, int32_t order, int32_t weighted);
+int svoxt_quantize_median_cut(const float* data, int64_t M, int32_t K, const float* weights, int32_t order, float* colors,
+                              int32_t* color_id_map, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* data_out[i] = map[data_in[i]] where data_in[i], read as unsigned, is < M (a feature row); other words (empty leaves)
+ * are copied.  data_in, data_out device int32 [n] (may be the same), map device int32 [M]: a tree's data words through
+ * a colour-id map. */
+int svoxt_remap_index(const int32_t* data_in, int32_t* data_out, int64_t n, const int32_t* map, int64_t M, void* stream);
 
 #ifdef __cplusplus
 }

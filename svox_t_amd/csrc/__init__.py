@@ -12,6 +12,7 @@ attribute names, same function names and argument order for the hot path:
     opacity_render_backward(tree, rays, opt, grad)    -> Tensor [M, K]
     query_vertical(tree, indices)                     -> (values, node_ids, data_ids, leaf_node)
     query_vertical_backward(tree, indices, grad)      -> Tensor [M, K]
+    quantize_median_cut(data, weights, order)         -> (colors [2^order, K], color_id_map [M])
 
 Underneath there is no pybind: tensors are marshalled to raw device pointers
 and handed to the C ABI of libsvoxt_hip.so (include/svoxt.h) through ctypes,
@@ -1175,4 +1176,4 @@ from ._extras import (assign_vertical, build_octree, bwd_check, bwd_counters, ca
                       count_forward, count_touched, grid_weight_render, motion_feature_render,
                       motion_feature_render_backward, motion_render, p2v, p2v_backward, p2v_order, quantize_median_cut,
                       query_vertical, query_vertical_backward, refine_leaves, warp_vertices, warp_vertices_backward)
-from ._extras import gather_rows, grid_weights, prune_tree  # noqa: E402,F401
+from ._extras import gather_rows, grid_weights, prune_tree, remap_index  # noqa: E402,F401

@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from ._abi import _CMotion, _CRays, _CTree, _lib
-from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _numel, _pack_opts, _pack_rays,
+from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _check_quantize, _numel, _pack_opts, _pack_rays,
                        _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
 
 def _check_indices(indices):
@@ -603,6 +603,52 @@ def grid_weights(sigma: torch.Tensor, cams_or_rays, opt: RenderOptions, offset: 
     return weight, hits
 
 
+def quantize_median_cut(data: torch.Tensor, weights, order: int):
+    """quantizer.cpp:130-157 on the GPU (csrc/svoxt_quant.hip): median-cut quantisation of the rows of data, float32
+    [M, K], into 2^order colours.  weights: float32 [M], or None / an empty tensor for unweighted.  Returns (colors
+    float32 [2^order, K], color_id_map int32 [M]); include/svoxt.h has the rule of a cut.  0 <= order <= 16,
+    2^order <= M < 2^31.
+
+    Where the reference leaves the result open it is fixed here: ties within a segment are ordered by row index (-0.0
+    equal to +0.0), weight prefixes and colour sums run in float64 in a fixed order, so the result is bit-identical
+    from run to run.  Three deliberate differences: the row of an empty segment is zero (reference: 0 / 0 = NaN; no
+    row maps to it); a non-empty segment whose weights sum to zero takes the plain mean (reference: NaN); NaN in data
+    is not checked and the result is then unspecified.  GPU tensors only; bad arguments raise RuntimeError before any
+    GPU work."""
+    weights, order = _check_quantize(data, weights, order)
+    dev = data.device
+    M, K = data.shape
+    nbytes = _lib.svoxt_quantize_workspace_bytes(M, K, order, int(weights is not None))
+    if nbytes < 0:                                 # the library names what is wrong, before it touches the GPU
+        _call("svoxt_quantize_median_cut", None, M, K, None, order, None, None, None, 0, None)
+    with _on(dev):
+        colors = torch.empty((1 << order, K), dtype=torch.float32, device=dev)      # zeroed by the call
+        color_id_map = torch.empty((M,), dtype=torch.int32, device=dev)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _call("svoxt_quantize_median_cut", _ptr(data), M, K, _ptr(weights), order, _ptr(colors), _ptr(color_id_map), _ptr(ws),
+              nbytes, _stream(dev))
+    return colors, color_id_map
+
+
+def remap_index(data: torch.Tensor, index_map: torch.Tensor) -> torch.Tensor:
+    """A new tensor with every word of data (int32, any shape) that names a row -- as an unsigned number below
+    len(index_map) -- replaced by index_map[word] (int32 [M]); other words (empty leaves) are copied."""
+    for name, x in (("data", data), ("index_map", index_map)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int32:
+            raise RuntimeError(f"{name} must be an int32 tensor")
+    if index_map.dim() != 1:
+        raise RuntimeError("index_map must be 1-D")
+    _check_input(data, "data")
+    _check_input(index_map, "index_map")
+    if index_map.device != data.device:
+        raise RuntimeError("index_map must be on the device of data")
+    dev = data.device
+    with _on(dev):
+        out = torch.empty_like(data)
+        _call("svoxt_remap_index", _ptr(data), _ptr(out), data.numel(), _ptr(index_map), index_map.shape[0], _stream(dev))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # Entry points of svox_t.csrc that are outside this project's hot path
 # (SURVEY.md section 2).  They exist so a caller gets a clear error, not an
@@ -619,7 +665,7 @@ def _out_of_scope(name, instead=None):
     return fn
 
 
-for _n in ("assign_vertical", "calc_corners", "quantize_median_cut"):
+for _n in ("assign_vertical", "calc_corners"):
     globals()[_n] = _out_of_scope(_n)
 # the reference's one-camera form of grid_weights; the name is kept a stub
 grid_weight_render = _out_of_scope(

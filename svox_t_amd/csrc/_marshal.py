@@ -102,6 +102,39 @@ def _ptr(x):
     return None if (x is None or x.numel() == 0) else x.data_ptr()
 
 
+def _check_quantize(data, weights, order):
+    """The argument checks of quantize_median_cut, shapes and values before devices, all before any GPU work.
+    Returns (weights or None, order)."""
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.float32 or data.dim() != 2:
+        raise RuntimeError("data must be a 2-D float32 tensor")
+    if isinstance(order, bool) or not isinstance(order, int):
+        raise RuntimeError("order must be an int")
+    if order < 0 or order > 16:
+        raise RuntimeError("order must be in [0, 16]")
+    M, K = data.shape
+    if K < 1:
+        raise RuntimeError("data needs at least one column")
+    if M >= 1 << 31:
+        raise RuntimeError("data must have fewer than 2^31 rows")
+    if (1 << order) > M:
+        raise RuntimeError(f"2^order = {1 << order} colours need at least that many rows; data has {M}")
+    if weights is not None and not isinstance(weights, torch.Tensor):
+        raise RuntimeError("weights must be a tensor or None")
+    if weights is not None and weights.numel() == 0:
+        weights = None                             # the reference's form of "unweighted"
+    if weights is not None:
+        if weights.dtype != torch.float32 or weights.dim() != 1:
+            raise RuntimeError("weights must be a 1-D float32 tensor")
+        if weights.shape[0] != M:
+            raise RuntimeError(f"weights must have one entry per row of data: {weights.shape[0]} != {M}")
+    _check_input(data, "data")
+    if weights is not None:
+        _check_input(weights, "weights")
+        if weights.device != data.device:
+            raise RuntimeError("weights must be on the device of data")
+    return weights, order
+
+
 def _pack_tree(tree: TreeSpec) -> _CTree:
     """TreeSpec.check() (data_spec.hpp:85-110) + pointer extraction."""
     _check_input(tree.features, "features")

@@ -30,13 +30,13 @@
 #include <hip/hip_runtime.h>
 
 #include "svoxt_host.h"
+#include "svoxt_sort.h"
 
 namespace svoxt {
 
 constexpr int kP2VTile = 4;                 // tiles of 4x4x4 voxels: a wavefront each
 constexpr int kP2VChunk = 1024;             // candidates per work item
 constexpr int kP2VBlock = 256;
-constexpr int kSortSteps = 16, kSortSpan = 64 * kSortSteps;     // keys per sort workgroup (one wavefront)
 constexpr size_t kGatherBlocksMax = (size_t)1 << 18;             // beyond 1 M work items the gather's waves stride
 
 struct P2VGeom {
@@ -98,56 +98,7 @@ p2v_key_kernel(const float* __restrict__ pts, uint32_t P, P2VGeom g, uint32_t* _
     }
 }
 
-// 2a. per-workgroup digit histogram: counts[d * nblocks + block]
-__global__ void __launch_bounds__(64)
-p2v_hist_kernel(const uint32_t* __restrict__ keys, uint32_t P, int shift, uint32_t radix, uint32_t nblocks,
-                uint32_t* __restrict__ counts) {
-    __shared__ uint32_t h[256];
-    for (uint32_t d = threadIdx.x; d < radix; d += 64) h[d] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * kSortSpan;
-    for (int s = 0; s < kSortSteps; ++s) {
-        const uint32_t idx = base + s * 64 + threadIdx.x;
-        if (idx < P) atomicAdd(&h[(keys[idx] >> shift) & (radix - 1)], 1u);
-    }
-    __syncthreads();
-    for (uint32_t d = threadIdx.x; d < radix; d += 64) counts[(size_t)d * nblocks + blockIdx.x] = h[d];
-}
-
-// 2b. stable scatter: the workgroup's keys in order, 64 at a time; a lane's rank among the lanes with its digit comes
-// from one ballot per digit bit, the running offset of each digit lives in LDS.  vals_in NULL = the identity.
-__global__ void __launch_bounds__(64)
-p2v_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t P, int shift, int bits,
-                   uint32_t nblocks, const uint32_t* __restrict__ starts, uint32_t* __restrict__ keys_out,
-                   uint32_t* __restrict__ vals_out) {
-    __shared__ uint32_t run[256];
-    const uint32_t radix = 1u << bits, lane = threadIdx.x;
-    for (uint32_t d = lane; d < radix; d += 64) run[d] = starts[(size_t)d * nblocks + blockIdx.x];
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const uint32_t base = blockIdx.x * kSortSpan;
-    for (int s = 0; s < kSortSteps; ++s) {
-        const uint32_t idx = base + s * 64 + lane;
-        const bool valid = idx < P;
-        const uint32_t key = valid ? keys_in[idx] : 0u;
-        const uint32_t dig = (key >> shift) & (radix - 1);
-        unsigned long long m = __ballot(valid);
-        for (int b = 0; b < bits; ++b) {
-            const bool bit = (dig >> b) & 1u;
-            const unsigned long long on = __ballot(bit);
-            m &= bit ? on : ~on;
-        }
-        const uint32_t rank = (uint32_t)__popcll(m & below);
-        const uint32_t at = valid ? run[dig] : 0u;
-        __syncthreads();                                     // every lane has read its digit's offset
-        if (valid) {
-            keys_out[at + rank] = key;
-            vals_out[at + rank] = vals_in != nullptr ? vals_in[idx] : idx;
-            if (rank == (uint32_t)__popcll(m) - 1u) run[dig] = at + rank + 1u;   // the digit's last lane moves it on
-        }
-        __syncthreads();
-    }
-}
+// 2. the sort's passes: svoxt_sort.h (shared with svoxt_quant.hip)
 
 // 3. the records the gather reads, in sorted order: xyz + last feature column, and the window packed 10 bits an axis
 __global__ void __launch_bounds__(kP2VBlock)
@@ -363,7 +314,7 @@ static bool p2v_plan(int64_t P, const P2VGeom& g, P2VPlan& p) {
     // candidates over all tiles: every point at most once per tile of its apron.  One tile has at most P of them (< 2^31);
     // what has to fit 32 bits is the number of work items, tiles + candidates / kP2VChunk (checked below)
     const double cand = (double)P * (g.ax + 1) * (g.ay + 1) * (g.az + 1);
-    p.nblocks = (uint32_t)((P + kSortSpan - 1) / kSortSpan);
+    p.nblocks = sort_blocks((uint64_t)P);
     p.bits = 0;
     while ((g.nt >> p.bits) != 0) ++p.bits;                  // the dropped key nt included
     p.max_slots = (size_t)(cand / kP2VChunk) + 1;
@@ -444,12 +395,8 @@ int svoxt_p2v_fwd(const float* points, const float* point_features, int64_t P, i
     int cur = 0;
     for (uint32_t shift = 0; shift < p.bits; shift += 8) {
         const int bits = (int)(p.bits - shift < 8 ? p.bits - shift : 8);
-        const uint32_t radix = 1u << bits;
-        hipLaunchKernelGGL(p2v_hist_kernel, dim3(p.nblocks), dim3(64), 0, st, keys[cur], n, (int)shift, radix, p.nblocks, sort_counts);
-        if ((rc = check_launch(fn)) || (rc = exclusive_scan(sort_counts, (size_t)radix * p.nblocks, chunks, sort_starts, st, fn))) return rc;
-        hipLaunchKernelGGL(p2v_scatter_kernel, dim3(p.nblocks), dim3(64), 0, st, keys[cur], shift == 0 ? nullptr : vals[cur], n,
-                           (int)shift, bits, p.nblocks, sort_starts, keys[cur ^ 1], vals[cur ^ 1]);
-        if ((rc = check_launch(fn))) return rc;
+        if ((rc = sort_pass(keys[cur], shift == 0 ? nullptr : vals[cur], n, (int)shift, bits, sort_counts, sort_starts, chunks,
+                            keys[cur ^ 1], vals[cur ^ 1], st, fn))) return rc;
         cur ^= 1;
     }
     const uint32_t* sorted = vals[cur];

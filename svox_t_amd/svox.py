@@ -35,6 +35,12 @@ class PruneResult(NamedTuple):
     row_map: Optional[torch.Tensor]
 
 
+class QuantizeResult(NamedTuple):
+    """What N3Tree.quantize did: the palette (the values of the new `features`) and the palette row of every old row."""
+    colors: torch.Tensor
+    color_id_map: torch.Tensor
+
+
 class _QueryVerticalFunction(autograd.Function):
     """svox_t/svox.py:38-56: gradient flows to argument 0 (the feature table) only."""
 
@@ -320,6 +326,42 @@ class N3Tree(nn.Module):
             self.filled = n
             self._invalidate()
         return PruneResult(n, before - n, dropped, row_map)
+
+    # --------------------------------------------------------------- quantize
+    def quantize(self, order, weights=None):
+        """Replace the feature table by a palette of 2^order rows: median-cut quantisation of the rows of
+        `self.features` (one HIP pipeline, csrc/svoxt_quant.hip; the reference's quantize_median_cut is a CPU
+        recursion, quantizer.cpp:48-157), every `data` word that names a row rewritten to the row's colour.  Empty
+        leaves stay empty (EMPTY_INDEX) and the topology (`child`, `parent_depth`) is untouched: the result is an
+        ordinary tree, rendered and differentiated with respect to the palette by the kernels there are.
+
+        `weights`: float32 [M], one per feature row, weighing the rows in the cuts and in the means (None: every row
+        counts once).  Where each row is named by exactly one leaf -- build_from_points, or prune() with
+        compact_features -- the per-row weights of `with tree.accumulate_weights() as accum:` renders are
+
+            w = torch.zeros(M, device=dev); leaf = (tree.child[:n] == 0) & (tree.data[:n, ..., 0] < M)
+            w[tree.data[:n, ..., 0][leaf].long()] = accum.value[:n][leaf]
+
+        Differences from the reference, as svox_t_amd.csrc.quantize_median_cut: an empty segment's palette row is zero
+        (reference: NaN), a segment whose weights sum to zero takes the plain mean (reference: NaN), NaN features are
+        not checked.  0 <= order <= 16 and 2^order <= M.
+
+        Replaces `self.features` by a NEW nn.Parameter(colors): an optimizer that holds the old parameter has to be
+        rebuilt (its state belongs to rows that no longer exist; the reference's warning on shrink_to_fit,
+        svox.py:606-607).  GPU only.
+        :return: QuantizeResult(colors float32 [2^order, K], color_id_map int32 [M])"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if not self.data.is_cuda:
+            raise RuntimeError("quantize: only the GPU (HIP) path exists; move the tree to a GPU")
+        with torch.no_grad():
+            colors, color_id_map = _C.quantize_median_cut(self.features.detach().contiguous(), weights, order)
+            data = _C.remap_index(self.data.contiguous(), color_id_map)
+            _C.invalidate_caches(self.child, self.data)     # what was cached of the old data words goes now
+            self.data = data
+            self.features = nn.Parameter(colors, requires_grad=self.features.requires_grad)
+            self._invalidate()
+        return QuantizeResult(colors, color_id_map)
 
     def shrink_to_fit(self):
         """Trim the topology buffers to the nodes in use (the reference's name, svox.py:600; its node
