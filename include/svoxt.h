@@ -849,6 +849,74 @@ int svoxt_quantize_median_cut(const float* data, int64_t M, int32_t K, const flo
  * a colour-id map. */
 int svoxt_remap_index(const int32_t* data_in, int32_t* data_out, int64_t n, const int32_t* map, int64_t M, void* stream);
 
+/* ---- Frontier reductions and merge: N3Tree.frontier / reduce_frontier / diam_frontier / merge (the reference's tensor
+ * ops, svox_t/svox.py:352-483, which read `data` as values; here data names rows of the feature table) -----------------
+ *
+ * The FRONTIER is the set of nodes other than the root whose N^3 slots are all leaves (child == 0).
+ * svoxt_frontier_count flags and scans (child device int32 [>= n_internal, N, N, N]); count (device int64[1]) receives
+ * F.  The host reads it -- the one host read -- allocates frontier (device int64 [F]) and calls svoxt_frontier_emit with
+ * the workspace unchanged: the ids, ascending.  workspace: svoxt_frontier_workspace_bytes(n_internal) device bytes.
+ *
+ * svoxt_frontier_reduce: out (device float32 [F, Kc]) row f = op over the children c = 0 .. N^3 - 1 of node nodes[f]
+ * (device int64 [F]; any nodes, their slots are read as leaves) of features[data[node, c], cols[j]].  cols: device
+ * int32 [n_cols] columns in [0, K) (not checked), or NULL with n_cols = 0 for all K columns (Kc = K).  A child is EMPTY
+ * when its data word, read as unsigned, is >= M.  empty_mode SVOXT_EMPTY_ZERO: an empty child counts as a row of zeros;
+ * SVOXT_EMPTY_SKIP: only the non-empty children are reduced, a node without one gives zeros.  SUM adds in slot order,
+ * sequential float32 (no fused multiply-add); MEAN is that sum divided by the number of children counted (N^3, or the
+ * non-empty ones); MAX / MIN take the first child in slot order that attains the extremum (strict comparisons: a NaN
+ * never replaces a number).  A node id outside [0, n_internal) gives a row of zeros.
+ * svoxt_frontier_reduce_bwd: grad_features (device float32 [M, K], zeroed by the call) receives the gradient of that
+ * with respect to features for the upstream grad_out [F, Kc]: SUM / MEAN scatter grad_out (divided by the count) to every
+ * non-empty child's row, MAX / MIN to the row of the first child that attains the extremum (nowhere if that child is
+ * empty).  Float atomics: bit-reproducible where no element receives more than one term.
+ * svoxt_frontier_diam: out (device float32 [F]) = the largest, over pairs of children (under SVOXT_EMPTY_SKIP: of
+ * non-empty children), of sqrt(sum_j ((x_a[cols[j]] - x_b[cols[j]]) * scale)^2); 0 without a pair.
+ *
+ * Merge.  selected (device uint8 [n_internal]): node i is MERGED iff selected[i] != 0 and i is a frontier node.  A
+ * merged node is removed and its parent slot becomes a leaf whose word is: the node's data word if all N^3 are equal;
+ * the first child's word if all children are empty; otherwise the index of a NEW feature row.  The nodes that stay
+ * keep their order and are renumbered as by svoxt_prune_emit (child offsets, parent_depth, empty_index at inner
+ * slots).  compact_features != 0: the old rows still named by a leaf are carried, in their order, and renumbered;
+ * row_map (device int64 [carried]) lists them.  == 0: all M rows are carried, row_map is not written.  New rows follow
+ * the carried ones in ascending id of their merged node; new_row_nodes (device int64 [rows_added]) lists those nodes:
+ * the caller fills row carried + i with svoxt_frontier_reduce over new_row_nodes (the tables it reads are the OLD
+ * ones).  svoxt_merge_count marks and scans; counts (device int64[3]) = nodes that stay, rows carried, rows added: the
+ * one host read.  svoxt_merge_emit, same inputs and the workspace unchanged, writes every row of the outputs.
+ * workspace: svoxt_merge_workspace_bytes(n_internal, M) device bytes.  Integer work: the outputs are a function of the
+ * inputs, identical from run to run.
+ * Every argument of every entry point here is checked before any HIP call (SVOXT_ERR_INVALID): N in [2, 16],
+ * n_internal * N^3 < 2^31, M in [0, 2^31), K >= 1, op and empty_mode among the constants, empty_index >= M and >= the
+ * new number of rows as an unsigned number, no NULL where a pointer is required. */
+#define SVOXT_REDUCE_MEAN 0
+#define SVOXT_REDUCE_SUM 1
+#define SVOXT_REDUCE_MAX 2
+#define SVOXT_REDUCE_MIN 3
+#define SVOXT_EMPTY_ZERO 0
+#define SVOXT_EMPTY_SKIP 1
+int64_t svoxt_frontier_workspace_bytes(int64_t n_internal);
+int svoxt_frontier_count(const int32_t* child, int64_t n_internal, int32_t N, void* workspace, int64_t workspace_bytes,
+                         int64_t* count, void* stream);
+int svoxt_frontier_emit(const void* workspace, int64_t workspace_bytes, int64_t n_internal, int64_t F, int64_t* frontier,
+                        void* stream);
+int svoxt_frontier_reduce(const float* features, int64_t M, int32_t K, const int32_t* data, int64_t n_internal, int32_t N,
+                          const int64_t* nodes, int64_t F, const int32_t* cols, int32_t n_cols, int32_t op,
+                          int32_t empty_mode, float* out, void* stream);
+int svoxt_frontier_reduce_bwd(const float* features, int64_t M, int32_t K, const int32_t* data, int64_t n_internal,
+                              int32_t N, const int64_t* nodes, int64_t F, const int32_t* cols, int32_t n_cols, int32_t op,
+                              int32_t empty_mode, const float* grad_out, float* grad_features, void* stream);
+int svoxt_frontier_diam(const float* features, int64_t M, int32_t K, const int32_t* data, int64_t n_internal, int32_t N,
+                        const int64_t* nodes, int64_t F, const int32_t* cols, int32_t n_cols, int32_t empty_mode,
+                        float scale, float* out, void* stream);
+int64_t svoxt_merge_workspace_bytes(int64_t n_internal, int64_t M);
+int svoxt_merge_count(const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n_internal,
+                      int32_t N, int64_t M, const uint8_t* selected, int32_t compact_features, void* workspace,
+                      int64_t workspace_bytes, int64_t* counts, void* stream);
+int svoxt_merge_emit(const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n_internal,
+                     int32_t N, int64_t M, const uint8_t* selected, int32_t compact_features, const void* workspace,
+                     int64_t workspace_bytes, int64_t new_n_internal, int64_t carried, int64_t rows_added,
+                     int32_t empty_index, int32_t* child_out, int32_t* data_out, int32_t* parent_depth_out,
+                     int64_t* row_map, int64_t* new_row_nodes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,16 @@ EXPORTS = {
     "svoxt_quantize_median_cut": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_remap_index": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "svoxt_grid_weights": (ctypes.c_int, [_vp, _i32, _P(_CRays), _i32, _i32, _P(_COptions), _vp, _vp, _i32, _vp, _vp, _vp]),
+    "svoxt_frontier_workspace_bytes": (_i64, [_i64]),
+    "svoxt_frontier_count": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "svoxt_frontier_emit": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "svoxt_frontier_reduce": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "svoxt_frontier_reduce_bwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "svoxt_frontier_diam": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, ctypes.c_float, _vp, _vp]),
+    "svoxt_merge_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_merge_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "svoxt_merge_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _i32,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -1,6 +1,7 @@
 """The operators of `svox_t.csrc` around the render path: point query (svox_kernel.cu:45-94, 240-324), the roofline
 counters, the motion variants (rt_kernel.cu:698-1061), point skinning (svox_kernel.cu:123-211), octree construction
-(svox.py:160-161, 488-560), pruning -- marshalling only, one C-ABI call each (two for the builder and for prune)."""
+(svox.py:160-161, 488-560), pruning, the frontier reductions and merge -- marshalling only, one C-ABI call each (two for
+the builder, prune, the frontier and merge)."""
 from __future__ import annotations
 
 import ctypes
@@ -429,6 +430,188 @@ def gather_rows(src: torch.Tensor, row_map: torch.Tensor) -> torch.Tensor:
         _call("svoxt_prune_gather_rows", _ptr(src), src.shape[0], _ptr(row_map), _ptr(dst), row_map.shape[0], src.shape[1],
               _stream(dev))
     return dst
+
+
+REDUCE_OPS = {"mean": 0, "sum": 1, "max": 2, "min": 3}        # SVOXT_REDUCE_* (include/svoxt.h)
+EMPTY_MODES = {"zero": 0, "skip": 1}                          # SVOXT_EMPTY_*
+
+
+def _check_tables(child, data, parent_depth, n_internal):
+    """Types and shapes of the tree tables (devices: _check_on_device_of_child).  Returns (cap, N, n)."""
+    for nm, x in (("child", child), ("data", data)) + ((("parent_depth", parent_depth),) if parent_depth is not None else ()):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int32:
+            raise RuntimeError(f"{nm} must be an int32 tensor")
+    if child.dim() != 4 or child.shape[1] < 2 or child.shape[1] > 16 or child.shape[2] != child.shape[1] \
+            or child.shape[3] != child.shape[1]:
+        raise RuntimeError("child must be int32 [cap, N, N, N] with N in [2, 16]")
+    cap, N = child.shape[0], child.shape[1]
+    if data.numel() != child.numel() or data.shape[0] != cap:
+        raise RuntimeError("data must be int32 [cap, N, N, N, 1] matching child")
+    if parent_depth is not None and tuple(parent_depth.shape) != (cap, 2):
+        raise RuntimeError("parent_depth must be int32 [cap, 2]")
+    n = int(n_internal)
+    if n < 1 or n > cap:
+        raise RuntimeError("n_internal must be in [1, cap]")
+    return cap, N, n
+
+
+def _check_on_device_of_child(child, **tensors):
+    """CHECK_INPUT of the tables (and what goes with them), last: shapes and values are refused before devices."""
+    for nm, x in (("child", child),) + tuple(tensors.items()):
+        _check_input(x, nm)
+        if x.device != child.device:
+            raise RuntimeError(f"{nm} must be on the device of child")
+
+
+def frontier_nodes(child: torch.Tensor, n_internal: int) -> torch.Tensor:
+    """int64 [F], ascending: the nodes other than the root whose N^3 slots are all leaves (the reference's _frontier,
+    svox.py:471-483, which lists the root too).  Flags, a scan, one host read (F), an emit (csrc/svoxt_merge.hip)."""
+    _, N, n = _check_tables(child, child, None, n_internal)
+    _check_on_device_of_child(child)
+    dev = child.device
+    with _on(dev):
+        nbytes = _lib.svoxt_frontier_workspace_bytes(n)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        count = torch.empty((1,), dtype=torch.int64, device=dev)
+        _call("svoxt_frontier_count", _ptr(child), n, N, _ptr(ws), nbytes, _ptr(count), _stream(dev))
+        F = int(count.item())                     # the one host read
+        out = torch.empty((F,), dtype=torch.int64, device=dev)
+        _call("svoxt_frontier_emit", _ptr(ws), nbytes, n, F, _ptr(out), _stream(dev))
+    return out
+
+
+def _reduce_args(features, data, n_internal, N, nodes, cols, op, empty):
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise RuntimeError("features must be float32 [M, K]")
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.int32:
+        raise RuntimeError("data must be an int32 tensor")
+    if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.int64 or nodes.dim() != 1:
+        raise RuntimeError("nodes must be int64 [F]")
+    if op not in REDUCE_OPS:
+        raise RuntimeError(f"op must be one of {sorted(REDUCE_OPS)}")
+    if empty not in EMPTY_MODES:
+        raise RuntimeError('empty must be "zero" or "skip"')
+    n, N = int(n_internal), int(N)
+    if N < 2 or N > 16 or n < 1 or data.numel() < n * N ** 3:
+        raise RuntimeError("data must hold n_internal * N^3 words, N in [2, 16]")
+    K = features.shape[1]
+    if cols is not None:
+        if not isinstance(cols, torch.Tensor) or cols.dtype != torch.int32 or cols.dim() != 1:
+            raise RuntimeError("cols must be int32 [K']")
+        if cols.numel() == 0:
+            raise RuntimeError("cols selects no column")
+    for nm, x in (("features", features), ("data", data), ("nodes", nodes)) + ((("cols", cols),) if cols is not None else ()):
+        _check_input(x, nm)
+        if x.device != features.device:
+            raise RuntimeError(f"{nm} must be on the device of features")
+    return n, N, K, (K if cols is None else cols.shape[0])
+
+
+def frontier_reduce(features, data, n_internal, N, nodes, cols=None, op="mean", empty="zero", out=None) -> torch.Tensor:
+    """[F, K'] float32: row f = op over the N^3 children of node nodes[f] of their (selected) feature rows, in slot
+    order (include/svoxt.h, svoxt_frontier_reduce).  cols: int32 [K'] columns in [0, K) or None (all).  out: a
+    contiguous float32 [F, K'] tensor to write instead of a new one."""
+    n, N, K, Kc = _reduce_args(features, data, n_internal, N, nodes, cols, op, empty)
+    if cols is not None and (int(cols.min()) < 0 or int(cols.max()) >= K):
+        raise RuntimeError("cols out of range")
+    dev = features.device
+    F = nodes.shape[0]
+    with _on(dev):
+        if out is None:
+            out = torch.empty((F, Kc), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (F, Kc) or not out.is_contiguous() or out.device != dev:
+            raise RuntimeError("out must be a contiguous float32 [F, K'] tensor on the device of features")
+        _call("svoxt_frontier_reduce", _ptr(features), features.shape[0], K, _ptr(data), n, N, _ptr(nodes), F, _ptr(cols),
+              0 if cols is None else Kc, REDUCE_OPS[op], EMPTY_MODES[empty], _ptr(out), _stream(dev))
+    return out
+
+
+def frontier_reduce_backward(features, data, n_internal, N, nodes, cols, op, empty, grad_out) -> torch.Tensor:
+    """Gradient of frontier_reduce with respect to features, float32 [M, K] (svoxt_frontier_reduce_bwd)."""
+    n, N, K, Kc = _reduce_args(features, data, n_internal, N, nodes, cols, op, empty)
+    _check_input(grad_out, "grad_out")
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (nodes.shape[0], Kc) or grad_out.device != features.device:
+        raise RuntimeError("grad_out must be float32 [F, K'] on the device of features")
+    dev = features.device
+    with _on(dev):
+        grad = torch.empty_like(features)             # zeroed by the call
+        _call("svoxt_frontier_reduce_bwd", _ptr(features), features.shape[0], K, _ptr(data), n, N, _ptr(nodes), nodes.shape[0],
+              _ptr(cols), 0 if cols is None else Kc, REDUCE_OPS[op], EMPTY_MODES[empty], _ptr(grad_out), _ptr(grad), _stream(dev))
+    return grad
+
+
+def frontier_diam(features, data, n_internal, N, nodes, cols=None, empty="zero", scale=1.0) -> torch.Tensor:
+    """float32 [F]: the largest Euclidean distance between the (selected, scaled) rows of two children of each node
+    (svoxt_frontier_diam; the reference's diam_frontier, svox.py:438-468)."""
+    n, N, K, Kc = _reduce_args(features, data, n_internal, N, nodes, cols, "max", empty)
+    scale = float(scale)
+    if scale != scale:
+        raise RuntimeError("scale is NaN")
+    if cols is not None and (int(cols.min()) < 0 or int(cols.max()) >= K):
+        raise RuntimeError("cols out of range")
+    dev = features.device
+    F = nodes.shape[0]
+    with _on(dev):
+        out = torch.empty((F,), dtype=torch.float32, device=dev)
+        _call("svoxt_frontier_diam", _ptr(features), features.shape[0], K, _ptr(data), n, N, _ptr(nodes), F, _ptr(cols),
+              0 if cols is None else Kc, EMPTY_MODES[empty], scale, _ptr(out), _stream(dev))
+    return out
+
+
+def merge_tree(child, data, parent_depth, n_internal, features, selected, op="mean", empty="zero", compact_features=True,
+               reserve=0, empty_index=1410065408):
+    """The tables and the feature table of a tree with the selected frontier nodes merged into leaves (include/svoxt.h,
+    svoxt_merge_count; csrc/svoxt_merge.hip).  selected: bool / uint8 [n_internal], per NODE; entries at nodes that are
+    not frontier nodes are ignored.  Returns (child [n' + reserve, N, N, N], data [n' + reserve, N, N, N, 1],
+    parent_depth [n' + reserve, 2], n', features [carried + rows_added, K], row_map int64 [carried] or None,
+    rows_added): new tensors.  One host read (the counts that size the outputs)."""
+    _, N, n = _check_tables(child, data, parent_depth, n_internal)
+    if op not in ("mean", "max", "min"):
+        raise RuntimeError('merge: op must be "mean", "max" or "min"')
+    if empty not in EMPTY_MODES:
+        raise RuntimeError('empty must be "zero" or "skip"')
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise RuntimeError("features must be float32 [M, K]")
+    if not isinstance(selected, torch.Tensor) or selected.dtype not in (torch.bool, torch.uint8) or tuple(selected.shape) != (n,):
+        raise RuntimeError("selected must be a bool or uint8 tensor [n_internal]")
+    reserve = int(reserve)
+    if reserve < 0:
+        raise RuntimeError("reserve must be >= 0")
+    _check_on_device_of_child(child, data=data, parent_depth=parent_depth, features=features, selected=selected)
+    dev = child.device
+    M, K = features.shape
+    compact = int(bool(compact_features))
+    with _on(dev):
+        nbytes = _lib.svoxt_merge_workspace_bytes(n, M)
+        if nbytes < 0:
+            raise RuntimeError("merge_tree: n_internal and M must be below 2^31")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((3,), dtype=torch.int64, device=dev)
+        _call("svoxt_merge_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(selected), compact, _ptr(ws), nbytes,
+              _ptr(counts), _stream(dev))
+        new_n, carried, added = (int(v) for v in counts.tolist())      # the one host read: sizes the outputs
+        rows = new_n + reserve
+        child_out = torch.empty((rows, N, N, N), dtype=torch.int32, device=dev)
+        data_out = torch.empty((rows, N, N, N, 1), dtype=torch.int32, device=dev)
+        pd_out = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+        if reserve > 0:
+            child_out[new_n:].zero_()
+            data_out[new_n:].fill_(int(empty_index))
+            pd_out[new_n:].zero_()
+        row_map = torch.empty((carried,), dtype=torch.int64, device=dev) if compact else None
+        new_nodes = torch.empty((added,), dtype=torch.int64, device=dev)
+        _call("svoxt_merge_emit", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(selected), compact, _ptr(ws), nbytes,
+              new_n, carried, added, int(empty_index), _ptr(child_out), _ptr(data_out), _ptr(pd_out), _ptr(row_map),
+              _ptr(new_nodes), _stream(dev))
+        table = torch.empty((carried + added, K), dtype=torch.float32, device=dev)
+        if compact:
+            if carried > 0:
+                _call("svoxt_prune_gather_rows", _ptr(features), M, _ptr(row_map), _ptr(table), carried, K, _stream(dev))
+        else:
+            table[:M].copy_(features)
+        if added > 0:                                                   # the reduced rows, behind the carried ones
+            frontier_reduce(features, data, n, N, new_nodes, None, op, empty, out=table[carried:])
+    return child_out, data_out, pd_out, new_n, table, row_map, added
 
 
 def _p2v_args(points, point_features, volume_corner, volume_size, n_voxels, kernel_radius, conv_radius):

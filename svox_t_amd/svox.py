@@ -41,6 +41,35 @@ class QuantizeResult(NamedTuple):
     color_id_map: torch.Tensor
 
 
+class MergeResult(NamedTuple):
+    """What N3Tree.merge did."""
+    n_internal: int
+    nodes_merged: int
+    row_map: Optional[torch.Tensor]   # old row of every carried feature row (None without compact_features)
+    rows_added: int                   # new feature rows, behind the carried ones
+
+
+_REDUCE_CALLABLES = {torch.mean: "mean", torch.sum: "sum", torch.max: "max", torch.min: "min"}
+
+
+class _FrontierReduceFunction(autograd.Function):
+    """reduce_frontier(grad=True): gradient flows to argument 0 (the feature table) only."""
+
+    @staticmethod
+    def forward(ctx, features, data, n, N, nodes, cols, op, empty):
+        ctx.args = (data, n, N, nodes, cols, op, empty)
+        ctx.save_for_backward(features)
+        return _C.frontier_reduce(features.detach().contiguous(), data, n, N, nodes, cols, op, empty)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        data, n, N, nodes, cols, op, empty = ctx.args
+        return (_C.frontier_reduce_backward(ctx.saved_tensors[0].detach().contiguous(), data, n, N, nodes, cols, op, empty,
+                                            grad_out.contiguous()),) + (None,) * 7
+
+
 class _QueryVerticalFunction(autograd.Function):
     """svox_t/svox.py:38-56: gradient flows to argument 0 (the feature table) only."""
 
@@ -132,6 +161,7 @@ class N3Tree(nn.Module):
             self.extra_data = None
         self._ver = 0
         self._last_all_leaves = None
+        self._last_frontier = None
         self._lock_tree_structure = False
         self._weight_accum = None
         self.filled = 1
@@ -286,7 +316,7 @@ class N3Tree(nn.Module):
     def prune(self, keep=None, *, weights=None, threshold=None, collapse=True, compact_features=True, reserve=0):
         """Drop leaves, collapse what is left empty, compact the tree (one HIP pipeline, csrc/svoxt_prune.hip; the
         reference has the halves as tensor ops, both stale in this fork: merge, svox.py:352-389, and shrink_to_fit,
-        :600-642, which never touches `features`).
+        :600-642, which never touches `features`; merging occupied leaves is merge() here).
 
         The decision is per slot of `child`, entries at slots that are not leaves are ignored: `keep`, bool / uint8
         with the shape of `child`, or `weights` (float32 of that shape: what `accumulate_weights()` gives as
@@ -363,6 +393,199 @@ class N3Tree(nn.Module):
             self._invalidate()
         return QuantizeResult(colors, color_id_map)
 
+    # --------------------------------------------------------------- frontier
+    def _frontier_guard(self, what):
+        if not self.data.is_cuda:
+            raise RuntimeError(f"{what}: only the GPU (HIP) path exists; move the tree to a GPU")
+
+    def frontier(self):
+        """int64 [F], ascending: the nodes whose N^3 slots are all leaves -- what merge() can turn into one leaf.  The
+        root is never listed (the reference's _frontier, svox.py:471-483, lists it when all its slots are leaves and
+        merge then refuses it).  Cached until the tree changes.  GPU only."""
+        self._frontier_guard("frontier")
+        if self._last_frontier is None:
+            self._last_frontier = _C.frontier_nodes(self.child, self.filled)
+        return self._last_frontier
+
+    def _columns(self, dim, K):
+        """`dim` (None, int, slice, list or tensor: what the reference indexes the last axis with) -> (int32 column
+        indices on the tree's device or None for all columns, whether the column axis is dropped)."""
+        if dim is None:
+            return None, False
+        if isinstance(dim, torch.Tensor):
+            dim = dim.cpu()
+        picked = torch.arange(K)[dim]
+        if picked.numel() == 0:
+            raise RuntimeError("dim selects no column")
+        return picked.reshape(-1).to(device=self.data.device, dtype=torch.int32), picked.dim() == 0
+
+    def _gathered(self, features, cols, empty):
+        """[F, N^3, K'] rows of the frontier nodes' children with torch ops (differentiable), the mask of the children
+        that name a row; empty children are zero rows."""
+        fr = self.frontier()
+        M = features.shape[0]
+        words = self.data[:self.filled].reshape(self.filled, -1)[fr].long() & 0xFFFFFFFF
+        has = words < M
+        rows = features[words.clamp(max=max(M - 1, 0))] if M > 0 else features.new_zeros(words.shape + (features.shape[1],))
+        if cols is not None:
+            rows = rows[..., cols.long()]
+        return rows * has[..., None].to(rows.dtype), has
+
+    def reduce_frontier(self, op="mean", dim=None, grad=False, features=None, empty="zero"):
+        """Reduce the feature rows of every frontier node's N^3 children (the reference's reduce_frontier,
+        svox.py:391-418): [F, K'], rows in `frontier()` order.
+
+        op: "mean" | "sum" | "max" | "min" -- one fused HIP kernel (csrc/svoxt_merge.hip) that reads each row once;
+        torch.mean / torch.sum / torch.max / torch.min are taken for these by identity.  Any other callable gets the
+        gathered [F, N^3, K'] tensor and dim=1, the reference's contract (a tuple result: its first element); that path
+        materialises the tensor and, under empty="skip", hands empty children over as zero rows all the same.
+        dim: columns of the feature table (int, slice, list, tensor), None for all; an int drops the column axis.
+        features: the table to read, self.features by default.
+        empty="zero": a child without a row (data word >= M as an unsigned number) counts as a zero row; "skip": only
+        the children with a row are reduced ("mean" divides by their number), a node without one gives zeros.
+        Sums run over slots 0 .. N^3 - 1 in order, sequential float32; "max" / "min" take the first slot that attains
+        the extremum.  grad=True: differentiable with respect to `features` (sum / mean scatter the upstream row, max
+        / min give it to the first attaining slot; float atomics where leaves share a row, else bit-reproducible).
+        GPU only."""
+        self._frontier_guard("reduce_frontier")
+        features = self.features if features is None else features
+        if empty not in ("zero", "skip"):
+            raise RuntimeError('empty must be "zero" or "skip"')
+        if not isinstance(op, str):
+            op = _REDUCE_CALLABLES.get(op, op)
+        cols, squeeze = self._columns(dim, features.shape[1])
+        if callable(op):
+            rows, _ = self._gathered(features if grad else features.detach(), cols, empty)
+            out = op(rows, dim=1)
+            out = out[0] if isinstance(out, tuple) else out
+            return out.squeeze(-1) if squeeze and out.dim() == 2 else out
+        if op not in ("mean", "sum", "max", "min"):
+            raise RuntimeError('op must be "mean", "sum", "max", "min" or a callable')
+        args = (self.data, self.filled, self.N, self.frontier(), cols, op, empty)
+        if grad:
+            out = _FrontierReduceFunction.apply(features, *args)
+        else:
+            out = _C.frontier_reduce(features.detach().contiguous(), *args)
+        return out.squeeze(-1) if squeeze else out
+
+    def max_frontier(self, dim=None, grad=False, features=None, empty="zero"):
+        """reduce_frontier("max", ...) (the reference's max_frontier, svox.py:420-436)."""
+        return self.reduce_frontier("max", dim=dim, grad=grad, features=features, empty=empty)
+
+    def diam_frontier(self, dim=None, grad=False, scale=1.0, features=None, empty="zero"):
+        """float32 [F]: per frontier node the largest Euclidean distance between the (selected) feature rows of two of
+        its children, times `scale` (the reference's diam_frontier, svox.py:438-468) -- small where merging the node
+        loses little.  empty="zero": an empty child is a zero row; "skip": pairs of children with a row only (0 without
+        a pair).  The forward is one fused HIP kernel.  grad=True does NOT use it: the value is then computed from the
+        gathered [F, N^3, K'] rows with torch ops and differentiated by torch's own autograd.  GPU only."""
+        self._frontier_guard("diam_frontier")
+        features = self.features if features is None else features
+        if empty not in ("zero", "skip"):
+            raise RuntimeError('empty must be "zero" or "skip"')
+        cols, _ = self._columns(dim, features.shape[1])
+        if not grad:
+            return _C.frontier_diam(features.detach().contiguous(), self.data, self.filled, self.N, self.frontier(), cols,
+                                    empty, scale)
+        rows, has = self._gathered(features, cols, empty)
+        delta = (rows[:, :, None, :] - rows[:, None, :, :]) * scale
+        d2 = (delta * delta).sum(-1)
+        if empty == "skip":
+            d2 = d2 * (has[:, :, None] & has[:, None, :]).to(d2.dtype)
+        best = d2.reshape(d2.shape[0], -1).max(dim=1)[0]
+        return torch.where(best > 0, best.clamp_min(1e-45).sqrt(), torch.zeros_like(best))
+
+    # ------------------------------------------------------------------ merge
+    def merge(self, frontier_sel=None, op="mean", *, empty="zero", compact_features=True, reserve=0):
+        """Coarsen the tree by one level: every selected frontier node is removed and its parent slot becomes ONE leaf
+        (one HIP pipeline, csrc/svoxt_merge.hip; the reference's merge + shrink_to_fit, svox.py:352-389, 600-642).
+
+        frontier_sel: None (every frontier node), a bool mask [F] or int64 indices into `frontier()` (duplicates are
+        fine) -- typically a condition on reduce_frontier() / diam_frontier().  op: "mean", "max" or "min" (or
+        torch.mean / torch.max / torch.min).  For each merged node:
+          - all N^3 data words equal (one shared row -- what refine() leaves -- or all the same empty word): the parent
+            slot takes that word, no row is created; so refine(sel) followed by a merge of exactly the new nodes gives
+            back the tables word for word (on a tree whose inner slots hold the empty index, as prune() leaves them);
+          - no child with a row: the parent slot takes the first child's (empty) word;
+          - otherwise the parent slot names a NEW feature row: `op` over the children as reduce_frontier(op, empty=empty).
+        The nodes that remain keep their order and are renumbered, with prune()'s layout (inner slots hold the empty
+        index, `reserve` free rows behind the tree).  The feature table becomes the carried old rows in their old order
+        -- with `compact_features` those a leaf still names, else all -- then the new rows in ascending id of their
+        merged node.  Every output word is a function of the input: two runs give the same bytes.
+
+        Replaces `child`, `data`, `parent_depth` and `self.features`, by a NEW nn.Parameter: an optimizer that holds
+        the old parameter has to be rebuilt, its state sliced with `row_map` (new rows start fresh) -- the reference's
+        warning on shrink_to_fit, svox.py:606-607.  The acceleration caches are invalidated.  One call merges one
+        level; see simplify().  GPU only.
+        :return: MergeResult(n_internal, nodes_merged, row_map, rows_added)"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if not isinstance(op, str):
+            op = _REDUCE_CALLABLES.get(op, op)
+        if op not in ("mean", "max", "min"):
+            raise RuntimeError('merge: op must be "mean", "max" or "min"')
+        if empty not in ("zero", "skip"):
+            raise RuntimeError('empty must be "zero" or "skip"')
+        if self.filled <= 1:
+            raise RuntimeError("Cannot merge root node")
+        self._frontier_guard("merge")
+        fr = self.frontier()
+        if frontier_sel is not None:
+            if not isinstance(frontier_sel, torch.Tensor):
+                frontier_sel = torch.as_tensor(frontier_sel)
+            if frontier_sel.dtype == torch.bool:
+                if tuple(frontier_sel.shape) != tuple(fr.shape):
+                    raise RuntimeError(f"merge: the mask must have one entry per frontier node, [{fr.shape[0]}]")
+            elif frontier_sel.dtype == torch.int64 and frontier_sel.dim() <= 1:
+                frontier_sel = frontier_sel.reshape(-1)
+                if frontier_sel.numel() and (int(frontier_sel.min()) < 0 or int(frontier_sel.max()) >= fr.shape[0]):
+                    raise RuntimeError("merge: index out of range of frontier()")
+            else:
+                raise RuntimeError("merge: frontier_sel must be None, a bool mask [F] or int64 indices into frontier()")
+            fr = fr[frontier_sel.to(fr.device)]
+        selected = torch.zeros(self.filled, dtype=torch.uint8, device=self.data.device)
+        selected[fr] = 1
+        return self._merge_nodes(selected, op, empty, compact_features, reserve)
+
+    def _merge_nodes(self, selected, op, empty, compact_features, reserve):
+        """merge() for a per-NODE uint8 selection (entries at nodes that are not frontier nodes are ignored)."""
+        with torch.no_grad():
+            before = self.filled
+            child, data, parent_depth, n, table, row_map, added = _C.merge_tree(
+                self.child, self.data, self.parent_depth, before, self.features.detach().contiguous(), selected, op, empty,
+                compact_features, reserve, EMPTY_INDEX)
+            _C.invalidate_caches(self.child)         # the old tables' acceleration grid goes now, not with the tensor
+            self.child, self.data, self.parent_depth = child, data, parent_depth
+            self.features = nn.Parameter(table, requires_grad=self.features.requires_grad)
+            self._n_internal.fill_(n)
+            self.filled = n
+            self._invalidate()
+        return MergeResult(n, before - n, row_map, added)
+
+    def simplify(self, tol, dim=None, scale=1.0, op="mean", max_rounds=None):
+        """Merge, level by level, every frontier node whose children are within `tol` of each other:
+        merge(diam_frontier(dim, scale=scale) <= tol, op) until a round merges nothing (or `max_rounds` rounds).  Plain
+        Python over the calls above; a round computes the diameter of every node's slots (the merge ignores the
+        selection at nodes that are not frontier nodes), so its only host read is merge's.
+        :return: the number of nodes merged"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if not isinstance(op, str):
+            op = _REDUCE_CALLABLES.get(op, op)
+        if op not in ("mean", "max", "min"):
+            raise RuntimeError('simplify: op must be "mean", "max" or "min"')
+        self._frontier_guard("simplify")
+        total, rounds = 0, 0
+        while self.filled > 1 and (max_rounds is None or rounds < max_rounds):
+            cols, _ = self._columns(dim, self.features.shape[1])
+            nodes = torch.arange(self.filled, device=self.data.device)
+            diam = _C.frontier_diam(self.features.detach().contiguous(), self.data, self.filled, self.N, nodes, cols, "zero", scale)
+            merged = self._merge_nodes((diam <= tol).to(torch.uint8), op, "zero", True, 0).nodes_merged
+            rounds += 1
+            if merged == 0:
+                break
+            total += merged
+        return total
+
     def shrink_to_fit(self):
         """Trim the topology buffers to the nodes in use (the reference's name, svox.py:600; its node
         defragmentation is what prune() does).  Returns True iff anything changed."""
@@ -438,6 +661,7 @@ class N3Tree(nn.Module):
     def _invalidate(self):
         self._ver += 1
         self._last_all_leaves = None
+        self._last_frontier = None
 
     def accumulate_weights(self):
         """`with tree.accumulate_weights() as accum:` -- per-leaf-slot sum of the
