@@ -917,6 +917,47 @@ int svoxt_merge_emit(const int32_t* child, const int32_t* data, const int32_t* p
                      int32_t empty_index, int32_t* child_out, int32_t* data_out, int32_t* parent_depth_out,
                      int64_t* row_map, int64_t* new_row_nodes, void* stream);
 
+/* ---- Write and locate leaves by position: N3Tree.set / snap / leaf_boxes (the reference's assign_vertical,
+ * svox_kernel.cu:96-108, 326-343, and its _calc_corners, svox.py:808-826) ------------------------------------------------
+ *
+ * svoxt_assign_leaves: every point (points, device float32 [Q, 3]) is taken to its leaf exactly as by svoxt_query_fwd
+ * (tree.offset / tree.scaling, the clamp, the descent); a point whose leaf's data word is not in [0, M) is ignored.
+ * The others are grouped by the feature ROW their leaf names -- slots that share a row form one group -- and row r of
+ * table (device float32 [tree.M, tree.K], written in place; tree.features is not read) becomes, over the rows q of
+ * values (device float32 [Q, K]) of its group:
+ *   SVOXT_ASSIGN_LAST   the row of the group's highest point index;
+ *   SVOXT_ASSIGN_SUM    acc = values[q0]; acc = acc + values[q] for q1 < q2 < ... : ASCENDING POINT INDEX, sequential
+ *                       float32 per column, no fused multiply-add;
+ *   SVOXT_ASSIGN_MEAN   that sum divided once by (float)count;
+ *   SVOXT_ASSIGN_MAX / _MIN  acc = values[q0]; x > acc ? x : acc (x < acc) in the same order.  Finite values are the
+ *                       contract: with a NaN in a group the result is unspecified.
+ * Rows without a point are not written.  row_count (device int32 [M], or NULL) is zeroed and receives the number of
+ * points of every row.  values must not overlap table.  The outputs are a function of the inputs: two runs give the
+ * same bytes.  workspace: svoxt_assign_workspace_bytes(Q, M, reduce) device bytes (-1 for arguments out of range),
+ * 4 (Q + M) for LAST, about 21 Q for the others; nothing is allocated by the call, no host read.  Q and M below
+ * 2^31 - 1, Q * K below 2^38.  Cost of the sorted modes: a group is reduced by one set of lanes in its fixed order, so
+ * a single group of L points takes L dependent steps however small the rest is.
+ *
+ * svoxt_leaf_corners: corners (device float32 [Q, 3]) = the lower corner in [0, 1]^3 of the slots leaf_node (device
+ * int64 [Q, 4]: node, x, y, z), by walking parent_depth (device int32 [>= n_internal, 2]; column 0 = the packed parent
+ * slot) to the root: corner = (corner + xyz) / N per level, IEEE divide -- the bits of N3Tree._calc_corners.  A slot
+ * out of range, or a walk that does not end within 128 levels, gives NaN.
+ * svoxt_snap_points: the descent of svoxt_query_fwd, then that corner, then (corner - tree.offset) / tree.scaling:
+ * the lower corner of each point's leaf in the coordinates the points came in.
+ * Every argument is checked before any HIP call (SVOXT_ERR_INVALID). */
+#define SVOXT_ASSIGN_LAST 0
+#define SVOXT_ASSIGN_SUM 1
+#define SVOXT_ASSIGN_MEAN 2
+#define SVOXT_ASSIGN_MAX 3
+#define SVOXT_ASSIGN_MIN 4
+int64_t svoxt_assign_workspace_bytes(int64_t Q, int64_t M, int32_t reduce);
+int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, const float* values, int32_t reduce,
+                        float* table, int32_t* row_count, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_leaf_corners(const int32_t* parent_depth, int64_t n_internal, int32_t N, const int64_t* leaf_node, int64_t Q,
+                       float* corners, void* stream);
+int svoxt_snap_points(const svoxt_tree* tree, const int32_t* parent_depth, const float* points, int64_t Q, float* corners,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

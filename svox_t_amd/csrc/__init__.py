@@ -1177,5 +1177,6 @@ from ._extras import (assign_vertical, build_octree, bwd_check, bwd_counters, ca
                       motion_feature_render_backward, motion_render, p2v, p2v_backward, p2v_order, quantize_median_cut,
                       query_vertical, query_vertical_backward, refine_leaves, warp_vertices, warp_vertices_backward)
 from ._extras import gather_rows, grid_weights, prune_tree, remap_index  # noqa: E402,F401
+from ._extras import assign_leaves, leaf_corners, snap_points  # noqa: E402,F401
 from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_reduce_backward,  # noqa: E402,F401
                       merge_tree)

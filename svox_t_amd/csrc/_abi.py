@@ -169,6 +169,10 @@ EXPORTS = {
     "svoxt_merge_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
     "svoxt_merge_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _i32,
                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_assign_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "svoxt_assign_leaves": (ctypes.c_int, [_P(_CTree), _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_leaf_corners": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "svoxt_snap_points": (ctypes.c_int, [_P(_CTree), _vp, _vp, _i64, _vp, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -832,6 +832,90 @@ def remap_index(data: torch.Tensor, index_map: torch.Tensor) -> torch.Tensor:
     return out
 
 
+ASSIGN_MODES = {"last": 0, "sum": 1, "mean": 2, "max": 3, "min": 4}        # SVOXT_ASSIGN_* (include/svoxt.h)
+
+
+def assign_leaves(tree: TreeSpec, indices: torch.Tensor, values: torch.Tensor, reduce: str = "last", return_counts: bool = False):
+    """Scatter values (float32 [Q, K]) into the rows of tree.features, IN PLACE, that the leaves of the points indices
+    (float32 [Q, 3]) name -- the leaf of a point is query_vertical's; points in empty leaves are ignored; the points of a
+    row are reduced by `reduce` ("last": the highest point index; "sum" / "mean" / "max" / "min": in ascending point
+    index, sequential float32; include/svoxt.h, svoxt_assign_leaves).  Rows without a point keep their bits; the result
+    is the same bits from run to run.  The table's version counter is bumped.  return_counts: the number of points of
+    every row, int32 [M] (else None).  Bad arguments raise RuntimeError before any GPU work."""
+    if reduce not in ASSIGN_MODES:
+        raise RuntimeError(f"reduce must be one of {sorted(ASSIGN_MODES)}")
+    table = tree.features
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError("features must be float32 [M, K]")
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.float32 or indices.dim() != 2 or indices.shape[1] != 3:
+        raise RuntimeError("indices must be float32 [Q, 3]")
+    Q, (M, K) = indices.shape[0], table.shape
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or tuple(values.shape) != (Q, K):
+        raise RuntimeError("values must be float32 [Q, K], K the width of the feature table")
+    if values.requires_grad or indices.requires_grad:
+        raise RuntimeError("values and indices must not require grad: set() is not differentiable")
+    if Q >= 2 ** 31 - 1 or M >= 2 ** 31 - 1:
+        raise RuntimeError("the number of points and of feature rows must be below 2^31 - 1")
+    _check_indices(indices)
+    _check_input(values, "values")
+    ct = _pack_tree(tree)
+    dev = table.device
+    if indices.device != dev or values.device != dev:
+        raise RuntimeError("indices and values must be on the device of the feature table")
+    mode = ASSIGN_MODES[reduce]
+    with _on(dev), torch.no_grad():
+        counts = torch.empty((M,), dtype=torch.int32, device=dev) if return_counts else None      # zeroed by the call
+        nbytes = _lib.svoxt_assign_workspace_bytes(Q, M, mode)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        _call("svoxt_assign_leaves", ctypes.byref(ct), _ptr(indices), Q, _ptr(values), mode, _ptr(table), _ptr(counts), _ptr(ws),
+              nbytes, _stream(dev))
+        torch.autograd.graph.increment_version(table)           # written behind torch's back: the counter says so
+    return counts
+
+
+def leaf_corners(child: torch.Tensor, parent_depth: torch.Tensor, N: int, leaf_node: torch.Tensor) -> torch.Tensor:
+    """float32 [Q, 3]: the lower corner in [0, 1]^3 of the slots leaf_node (int64 [Q, 4]: node, x, y, z) -- one lane per
+    slot walks parent_depth[:, 0] to the root with the operations of N3Tree._calc_corners' torch walk, in its order: the
+    same bits (svoxt_leaf_corners).  A slot out of range gives NaN."""
+    for nm, x in (("child", child), ("parent_depth", parent_depth)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int32:
+            raise RuntimeError(f"{nm} must be an int32 tensor")
+    N = int(N)
+    if child.dim() != 4 or N < 2 or N > 16 or tuple(child.shape[1:]) != (N, N, N) or child.shape[0] < 1:
+        raise RuntimeError("child must be int32 [cap, N, N, N] with N in [2, 16]")
+    if tuple(parent_depth.shape) != (child.shape[0], 2):
+        raise RuntimeError("parent_depth must be int32 [cap, 2]")
+    if not isinstance(leaf_node, torch.Tensor) or leaf_node.dtype != torch.int64 or leaf_node.dim() != 2 or leaf_node.shape[1] != 4:
+        raise RuntimeError("leaf_node must be int64 [Q, 4]")
+    _check_on_device_of_child(child, parent_depth=parent_depth, leaf_node=leaf_node)
+    dev = child.device
+    Q = leaf_node.shape[0]
+    with _on(dev):
+        out = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_leaf_corners", _ptr(parent_depth), child.shape[0], N, _ptr(leaf_node), Q, _ptr(out), _stream(dev))
+    return out
+
+
+def snap_points(tree: TreeSpec, indices: torch.Tensor) -> torch.Tensor:
+    """float32 [Q, 3]: the lower corner of the leaf of every point, in the coordinates the points came in (world, or the
+    tree's own where the spec's offset / scaling are 0 / 1): query_vertical's descent, the corner walk, one launch
+    (svoxt_snap_points)."""
+    _check_indices(indices)
+    ct = _pack_tree(tree)
+    pd = tree.parent_depth
+    if not isinstance(pd, torch.Tensor) or pd.dtype != torch.int32 or pd.dim() != 2 or pd.shape[1] != 2 or pd.shape[0] < ct.n_internal:
+        raise RuntimeError("parent_depth must be int32 [>= n_internal, 2]")
+    _check_input(pd, "parent_depth")
+    dev = indices.device
+    if pd.device != dev:
+        raise RuntimeError("parent_depth must be on the device of indices")
+    Q = indices.shape[0]
+    with _on(dev):
+        out = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_snap_points", ctypes.byref(ct), _ptr(pd), _ptr(indices), Q, _ptr(out), _stream(dev))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # Entry points of svox_t.csrc that are outside this project's hot path
 # (SURVEY.md section 2).  They exist so a caller gets a clear error, not an
@@ -848,8 +932,15 @@ def _out_of_scope(name, instead=None):
     return fn
 
 
-for _n in ("assign_vertical", "calc_corners"):
-    globals()[_n] = _out_of_scope(_n)
+# the reference's names stay stubs (their argument lists are the reference's, svox.cpp:80-83); the operators live under new names
+assign_vertical = _out_of_scope(
+    "assign_vertical", "served under another name: assign_vertical(tree, indices, values) is "
+    "assign_leaves(tree, indices, values, reduce='last') -- N3Tree.set(indices, values), which also reduces the points "
+    "of a leaf by sum / mean / max / min; see INTEGRATION.md")
+calc_corners = _out_of_scope(
+    "calc_corners", "served under another name: calc_corners(tree, indexer) is leaf_corners(child, parent_depth, N, "
+    "leaf_node); snap_points(tree, indices) descends and takes the corner in one launch -- N3Tree.snap / leaf_boxes; see "
+    "INTEGRATION.md")
 # the reference's one-camera form of grid_weights; the name is kept a stub
 grid_weight_render = _out_of_scope(
     "grid_weight_render", "served under another name: grid_weight_render(data, cam, opt, offset, scaling) is "

@@ -348,6 +348,22 @@ __device__ __forceinline__ void locate(const TreeDev& tr, float px, float py, fl
     }
 }
 
+// The leaf of point q (q < Q) of a point query: its slot, and its feature row or -1 (an empty leaf).  The one place
+// where a query point is transformed, clamped and descended: svoxt_query_fwd / _bwd and svoxt_assign_leaves /
+// svoxt_snap_points all come through here, so they agree on the leaf of every point.
+template <bool N2>
+__device__ __forceinline__ int32_t query_locate(const TreeDev& tr, const float* __restrict__ points, int64_t q, uint32_t& slot) {
+    const float* p = points + 3 * q;
+    const float px = tr.offset[0] + tr.scaling[0] * p[0];
+    const float py = tr.offset[1] + tr.scaling[1] * p[1];
+    const float pz = tr.offset[2] + tr.scaling[2] * p[2];
+    Leaf lf;
+    locate<N2>(tr, px, py, pz, lf);
+    slot = lf.slot;
+    const int32_t idx = tr.data[lf.slot];
+    return (idx >= 0 && (int64_t)idx < tr.M) ? idx : -1;
+}
+
 // Acceleration grid.  Cell (cx,cy,cz) of the 2^G grid caches the state of the
 // root descent after (at most) G levels for any point inside the cell, in 4 bytes:
 //   bit 31 set  : the descent ended in a leaf at depth (bits 27-30) <= G whose data word

@@ -365,19 +365,7 @@ __device__ __forceinline__ void query_rows(const TreeDev& tr, int32_t ridx, int6
     }
 }
 
-// the leaf of point q (q < Q): its slot, and its feature row or -1
-template <bool N2>
-__device__ __forceinline__ int32_t query_locate(const TreeDev& tr, const float* __restrict__ points, int64_t q, uint32_t& slot) {
-    const float* p = points + 3 * q;
-    const float px = tr.offset[0] + tr.scaling[0] * p[0];
-    const float py = tr.offset[1] + tr.scaling[1] * p[1];
-    const float pz = tr.offset[2] + tr.scaling[2] * p[2];
-    Leaf lf;
-    locate<N2>(tr, px, py, pz, lf);
-    slot = lf.slot;
-    const int32_t idx = tr.data[lf.slot];
-    return (idx >= 0 && (int64_t)idx < tr.M) ? idx : -1;
-}
+// (query_locate, the leaf of a point: svoxt_device.h -- svoxt_assign.hip descends with the same function)
 
 template <bool N2>
 __global__ void __launch_bounds__(kBlock)

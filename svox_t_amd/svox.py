@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional
 import torch
 from torch import autograd, nn
 
-from svox_t_amd.helpers import DataFormat, N3TreeView, _get_c_extension
+from svox_t_amd.helpers import DataFormat, LocalIndex, N3TreeView, _get_c_extension
 
 _C = _get_c_extension()
 
@@ -48,6 +48,17 @@ class MergeResult(NamedTuple):
     row_map: Optional[torch.Tensor]   # old row of every carried feature row (None without compact_features)
     rows_added: int                   # new feature rows, behind the carried ones
 
+
+class LeafBoxes(NamedTuple):
+    """What N3Tree.leaf_boxes returns: every leaf slot in `_all_leaves()` order, on the tree's device."""
+    leaf_node: torch.Tensor           # int64 [L, 4]: node, x, y, z
+    corners: torch.Tensor             # float32 [L, 3]: lower corner
+    lengths: torch.Tensor             # float32 [L, 3]: side lengths
+    depths: torch.Tensor              # int32 [L]
+    rows: torch.Tensor                # int64 [L]: the feature row the leaf names, -1 for an empty leaf
+
+
+_ASSIGN_REDUCE = ("last", "sum", "mean", "max", "min")
 
 _REDUCE_CALLABLES = {torch.mean: "mean", torch.sum: "sum", torch.max: "max", torch.min: "min"}
 
@@ -247,6 +258,117 @@ class N3Tree(nn.Module):
 
     def __getitem__(self, key):
         return N3TreeView(self, key)
+
+    def __setitem__(self, key, values):
+        """tree[points] = values: set(points, values, reduce="last") for point keys [Q, 3] (world coordinates) and
+        LocalIndex(points) (the tree's own); values float32 [Q, K] or anything that broadcasts to it."""
+        local = isinstance(key, LocalIndex)
+        if local:
+            key = key.val
+        if not (torch.is_tensor(key) and key.dim() == 2 and key.shape[1] == 3):
+            raise NotImplementedError("N3Tree[key] = values: only point keys of shape [Q, 3] (and LocalIndex) are supported")
+        dev = self.data.device
+        pts = key.to(device=dev, dtype=torch.float32).contiguous()
+        values = torch.as_tensor(values, dtype=torch.float32, device=dev).detach()
+        values = values.expand(pts.shape[0], self.features.shape[1]).contiguous()
+        self.set(pts, values, world=not local)
+
+    def set(self, indices, values, cuda=True, *, world=True, reduce="last", features=None, return_rows=False):
+        """Write `values` (float32 [Q, K], no grad) into the feature rows of the leaves that contain the points
+        `indices` (float32 [Q, 3]; world coordinates, the tree's own with world=False) -- the reference's
+        N3Tree.set / assign_vertical (svox.py:287-309), with the case it leaves open ("if multiple indices point to same
+        leaf node, only one of them will be taken") defined.  One HIP pipeline (csrc/svoxt_assign.hip).
+
+        The leaf of a point is the one forward() / query_vertical reports for it (same transform, clamp, descent); a
+        point in an EMPTY leaf (data word >= M) is ignored.  Points are grouped by feature ROW: after refine, merge or
+        quantize several slots name one row, and all their points form one group.  Per group:
+          reduce="last"           the row takes the values of the group's highest-index point;
+          "sum" / "mean"          float32 sum of the group's rows per column, in ASCENDING POINT INDEX, sequential
+                                  (acc = v[q0]; acc += v[q1]; ...); mean divides that sum once by float(count);
+          "max" / "min"           elementwise over the group, in the same order (x > acc ? x : acc).  Finite values are
+                                  the contract: with a NaN in a group the result is unspecified.
+        Rows without a point keep their bits; the result is bit-identical from run to run in every mode.
+
+        The table written is `features` if given (float32 [M, K] on the tree's device), else self.features: in place,
+        under no_grad, its version counter moves.  Not differentiable.  The topology is not touched, so set() is
+        allowed inside accumulate_weights().  GPU only.
+        :return: None; with return_rows=True (rows int64 [U] ascending, counts int64 [U]): the rows written and the
+                 number of points each received (one host read, as in forward())"""
+        if reduce not in _ASSIGN_REDUCE:
+            raise RuntimeError(f"set: reduce must be one of {_ASSIGN_REDUCE}")
+        if not cuda or not self.data.is_cuda:
+            raise RuntimeError("set: only the GPU (HIP) path exists; move the tree to a GPU and call with cuda=True")
+        table = self.features if features is None else features
+        with torch.no_grad():
+            counts = _C.assign_leaves(self._spec(table, world=world), indices, values, reduce, return_counts=return_rows)
+        if not return_rows:
+            return None
+        rows = counts.nonzero(as_tuple=False).squeeze(1)
+        return rows, counts[rows].long()
+
+    def snap(self, indices, world=True):
+        """float32 [Q, 3]: the lower corner of the leaf that contains each point of `indices` (float32 [Q, 3]) -- what the
+        reference writes as tree[indices].corners -- in one launch (descend, then walk up).  World coordinates in and
+        out; the tree's own with world=False.  GPU only."""
+        if not self.data.is_cuda:
+            raise RuntimeError("snap: only the GPU (HIP) path exists; move the tree to a GPU")
+        return _C.snap_points(self._spec(self.features, world=world), indices)
+
+    def leaf_boxes(self, world=True):
+        """LeafBoxes(leaf_node, corners, lengths, depths, rows) of EVERY leaf slot, in `_all_leaves()` order, computed
+        and kept on the device (a nonzero, one kernel for the corners, three gathers): what a caller samples from
+        before set() -- points inside leaf i are corners[i] + u * lengths[i], u in [0, 1)^3.  corners / lengths
+        float32 [L, 3] in world coordinates (N3TreeView.corners / .lengths), in the tree's own with world=False (all
+        three lengths then equal N^-(depth + 1)); rows: the data word, -1 for empty leaves.  GPU only."""
+        if not self.data.is_cuda:
+            raise RuntimeError("leaf_boxes: only the GPU (HIP) path exists; move the tree to a GPU")
+        with torch.no_grad():
+            n = self.filled
+            leaf_node = (self.child[:n] == 0).nonzero(as_tuple=False).contiguous()     # (a transposed view on the GPU)
+            corners = _C.leaf_corners(self.child, self.parent_depth, self.N, leaf_node)
+            depths = self.parent_depth[leaf_node[:, 0], 1]
+            lengths = (float(self.N) ** (-depths.float() - 1.0))[:, None]
+            if world:
+                corners = (corners - self.offset) / self.invradius
+                lengths = lengths / self.invradius
+            else:
+                lengths = lengths.expand(-1, 3).contiguous()
+            words = self.data[:n].reshape(n, self.N, self.N, self.N)[tuple(leaf_node.T)].long()
+            rows = torch.where((words >= 0) & (words < self.features.shape[0]), words, torch.full_like(words, -1))
+        return LeafBoxes(leaf_node, corners, lengths, depths, rows)
+
+    # ------------------------------------------------------------------ copies
+    def partial(self, data_sel=None, device=None, data_format=None):
+        """A deep copy of the tree on `device` (default: where it is) that keeps the feature columns
+        torch.arange(K)[data_sel] -- partial(-1) is the sigma-only tree, a slice or a list keeps several; None keeps all
+        (the reference's partial, svox.py:311-337).  `data_dim` follows.  Topology, invradius / offset, extra_data and the
+        bookkeeping are copied; no storage is shared.  data_format: kept with data_sel=None, else the copy is a
+        plain-row tree ("RGBA") unless `data_format` names another.  `features` is a new nn.Parameter with the
+        source's requires_grad.  Works on CPU trees."""
+        dev = self.data.device if device is None else torch.device(device)
+        feats = self.features.detach()
+        if data_sel is not None:
+            sel = data_sel.cpu() if isinstance(data_sel, torch.Tensor) else data_sel
+            cols = torch.arange(feats.shape[1])[sel].reshape(-1)
+            if cols.numel() == 0:
+                raise RuntimeError("data_sel selects no column")
+            feats = feats[:, cols.to(feats.device)]
+        if data_format is None:
+            data_format = "RGBA" if data_sel is not None else (None if self.data_format is None else repr(self.data_format))
+        extra = None if self.extra_data is None else self.extra_data.to(device=dev, copy=True)
+        t = N3Tree(N=self.N, data_dim=feats.shape[1], depth_limit=self.depth_limit, init_reserve=1,
+                   geom_resize_fact=self.geom_resize_fact, data_format=data_format, extra_data=extra, map_location=dev)
+        with torch.no_grad():
+            t.features = nn.Parameter(feats.to(device=dev, copy=True).contiguous(), requires_grad=self.features.requires_grad)
+            for nm in ("data", "child", "parent_depth", "_n_internal", "_n_free", "invradius", "offset"):
+                setattr(t, nm, getattr(self, nm).to(device=dev, copy=True))
+        t.filled = self.filled
+        t._invalidate()
+        return t
+
+    def clone(self, device=None):
+        """A deep copy of the tree on `device` (default: where it is): partial() with every column (svox.py:339-340)."""
+        return self.partial(device=device)
 
     # ----------------------------------------------------------------- refine
     def refine(self, repeats=1, sel=None, leaf_node=None, node_id=None):
@@ -636,8 +758,12 @@ class N3Tree(nn.Module):
 
     def _calc_corners(self, nodes):
         """Lower corner in [0,1]^3 of each leaf slot in `nodes` [Q, 4]
-        (svox.py:808-826), walking the parent chain with torch ops."""
+        (svox.py:808-826): on a GPU one kernel (svox_t_amd.csrc.leaf_corners), on the CPU the reference's walk of the
+        parent chain with torch ops."""
         nodes = nodes.to(self.parent_depth.device).long()
+        if self.parent_depth.is_cuda and nodes.dim() == 2 and nodes.shape[1] == 4:
+            # one kernel, a lane per slot: the same operations in the same order, the same bits, no host read per level
+            return _C.leaf_corners(self.child, self.parent_depth, self.N, nodes.contiguous())
         corner = torch.zeros(nodes.shape[0], 3, device=nodes.device)
         curr = nodes.clone()
         live = torch.ones(nodes.shape[0], dtype=torch.bool, device=nodes.device)
