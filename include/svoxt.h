@@ -958,6 +958,54 @@ int svoxt_leaf_corners(const int32_t* parent_depth, int64_t n_internal, int32_t 
 int svoxt_snap_points(const svoxt_tree* tree, const int32_t* parent_depth, const float* points, int64_t Q, float* corners,
                       void* stream);
 
+/* ---- Feature-table optimizers: SGD, RMSprop and Adam as one streaming kernel that can skip untouched rows ------------
+ *
+ * svoxt_optim_step updates param (device float32 [M, K], in place) from grad (device float32 [M, K], read only) and the
+ * kind's state tables (device float32 [M, K] each, in place; svoxt_optim_state_count(kind) of them: 0, 1 or 2, -1 for an
+ * unknown kind; a table the kind does not keep is not read and may be NULL).  Everything is float32, element by
+ * element, every operation a separate correctly rounded + - * / sqrt, no fused multiply-add, in exactly this order:
+ *   SVOXT_OPTIM_SGD           p = p + neg_step * g
+ *   SVOXT_OPTIM_SGD_MOMENTUM  b = momentum * b + g;  p = p + neg_step * b                     (b: state1, zero at first)
+ *   SVOXT_OPTIM_RMSPROP       v = beta2 * v + one_minus_beta2 * (g * g)
+ *                             p = p + neg_step * (g / (sqrt(v) + eps))                        (v: state1; beta2 = alpha)
+ *   SVOXT_OPTIM_ADAM          m = m + (g - m) * one_minus_beta1
+ *                             v = beta2 * v + one_minus_beta2 * (g * g)
+ *                             d = sqrt(v) / bias2_sqrt + eps
+ *                             p = p + neg_step * (m / d)                                      (m: state1, v: state2)
+ * The scalars of svoxt_optim_hyper are the caller's: each computed in double precision and rounded to float32 once --
+ * neg_step = -lr (SGD, RMSprop) or -lr / (1 - beta1^t) (Adam), one_minus_beta1 = 1 - beta1, one_minus_beta2 = 1 - beta2
+ * (1 - alpha), bias2_sqrt = sqrt(1 - beta2^t), t the 1-based count of steps taken (global: it advances for every row).
+ * This is torch.optim.Adam's form (eps added after the bias correction), not SparseAdam's.  Fields a kind does not name
+ * are not read.  There is no weight decay, Nesterov momentum, amsgrad, centered RMSprop or maximize.
+ *
+ * A row is TOUCHED iff some element of its row of grad compares != 0: +0 and -0 do not touch, a NaN does.  lazy = 1:
+ * an untouched row keeps every bit of param and of the state tables, and those are not read for it (the gradient is
+ * read once for every row).  lazy = 0: every row is updated -- the moments decay where g = 0, torch.optim's dense
+ * semantics.  SVOXT_OPTIM_SGD gives the same table either way.
+ * 16 bytes a lane where K % 4 == 0 and every table is 16-byte aligned, 4 bytes otherwise; any K >= 1.  The tables must
+ * be distinct and must not overlap.  Checked before any HIP call (SVOXT_ERR_INVALID): kind, M >= 1, K >= 1, M * K < 2^37
+ * (indices are 64-bit) and M * G < 2^32 - 256, G the lanes a row takes in the one launch: the power of two >= K / 4 (>= K
+ * on the 4-byte path), at most 64 -- K = 28 or 32: M < 2^29; lazy in {0, 1}, no NULL where the kind needs a table, the
+ * tables pairwise different.
+ * One launch on `stream`; no workspace, no allocation, no host read, no synchronisation.  The result is a function of
+ * the inputs: two runs give the same bytes. */
+#define SVOXT_OPTIM_SGD 0
+#define SVOXT_OPTIM_SGD_MOMENTUM 1
+#define SVOXT_OPTIM_RMSPROP 2
+#define SVOXT_OPTIM_ADAM 3
+typedef struct svoxt_optim_hyper {
+    float neg_step;        /* -lr, or -lr / (1 - beta1^t) for Adam */
+    float momentum;        /* SGD_MOMENTUM */
+    float one_minus_beta1; /* ADAM */
+    float beta2;           /* ADAM; RMSPROP: alpha */
+    float one_minus_beta2; /* ADAM; RMSPROP: 1 - alpha */
+    float bias2_sqrt;      /* ADAM: sqrt(1 - beta2^t) */
+    float eps;             /* RMSPROP, ADAM */
+} svoxt_optim_hyper;
+int svoxt_optim_state_count(int32_t kind);
+int svoxt_optim_step(int32_t kind, float* param, const float* grad, float* state1, float* state2, int64_t M, int32_t K,
+                     svoxt_optim_hyper hyper, int32_t lazy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

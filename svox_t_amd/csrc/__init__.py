@@ -1178,5 +1178,6 @@ from ._extras import (assign_vertical, build_octree, bwd_check, bwd_counters, ca
                       query_vertical, query_vertical_backward, refine_leaves, warp_vertices, warp_vertices_backward)
 from ._extras import gather_rows, grid_weights, prune_tree, remap_index  # noqa: E402,F401
 from ._extras import assign_leaves, leaf_corners, snap_points  # noqa: E402,F401
+from ._extras import OPTIM_KINDS, OPTIM_STATES, optim_step  # noqa: E402,F401
 from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_reduce_backward,  # noqa: E402,F401
                       merge_tree)

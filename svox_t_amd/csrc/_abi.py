@@ -1,4 +1,4 @@
-"""The C ABI of libsvoxt_hip.so (include/svoxt.h) as ctypes sees it: the library, the five structs, every export with
+"""The C ABI of libsvoxt_hip.so (include/svoxt.h) as ctypes sees it: the library, the structs, every export with
 its signature, the version check.  Nothing here knows about torch tensors (svox_t_amd/csrc/_marshal.py does)."""
 from __future__ import annotations
 
@@ -78,6 +78,11 @@ class _CStep(ctypes.Structure):          # struct svoxt_step
                                               "off_terms", "terms_bytes", "off_grad_rows", "off_bwd_ws", "bwd_ws_bytes", "nt")] + \
                [(n, ctypes.c_int32) for n in ("pad_K", "pad_real", "pad_dummy", "pad_w")] + \
                [(n, ctypes.c_int64) for n in ("off_pad_features", "off_pad_out", "off_pad_gout", "off_pad_grad")]
+
+
+class _COptimHyper(ctypes.Structure):    # struct svoxt_optim_hyper
+    _fields_ = [(n, ctypes.c_float) for n in ("neg_step", "momentum", "one_minus_beta1", "beta2", "one_minus_beta2",
+                                              "bias2_sqrt", "eps")]
 
 
 # svoxt_sample_lists.flags (include/svoxt.h)
@@ -173,6 +178,8 @@ EXPORTS = {
     "svoxt_assign_leaves": (ctypes.c_int, [_P(_CTree), _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_leaf_corners": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "svoxt_snap_points": (ctypes.c_int, [_P(_CTree), _vp, _vp, _i64, _vp, _vp]),
+    "svoxt_optim_state_count": (ctypes.c_int, [_i32]),
+    "svoxt_optim_step": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _COptimHyper, _i32, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

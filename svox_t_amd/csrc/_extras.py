@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from ._abi import _CMotion, _CRays, _CTree, _lib
+from ._abi import _CMotion, _COptimHyper, _CRays, _CTree, _lib
 from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _check_quantize, _numel, _pack_opts, _pack_rays,
                        _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
 
@@ -914,6 +914,57 @@ def snap_points(tree: TreeSpec, indices: torch.Tensor) -> torch.Tensor:
         out = torch.empty((Q, 3), dtype=torch.float32, device=dev)
         _call("svoxt_snap_points", ctypes.byref(ct), _ptr(pd), _ptr(indices), Q, _ptr(out), _stream(dev))
     return out
+
+
+OPTIM_KINDS = {"sgd": 0, "sgd_momentum": 1, "rmsprop": 2, "adam": 3}        # SVOXT_OPTIM_* (include/svoxt.h)
+OPTIM_STATES = {"sgd": 0, "sgd_momentum": 1, "rmsprop": 1, "adam": 2}        # svoxt_optim_state_count
+_HYPER_FIELDS = tuple(n for n, _ in _COptimHyper._fields_)
+
+
+def optim_step(kind: str, param: torch.Tensor, grad: torch.Tensor, state1, state2, hyper: dict, lazy: bool = True) -> None:
+    """One optimizer step on a feature table, IN PLACE, as one launch on torch's current stream (svoxt_optim_step;
+    include/svoxt.h has the arithmetic).  kind: "sgd", "sgd_momentum" (state1 = the momentum buffer), "rmsprop" (state1 =
+    the square average) or "adam" (state1, state2 = the two moments); param, grad and the kind's state tables are
+    float32 [M, K], contiguous, on one GPU; a table the kind does not keep must be None.  hyper: the float32 scalars of
+    svoxt_optim_hyper by name (neg_step, momentum, one_minus_beta1, beta2, one_minus_beta2, bias2_sqrt, eps; the ones
+    left out are 0), each computed by the caller in double precision.  lazy: rows whose gradient is all zeros keep
+    their bits and are not read.  The version counters of param and of the state tables are bumped (the renderer's
+    caches key on them).  Bad arguments raise RuntimeError before any GPU work."""
+    if kind not in OPTIM_KINDS:
+        raise RuntimeError(f"kind must be one of {sorted(OPTIM_KINDS)}")
+    ns = OPTIM_STATES[kind]
+    states = (state1, state2)
+    for i, x in enumerate(states):
+        if (x is not None) != (i < ns):
+            raise RuntimeError(f'"{kind}" keeps {ns} state table(s): state{i + 1} must be ' + ("given" if i < ns else "None"))
+    tables = [("param", param), ("grad", grad)] + [(f"state{i + 1}", x) for i, x in enumerate(states[:ns])]
+    for name, x in tables:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.layout != torch.strided:
+            raise RuntimeError(f"{name} must be a dense float32 tensor")
+    if param.dim() != 2 or param.shape[0] < 1 or param.shape[1] < 1:
+        raise RuntimeError("param must be [M, K] with M, K >= 1")
+    for name, x in tables[1:]:
+        if tuple(x.shape) != tuple(param.shape):
+            raise RuntimeError(f"{name} must have the shape of param, {tuple(param.shape)}")
+    for name, x in tables:
+        if not x.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    if not isinstance(hyper, dict) or any(k not in _HYPER_FIELDS for k in hyper):
+        raise RuntimeError(f"hyper must be a dict with keys among {_HYPER_FIELDS}")
+    ch = _COptimHyper(**{k: float(v) for k, v in hyper.items()})
+    for name, x in tables:
+        _check_input(x, name)
+        if x.device != param.device:
+            raise RuntimeError(f"{name} must be on the device of param")
+    if len({x.data_ptr() for _, x in tables}) != len(tables):
+        raise RuntimeError("param, grad and the state tables must be distinct tensors")
+    dev = param.device
+    M, K = param.shape
+    with _on(dev), torch.no_grad():
+        _call("svoxt_optim_step", OPTIM_KINDS[kind], _ptr(param), _ptr(grad), _ptr(state1), _ptr(state2), M, K, ch,
+              int(bool(lazy)), _stream(dev))
+        for _, x in tables[:1] + tables[2:]:                    # written behind torch's back: the counters say so
+            torch.autograd.graph.increment_version(x)
 
 
 # ---------------------------------------------------------------------------

@@ -456,7 +456,8 @@ class N3Tree(nn.Module):
 
         Replaces `child`, `data`, `parent_depth` and, with `compact_features`, `self.features` by a NEW
         nn.Parameter(features[row_map]): an optimizer that holds the old parameter has to be rebuilt, its state sliced
-        with the result's `row_map` (the reference's warning on shrink_to_fit, svox.py:606-607).  A tree left without a
+        with the result's `row_map` -- FeatureSGD / FeatureRMSprop / FeatureAdam do both as `opt.rebind(old, tree.features,
+        result.row_map)` (the reference's warning on shrink_to_fit, svox.py:606-607).  A tree left without a
         feature row (nothing kept) is refused by the renderer and the point query (RuntimeError) until it has rows again.  GPU only.
         :return: PruneResult(n_internal, nodes_removed, leaves_dropped, row_map); row_map int64 [M'] = the old row of
                  every new feature row, None without `compact_features`"""
@@ -499,7 +500,8 @@ class N3Tree(nn.Module):
         not checked.  0 <= order <= 16 and 2^order <= M.
 
         Replaces `self.features` by a NEW nn.Parameter(colors): an optimizer that holds the old parameter has to be
-        rebuilt (its state belongs to rows that no longer exist; the reference's warning on shrink_to_fit,
+        rebuilt (its state belongs to rows that no longer exist; FeatureSGD / FeatureRMSprop / FeatureAdam:
+        `opt.rebind(old, tree.features)`, fresh state; the reference's warning on shrink_to_fit,
         svox.py:606-607).  GPU only.
         :return: QuantizeResult(colors float32 [2^order, K], color_id_map int32 [M])"""
         if self._lock_tree_structure:
@@ -635,7 +637,9 @@ class N3Tree(nn.Module):
         merged node.  Every output word is a function of the input: two runs give the same bytes.
 
         Replaces `child`, `data`, `parent_depth` and `self.features`, by a NEW nn.Parameter: an optimizer that holds
-        the old parameter has to be rebuilt, its state sliced with `row_map` (new rows start fresh) -- the reference's
+        the old parameter has to be rebuilt, its state sliced with `row_map` (new rows start fresh; FeatureSGD /
+        FeatureRMSprop / FeatureAdam: `opt.rebind(old, tree.features, row_map)` where no rows were added, without
+        `row_map` where some were) -- the reference's
         warning on shrink_to_fit, svox.py:606-607.  The acceleration caches are invalidated.  One call merges one
         level; see simplify().  GPU only.
         :return: MergeResult(n_internal, nodes_merged, row_map, rows_added)"""
