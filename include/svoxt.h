@@ -791,6 +791,51 @@ int svoxt_prune_emit(const int32_t* child, const int32_t* data, const int32_t* p
 int svoxt_prune_gather_rows(const float* src, int64_t src_rows, const int64_t* row_map, float* dst, int64_t n,
                             int32_t cols, void* stream);
 
+/* ---- Growing: N3Tree.subdivide and N3Tree.unshare (the reference has refine, svox.py:488-560, whose new leaves share
+ * the parent's data word) ---------------------------------------------------------------------------------------------
+ *
+ * subdivide.  From the tree tables (as for svoxt_prune_count), the number M of feature rows and a selection per slot
+ * of child -- sel (device uint8, non-zero = selected) or weights (device float32; selected iff weights >= threshold, so
+ * a NaN weight never splits), at most one of the two, neither = every slot; entries at slots that are not leaves are
+ * ignored.  A slot of a node < n_internal splits iff child == 0, it is selected, parent_depth[node, 1] < depth_limit
+ * and its data word, read as unsigned, is < M (split_empty != 0: empty leaves split too).  The splitting slots, in
+ * ascending flat order, become the nodes n_internal, n_internal + 1, ...: child[slot] = new id - node, the new node has
+ * child 0 everywhere and parent_depth (flat slot index, depth + 1); the split slot's own data word stays as it is.
+ *   own_rows == 0: every slot of a new node takes the parent's data word (what svoxt_refine writes); no rows.
+ *   own_rows != 0: below a split leaf that names row r, the k-th such leaf in slot order, slot 0 keeps r and slot
+ *      j > 0 gets row M + k (N^3 - 1) + (j - 1); below an empty split leaf every slot is empty_index.  row_map (device
+ *      int64 [M + rows_added]) lists the old row of every new row: 0 .. M - 1, then each r N^3 - 1 times.
+ * Integer work, no order dependence: the outputs are a function of the inputs, identical from run to run.
+ *
+ * svoxt_subdivide_count marks, scans and lists; counts (device int64[2]) receives the nodes added and the rows added.
+ * The host reads it -- the one host read --, makes sure the three tables have n_internal + nodes_added rows (they may
+ * be reallocated and copied: the selection is not read again), allocates row_map and calls svoxt_subdivide_emit with
+ * the workspace unchanged.  The emit works IN PLACE: it writes the rows [n_internal, n_internal + nodes_added) of the
+ * three tables and the child word of every split slot, nothing else.  capacity = the rows the tables have.
+ *
+ * unshare.  Every leaf slot of a node < n_internal that names a row which a slot with a smaller flat index names too
+ * gets a row of its own: rows M, M + 1, ... in ascending slot order; row_map (device int64 [M + rows_added]) as above.
+ * svoxt_unshare_count finds the first slot of every row (an integer atomicMin per row), marks and scans; counts
+ * (device int64[1]) receives the rows added.  svoxt_unshare_emit rewrites the data words in place and writes row_map.
+ *
+ * The new feature table (and per-row optimizer state) is svoxt_prune_gather_rows through row_map.
+ * workspace: svoxt_subdivide_workspace_bytes(n_internal, N, M) device bytes for either operation (20 bytes per slot;
+ * -1 for extents out of range).  Every argument is checked before any HIP call (SVOXT_ERR_INVALID): N in [2, 16],
+ * n_internal * N^3 < 2^31, capacity * N^3 < 2^31, M + rows_added < empty_index as an unsigned number, the counts
+ * consistent with each other, no NULL where a pointer is required. */
+int64_t svoxt_subdivide_workspace_bytes(int64_t n_internal, int32_t N, int64_t M);
+int svoxt_subdivide_count(const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n_internal,
+                          int32_t N, int64_t M, const uint8_t* sel, const float* weights, float threshold,
+                          int32_t depth_limit, int32_t split_empty, int32_t own_rows, void* workspace,
+                          int64_t workspace_bytes, int64_t* counts, void* stream);
+int svoxt_subdivide_emit(int32_t* child, int32_t* data, int32_t* parent_depth, int64_t n_internal, int32_t N, int64_t M,
+                         int64_t capacity, int32_t own_rows, const void* workspace, int64_t workspace_bytes,
+                         int64_t nodes_added, int64_t rows_added, int32_t empty_index, int64_t* row_map, void* stream);
+int svoxt_unshare_count(const int32_t* child, const int32_t* data, int64_t n_internal, int32_t N, int64_t M,
+                        void* workspace, int64_t workspace_bytes, int64_t* counts, void* stream);
+int svoxt_unshare_emit(int32_t* data, int64_t n_internal, int32_t N, int64_t M, const void* workspace,
+                       int64_t workspace_bytes, int64_t rows_added, int32_t empty_index, int64_t* row_map, void* stream);
+
 /* ---- Dense-grid weights: grid_weights (the reference's grid_weight_render, rt_kernel.cu:1240-1344, 1454-1478) ----
  *
  * Marches rays through a dense density volume sigma (device float32 [R, R, R], cell (u, v, w) at (u R + v) R + w) and

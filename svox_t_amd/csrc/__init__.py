@@ -1181,3 +1181,4 @@ from ._extras import assign_leaves, leaf_corners, snap_points  # noqa: E402,F401
 from ._extras import OPTIM_KINDS, OPTIM_STATES, optim_step  # noqa: E402,F401
 from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_reduce_backward,  # noqa: E402,F401
                       merge_tree)
+from ._extras import subdivide_tree, unshare_rows  # noqa: E402,F401

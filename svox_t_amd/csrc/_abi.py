@@ -160,7 +160,12 @@ EXPORTS = {
     "svoxt_prune_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _i64, _i32,
                                         _vp, _vp, _vp, _vp, _vp]),
     "svoxt_prune_gather_rows": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp]),
-    "svoxt_quantize_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "svoxt_subdivide_workspace_bytes": (_i64, [_i64, _i32, _i64]),
+    "svoxt_subdivide_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, ctypes.c_float, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "svoxt_subdivide_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "svoxt_unshare_count": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp]),
+    "svoxt_unshare_emit": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "svoxt_quantize_workspace_bytes":(_i64, [_i64, _i32, _i32, _i32]),
     "svoxt_quantize_median_cut": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_remap_index": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "svoxt_grid_weights": (ctypes.c_int, [_vp, _i32, _P(_CRays), _i32, _i32, _P(_COptions), _vp, _vp, _i32, _vp, _vp, _vp]),

@@ -1,7 +1,7 @@
 """The operators of `svox_t.csrc` around the render path: point query (svox_kernel.cu:45-94, 240-324), the roofline
 counters, the motion variants (rt_kernel.cu:698-1061), point skinning (svox_kernel.cu:123-211), octree construction
-(svox.py:160-161, 488-560), pruning, the frontier reductions and merge -- marshalling only, one C-ABI call each (two for
-the builder, prune, the frontier and merge)."""
+(svox.py:160-161, 488-560), pruning, subdividing, the frontier reductions and merge -- marshalling only, one C-ABI call
+each (two for the builder, prune, subdivide, unshare, the frontier and merge)."""
 from __future__ import annotations
 
 import ctypes
@@ -430,6 +430,119 @@ def gather_rows(src: torch.Tensor, row_map: torch.Tensor) -> torch.Tensor:
         _call("svoxt_prune_gather_rows", _ptr(src), src.shape[0], _ptr(row_map), _ptr(dst), row_map.shape[0], src.shape[1],
               _stream(dev))
     return dst
+
+
+def _grown_tables(child, data, parent_depth, rows, empty_index):
+    """The three tables with `rows` rows: the old ones copied, the rows behind them initialised like unused rows of an N3Tree."""
+    cap, N = child.shape[0], child.shape[1]
+    dev = child.device
+    child2 = torch.zeros((rows, N, N, N), dtype=torch.int32, device=dev)
+    data2 = torch.full((rows, N, N, N, 1), int(empty_index), dtype=torch.int32, device=dev)
+    pd2 = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
+    child2[:cap], data2[:cap], pd2[:cap] = child, data.reshape(cap, N, N, N, 1), parent_depth
+    return child2, data2, pd2
+
+
+def subdivide_tree(child: torch.Tensor, data: torch.Tensor, parent_depth: torch.Tensor, n_internal: int, M: int,
+                   sel: torch.Tensor = None, weights: torch.Tensor = None, threshold: float = None, depth_limit: int = 0x7fffffff,
+                   split_empty: bool = False, own_rows: bool = True, empty_index: int = 1410065408, grow=None,
+                   slot_limit: int = 1 << 31):
+    """Split the selected leaves of a tree into new nodes behind `n_internal`, in one pipeline (csrc/svoxt_subdivide.hip;
+    include/svoxt.h, svoxt_subdivide_count has the rules): the topology N3Tree.refine(sel) writes, with `own_rows` a
+    feature row of its own for every new leaf but the first of each node.
+
+    sel: bool / uint8 with the shape of child, or weights: float32 of that shape with `threshold` (selected iff
+    weights >= threshold; NaN never splits), or neither: every leaf.  The tables are written IN PLACE where their
+    capacity suffices; otherwise `grow(rows_needed)` has to return larger (child, data, parent_depth) holding the old
+    rows (None: new tables of exactly the rows needed).  Returns (child, data, parent_depth, nodes_added, rows_added,
+    row_map): row_map int64 [M + rows_added] = the old row of every new feature row, None without own_rows.  Refused
+    before anything is written: (n_internal + nodes_added) * N^3 >= slot_limit (2^31: slot indices are int32),
+    M + rows_added >= empty_index.  One host read (the counts)."""
+    cap, N, n = _check_tables(child, data, parent_depth, n_internal)
+    M = int(M)
+    if M < 0:
+        raise RuntimeError("M must be >= 0")
+    if sel is not None and weights is not None:
+        raise RuntimeError("at most one of sel / weights may be given")
+    if sel is not None:
+        if not isinstance(sel, torch.Tensor) or sel.dtype not in (torch.bool, torch.uint8) or tuple(sel.shape) != tuple(child.shape):
+            raise RuntimeError("sel must be a bool or uint8 tensor with the shape of child")
+        if threshold is not None:
+            raise RuntimeError("threshold goes with weights, not with sel")
+    thr = 0.0
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(child.shape):
+            raise RuntimeError("weights must be a float32 tensor with the shape of child")
+        if threshold is None or float(threshold) != float(threshold):
+            raise RuntimeError("weights needs a threshold (not NaN)")
+        thr = float(threshold)
+    elif threshold is not None and sel is None:
+        raise RuntimeError("threshold goes with weights")
+    extra = {k: v for k, v in (("sel", sel), ("weights", weights)) if v is not None}
+    if any(isinstance(v, torch.Tensor) and v.device != child.device for v in extra.values()):
+        raise RuntimeError("sel / weights must be on the device of child")
+    _check_on_device_of_child(child, data=data, parent_depth=parent_depth, **extra)
+    dev = child.device
+    n3 = N ** 3
+    limit = max(-0x80000000, min(0x7fffffff, int(depth_limit)))
+    with _on(dev):
+        nbytes = _lib.svoxt_subdivide_workspace_bytes(n, N, M)
+        if nbytes < 0:
+            raise RuntimeError("subdivide_tree: n_internal * N^3 and M must be below 2^31")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((2,), dtype=torch.int64, device=dev)
+        _call("svoxt_subdivide_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(sel), _ptr(weights), thr, limit,
+              int(bool(split_empty)), int(bool(own_rows)), _ptr(ws), nbytes, _ptr(counts), _stream(dev))
+        added, rows_added = (int(v) for v in counts.tolist())         # the one host read: sizes the outputs
+        if (n + added) * n3 >= int(slot_limit):
+            raise RuntimeError(f"subdivide_tree: {n} + {added} nodes of {n3} slots do not fit 32-bit slot indices "
+                               f"((n_internal + nodes_added) * N^3 must be < {int(slot_limit)})")
+        if M + rows_added >= int(empty_index):
+            raise RuntimeError(f"subdivide_tree: {M} + {rows_added} feature rows reach the empty index {int(empty_index)}")
+        row_map = torch.empty((M + rows_added,), dtype=torch.int64, device=dev) if own_rows else None
+        if n + added > cap:
+            child, data, parent_depth = grow(n + added) if grow is not None else \
+                _grown_tables(child, data, parent_depth, n + added, empty_index)
+            _check_tables(child, data, parent_depth, n + added)
+            _check_on_device_of_child(child, data=data, parent_depth=parent_depth)
+            if child.device != dev:
+                raise RuntimeError("grow() must return tables on the device of the old ones")
+        _call("svoxt_subdivide_emit", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, child.shape[0], int(bool(own_rows)),
+              _ptr(ws), nbytes, added, rows_added, int(empty_index), _ptr(row_map), _stream(dev))
+    if added > 0:                                     # (nothing splits: row_map = 0 .. M - 1 is all the emit wrote)
+        for t in (child, data, parent_depth):
+            torch.autograd.graph.increment_version(t)
+        _drop_accel(child)
+    return child, data, parent_depth, added, rows_added, row_map
+
+
+def unshare_rows(child: torch.Tensor, data: torch.Tensor, n_internal: int, M: int, empty_index: int = 1410065408):
+    """Give every leaf slot that names a feature row an earlier slot names too a row of its own (csrc/svoxt_subdivide.hip;
+    include/svoxt.h, svoxt_unshare_count): the slot with the smallest flat index keeps the row, the others get rows M,
+    M + 1, ... in slot order.  `data` is rewritten IN PLACE.  Returns (rows_added, row_map int64 [M + rows_added] = the old
+    row of every new row).  One host read (the count)."""
+    _, N, n = _check_tables(child, data, None, n_internal)
+    M = int(M)
+    if M < 0:
+        raise RuntimeError("M must be >= 0")
+    _check_on_device_of_child(child, data=data)
+    dev = child.device
+    with _on(dev):
+        nbytes = _lib.svoxt_subdivide_workspace_bytes(n, N, M)
+        if nbytes < 0:
+            raise RuntimeError("unshare_rows: n_internal * N^3 and M must be below 2^31")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        count = torch.empty((1,), dtype=torch.int64, device=dev)
+        _call("svoxt_unshare_count", _ptr(child), _ptr(data), n, N, M, _ptr(ws), nbytes, _ptr(count), _stream(dev))
+        rows_added = int(count.item())                                  # the one host read: sizes row_map
+        if M + rows_added >= int(empty_index):
+            raise RuntimeError(f"unshare_rows: {M} + {rows_added} feature rows reach the empty index {int(empty_index)}")
+        row_map = torch.empty((M + rows_added,), dtype=torch.int64, device=dev)
+        _call("svoxt_unshare_emit", _ptr(data), n, N, M, _ptr(ws), nbytes, rows_added, int(empty_index), _ptr(row_map), _stream(dev))
+    if rows_added > 0:
+        torch.autograd.graph.increment_version(data)
+        _drop_accel(child)
+    return rows_added, row_map
 
 
 REDUCE_OPS = {"mean": 0, "sum": 1, "max": 2, "min": 3}        # SVOXT_REDUCE_* (include/svoxt.h)

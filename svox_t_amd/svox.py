@@ -49,6 +49,20 @@ class MergeResult(NamedTuple):
     rows_added: int                   # new feature rows, behind the carried ones
 
 
+class SubdivideResult(NamedTuple):
+    """What N3Tree.subdivide did."""
+    n_internal: int
+    nodes_added: int
+    rows_added: int                   # new feature rows, behind the old ones
+    row_map: Optional[torch.Tensor]   # old row of every new feature row (None without own_rows)
+
+
+class UnshareResult(NamedTuple):
+    """What N3Tree.unshare did."""
+    rows_added: int
+    row_map: torch.Tensor             # old row of every new feature row
+
+
 class LeafBoxes(NamedTuple):
     """What N3Tree.leaf_boxes returns: every leaf slot in `_all_leaves()` order, on the tree's device."""
     leaf_node: torch.Tensor           # int64 [L, 4]: node, x, y, z
@@ -380,7 +394,9 @@ class N3Tree(nn.Module):
         `sel` = tuple of four index tensors (node, x, y, z); default: all leaves
         shallower than depth_limit.  Unlike the reference, `repeats > 1`
         recomputes the selector each round (the reference reuses a stale
-        `leaf_node`, svox.py:521-522)."""
+        `leaf_node`, svox.py:521-522).  subdivide() selects on the device and
+        gives the new leaves feature rows of their own; unshare() does the
+        latter for a tree refined here."""
         if self._lock_tree_structure:
             raise RuntimeError("Tree locked")
         resized = False
@@ -459,6 +475,7 @@ class N3Tree(nn.Module):
         with the result's `row_map` -- FeatureSGD / FeatureRMSprop / FeatureAdam do both as `opt.rebind(old, tree.features,
         result.row_map)` (the reference's warning on shrink_to_fit, svox.py:606-607).  A tree left without a
         feature row (nothing kept) is refused by the renderer and the point query (RuntimeError) until it has rows again.  GPU only.
+        subdivide() is the growing counterpart: it takes the same per-slot weights and splits the leaves that matter.
         :return: PruneResult(n_internal, nodes_removed, leaves_dropped, row_map); row_map int64 [M'] = the old row of
                  every new feature row, None without `compact_features`"""
         if self._lock_tree_structure:
@@ -480,6 +497,100 @@ class N3Tree(nn.Module):
             self._invalidate()
         return PruneResult(n, before - n, dropped, row_map)
 
+    # -------------------------------------------------------------- subdivide
+    _slot_limit = 1 << 31             # slot indices are int32: (filled + nodes_added) * N^3 has to stay below this
+
+    def subdivide(self, sel=None, *, weights=None, threshold=None, max_depth=None, split_empty=False, own_rows=True):
+        """Split leaves into new nodes and give the new leaves feature rows of their own: the growing counterpart of
+        prune(), one HIP pipeline with one host read (csrc/svoxt_subdivide.hip).  refine() writes the same topology,
+        but selects on the host and leaves the N^3 new leaves of a split leaf on ONE feature row, where they cannot
+        diverge and there is no row_map for an optimizer.
+
+        The decision is per slot of `child`, entries at slots that are not leaves are ignored: `sel`, bool / uint8
+        with the shape of `child`, or `weights` (float32 of that shape: what `accumulate_weights()` gives as
+        `accum.value`) with `threshold` -- a slot is selected iff weights >= threshold, so a NaN weight never splits --
+        or neither: every leaf.  A selected leaf splits iff its node's depth is below min(depth_limit, max_depth)
+        (refine's test) and it is not empty (`split_empty`: empty leaves split too, into N^3 empty leaves).  The
+        splitting slots, in `_all_leaves()` order, become the nodes filled, filled + 1, ... exactly as
+        refine(sel=<those leaves>) writes them; the tables are regrown geometrically where the capacity does not
+        suffice.
+          `own_rows` (default): below the k-th split non-empty leaf (row r) slot 0 keeps r, slot j > 0 gets the new row
+             M + k (N^3 - 1) + (j - 1), a copy of r: every point query returns the bits it returned before.
+             `self.features` becomes a NEW nn.Parameter(features[row_map]); an optimizer that holds the old one:
+             `opt.rebind(old, tree.features, result.row_map)` (FeatureSGD / FeatureRMSprop / FeatureAdam).
+          `own_rows=False`: every new leaf takes the parent's data word, as after refine(); `features` is untouched.
+             unshare() separates the rows later.
+        A result with (filled + nodes_added) N^3 >= 2^31 or M' >= EMPTY_INDEX is refused and the tree left as it was.
+        GPU only.
+        :return: SubdivideResult(n_internal, nodes_added, rows_added, row_map); row_map int64 [M'] = the old row of
+                 every new feature row (arange(M), then each r N^3 - 1 times), None without `own_rows`"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if sel is not None and weights is not None:
+            raise RuntimeError("subdivide: at most one of sel / weights may be given")
+        if weights is not None and threshold is None:
+            raise RuntimeError("subdivide: weights needs a threshold")
+        if weights is None and threshold is not None:
+            raise RuntimeError("subdivide: threshold goes with weights")
+        for nm, x, dtypes in (("sel", sel, (torch.bool, torch.uint8)), ("weights", weights, (torch.float32,))):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or tuple(x.shape) != tuple(self.child.shape):
+                raise RuntimeError(f"subdivide: {nm} must be a {' / '.join(str(d) for d in dtypes)} tensor with the shape of child")
+            if x.device != self.child.device:
+                raise RuntimeError(f"subdivide: {nm} must be on the device of the tree")
+        if not self.data.is_cuda:
+            raise RuntimeError("subdivide: only the GPU (HIP) path exists; move the tree to a GPU")
+        limit = self.depth_limit if max_depth is None else min(self.depth_limit, int(max_depth))
+        with torch.no_grad():
+            before, M = self.filled, self.features.shape[0]
+            old_child = self.child
+
+            def grow(rows):
+                self._resize_add_cap(rows - self.capacity)
+                return self.child, self.data, self.parent_depth
+
+            child, data, parent_depth, added, rows_added, row_map = _C.subdivide_tree(
+                self.child, self.data.contiguous(), self.parent_depth, before, M,
+                None if sel is None else sel.contiguous(), None if weights is None else weights.contiguous(), threshold,
+                limit, split_empty, own_rows, EMPTY_INDEX, grow, self._slot_limit)
+            if added == 0:
+                return SubdivideResult(before, 0, 0, row_map)
+            _C.invalidate_caches(old_child, child, data)   # what was cached of the old words goes now
+            self.child, self.data, self.parent_depth = child, data, parent_depth
+            if rows_added > 0:
+                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
+                                             requires_grad=self.features.requires_grad)
+            self._n_internal.fill_(before + added)
+            self.filled = before + added
+            self._invalidate()
+        return SubdivideResult(self.filled, added, rows_added, row_map)
+
+    def unshare(self):
+        """Give every non-empty leaf a feature row of its own (csrc/svoxt_subdivide.hip): of the leaf slots that name
+        one row the slot with the smallest flat index keeps it (an integer atomicMin per row: the same result in every
+        run), the others get the rows M, M + 1, ... in slot order, each a copy.  Rows no leaf names stay where they
+        are, the topology is untouched, every point query returns the bits it returned before.  For trees after
+        refine(), subdivide(own_rows=False), merge() or quantize() whose leaves are to be optimised one by one.
+
+        Replaces `self.features` by a NEW nn.Parameter(features[row_map]) when rows were added (an optimizer:
+        `opt.rebind(old, tree.features, result.row_map)`).  GPU only.
+        :return: UnshareResult(rows_added, row_map); row_map int64 [M'] = the old row of every new feature row"""
+        if self._lock_tree_structure:
+            raise RuntimeError("Tree locked")
+        if not self.data.is_cuda:
+            raise RuntimeError("unshare: only the GPU (HIP) path exists; move the tree to a GPU")
+        with torch.no_grad():
+            if not self.data.is_contiguous():
+                self.data = self.data.contiguous()
+            rows_added, row_map = _C.unshare_rows(self.child, self.data, self.filled, self.features.shape[0], EMPTY_INDEX)
+            if rows_added > 0:
+                _C.invalidate_caches(self.child, self.data)
+                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
+                                             requires_grad=self.features.requires_grad)
+                self._invalidate()
+        return UnshareResult(rows_added, row_map)
+
     # --------------------------------------------------------------- quantize
     def quantize(self, order, weights=None):
         """Replace the feature table by a palette of 2^order rows: median-cut quantisation of the rows of
@@ -494,6 +605,9 @@ class N3Tree(nn.Module):
 
             w = torch.zeros(M, device=dev); leaf = (tree.child[:n] == 0) & (tree.data[:n, ..., 0] < M)
             w[tree.data[:n, ..., 0][leaf].long()] = accum.value[:n][leaf]
+
+        (after refine(), merge() or subdivide(own_rows=False) leaves share rows: unshare() first, or to fine-tune the
+        leaves of a quantized tree one by one afterwards).
 
         Differences from the reference, as svox_t_amd.csrc.quantize_median_cut: an empty segment's palette row is zero
         (reference: NaN), a segment whose weights sum to zero takes the plain mean (reference: NaN), NaN features are
