@@ -1051,6 +1051,89 @@ int svoxt_optim_state_count(int32_t kind);
 int svoxt_optim_step(int32_t kind, float* param, const float* grad, float* state1, float* state2, int64_t M, int32_t K,
                      svoxt_optim_hyper hyper, int32_t lazy, void* stream);
 
+/* ---- Face neighbours of the leaves and the smoothness loss over them: N3Tree.leaf_neighbors / tv / tv_add_grad (not in
+ * the reference) ------------------------------------------------------------------------------------------------------
+ *
+ * The LEAF INDEX of a leaf slot is the number of leaf slots (child == 0) with a smaller flat index among the slots of
+ * the nodes below n_internal: its place in the list N3Tree._all_leaves() gives.  Leaf i in node `node` at depth d =
+ * parent_depth[node, 1] has the integer CELL COORDINATE c in [0, N^(d + 1))^3: its own slot (x, y, z) is the least
+ * significant base-N digit per axis, each ancestor's slot (parent_depth[:, 0], the packed parent slot, walked to the
+ * root) the next more significant one.
+ *
+ * svoxt_leaf_neighbors: neighbors (device int32 [L, 6], columns -x +x -y +y -z +z) row i = for each face the cell t =
+ * c +- e_a of the leaf's own level, looked up by ONE descent from node 0: for l = 0 .. d the slot digits are
+ * (t / N^(d - l)) mod N; where child[node, slot] == 0 the neighbour is that leaf (of depth l <= d: the same size or
+ * coarser) and its leaf index is written, otherwise node += child[node, slot].  -1: t lies outside the cube.  -2: the
+ * cell is still a node after level d -- the face is covered by several finer leaves, each of which names leaf i from
+ * its side.  A leaf whose depth is outside [0, max_depth], or tables that lead out of range, give -1.  Integer
+ * arithmetic only.  L must be the number of leaf slots (the host knows it from the nonzero that lists them).
+ * workspace: svoxt_neighbors_workspace_bytes(n_internal, N) device bytes (8 per slot; -1 for arguments out of range).
+ * Checked before any HIP call (SVOXT_ERR_INVALID): N in [2, 16]; n_internal >= 1 with n_internal * N^3 < 2^31;
+ * max_depth >= 0 with N^(max_depth + 1) < 2^31; L in [0, n_internal * N^3] with 12 L < 2^31; child, parent_depth,
+ * neighbors (L > 0) and workspace not NULL; workspace_bytes at least the query's.
+ *
+ * The EDGE PLAN.  Slot (i, k) of neighbors is an EDGE iff j = neighbors[i, k] >= 0, and depths[j] < depths[i] or the
+ * depths are equal and k is odd (every pair of face-adjacent leaves once: from the finer side, at equal sizes from the
+ * lower), and both leaves name a feature row (rows, device int64 [L]: the data word where it is in [0, M), anything
+ * else -- N3Tree writes -1 -- for an empty leaf), and the two rows differ.  Edge e = 6 i + k yields two INCIDENCES: id
+ * 2 e belongs to rows[i] (other row rows[j], sign +), id 2 e + 1 to rows[j] (other row rows[i], sign -).  The plan is
+ * a CSR over feature rows: row_ptr (device int32 [M + 1]), other (device int32 [2 E]: of every incidence the other
+ * row, each row's incidences in ASCENDING INCIDENCE ID) and meta (device uint8 [2 E]: bit 0 the sign, 1 = -; bits
+ * 1 .. 6 depths[i] of the edge's emitting leaf) -- 5 bytes an incidence and 4 a row.
+ * svoxt_tv_plan_count marks and scans into marks (svoxt_tv_plan_workspace_bytes(L, -1) device bytes); count (device
+ * int64[1]) receives E, the one host read.  svoxt_tv_plan_emit, same inputs and marks unchanged, lists the incidences,
+ * sorts them by owning row (a stable radix sort: ids stay ascending within a row) and writes the plan; workspace:
+ * svoxt_tv_plan_workspace_bytes(L, E) device bytes (about 36 E; the query gives -1 for L < 0, 12 L >= 2^31 or E > 6 L).
+ * Integer work: the plan is a function of the inputs, identical from run to run.
+ * Checked before any HIP call (SVOXT_ERR_INVALID), both entry points: L >= 0 with 12 L < 2^31; M in [0, 2^31);
+ * neighbors, depths, rows not NULL (L > 0); marks not NULL and marks_bytes at least the query's; count not NULL; emit:
+ * E in [0, 6 L], E > 0 only with M >= 2; row_ptr not NULL; with E > 0 other, meta and workspace not NULL and
+ * workspace_bytes at least the query's.
+ *
+ * svoxt_tv_rows: loss = sum over edges of w_e * sum over the selected columns c of rho(f[rows[i], c] - f[rows[j], c]),
+ * rho(v) = v * v (p = 2) or |v| (p = 1), w_e = 1 (depth_weights NULL) or depth_weights[depth of leaf i] (device
+ * float32 [32]; N3Tree passes N^(-2 (d + 1)), the shared face's area, computed in double and rounded once) -- and
+ * G [M, K], its gradient with respect to features (device float32 [M, K]).  One kernel, a lane per (row r, selected
+ * column c), lane number r * columns + j; cols: device int32 [n_cols] DISTINCT columns in [0, K) (not checked; a column
+ * out of range is skipped), or NULL with n_cols = 0 for all K.  Every operation a separate float32 + - * /, no fused
+ * multiply-add, in exactly this order:
+ *   a = f[r, c]; g = 0; l = 0; for the row's incidences in ascending id: b = f[other, c]; diff = a - b;
+ *     p = 2:  t = w * diff;  g = g + (t + t);  on a + incidence  l = l + t * diff
+ *     p = 1:  s = diff > 0 ? 1 : diff < 0 ? -1 : 0;  g = g + s * w;  on a + incidence  l = l + w * |diff|
+ * The lanes' l (0 for rows without an incidence and for the lanes behind M * columns) are summed per workgroup of 256
+ * consecutive lanes by the tree v[i] = v[i] + v[i + s], s = 128, 64 .. 1; workgroup sums B0, B1, ... are then summed
+ * as: u[i] = ((0 + B[i]) + B[i + 256]) + ... for i < 256, the same tree over u; loss = that, divided once by divisor
+ * when divisor != 0 (N3Tree: E * columns for reduction = "mean").  Gather only, no atomics: the same bytes in every run.
+ *   SVOXT_TV_LOSS        loss (device float32[1]) only; table is not touched;
+ *   SVOXT_TV_LOSS_GRAD   and table [M, K] = G: every element written -- g (g / divisor when divisor != 0) at the
+ *                        selected columns of rows with an incidence, 0 elsewhere; rows without one are not read;
+ *   SVOXT_TV_ACCUMULATE  table[r, c] = table[r, c] + scale * g (one multiply, one add, each rounded) at the selected
+ *                        columns of rows with an incidence; everything else keeps its bits; no loss, divisor not read.
+ * M = 0 or E = 0: loss = 0, G = 0, nothing accumulated.  workspace (the workgroup sums; not needed by ACCUMULATE):
+ * svoxt_tv_workspace_bytes(M, columns) device bytes.  A row shared by many leaves is walked by one lane per column, in
+ * its fixed order: a row with J incidences costs J dependent steps.
+ * Checked before any HIP call (SVOXT_ERR_INVALID): p in {1, 2}; mode among the constants; M in [0, 2^31); K >= 1;
+ * E >= 0 with 2 E < 2^31; cols / n_cols NULL / 0 or not NULL / in [1, K]; M * columns < 2^38; divisor finite and >= 0;
+ * scale not NaN; loss not NULL (LOSS, LOSS_GRAD); table not NULL (LOSS_GRAD, ACCUMULATE; M > 0); with M > 0 and E > 0
+ * features, row_ptr, other, meta not NULL and, for LOSS / LOSS_GRAD, workspace not NULL and workspace_bytes at least
+ * the query's. */
+#define SVOXT_TV_LOSS 0
+#define SVOXT_TV_LOSS_GRAD 1
+#define SVOXT_TV_ACCUMULATE 2
+int64_t svoxt_neighbors_workspace_bytes(int64_t n_internal, int32_t N);
+int svoxt_leaf_neighbors(const int32_t* child, const int32_t* parent_depth, int64_t n_internal, int32_t N, int32_t max_depth,
+                         int64_t L, int32_t* neighbors, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t svoxt_tv_plan_workspace_bytes(int64_t L, int64_t E);
+int svoxt_tv_plan_count(const int32_t* neighbors, const int32_t* depths, const int64_t* rows, int64_t L, int64_t M, void* marks,
+                        int64_t marks_bytes, int64_t* count, void* stream);
+int svoxt_tv_plan_emit(const int32_t* neighbors, const int32_t* depths, const int64_t* rows, int64_t L, int64_t M, int64_t E,
+                       const void* marks, int64_t marks_bytes, void* workspace, int64_t workspace_bytes, int32_t* row_ptr,
+                       int32_t* other, uint8_t* meta, void* stream);
+int64_t svoxt_tv_workspace_bytes(int64_t M, int32_t n_cols);
+int svoxt_tv_rows(const float* features, int64_t M, int32_t K, const int32_t* row_ptr, const int32_t* other, const uint8_t* meta,
+                  int64_t E, const int32_t* cols, int32_t n_cols, int32_t p, const float* depth_weights, float divisor,
+                  float scale, int32_t mode, float* loss, float* table, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

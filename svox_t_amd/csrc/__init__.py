@@ -1182,3 +1182,5 @@ from ._extras import OPTIM_KINDS, OPTIM_STATES, optim_step  # noqa: E402,F401
 from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_reduce_backward,  # noqa: E402,F401
                       merge_tree)
 from ._extras import subdivide_tree, unshare_rows  # noqa: E402,F401
+from ._extras import TVPlan, leaf_neighbors, tv_plan, tv_rows  # noqa: E402,F401
+from . import _extras  # noqa: E402,F401

@@ -185,6 +185,14 @@ EXPORTS = {
     "svoxt_snap_points": (ctypes.c_int, [_P(_CTree), _vp, _vp, _i64, _vp, _vp]),
     "svoxt_optim_state_count": (ctypes.c_int, [_i32]),
     "svoxt_optim_step": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _COptimHyper, _i32, _vp]),
+    "svoxt_neighbors_workspace_bytes": (_i64, [_i64, _i32]),
+    "svoxt_leaf_neighbors": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _i64, _vp]),
+    "svoxt_tv_plan_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_tv_plan_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "svoxt_tv_plan_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "svoxt_tv_workspace_bytes": (_i64, [_i64, _i32]),
+    "svoxt_tv_rows": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, ctypes.c_float, ctypes.c_float,
+                                     _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -1080,6 +1080,142 @@ def optim_step(kind: str, param: torch.Tensor, grad: torch.Tensor, state1, state
             torch.autograd.graph.increment_version(x)
 
 
+def leaf_neighbors(child: torch.Tensor, parent_depth: torch.Tensor, n_internal: int, L: int, max_depth: int) -> torch.Tensor:
+    """int32 [L, 6]: for every leaf slot of the nodes below n_internal (in slot order: row i is leaf index i) the leaf
+    index of its face neighbour across -x +x -y +y -z +z, -1 outside the cube, -2 where the face is covered by finer
+    leaves (svoxt_leaf_neighbors; include/svoxt.h has the rule).  L: the number of those leaf slots; max_depth: the
+    deepest node's depth (N^(max_depth + 1) must stay below 2^31).  Integer work, two scans' launches and one kernel."""
+    _, N, n = _check_tables(child, child, parent_depth, n_internal)
+    L, max_depth = int(L), int(max_depth)
+    if L < 0 or 12 * L >= 2 ** 31:
+        raise RuntimeError("leaf_neighbors: the number of leaves must be >= 0 with 12 * L < 2^31")
+    if max_depth < 0 or N ** (max_depth + 1) >= 2 ** 31:
+        raise RuntimeError(f"leaf_neighbors: N^(depth + 1) = {N}^{max_depth + 1} must be below 2^31 (cell coordinates are int32)")
+    _check_on_device_of_child(child, parent_depth=parent_depth)
+    dev = child.device
+    with _on(dev):
+        nbytes = _lib.svoxt_neighbors_workspace_bytes(n, N)
+        if nbytes < 0:
+            raise RuntimeError("leaf_neighbors: n_internal * N^3 must be below 2^31")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        out = torch.empty((L, 6), dtype=torch.int32, device=dev)
+        _call("svoxt_leaf_neighbors", _ptr(child), _ptr(parent_depth), n, N, max_depth, L, _ptr(out), _ptr(ws), nbytes, _stream(dev))
+    return out
+
+
+class TVPlan:
+    """The edge plan of N3Tree.tv: a CSR over feature rows (include/svoxt.h).  row_ptr int32 [M + 1], other int32 [2 E],
+    meta uint8 [2 E], E edges; area_weights float32 [32] on the device: N^(-2 (d + 1)) by depth d."""
+    __slots__ = ("row_ptr", "other", "meta", "E", "M", "area_weights")
+
+    def __init__(self, row_ptr, other, meta, E, M, area_weights):
+        self.row_ptr, self.other, self.meta, self.E, self.M, self.area_weights = row_ptr, other, meta, E, M, area_weights
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.row_ptr, self.other, self.meta, self.area_weights))
+
+
+TV_PLAN_BUILDS = 0            # plans built so far (tests count them: N3Tree caches its plan)
+
+
+def tv_plan(neighbors: torch.Tensor, depths: torch.Tensor, rows: torch.Tensor, M: int, N: int) -> TVPlan:
+    """The edge plan for leaf_neighbors' table, the leaves' depths (int32 [L]) and feature rows (int64 [L], -1 = empty)
+    and a feature table of M rows: svoxt_tv_plan_count, one host read (E), svoxt_tv_plan_emit."""
+    global TV_PLAN_BUILDS
+    for nm, x, dt in (("neighbors", neighbors, torch.int32), ("depths", depths, torch.int32), ("rows", rows, torch.int64)):
+        if not isinstance(x, torch.Tensor) or x.dtype != dt:
+            raise RuntimeError(f"{nm} must be a tensor of {dt}")
+    L = depths.shape[0] if depths.dim() == 1 else -1
+    if L < 0 or tuple(neighbors.shape) != (L, 6) or tuple(rows.shape) != (L,):
+        raise RuntimeError("neighbors must be int32 [L, 6], depths int32 [L], rows int64 [L]")
+    M, N = int(M), int(N)
+    if M < 0 or M >= 2 ** 31 or N < 2 or N > 16 or 12 * L >= 2 ** 31:
+        raise RuntimeError("tv_plan: M must be in [0, 2^31), N in [2, 16], 12 * L below 2^31")
+    for nm, x in (("neighbors", neighbors), ("depths", depths), ("rows", rows)):
+        _check_input(x, nm)
+        if x.device != neighbors.device:
+            raise RuntimeError(f"{nm} must be on the device of neighbors")
+    dev = neighbors.device
+    with _on(dev):
+        mbytes = _lib.svoxt_tv_plan_workspace_bytes(L, -1)
+        marks = torch.empty((mbytes,), dtype=torch.uint8, device=dev)
+        count = torch.empty((1,), dtype=torch.int64, device=dev)
+        _call("svoxt_tv_plan_count", _ptr(neighbors), _ptr(depths), _ptr(rows), L, M, _ptr(marks), mbytes, _ptr(count), _stream(dev))
+        E = int(count.item())                                           # the one host read: sizes the plan
+        row_ptr = torch.empty((M + 1,), dtype=torch.int32, device=dev)
+        other = torch.empty((2 * E,), dtype=torch.int32, device=dev)
+        meta = torch.empty((2 * E,), dtype=torch.uint8, device=dev)
+        nbytes = _lib.svoxt_tv_plan_workspace_bytes(L, E)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        _call("svoxt_tv_plan_emit", _ptr(neighbors), _ptr(depths), _ptr(rows), L, M, E, _ptr(marks), mbytes, _ptr(ws), nbytes,
+              _ptr(row_ptr), _ptr(other), _ptr(meta), _stream(dev))
+        area = torch.tensor([float(N) ** (-2 * (d + 1)) for d in range(32)], dtype=torch.float64).to(torch.float32).to(dev)
+    TV_PLAN_BUILDS += 1
+    return TVPlan(row_ptr, other, meta, E, M, area)
+
+
+TV_MODES = {"loss": 0, "loss_grad": 1, "accumulate": 2}       # SVOXT_TV_* (include/svoxt.h)
+
+
+def tv_rows(features: torch.Tensor, plan: TVPlan, cols=None, p: int = 2, weight: str = "uniform", mean: bool = False,
+            mode: str = "loss", out: torch.Tensor = None, scale: float = 0.0):
+    """The smoothness loss over a plan's edges as one gather-only kernel (svoxt_tv_rows; include/svoxt.h has the
+    arithmetic and the summation order).  features: float32 [M, K], contiguous; cols: int32 [K'] distinct columns or None.
+    mode "loss" -> (loss float32 scalar tensor, None); "loss_grad" -> (loss, G float32 [M, K]); "accumulate":
+    out[r, c] += scale * G[r, c] in place on `out` (float32 [M, K], contiguous) -> None.  mean: loss and G divided once
+    by E * columns.  Bad arguments raise RuntimeError before any GPU work."""
+    if p not in (1, 2):
+        raise RuntimeError("p must be 1 or 2")
+    if weight not in ("uniform", "area"):
+        raise RuntimeError('weight must be "uniform" or "area"')
+    if mode not in TV_MODES:
+        raise RuntimeError(f"mode must be one of {sorted(TV_MODES)}")
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise RuntimeError("features must be float32 [M, K]")
+    M, K = features.shape
+    if not isinstance(plan, TVPlan) or plan.M != M:
+        raise RuntimeError("the plan was built for another number of feature rows")
+    Kc = K
+    if cols is not None:
+        if not isinstance(cols, torch.Tensor) or cols.dtype != torch.int32 or cols.dim() != 1 or cols.numel() == 0:
+            raise RuntimeError("cols must be int32 [K'], K' >= 1")
+        Kc = cols.shape[0]
+        if Kc > K:
+            raise RuntimeError("cols must be distinct columns")
+    tensors = [("features", features), ("row_ptr", plan.row_ptr)] + ([("cols", cols)] if cols is not None else [])
+    scale = float(scale)
+    if mode == "accumulate":
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (M, K):
+            raise RuntimeError("out must be float32 [M, K], the shape of features")
+        if scale != scale:
+            raise RuntimeError("scale is NaN")
+        tensors.append(("out", out))
+    for nm, x in tensors:
+        _check_input(x, nm)
+        if x.device != features.device:
+            raise RuntimeError(f"{nm} must be on the device of features")
+    if mode == "accumulate" and out.data_ptr() == features.data_ptr() and M > 0:
+        raise RuntimeError("out must not be the feature table")
+    dev = features.device
+    divisor = float(plan.E * Kc) if mean else 0.0
+    wants_loss = mode != "accumulate"
+    with _on(dev), torch.no_grad():
+        loss = torch.empty((), dtype=torch.float32, device=dev) if wants_loss else None
+        table = out if mode == "accumulate" else (torch.empty((M, K), dtype=torch.float32, device=dev) if mode == "loss_grad" else None)
+        nbytes = _lib.svoxt_tv_workspace_bytes(M, Kc) if wants_loss else 0
+        if nbytes < 0:
+            raise RuntimeError("tv_rows: M * columns must be below 2^38")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        _call("svoxt_tv_rows", _ptr(features), M, K, _ptr(plan.row_ptr), _ptr(plan.other), _ptr(plan.meta), plan.E, _ptr(cols),
+              0 if cols is None else Kc, int(p), _ptr(plan.area_weights) if weight == "area" else None, divisor, scale,
+              TV_MODES[mode], _ptr(loss), _ptr(table), _ptr(ws), nbytes, _stream(dev))
+        if mode == "accumulate":
+            torch.autograd.graph.increment_version(out)             # written behind torch's back: the counter says so
+            return None
+    return loss, table
+
+
 # ---------------------------------------------------------------------------
 # Entry points of svox_t.csrc that are outside this project's hot path
 # (SURVEY.md section 2).  They exist so a caller gets a clear error, not an

@@ -72,6 +72,14 @@ class LeafBoxes(NamedTuple):
     rows: torch.Tensor                # int64 [L]: the feature row the leaf names, -1 for an empty leaf
 
 
+class LeafNeighbors(NamedTuple):
+    """What N3Tree.leaf_neighbors returns: every leaf slot in `_all_leaves()` order, on the tree's device."""
+    leaf_node: torch.Tensor           # int64 [L, 4]: node, x, y, z
+    depths: torch.Tensor              # int32 [L]
+    rows: torch.Tensor                # int64 [L]: the feature row the leaf names, -1 for an empty leaf
+    neighbors: torch.Tensor           # int32 [L, 6]: leaf index across -x +x -y +y -z +z; -1 outside, -2 finer leaves
+
+
 _ASSIGN_REDUCE = ("last", "sum", "mean", "max", "min")
 
 _REDUCE_CALLABLES = {torch.mean: "mean", torch.sum: "sum", torch.max: "max", torch.min: "min"}
@@ -93,6 +101,24 @@ class _FrontierReduceFunction(autograd.Function):
         data, n, N, nodes, cols, op, empty = ctx.args
         return (_C.frontier_reduce_backward(ctx.saved_tensors[0].detach().contiguous(), data, n, N, nodes, cols, op, empty,
                                             grad_out.contiguous()),) + (None,) * 7
+
+
+class _TVFunction(autograd.Function):
+    """N3Tree.tv: gradient flows to argument 0 (the feature table) only.  The forward's one kernel writes the loss and,
+    where the table requires a gradient, G = d loss / d features; the backward is grad_out * G."""
+
+    @staticmethod
+    def forward(ctx, features, plan, cols, p, weight, mean):
+        want = ctx.needs_input_grad[0]
+        loss, G = _C.tv_rows(features.detach().contiguous(), plan, cols, p, weight, mean, "loss_grad" if want else "loss")
+        ctx.G = G
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0] or ctx.G is None:
+            return (None,) * 6
+        return (grad_out * ctx.G,) + (None,) * 5
 
 
 class _QueryVerticalFunction(autograd.Function):
@@ -187,6 +213,8 @@ class N3Tree(nn.Module):
         self._ver = 0
         self._last_all_leaves = None
         self._last_frontier = None
+        self._last_neighbors = None
+        self._last_tv_plan = None
         self._lock_tree_structure = False
         self._weight_accum = None
         self.filled = 1
@@ -732,6 +760,112 @@ class N3Tree(nn.Module):
         best = d2.reshape(d2.shape[0], -1).max(dim=1)[0]
         return torch.where(best > 0, best.clamp_min(1e-45).sqrt(), torch.zeros_like(best))
 
+    # -------------------------------------------------------------- neighbours
+    def _table_key(self, M):
+        """What the neighbour table and the edge plan were computed from: the topology (`_ver`), the data words (the
+        tensor and its version counter: they are also written by callers that change no topology) and the number of
+        feature rows (a data word >= M is an empty leaf)."""
+        return (self._ver, int(M), self.data.data_ptr(), self.data._version, self.data.device)
+
+    def leaf_neighbors(self):
+        """LeafNeighbors(leaf_node, depths, rows, neighbors) of EVERY leaf slot, in `_all_leaves()` order, on the device
+        (one HIP pipeline, csrc/svoxt_neighbors.hip; the reference has no such operator): leaf_node / depths / rows as
+        in leaf_boxes(), neighbors int32 [L, 6] -- per face, in the order -x +x -y +y -z +z, the index INTO THIS LIST of
+        the leaf across it.  A leaf at depth d has the integer cell coordinate c in [0, N^(d + 1))^3 (its slot the least
+        significant base-N digit per axis, its ancestors' slots above it); the neighbour is the leaf that holds the
+        cell c +- e_a of the same level: the same size or coarser.  -1: outside the cube.  -2: that cell is an internal
+        node, the face is covered by several finer leaves -- each of those names this leaf from its side, so every pair
+        of face-adjacent leaves appears in the table at least once.  Integer arithmetic only.
+
+        Two host reads (the number of leaves, as in leaf_boxes(), and the deepest node's depth); refused where
+        N^(depth + 1) >= 2^31 or 12 L >= 2^31.  Cached until the topology, the data words or the number of feature
+        rows change.  GPU only."""
+        if not self.data.is_cuda:
+            raise RuntimeError("leaf_neighbors: only the GPU (HIP) path exists; move the tree to a GPU")
+        key = self._table_key(self.features.shape[0])
+        if self._last_neighbors is None or self._last_neighbors[0] != key:
+            with torch.no_grad():
+                n, N = self.filled, self.N
+                leaf_node = (self.child[:n] == 0).nonzero(as_tuple=False).contiguous()
+                depths = self.parent_depth[leaf_node[:, 0], 1].contiguous()
+                words = self.data[:n].reshape(n, N, N, N)[tuple(leaf_node.T)].long()
+                rows = torch.where((words >= 0) & (words < self.features.shape[0]), words, torch.full_like(words, -1))
+                deepest = int(self.parent_depth[:n, 1].max().item())
+                neighbors = _C.leaf_neighbors(self.child, self.parent_depth, n, leaf_node.shape[0], deepest)
+            self._last_neighbors = (key, LeafNeighbors(leaf_node, depths, rows, neighbors))
+        return self._last_neighbors[1]
+
+    def _tv_plan(self, M):
+        """The edge plan of tv() for a feature table of M rows (csrc.TVPlan): every pair of
+        face-adjacent leaves that name two different rows, once, grouped by row.  Cached like leaf_neighbors()."""
+        key = self._table_key(M)
+        if self._last_tv_plan is None or self._last_tv_plan[0] != key:
+            nb = self.leaf_neighbors()
+            rows = nb.rows
+            if M != self.features.shape[0]:                  # a table of another height: which leaves are empty follows it
+                with torch.no_grad():
+                    n, N = self.filled, self.N
+                    words = self.data[:n].reshape(n, N, N, N)[tuple(nb.leaf_node.T)].long()
+                    rows = torch.where((words >= 0) & (words < M), words, torch.full_like(words, -1))
+            self._last_tv_plan = (key, _C.tv_plan(nb.neighbors, nb.depths, rows.contiguous(), M, self.N))
+        return self._last_tv_plan[1]
+
+    def _tv_args(self, what, features, dim, p, weight):
+        if not self.data.is_cuda:
+            raise RuntimeError(f"{what}: only the GPU (HIP) path exists; move the tree to a GPU")
+        features = self.features if features is None else features
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+            raise RuntimeError(f"{what}: features must be float32 [M, K]")
+        if features.device != self.data.device:
+            raise RuntimeError(f"{what}: features must be on the device of the tree")
+        if p not in (1, 2):
+            raise RuntimeError(f"{what}: p must be 1 or 2")
+        if weight not in ("uniform", "area"):
+            raise RuntimeError(f'{what}: weight must be "uniform" or "area"')
+        cols, _ = self._columns(dim, features.shape[1])
+        if cols is not None and cols.unique().numel() != cols.numel():
+            raise RuntimeError(f"{what}: dim selects a column twice")
+        return features, cols
+
+    def tv(self, features=None, dim=None, *, p=2, weight="uniform", reduction="sum"):
+        """Total-variation (smoothness) loss over the faces between leaves, a scalar tensor:
+
+            loss = sum over edges of  w_e * sum over the selected columns c of  rho(f[row_i, c] - f[row_j, c])
+
+        An EDGE is a pair of face-adjacent leaves (leaf_neighbors()) that name two different feature rows -- every such
+        pair once, found from its finer leaf i (at equal sizes from the lower one); empty leaves and leaves that share
+        a row contribute nothing.  p=2: rho(v) = v^2; p=1: rho(v) = |v| (subgradient sign(v), sign(0) = 0).
+        weight="uniform": w = 1; "area": w = N^(-2 (depth_i + 1)), the shared face's area in tree units (computed in
+        double, rounded once to float32).  reduction="mean": divided once by E * columns (0 where E = 0).  dim: columns
+        of the table (int, slice, list, tensor; distinct), None for all -- tv(dim=-1) smooths sigma only.  features:
+        the table, self.features by default.
+
+        One gather-only HIP kernel over feature rows (csrc/svoxt_neighbors.hip) on a cached plan: no atomics, float32
+        sums in a fixed order (include/svoxt.h), so loss and gradient are bit-identical from run to run.  A row shared
+        by many leaves (a palette after quantize()) is walked sequentially: correct, not fast.  Differentiable with
+        respect to `features` only; the gradient touches every row that has a neighbour, so a lazy=True optimizer skips
+        nothing after it.  GPU only."""
+        features, cols = self._tv_args("tv", features, dim, p, weight)
+        if reduction not in ("sum", "mean"):
+            raise RuntimeError('tv: reduction must be "sum" or "mean"')
+        plan = self._tv_plan(features.shape[0])
+        return _TVFunction.apply(features, plan, cols, p, weight, reduction == "mean")
+
+    def tv_add_grad(self, out, scale, features=None, dim=None, *, p=2, weight="uniform"):
+        """out[r, c] = out[r, c] + scale * G[r, c], G the gradient of tv(features, dim, p=p, weight=weight) (reduction
+        "sum"), in place, by the same kernel in accumulate mode: one multiply, one add, each rounded, at the selected
+        columns of the rows that have an edge; everything else keeps its bits.  The usual way to apply the regulariser:
+        `tree.tv_add_grad(tree.features.grad, 1e-3, dim=-1)` in front of `opt.step()`, without a second [M, K] buffer.
+        out: float32 [M, K], contiguous, not the table itself; scale: a Python float.  Under no_grad; `out`'s version
+        counter moves.  GPU only.
+        :return: None"""
+        features, cols = self._tv_args("tv_add_grad", features, dim, p, weight)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != tuple(features.shape):
+            raise RuntimeError("tv_add_grad: out must be float32 [M, K], the shape of features")
+        plan = self._tv_plan(features.shape[0])
+        _C.tv_rows(features.detach().contiguous(), plan, cols, p, weight, False, "accumulate", out=out, scale=float(scale))
+        return None
+
     # ------------------------------------------------------------------ merge
     def merge(self, frontier_sel=None, op="mean", *, empty="zero", compact_features=True, reserve=0):
         """Coarsen the tree by one level: every selected frontier node is removed and its parent slot becomes ONE leaf
@@ -906,6 +1040,8 @@ class N3Tree(nn.Module):
         self._ver += 1
         self._last_all_leaves = None
         self._last_frontier = None
+        self._last_neighbors = None
+        self._last_tv_plan = None
 
     def accumulate_weights(self):
         """`with tree.accumulate_weights() as accum:` -- per-leaf-slot sum of the
