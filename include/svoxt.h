@@ -1134,6 +1134,40 @@ int svoxt_tv_rows(const float* features, int64_t M, int32_t K, const int32_t* ro
                   int64_t E, const int32_t* cols, int32_t n_cols, int32_t p, const float* depth_weights, float divisor,
                   float scale, int32_t mode, float* loss, float* table, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- depth moments (svoxt_depthmom.hip; not in the reference) --------------------------------------
+ * out: device float32 [Q, 3] = {m1, m2, alpha} per ray,
+ *     m1 = sum_k w_k z_k    m2 = sum_k w_k z_k^2    alpha = 1 - T_end    w_k = T_k (1 - att_k)
+ * over the samples opacity_render composites (sigma > sigma_thresh, until T <= stop_thresh), float32, in this order:
+ *     att = exp(-delta_t * delta_scale * sigma);  w = T * (1 - att);
+ *     z = delta_scale * t (SVOXT_DEPTH_AT_ENTRY: what svoxt_render_depth reports) or
+ *         delta_scale * (t + 0.5 * delta_t) (SVOXT_DEPTH_AT_MID);
+ *     m1 += w * z;  m2 += w * (z * z);  T *= att;
+ *     T <= stop_thresh: m1 and m2 are multiplied by float(1.0 / (1.0 - double(T))) as the colour forward's channels are,
+ *     and the ray ends.
+ * A ray that misses the volume gives {0, 0, 0}; the background adds nothing (it has no depth).  With NDC options z is in
+ * the space the march runs in, as svoxt_render_depth's is.  Expected depth is m1 / alpha, its variance
+ * m2 / alpha - (m1 / alpha)^2.  alpha has the bits of svoxt_opacity_render_fwd.
+ * The backward ADDS to grad [M, gstride] (gstride 0: data_dim; the caller zeroes it), column data_dim - 1 only,
+ *     delta_t delta_scale (c_k T_{k+1} - sum_{i>k} w_i c_i) + delta_t delta_scale ga T_end,  c_k = g1 z_k + g2 z_k^2
+ * for grad_out [Q, 3] rows (g1, g2, ga), by the reference's convention for its backward (rt_kernel.cu:382, 456, 486-490
+ * with total_color = c_k): every sample with sigma > 0, no early stop, no rescale, the exponent associated as
+ * -delta_t * sigma * delta_scale -- the true gradient at thresholds 0.
+ * workspace (optional, both calls): a forward given svoxt_depth_moments_workspace_bytes(Q, max_samples) device bytes
+ * (8-byte aligned; 8 bytes + 12 a sample for every ray of the batch rounded up to 64) records up to max_samples
+ * (row, delta_t, z) a ray; a backward given the same bytes, the same tree, rays and options reads them instead of
+ * marching and marches only behind the end of an over-long ray's records.  A smaller workspace holds as many records a
+ * ray as fit; NULL / 0: nothing is recorded, the backward marches (two sweeps).  Every path sums the per-sample values
+ * by feature row in LDS per tile of 64 rays and issues one atomic per distinct row and pass.  The result does not
+ * depend on the workspace beyond the order of float additions.  No allocation, no synchronisation. */
+#define SVOXT_DEPTH_AT_ENTRY 0
+#define SVOXT_DEPTH_AT_MID 1
+int64_t svoxt_depth_moments_workspace_bytes(int64_t Q, int64_t max_samples);    /* -1: negative argument */
+int svoxt_depth_moments_fwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
+                            float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_depth_moments_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
+                            const float* grad_out, float* grad, int32_t gstride,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,9 @@ EXPORTS = {
     "svoxt_tv_workspace_bytes": (_i64, [_i64, _i32]),
     "svoxt_tv_rows": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, ctypes.c_float, ctypes.c_float,
                                      _i32, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_depth_moments_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_depth_moments_fwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _i32, _vp, _vp, _i64, _vp]),
+    "svoxt_depth_moments_bwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -1246,3 +1246,89 @@ grid_weight_render = _out_of_scope(
     "grid_weight_render", "served under another name: grid_weight_render(data, cam, opt, offset, scaling) is "
     "grid_weights(data, cameras=cam.c2w[None], ...) -- svox_t_amd.grid_weights, or svox_t_amd.csrc.grid_weights(data, cam, "
     "opt, offset, scaling), which returns the reference's (weight, hits); see INTEGRATION.md")
+
+
+# ---------------------------------------------------------------------------
+# Depth moments (svoxt_depthmom.hip; not in the reference; DESIGN.md 4.17)
+# ---------------------------------------------------------------------------
+DEPTH_AT = {"entry": 0, "mid": 1}
+DEPTHMOM_SAMPLES = 128    # samples recorded per ray for the backward (12 bytes each, written only where a ray has them; a longer
+                          # ray's tail is marched: at 64 the 1.5 % longer rays of the headline view cost 0.15 ms); 0: never record
+
+
+def _depth_at(at) -> int:
+    if isinstance(at, str):
+        if at not in DEPTH_AT:
+            raise RuntimeError(f"at must be 'entry' or 'mid' (or 0 / 1), not {at!r}")
+        return DEPTH_AT[at]
+    if isinstance(at, bool) or not isinstance(at, int) or at not in (0, 1):
+        raise RuntimeError(f"at must be 'entry' or 'mid' (or 0 / 1), not {at!r}")
+    return at
+
+
+def _spec_ray_count(rays) -> int:
+    if isinstance(rays, CameraSpec):
+        return int(rays.width) * int(rays.height)
+    if not isinstance(rays.origins, torch.Tensor) or rays.origins.dim() != 2:
+        raise RuntimeError("origins must have shape [Q, 3]")
+    return rays.origins.shape[0]
+
+
+def _depth_plan_key(csrc, tree, rays, opt, at):
+    f = tree.features
+    return (at, id(f), f._version, f.data_ptr(), csrc._opt_key(opt), csrc._tree_key(tree), csrc._rays_key(rays))
+
+
+def depth_moments(tree: TreeSpec, rays, opt: RenderOptions, at=0) -> torch.Tensor:
+    """[Q, 3] = (m1, m2, alpha) per ray: the first two moments of the compositing weights over distance and the
+    accumulated alpha (include/svoxt.h, svoxt_depth_moments_fwd).  `rays`: a RaysSpec or a CameraSpec.  `at`: "entry" / 0
+    (z = delta_scale * t, what render_depth reports) or "mid" / 1 (the middle of the leaf crossing).  A batch that is not
+    an image is walked in svoxt_ray_order's order where that pays (RaysSpec.sort), a declared image in 8 x 8 tiles; every
+    ray's row stays at its own index.  Where a backward will follow (rays.need_grad, else the feature table's
+    requires_grad) the samples are recorded and left on the spec for depth_moments_backward."""
+    import svox_t_amd.csrc as csrc
+    at = _depth_at(at)
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    record = csrc._need_grad(tree, rays) and DEPTHMOM_SAMPLES > 0 and cr.Q > 0
+    with _on(dev):
+        out = torch.empty((cr.Q, 3), dtype=torch.float32, device=dev)
+        ws, nbytes = None, 0
+        if record:
+            nbytes = _lib.svoxt_depth_moments_workspace_bytes(cr.Q, int(DEPTHMOM_SAMPLES))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _call("svoxt_depth_moments_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), at, _ptr(out), _ptr(ws), nbytes,
+              _stream(dev))
+    # (the records are only read by the backward: they serve as many backward calls as the graph is kept for)
+    rays._svoxt_depth_plan = (_depth_plan_key(csrc, tree, rays, opt, at), tree.features, ws, nbytes,
+                              None if rr is rays else rr) if record else None
+    return out
+
+
+def depth_moments_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: torch.Tensor, at=0) -> torch.Tensor:
+    """[M, K] gradient of depth_moments with respect to the feature table for grad_output [Q, 3]: the sigma column only
+    (every other column is zero), by the reference's convention for its backward -- every sample with sigma > 0, no early
+    stop: the true gradient at thresholds 0 (include/svoxt.h, svoxt_depth_moments_bwd).  Reads what the forward of the same
+    spec objects recorded if nothing it depends on has changed since; marches otherwise."""
+    import svox_t_amd.csrc as csrc
+    at = _depth_at(at)
+    Q = _spec_ray_count(rays)
+    if not isinstance(grad_output, torch.Tensor) or grad_output.dtype != torch.float32 or grad_output.dim() != 2 \
+            or grad_output.shape[0] != Q or grad_output.shape[1] != 3:
+        raise RuntimeError(f"grad_output must be float32 [Q, 3] with Q = {Q} rays")
+    _check_input(grad_output, "grad_output")
+    plan = getattr(rays, "_svoxt_depth_plan", None)
+    ws, nbytes, rr = None, 0, None
+    if plan is not None and plan[1] is tree.features and plan[0] == _depth_plan_key(csrc, tree, rays, opt, at):
+        ws, nbytes, rr = plan[2], plan[3], plan[4]
+    if rr is None:
+        # (the same walk as the forward's where there is a plan; any coherent one otherwise)
+        rr = rays if isinstance(rays, CameraSpec) or plan is not None else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    with _on(dev):
+        grad = torch.zeros_like(tree.features)
+        _call("svoxt_depth_moments_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), at, _ptr(grad_output), _ptr(grad), 0,
+              _ptr(ws), nbytes, _stream(dev))
+    return grad

@@ -178,6 +178,26 @@ class _OpacityRenderFunction(autograd.Function):
         return None, None, None, None
 
 
+class _DepthMomentsFunction(autograd.Function):
+    """Not in the reference: (m1, m2, alpha) per ray, differentiable wrt the feature table's sigma column."""
+
+    @staticmethod
+    def forward(ctx, data, tree, rays, opt, at):
+        out = _C.depth_moments(tree, rays, opt, at)
+        ctx.tree = tree
+        ctx.rays = rays
+        ctx.opt = opt
+        ctx.at = at
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if ctx.needs_input_grad[0]:
+            return _C.depth_moments_backward(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous(), ctx.at), \
+                None, None, None, None
+        return None, None, None, None, None
+
+
 class VolumeRenderer(nn.Module):
     def __init__(self, tree, step_size: float = 1e-3, background_brightness: float = 1.0,
                  ndc: NDCConfig = None, min_comp=0, max_comp=-1):
@@ -293,6 +313,37 @@ class VolumeRenderer(nn.Module):
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
         rspec.need_grad = _will_differentiate(features)
         return _OpacityRenderFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast))
+
+    def render_depth_moments(self, features, rays: Rays, *, at="entry", cuda=True, fast=False, image_shape=None,
+                             sort_rays=None):
+        """[Q, 3] = (m1, m2, alpha): the first two moments of the compositing weights over distance and the
+        accumulated alpha, m1 = sum_k w_k z_k, m2 = sum_k w_k z_k^2, alpha = 1 - T_end with w_k = T_k (1 - att_k);
+        differentiable wrt `features` (its sigma column).  Expected depth is m1 / alpha (render_expected_depth), the
+        depth variance m2 / alpha - (m1 / alpha)^2.
+
+        :param at: "entry": z_k is the distance at which the ray enters the sample's leaf -- the quantity render_depth
+               reports; "mid": the middle of the leaf crossing
+        :param fast: sigma_thresh = stop_thresh = 1e-2 in the forward; the gradient is the one at thresholds 0
+               (the reference's convention for its backwards)
+        :param image_shape, sort_rays: see forward
+
+        A ray that misses the volume gives (0, 0, 0); the background adds nothing (it has no depth).  With an `ndc`
+        config z is a distance in the space the march runs in (NDC space), as render_depth's is."""
+        self._require_gpu(cuda, "render_depth_moments")
+        if at not in ("entry", "mid"):
+            raise ValueError(f"at must be 'entry' or 'mid', not {at!r}")
+        rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+        rspec.need_grad = _will_differentiate(features)
+        return _DepthMomentsFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
+                                           0 if at == "entry" else 1)
+
+    def render_expected_depth(self, features, rays: Rays, *, at="entry", cuda=True, fast=False, image_shape=None,
+                              sort_rays=None, eps=1e-10):
+        """[Q, 1] expected depth m1 / (alpha + eps) of render_depth_moments, in torch ops on top of it: autograd chains
+        through (0 where the ray meets nothing)."""
+        m = self.render_depth_moments(features, rays, at=at, cuda=cuda, fast=fast, image_shape=image_shape,
+                                      sort_rays=sort_rays)
+        return m[:, 0:1] / (m[:, 2:3] + eps)
 
     def _get_options(self, fast=False):
         """RenderOptions for the operator boundary (svox_t/renderer.py:408-439)."""
