@@ -1168,6 +1168,41 @@ int svoxt_depth_moments_bwd(const svoxt_tree* tree, const svoxt_rays* rays, cons
                             const float* grad_out, float* grad, int32_t gstride,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- distortion loss (svoxt_distort.hip; not in the reference) -------------------------------------
+ * out: device float32 [Q, 2] = {L, alpha} per ray, the distortion loss of mip-NeRF 360 over the ray's leaf crossings,
+ *     L = sum_i sum_j w_i w_j |s_i - s_j| + (1/3) sum_i w_i^2 d_i    alpha = 1 - T_end    w_k = T_k (1 - att_k)
+ * over the samples opacity_render composites (sigma > sigma_thresh, until T <= stop_thresh), float32, in this order,
+ * with A, D, Lb, Lu = 0 and T = 1 at the start:
+ *     att = exp(-delta_t * delta_scale * sigma);  w = T * (1 - att);
+ *     s = delta_scale * (t + 0.5 * delta_t);  d = delta_t * delta_scale;
+ *     not the first sample: D += A * (s - s_previous);          D = sum_{j<k} w_j (s_k - s_j), every addend >= 0
+ *     Lb += w * D;  Lu += (w * w) * d;  A += w;  T *= att;
+ *     T <= stop_thresh: Lb and Lu are each multiplied twice by float(1.0 / (1.0 - double(T))) -- the moments' rescale,
+ *     once per factor of w -- and the ray ends.
+ *     L = 2 * Lb + Lu * (1 / 3)
+ * A ray that misses the volume gives {0, 0}; the background adds nothing.  s is not normalised to the ray's span; with
+ * NDC options it is in the space the march runs in.  alpha has the bits of svoxt_opacity_render_fwd.
+ * The backward ADDS to grad [M, gstride] (gstride 0: data_dim; the caller zeroes it), column data_dim - 1 only,
+ *     d_k gd (u_k T_{k+1} - sum_{i>k} w_i u_i) + d_k ga T_end
+ *     u_k = dL/dw_k = 2 (D_k + E_k) + (2/3) w_k d_k        E_k = sum_{j>k} w_j (s_j - s_k)
+ * for grad_out [Q, 2] rows (gd, ga), by the reference's convention for its backward: every sample with sigma > 0, no
+ * early stop, no rescale, the exponent associated as -delta_t * sigma * delta_scale -- the true gradient at
+ * thresholds 0.  The suffix sum is subtracted down from sum_all w_i u_i = 2 L (L is homogeneous of degree 2 in w).
+ * workspace (optional, both calls): as the depth moments' -- a forward given
+ * svoxt_distortion_workspace_bytes(Q, max_samples) device bytes (8-byte aligned; 8 bytes + 12 a sample for every ray of
+ * the batch rounded up to 64) records up to max_samples (row, delta_t, s) a ray; a backward given the same bytes, the same
+ * tree, rays and options reads them instead of marching and marches only behind the end of an over-long ray's records.
+ * A smaller workspace holds as many records a ray as fit; NULL / 0: nothing is recorded, the backward marches (two
+ * sweeps).  Every path sums the per-sample values by feature row in LDS per tile of 64 rays and issues one atomic per
+ * distinct row and pass.  The result does not depend on the workspace beyond the order of float additions.  No
+ * allocation, no synchronisation. */
+int64_t svoxt_distortion_workspace_bytes(int64_t Q, int64_t max_samples);       /* -1: negative argument */
+int svoxt_distortion_fwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                         float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_distortion_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                         const float* grad_out, float* grad, int32_t gstride,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1184,4 +1184,5 @@ from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_r
 from ._extras import subdivide_tree, unshare_rows  # noqa: E402,F401
 from ._extras import TVPlan, leaf_neighbors, tv_plan, tv_rows  # noqa: E402,F401
 from ._extras import depth_moments, depth_moments_backward  # noqa: E402,F401
+from ._extras import distortion, distortion_backward  # noqa: E402,F401
 from . import _extras  # noqa: E402,F401

@@ -196,6 +196,9 @@ EXPORTS = {
     "svoxt_depth_moments_workspace_bytes": (_i64, [_i64, _i64]),
     "svoxt_depth_moments_fwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _i32, _vp, _vp, _i64, _vp]),
     "svoxt_depth_moments_bwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_distortion_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_distortion_fwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _i64, _vp]),
+    "svoxt_distortion_bwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _i32, _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

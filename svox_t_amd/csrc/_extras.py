@@ -1332,3 +1332,64 @@ def depth_moments_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output
         _call("svoxt_depth_moments_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), at, _ptr(grad_output), _ptr(grad), 0,
               _ptr(ws), nbytes, _stream(dev))
     return grad
+
+
+# ---------------------------------------------------------------------------
+# Distortion loss (svoxt_distort.hip; not in the reference; DESIGN.md 4.18)
+# ---------------------------------------------------------------------------
+DISTORTION_SAMPLES = 128  # samples recorded per ray for the backward, as DEPTHMOM_SAMPLES; 0: never record
+
+
+def _distortion_plan_key(csrc, tree, rays, opt):
+    f = tree.features
+    return (id(f), f._version, f.data_ptr(), csrc._opt_key(opt), csrc._tree_key(tree), csrc._rays_key(rays))
+
+
+def distortion(tree: TreeSpec, rays, opt: RenderOptions) -> torch.Tensor:
+    """[Q, 2] = (L, alpha) per ray: the distortion loss of mip-NeRF 360 over the ray's leaf crossings,
+    L = sum_ij w_i w_j |s_i - s_j| + 1/3 sum_i w_i^2 d_i (s: the middle of a crossing, d: its length, both in world
+    units), and the accumulated alpha (include/svoxt.h, svoxt_distortion_fwd).  `rays`: a RaysSpec or a CameraSpec; walked
+    as depth_moments walks them, every ray's row at its own index.  Where a backward will follow (rays.need_grad, else the
+    feature table's requires_grad) the samples are recorded and left on the spec for distortion_backward."""
+    import svox_t_amd.csrc as csrc
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    record = csrc._need_grad(tree, rays) and DISTORTION_SAMPLES > 0 and cr.Q > 0
+    with _on(dev):
+        out = torch.empty((cr.Q, 2), dtype=torch.float32, device=dev)
+        ws, nbytes = None, 0
+        if record:
+            nbytes = _lib.svoxt_distortion_workspace_bytes(cr.Q, int(DISTORTION_SAMPLES))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _call("svoxt_distortion_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), _ptr(ws), nbytes,
+              _stream(dev))
+    rays._svoxt_distortion_plan = (_distortion_plan_key(csrc, tree, rays, opt), tree.features, ws, nbytes,
+                                   None if rr is rays else rr) if record else None
+    return out
+
+
+def distortion_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: torch.Tensor) -> torch.Tensor:
+    """[M, K] gradient of distortion with respect to the feature table for grad_output [Q, 2]: the sigma column only,
+    by the reference's convention for its backward -- every sample with sigma > 0, no early stop, no rescale: the true
+    gradient at thresholds 0 (include/svoxt.h, svoxt_distortion_bwd).  Reads what the forward of the same spec objects
+    recorded if nothing it depends on has changed since; marches otherwise."""
+    import svox_t_amd.csrc as csrc
+    Q = _spec_ray_count(rays)
+    if not isinstance(grad_output, torch.Tensor) or grad_output.dtype != torch.float32 or grad_output.dim() != 2 \
+            or grad_output.shape[0] != Q or grad_output.shape[1] != 2:
+        raise RuntimeError(f"grad_output must be float32 [Q, 2] with Q = {Q} rays")
+    _check_input(grad_output, "grad_output")
+    plan = getattr(rays, "_svoxt_distortion_plan", None)
+    ws, nbytes, rr = None, 0, None
+    if plan is not None and plan[1] is tree.features and plan[0] == _distortion_plan_key(csrc, tree, rays, opt):
+        ws, nbytes, rr = plan[2], plan[3], plan[4]
+    if rr is None:
+        rr = rays if isinstance(rays, CameraSpec) or plan is not None else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    with _on(dev):
+        grad = torch.zeros_like(tree.features)
+        _call("svoxt_distortion_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(grad_output), _ptr(grad), 0,
+              _ptr(ws), nbytes, _stream(dev))
+    return grad

@@ -35,30 +35,11 @@
 #include "svoxt_device.h"
 #include "svoxt_host.h"
 #include "svoxt_launch.h"
+#include "svoxt_raylists.h"
 
 #pragma clang fp contract(off)
 
 namespace svoxt {
-
-constexpr int kDmGroup = 4;          // records a lane fetches together
-constexpr int kDmTable = 1024;       // rows of the tile's hash table (8 KiB of LDS a wavefront)
-constexpr int kDmRounds = 12;        // samples a lane between two flushes: 64 x 12 = 768 entries at most in 1024 slots
-constexpr int kDmMaxSamples = 4096;
-constexpr uint32_t kDmOver = 0x80000000u;
-static_assert(kDmRounds % kDmGroup == 0 && 64 * kDmRounds < kDmTable, "a pass must fit the table with room to probe");
-static_assert(kBlock == 64, "one wavefront per tile");
-
-struct DmLists {
-    uint2* __restrict__ aux;         // [Qpad] {records | kDmOver if the ray has more, t of the first unrecorded sample}
-    uint32_t* __restrict__ row;      // [tiles][S][64]
-    float* __restrict__ dt;
-    float* __restrict__ z;
-    int S;                           // 0: no lists
-};
-
-__device__ __forceinline__ int64_t dm_index(int64_t tile, int S, int k, int lane) {
-    return ((tile * S + k) << 6) + lane;
-}
 
 template <bool MID>
 __device__ __forceinline__ float dm_z(const Ray& r, float t, float delta_t) {
@@ -166,30 +147,10 @@ depthmom_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
     for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
     maxn = __builtin_amdgcn_readfirstlane(maxn);
     if (maxn == 0 && !__any(over)) return;
-    for (int i = lane; i < kDmTable; i += 64) { keys[i] = -1; vals[i] = 0.f; }
-    __syncthreads();
+    dm_table_clear(keys, vals, lane);
 
-    auto put = [&](int32_t idx, float v) {
-        uint32_t h = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(kDmTable));
-        while (true) {
-            const int32_t old = atomicCAS(keys + h, -1, idx);
-            if (old == -1 || old == idx) break;
-            h = (h + 1u) & (uint32_t)(kDmTable - 1);
-        }
-        atomicAdd(vals + h, v);
-    };
-    auto flush = [&]() {
-        __syncthreads();
-        for (int i = lane; i < kDmTable; i += 64) {
-            const int32_t key = keys[i];
-            if (key >= 0) {
-                atomicAdd(grad + (int64_t)key * gstride + (K - 1), vals[i]);
-                keys[i] = -1;
-                vals[i] = 0.f;
-            }
-        }
-        __syncthreads();
-    };
+    auto put = [&](int32_t idx, float v) { dm_table_put(keys, vals, idx, v); };
+    auto flush = [&]() { dm_table_flush(keys, vals, lane, grad, gstride, K - 1); };
     // four records of a lane: rows, steps and distances, the rows' sigma, the exponentials (slots past the count hold
     // stale bits: row 0 is gathered for them and nothing is used)
     auto fetch = [&](int kb, float (&dt)[kDmGroup], float (&z)[kDmGroup], float (&att)[kDmGroup], int32_t (&row)[kDmGroup]) {
@@ -302,23 +263,6 @@ depthmom_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
     if (round != 0) flush();
 }
 
-// the kernels' view of a workspace of `bytes` for Q rays: as many records a ray as fit (a multiple of kDmGroup), 0: none
-static DmLists dm_lists(void* workspace, int64_t bytes, int64_t Q) {
-    DmLists L = {};
-    if (workspace == nullptr || bytes <= 0 || Q <= 0) return L;
-    const int64_t qpad = rec_rays(Q);
-    int64_t S = (bytes / qpad - 8) / 12 / kDmGroup * kDmGroup;
-    if (S < kDmGroup) return L;
-    if (S > kDmMaxSamples) S = kDmMaxSamples;
-    char* p = reinterpret_cast<char*>(workspace);
-    L.aux = reinterpret_cast<uint2*>(p);
-    L.row = reinterpret_cast<uint32_t*>(p + qpad * 8);
-    L.dt = reinterpret_cast<float*>(p + qpad * 8 + qpad * S * 4);
-    L.z = reinterpret_cast<float*>(p + qpad * 8 + qpad * S * 8);
-    L.S = (int)S;
-    return L;
-}
-
 static int dm_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
                     const void* workspace, int64_t workspace_bytes, const char* fn) {
     int rc;
@@ -338,11 +282,7 @@ using namespace svoxt;
 extern "C" {
 
 int64_t svoxt_depth_moments_workspace_bytes(int64_t Q, int64_t max_samples) {
-    if (Q < 0 || max_samples < 0) return -1;
-    if (Q == 0 || max_samples == 0) return 0;
-    int64_t S = (max_samples + kDmGroup - 1) / kDmGroup * kDmGroup;
-    if (S > kDmMaxSamples) S = kDmMaxSamples;
-    return rec_rays(Q) * (8 + 12 * S);
+    return dm_workspace_bytes(Q, max_samples);
 }
 
 int svoxt_depth_moments_fwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,

@@ -198,6 +198,24 @@ class _DepthMomentsFunction(autograd.Function):
         return None, None, None, None, None
 
 
+class _DistortionFunction(autograd.Function):
+    """Not in the reference: (distortion loss, alpha) per ray, differentiable wrt the feature table's sigma column."""
+
+    @staticmethod
+    def forward(ctx, data, tree, rays, opt):
+        out = _C.distortion(tree, rays, opt)
+        ctx.tree = tree
+        ctx.rays = rays
+        ctx.opt = opt
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if ctx.needs_input_grad[0]:
+            return _C.distortion_backward(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous()), None, None, None
+        return None, None, None, None
+
+
 class VolumeRenderer(nn.Module):
     def __init__(self, tree, step_size: float = 1e-3, background_brightness: float = 1.0,
                  ndc: NDCConfig = None, min_comp=0, max_comp=-1):
@@ -344,6 +362,37 @@ class VolumeRenderer(nn.Module):
         m = self.render_depth_moments(features, rays, at=at, cuda=cuda, fast=fast, image_shape=image_shape,
                                       sort_rays=sort_rays)
         return m[:, 0:1] / (m[:, 2:3] + eps)
+
+    def render_distortion(self, features, rays: Rays, *, cuda=True, fast=False, image_shape=None, sort_rays=None):
+        """[Q, 2] = (L, alpha): the distortion loss of mip-NeRF 360 per ray and the accumulated alpha,
+
+            L = sum_i sum_j w_i w_j |s_i - s_j| + (1/3) sum_i w_i^2 d_i        w_k = T_k (1 - att_k)
+
+        over the ray's leaf crossings: s_k is the distance to the middle of crossing k, d_k its length.  Leaves are
+        piecewise constant, so the interval form is exact.  Differentiable wrt `features` (its sigma column).
+
+        :param fast: sigma_thresh = stop_thresh = 1e-2 in the forward; the gradient is the one at thresholds 0
+               (the reference's convention for its backwards)
+        :param image_shape, sort_rays: see forward
+
+        A ray that misses the volume gives (0, 0); the background adds nothing.  s is not normalised to the ray's
+        near / far span: distances are those of render_depth_moments(at="mid")."""
+        self._require_gpu(cuda, "render_distortion")
+        rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+        rspec.need_grad = _will_differentiate(features)
+        return _DistortionFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast))
+
+    def distortion_loss(self, features, rays: Rays, *, reduction="mean", cuda=True, fast=False, image_shape=None,
+                        sort_rays=None):
+        """The distortion column of render_distortion reduced over the rays, in torch ops on top of it: "mean" and
+        "sum" give a scalar, "none" the [Q] per-ray values; autograd chains through."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none', not {reduction!r}")
+        per_ray = self.render_distortion(features, rays, cuda=cuda, fast=fast, image_shape=image_shape,
+                                         sort_rays=sort_rays)[:, 0]
+        if reduction == "mean":
+            return per_ray.mean()
+        return per_ray.sum() if reduction == "sum" else per_ray
 
     def _get_options(self, fast=False):
         """RenderOptions for the operator boundary (svox_t/renderer.py:408-439)."""
