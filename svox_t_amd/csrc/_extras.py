@@ -5,6 +5,7 @@ each (two for the builder, prune, subdivide, unshare, the frontier and merge).""
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import torch
 
@@ -1274,9 +1275,70 @@ def _spec_ray_count(rays) -> int:
     return rays.origins.shape[0]
 
 
-def _depth_plan_key(csrc, tree, rays, opt, at):
+def _raysweep_plan_key(csrc, tree, rays, opt, lead):
     f = tree.features
-    return (at, id(f), f._version, f.data_ptr(), csrc._opt_key(opt), csrc._tree_key(tree), csrc._rays_key(rays))
+    return lead + (id(f), f._version, f.data_ptr(), csrc._opt_key(opt), csrc._tree_key(tree), csrc._rays_key(rays))
+
+
+class _RaySweepOp(NamedTuple):
+    """A per-ray operator of csrc/svoxt_raysweep.h: what its forward and backward have to agree on."""
+    name: str           # the entry points are svoxt_<name>_workspace_bytes / _fwd / _bwd
+    cols: int           # floats per ray of the output and of grad_output
+    plan_attr: str      # the attribute of the rays spec that keeps the forward's plan
+    samples: str        # the module constant with the records kept per ray, read at call time (tests assign it)
+
+
+def _raysweep_forward(op: _RaySweepOp, tree, rays, opt, lead=()):
+    """[Q, op.cols] from svoxt_<op.name>_fwd, whose arguments are the specs, `lead`, the output and the workspace.  Where a
+    backward will follow the samples are recorded and the plan (key, feature table, workspace, its size, the rays in the
+    order walked or None) is left on the rays spec under op.plan_attr."""
+    import svox_t_amd.csrc as csrc
+    name, cols, plan_attr, samples = op.name, op.cols, op.plan_attr, globals()[op.samples]
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    record = csrc._need_grad(tree, rays) and samples > 0 and cr.Q > 0
+    with _on(dev):
+        out = torch.empty((cr.Q, cols), dtype=torch.float32, device=dev)
+        ws, nbytes = None, 0
+        if record:
+            nbytes = getattr(_lib, f"svoxt_{name}_workspace_bytes")(cr.Q, int(samples))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _call(f"svoxt_{name}_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), *lead, _ptr(out), _ptr(ws), nbytes,
+              _stream(dev))
+    # (the records are only read by the backward: they serve as many backward calls as the graph is kept for)
+    setattr(rays, plan_attr, (_raysweep_plan_key(csrc, tree, rays, opt, lead), tree.features, ws, nbytes,
+                              None if rr is rays else rr) if record else None)
+    return out
+
+
+def _raysweep_backward(op: _RaySweepOp, tree, rays, opt, grad_output, lead=()):
+    """The backward that goes with _raysweep_forward: [M, K] from svoxt_<op.name>_bwd for grad_output [Q, op.cols], over
+    the plan the forward left where it still matches, marching otherwise."""
+    import svox_t_amd.csrc as csrc
+    name, cols, plan_attr = op.name, op.cols, op.plan_attr
+    Q = _spec_ray_count(rays)
+    if not isinstance(grad_output, torch.Tensor) or grad_output.dtype != torch.float32 or grad_output.dim() != 2 \
+            or grad_output.shape[0] != Q or grad_output.shape[1] != cols:
+        raise RuntimeError(f"grad_output must be float32 [Q, {cols}] with Q = {Q} rays")
+    _check_input(grad_output, "grad_output")
+    plan = getattr(rays, plan_attr, None)
+    ws, nbytes, rr = None, 0, None
+    if plan is not None and plan[1] is tree.features and plan[0] == _raysweep_plan_key(csrc, tree, rays, opt, lead):
+        ws, nbytes, rr = plan[2], plan[3], plan[4]
+    if rr is None:
+        # (the same walk as the forward's where there is a plan; any coherent one otherwise)
+        rr = rays if isinstance(rays, CameraSpec) or plan is not None else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    with _on(dev):
+        grad = torch.zeros_like(tree.features)
+        _call(f"svoxt_{name}_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), *lead, _ptr(grad_output), _ptr(grad), 0,
+              _ptr(ws), nbytes, _stream(dev))
+    return grad
+
+
+_DEPTH_MOMENTS = _RaySweepOp("depth_moments", 3, "_svoxt_depth_plan", "DEPTHMOM_SAMPLES")
 
 
 def depth_moments(tree: TreeSpec, rays, opt: RenderOptions, at=0) -> torch.Tensor:
@@ -1286,24 +1348,7 @@ def depth_moments(tree: TreeSpec, rays, opt: RenderOptions, at=0) -> torch.Tenso
     an image is walked in svoxt_ray_order's order where that pays (RaysSpec.sort), a declared image in 8 x 8 tiles; every
     ray's row stays at its own index.  Where a backward will follow (rays.need_grad, else the feature table's
     requires_grad) the samples are recorded and left on the spec for depth_moments_backward."""
-    import svox_t_amd.csrc as csrc
-    at = _depth_at(at)
-    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
-    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
-    dev = tree.features.device
-    record = csrc._need_grad(tree, rays) and DEPTHMOM_SAMPLES > 0 and cr.Q > 0
-    with _on(dev):
-        out = torch.empty((cr.Q, 3), dtype=torch.float32, device=dev)
-        ws, nbytes = None, 0
-        if record:
-            nbytes = _lib.svoxt_depth_moments_workspace_bytes(cr.Q, int(DEPTHMOM_SAMPLES))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        _call("svoxt_depth_moments_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), at, _ptr(out), _ptr(ws), nbytes,
-              _stream(dev))
-    # (the records are only read by the backward: they serve as many backward calls as the graph is kept for)
-    rays._svoxt_depth_plan = (_depth_plan_key(csrc, tree, rays, opt, at), tree.features, ws, nbytes,
-                              None if rr is rays else rr) if record else None
-    return out
+    return _raysweep_forward(_DEPTH_MOMENTS, tree, rays, opt, (_depth_at(at),))
 
 
 def depth_moments_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: torch.Tensor, at=0) -> torch.Tensor:
@@ -1311,38 +1356,14 @@ def depth_moments_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output
     (every other column is zero), by the reference's convention for its backward -- every sample with sigma > 0, no early
     stop: the true gradient at thresholds 0 (include/svoxt.h, svoxt_depth_moments_bwd).  Reads what the forward of the same
     spec objects recorded if nothing it depends on has changed since; marches otherwise."""
-    import svox_t_amd.csrc as csrc
-    at = _depth_at(at)
-    Q = _spec_ray_count(rays)
-    if not isinstance(grad_output, torch.Tensor) or grad_output.dtype != torch.float32 or grad_output.dim() != 2 \
-            or grad_output.shape[0] != Q or grad_output.shape[1] != 3:
-        raise RuntimeError(f"grad_output must be float32 [Q, 3] with Q = {Q} rays")
-    _check_input(grad_output, "grad_output")
-    plan = getattr(rays, "_svoxt_depth_plan", None)
-    ws, nbytes, rr = None, 0, None
-    if plan is not None and plan[1] is tree.features and plan[0] == _depth_plan_key(csrc, tree, rays, opt, at):
-        ws, nbytes, rr = plan[2], plan[3], plan[4]
-    if rr is None:
-        # (the same walk as the forward's where there is a plan; any coherent one otherwise)
-        rr = rays if isinstance(rays, CameraSpec) or plan is not None else csrc._in_coherent_order(tree, rays, opt)[0]
-    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
-    dev = tree.features.device
-    with _on(dev):
-        grad = torch.zeros_like(tree.features)
-        _call("svoxt_depth_moments_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), at, _ptr(grad_output), _ptr(grad), 0,
-              _ptr(ws), nbytes, _stream(dev))
-    return grad
+    return _raysweep_backward(_DEPTH_MOMENTS, tree, rays, opt, grad_output, (_depth_at(at),))
 
 
 # ---------------------------------------------------------------------------
 # Distortion loss (svoxt_distort.hip; not in the reference; DESIGN.md 4.18)
 # ---------------------------------------------------------------------------
 DISTORTION_SAMPLES = 128  # samples recorded per ray for the backward, as DEPTHMOM_SAMPLES; 0: never record
-
-
-def _distortion_plan_key(csrc, tree, rays, opt):
-    f = tree.features
-    return (id(f), f._version, f.data_ptr(), csrc._opt_key(opt), csrc._tree_key(tree), csrc._rays_key(rays))
+_DISTORTION = _RaySweepOp("distortion", 2, "_svoxt_distortion_plan", "DISTORTION_SAMPLES")
 
 
 def distortion(tree: TreeSpec, rays, opt: RenderOptions) -> torch.Tensor:
@@ -1351,22 +1372,7 @@ def distortion(tree: TreeSpec, rays, opt: RenderOptions) -> torch.Tensor:
     units), and the accumulated alpha (include/svoxt.h, svoxt_distortion_fwd).  `rays`: a RaysSpec or a CameraSpec; walked
     as depth_moments walks them, every ray's row at its own index.  Where a backward will follow (rays.need_grad, else the
     feature table's requires_grad) the samples are recorded and left on the spec for distortion_backward."""
-    import svox_t_amd.csrc as csrc
-    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
-    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
-    dev = tree.features.device
-    record = csrc._need_grad(tree, rays) and DISTORTION_SAMPLES > 0 and cr.Q > 0
-    with _on(dev):
-        out = torch.empty((cr.Q, 2), dtype=torch.float32, device=dev)
-        ws, nbytes = None, 0
-        if record:
-            nbytes = _lib.svoxt_distortion_workspace_bytes(cr.Q, int(DISTORTION_SAMPLES))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        _call("svoxt_distortion_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), _ptr(ws), nbytes,
-              _stream(dev))
-    rays._svoxt_distortion_plan = (_distortion_plan_key(csrc, tree, rays, opt), tree.features, ws, nbytes,
-                                   None if rr is rays else rr) if record else None
-    return out
+    return _raysweep_forward(_DISTORTION, tree, rays, opt)
 
 
 def distortion_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: torch.Tensor) -> torch.Tensor:
@@ -1374,22 +1380,4 @@ def distortion_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: t
     by the reference's convention for its backward -- every sample with sigma > 0, no early stop, no rescale: the true
     gradient at thresholds 0 (include/svoxt.h, svoxt_distortion_bwd).  Reads what the forward of the same spec objects
     recorded if nothing it depends on has changed since; marches otherwise."""
-    import svox_t_amd.csrc as csrc
-    Q = _spec_ray_count(rays)
-    if not isinstance(grad_output, torch.Tensor) or grad_output.dtype != torch.float32 or grad_output.dim() != 2 \
-            or grad_output.shape[0] != Q or grad_output.shape[1] != 2:
-        raise RuntimeError(f"grad_output must be float32 [Q, 2] with Q = {Q} rays")
-    _check_input(grad_output, "grad_output")
-    plan = getattr(rays, "_svoxt_distortion_plan", None)
-    ws, nbytes, rr = None, 0, None
-    if plan is not None and plan[1] is tree.features and plan[0] == _distortion_plan_key(csrc, tree, rays, opt):
-        ws, nbytes, rr = plan[2], plan[3], plan[4]
-    if rr is None:
-        rr = rays if isinstance(rays, CameraSpec) or plan is not None else csrc._in_coherent_order(tree, rays, opt)[0]
-    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
-    dev = tree.features.device
-    with _on(dev):
-        grad = torch.zeros_like(tree.features)
-        _call("svoxt_distortion_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(grad_output), _ptr(grad), 0,
-              _ptr(ws), nbytes, _stream(dev))
-    return grad
+    return _raysweep_backward(_DISTORTION, tree, rays, opt, grad_output)

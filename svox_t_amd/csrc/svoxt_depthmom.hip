@@ -3,277 +3,61 @@
 //
 //     m1 = sum_k w_k z_k     m2 = sum_k w_k z_k^2     alpha = 1 - T_end     w_k = T_k (1 - att_k)
 //
-// The march is the shared one (setup_ray / march_step / march_advance / pexpf of svoxt_device.h), walked exactly as
-// opacity_fwd_kernel walks it; only the payload is new.  Not in the reference.
-//
-//   depthmom_fwd_kernel<N2, MID, REC>   one lane per ray (ray_of_thread: 8 x 8 tiles of a declared image, the order of a
-//                                       sorted batch), accumulators in registers, one 12-byte row stored per ray.  REC: a
-//                                       backward will follow -- every sample with sigma > 0 (the backward's set,
-//                                       rt_kernel.cu:382) is also written as (feature row, delta_t, z) into the caller's
-//                                       workspace, three planes of [tile][k][lane] words (a wavefront's k-th records are
-//                                       one 256-byte line per plane), up to S a ray; where a longer ray's records end is
-//                                       kept as the t to resume the march from.
-//   depthmom_bwd_kernel<N2, MID>        one wavefront per tile of 64 rays.  Sweep 1 forms each ray's full sum
-//                                       sum_k w_k c_k (c_k = g1 z_k + g2 z_k^2) and final transmittance with the backward's
-//                                       association of the exponent (:397); sweep 2 subtracts it down sample by sample
-//                                       (:480) and forms (:486-490 with total_color = c_k)
-//                                           delta_t ds (c_k T_{k+1} - sum_{i>k} w_i c_i) + delta_t ds ga T_end.
-//                                       Both sweeps read the recorded lists (four records a lane at a time: their sigma
-//                                       gathers and exponentials are independent, only the products run in list order)
-//                                       and march what was not recorded -- the tail of an over-long ray, or all of it
-//                                       when there is no workspace.  The values go into one column of the table: one
-//                                       4-byte float atomic per sample with one lane per row is the slowest atomic shape
-//                                       of this target, so they are summed per tile first -- an LDS hash table keyed by
-//                                       feature row (integer atomicCAS on the key, LDS float add on the value), flushed as
-//                                       one global atomicAdd per distinct row after every kDmRounds samples a lane.  The
-//                                       marched part goes through the same table, in lock step: every round each lane
-//                                       marches to its next sample with sigma > 0.  No path adds to global memory per
-//                                       sample and lane.
+// Not in the reference.  The loop is svoxt_raysweep.h's; this file is its payload.  Forward: one 12-byte row per ray; at
+// the stop threshold m1 and m2 are rescaled once each.  Backward: with c_k = g1 z_k + g2 z_k^2, sweep 1 forms the ray's
+// full sum sum_k w_k c_k, sweep 2 subtracts it down sample by sample (rt_kernel.cu:480) and hands the table (:486-490
+// with total_color = c_k; the skeleton adds delta_t ds ga T_end)
+//     delta_t ds (c_k T_{k+1} - sum_{i>k} w_i c_i).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "svoxt_device.h"
-#include "svoxt_host.h"
-#include "svoxt_launch.h"
-#include "svoxt_raylists.h"
+#include "svoxt_raysweep.h"
 
 #pragma clang fp contract(off)
 
 namespace svoxt {
 
 template <bool MID>
-__device__ __forceinline__ float dm_z(const Ray& r, float t, float delta_t) {
-    if constexpr (MID) return r.delta_scale * (t + 0.5f * delta_t);
-    else return r.delta_scale * t;
-}
+struct DepthMoments {
+    static constexpr int kOut = 3;
 
-template <bool N2, bool MID, bool REC>
-__global__ void __launch_bounds__(kBlock)
-depthmom_fwd_kernel(TreeDev tr, RaysDev rays, Opts opt, float* __restrict__ out, DmLists L) {
-    const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t q = ray_of_thread(rays, tid);
-    if (q >= rays.Q) {
-        if constexpr (REC) L.aux[tid] = make_uint2(0u, 0u);
-        return;
+    static __device__ __forceinline__ float z(const Ray& r, float t, float delta_t) {
+        if constexpr (MID) return r.delta_scale * (t + 0.5f * delta_t);
+        else return r.delta_scale * t;
     }
-    float m1 = 0.f, m2 = 0.f, light = 1.f;
-    int nrec = 0;
-    bool over = false;
-    float t_resume = 0.f;
-    Ray r;
-    if (setup_ray(tr, rays, opt, q, r)) {
-        const int K = tr.K;
-        const int S = L.S;
-        float t = r.tmin;
-        bool stopped = false;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                // (REC: every sigma > 0 is recorded, and composited only by the forward's own rules)
-                if (sigma > (REC ? 0.f : opt.sigma_thresh)) {
-                    const float z = dm_z<MID>(r, t, s.delta_t);
-                    if constexpr (REC) {
-                        if (nrec < S) {
-                            const int64_t i = dm_index(tid >> 6, S, nrec, (int)threadIdx.x);
-                            L.row[i] = (uint32_t)s.idx;
-                            L.dt[i] = s.delta_t;
-                            L.z[i] = z;
-                            ++nrec;
-                        } else if (!over) {
-                            over = true;
-                            t_resume = t;
-                        }
-                    }
-                    if (!REC || (sigma > opt.sigma_thresh && !stopped)) {
-                        const float att = pexpf(-s.delta_t * r.delta_scale * sigma);
-                        const float w = light * (1.f - att);
-                        m1 += w * z;
-                        m2 += w * (z * z);
-                        light *= att;
-                        if (light <= opt.stop_thresh) {          // as the colour forward scales its channels (rt_kernel.cu:313-319)
-                            const float scale = (float)(1.0 / (1.0 - (double)light));
-                            m1 *= scale;
-                            m2 *= scale;
-                            if constexpr (!REC) break;
-                            stopped = true;
-                        }
-                    }
-                    if (REC && over && stopped) break;           // nothing left to record or to composite
-                }
-            }
-            t = march_advance(t, s.delta_t);
-        }
-    }
-    out[q * 3 + 0] = m1;
-    out[q * 3 + 1] = m2;
-    out[q * 3 + 2] = 1.f - light;
-    if constexpr (REC) L.aux[tid] = make_uint2((uint32_t)nrec | (over ? kDmOver : 0u), __float_as_uint(t_resume));
-}
 
-template <bool N2, bool MID>
-__global__ void __launch_bounds__(64)
-depthmom_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ grad_out,
-                    float* __restrict__ grad, int gstride, DmLists L) {
-    __shared__ int32_t keys[kDmTable];
-    __shared__ float vals[kDmTable];
-    const int lane = threadIdx.x;
-    const int64_t tile = blockIdx.x;
-    const int64_t tid = tile * 64 + lane;
-    const int64_t q = ray_of_thread(rays, tid);
-    const int K = tr.K, S = L.S;
-    Ray r;
-    bool live = q < rays.Q;
-    if (live) live = setup_ray(tr, rays, opt, q, r);
-    int nrec = 0;
-    bool over = false;
-    float t_tail = 0.f, g1 = 0.f, g2 = 0.f, ga = 0.f;
-    if (live) {
-        if (S > 0) {
-            const uint2 a = L.aux[tid];
-            nrec = min((int)(a.x & ~kDmOver), S);
-            over = (a.x & kDmOver) != 0u;
-            t_tail = __uint_as_float(a.y);
-        } else {
-            over = true;
-            t_tail = r.tmin;
+    struct Fwd {
+        float m1, m2;
+        __device__ __forceinline__ void add(float w, float z, float) {
+            m1 += w * z;
+            m2 += w * (z * z);
         }
-        g1 = grad_out[q * 3 + 0];
-        g2 = grad_out[q * 3 + 1];
-        ga = grad_out[q * 3 + 2];
-    }
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);
-    if (maxn == 0 && !__any(over)) return;
-    dm_table_clear(keys, vals, lane);
-
-    auto put = [&](int32_t idx, float v) { dm_table_put(keys, vals, idx, v); };
-    auto flush = [&]() { dm_table_flush(keys, vals, lane, grad, gstride, K - 1); };
-    // four records of a lane: rows, steps and distances, the rows' sigma, the exponentials (slots past the count hold
-    // stale bits: row 0 is gathered for them and nothing is used)
-    auto fetch = [&](int kb, float (&dt)[kDmGroup], float (&z)[kDmGroup], float (&att)[kDmGroup], int32_t (&row)[kDmGroup]) {
-        float sig[kDmGroup];
-#pragma unroll
-        for (int j = 0; j < kDmGroup; ++j) {
-            const bool have = kb + j < nrec;
-            const int64_t i = dm_index(tile, S, have ? kb + j : 0, lane);
-            row[j] = have ? (int32_t)L.row[i] : 0;
-            dt[j] = have ? L.dt[i] : 0.f;
-            z[j] = have ? L.z[i] : 0.f;
+        __device__ __forceinline__ void rescale(float scale) {
+            m1 *= scale;
+            m2 *= scale;
         }
-#pragma unroll
-        for (int j = 0; j < kDmGroup; ++j) sig[j] = tr.features[(int64_t)row[j] * K + (K - 1)];
-#pragma unroll
-        for (int j = 0; j < kDmGroup; ++j) att[j] = pexpf(-dt[j] * sig[j] * r.delta_scale);
+        __device__ __forceinline__ void store(float* __restrict__ row, float light) const {
+            row[0] = m1;
+            row[1] = m2;
+            row[2] = 1.f - light;
+        }
     };
 
-    // sweep 1: the ray's full sum and final transmittance (rt_kernel.cu:397-428, no background: it has no depth)
-    float light = 1.f, accum = 0.f;
-    for (int kb = 0; kb < nrec; kb += kDmGroup) {
-        float dt[kDmGroup], z[kDmGroup], att[kDmGroup];
-        int32_t row[kDmGroup];
-        fetch(kb, dt, z, att, row);
-#pragma unroll
-        for (int j = 0; j < kDmGroup; ++j) {
-            if (kb + j < nrec) {
-                const float w = light * (1.f - att[j]);
-                const float c = g1 * z[j] + g2 * (z[j] * z[j]);
-                light *= att[j];
-                accum += w * c;
-            }
+    struct Bwd {
+        float g1, g2, accum;
+        __device__ __forceinline__ void init(const float* __restrict__ g) {
+            g1 = g[0];
+            g2 = g[1];
         }
-    }
-    if (over) {
-        float t = t_tail;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                if (sigma > 0.f) {
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    const float w = light * (1.f - att);
-                    const float z = dm_z<MID>(r, t, s.delta_t);
-                    const float c = g1 * z + g2 * (z * z);
-                    light *= att;
-                    accum += w * c;
-                }
-            }
-            t = march_advance(t, s.delta_t);
+        __device__ __forceinline__ void sweep1(float w, float, float z, float) { accum += w * (g1 * z + g2 * (z * z)); }
+        __device__ __forceinline__ void turn() {}
+        __device__ __forceinline__ float sweep2(float w, float light, float z, float d) {
+            const float c = g1 * z + g2 * (z * z);
+            accum -= w * c;
+            return d * (c * light - accum);
         }
-    }
-    const float light_ray = light;
-
-    // sweep 2 (:461-490)
-    light = 1.f;
-    for (int k0 = 0; k0 < maxn; k0 += kDmRounds) {
-#pragma unroll 1
-        for (int kb = k0; kb < min(k0 + kDmRounds, maxn); kb += kDmGroup) {
-            if (kb >= nrec) continue;
-            float dt[kDmGroup], z[kDmGroup], att[kDmGroup];
-            int32_t row[kDmGroup];
-            fetch(kb, dt, z, att, row);
-#pragma unroll
-            for (int j = 0; j < kDmGroup; ++j) {
-                if (kb + j < nrec) {
-                    const float w = light * (1.f - att[j]);
-                    const float c = g1 * z[j] + g2 * (z[j] * z[j]);
-                    light *= att[j];
-                    accum -= w * c;
-                    put(row[j], dt[j] * r.delta_scale * (c * light - accum) + dt[j] * r.delta_scale * ga * light_ray);
-                }
-            }
-        }
-        flush();
-    }
-    // what was not recorded, in lock step: a round takes every such lane to its next sample with sigma > 0
-    bool more = over;
-    float t = t_tail;
-    int round = 0;
-    while (__any(more)) {
-        if (more) {
-            bool found = false;
-            while (!found && t < r.tmax) {
-                Sample s;
-                march_step<N2>(tr, r, opt.step_size, t, s);
-                if (s.valid) {
-                    const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                    if (sigma > 0.f) {
-                        const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                        const float w = light * (1.f - att);
-                        const float z = dm_z<MID>(r, t, s.delta_t);
-                        const float c = g1 * z + g2 * (z * z);
-                        light *= att;
-                        accum -= w * c;
-                        put(s.idx, s.delta_t * r.delta_scale * (c * light - accum) + s.delta_t * r.delta_scale * ga * light_ray);
-                        found = true;
-                    }
-                }
-                t = march_advance(t, s.delta_t);
-            }
-            more = found;
-        }
-        if (++round == kDmRounds) {
-            flush();
-            round = 0;
-        }
-    }
-    if (round != 0) flush();
-}
-
-static int dm_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
-                    const void* workspace, int64_t workspace_bytes, const char* fn) {
-    int rc;
-    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, false))) return rc;
-    if (at != SVOXT_DEPTH_AT_ENTRY && at != SVOXT_DEPTH_AT_MID)
-        return fail(SVOXT_ERR_INVALID, "%s: at must be SVOXT_DEPTH_AT_ENTRY (0) or SVOXT_DEPTH_AT_MID (1)", fn);
-    if (workspace_bytes < 0 || (workspace_bytes > 0 && workspace == nullptr) || ((uintptr_t)workspace & 7u) != 0)
-        return fail(SVOXT_ERR_INVALID, "%s: workspace is NULL with a size, not 8-byte aligned, or its size negative", fn);
-    if (rays->Q > 0x7fffffffLL * 64) return fail(SVOXT_ERR_INVALID, "%s: too many rays", fn);
-    return SVOXT_OK;
-}
+    };
+};
 
 }  // namespace svoxt
 
@@ -287,54 +71,20 @@ int64_t svoxt_depth_moments_workspace_bytes(int64_t Q, int64_t max_samples) {
 
 int svoxt_depth_moments_fwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
                             float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* fn = "svoxt_depth_moments_fwd";
-    int rc;
-    if ((rc = dm_check(tree, rays, opt, at, workspace, workspace_bytes, fn))) return rc;
-    if (rays->Q == 0) return SVOXT_OK;
-    if (out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: out is NULL", fn);
-    const DmLists L = dm_lists(workspace, workspace_bytes, rays->Q);
-    const TreeDev tr = to_dev(tree);
-    const RaysDev rd = to_dev(rays, tree);
-    const Opts od = to_dev(opt);
-    const unsigned nb = nblocks(rays->Q);
-    hipStream_t st = (hipStream_t)stream;
-    with_bool(tree->N == 2, [&](auto N2) {
-        return with_bool(at == SVOXT_DEPTH_AT_MID, [&](auto MID) {
-            return with_bool(L.S > 0, [&](auto REC) {
-                hipLaunchKernelGGL((depthmom_fwd_kernel<N2.value, MID.value, REC.value>), dim3(nb), dim3(kBlock), 0, st,
-                                   tr, rd, od, out, L);
-                return true;
-            });
-        });
+    // (&at: this operator has the argument; raysweep_check refuses an invalid one, which is dispatched as ENTRY until then)
+    return with_bool(at == SVOXT_DEPTH_AT_MID, [&](auto MID) {
+        return raysweep_fwd<DepthMoments<MID.value>>(tree, rays, opt, &at, out, workspace, workspace_bytes, stream,
+                                                     "svoxt_depth_moments_fwd");
     });
-    return check_launch(fn);
 }
 
 int svoxt_depth_moments_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int32_t at,
                             const float* grad_out, float* grad, int32_t gstride,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* fn = "svoxt_depth_moments_bwd";
-    int rc;
-    if ((rc = dm_check(tree, rays, opt, at, workspace, workspace_bytes, fn))) return rc;
-    if (grad == nullptr && tree->M > 0) return fail(SVOXT_ERR_INVALID, "%s: grad is NULL", fn);
-    if (rays->Q > 0 && grad_out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad_out is NULL", fn);
-    const int gs = gstride > 0 ? gstride : tree->K;
-    if (gs < tree->K) return fail(SVOXT_ERR_INVALID, "%s: gstride smaller than data_dim", fn);
-    if (rays->Q == 0 || tree->M == 0) return SVOXT_OK;
-    const DmLists L = dm_lists(workspace, workspace_bytes, rays->Q);
-    const TreeDev tr = to_dev(tree);
-    const RaysDev rd = to_dev(rays, tree);
-    const Opts od = to_dev(opt);
-    const unsigned nb = nblocks(rays->Q);
-    hipStream_t st = (hipStream_t)stream;
-    with_bool(tree->N == 2, [&](auto N2) {
-        return with_bool(at == SVOXT_DEPTH_AT_MID, [&](auto MID) {
-            hipLaunchKernelGGL((depthmom_bwd_kernel<N2.value, MID.value>), dim3(nb), dim3(64), 0, st,
-                               tr, rd, od, grad_out, grad, gs, L);
-            return true;
-        });
+    return with_bool(at == SVOXT_DEPTH_AT_MID, [&](auto MID) {
+        return raysweep_bwd<DepthMoments<MID.value>>(tree, rays, opt, &at, grad_out, grad, gstride, workspace, workspace_bytes,
+                                                     stream, "svoxt_depth_moments_bwd");
     });
-    return check_launch(fn);
 }
 
 }  // extern "C"

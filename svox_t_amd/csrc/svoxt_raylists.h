@@ -1,4 +1,4 @@
-// svoxt_raylists.h -- what the per-ray operators with a sigma-only gradient share (svoxt_depthmom.hip, svoxt_distort.hip):
+// svoxt_raylists.h -- the storage of the per-ray operators with a sigma-only gradient (the kernels of svoxt_raysweep.h):
 // the recorded sample lists a forward leaves for its backward, and the tile's LDS hash table that turns the backward's
 // per-sample values into one global atomic per distinct feature row.
 //

@@ -178,42 +178,27 @@ class _OpacityRenderFunction(autograd.Function):
         return None, None, None, None
 
 
-class _DepthMomentsFunction(autograd.Function):
-    """Not in the reference: (m1, m2, alpha) per ray, differentiable wrt the feature table's sigma column."""
+class _RaySweepFunction(autograd.Function):
+    """Not in the reference: the per-ray operators that are differentiable wrt the feature table's sigma column --
+    depth moments (m1, m2, alpha) and distortion (distortion loss, alpha).  `fwd` / `bwd`: the operator's pair of _C,
+    `lead`: what they take behind their common arguments."""
 
     @staticmethod
-    def forward(ctx, data, tree, rays, opt, at):
-        out = _C.depth_moments(tree, rays, opt, at)
+    def forward(ctx, data, tree, rays, opt, fwd, bwd, *lead):
+        out = fwd(tree, rays, opt, *lead)
         ctx.tree = tree
         ctx.rays = rays
         ctx.opt = opt
-        ctx.at = at
+        ctx.bwd = bwd
+        ctx.lead = lead
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
+        grad = None
         if ctx.needs_input_grad[0]:
-            return _C.depth_moments_backward(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous(), ctx.at), \
-                None, None, None, None
-        return None, None, None, None, None
-
-
-class _DistortionFunction(autograd.Function):
-    """Not in the reference: (distortion loss, alpha) per ray, differentiable wrt the feature table's sigma column."""
-
-    @staticmethod
-    def forward(ctx, data, tree, rays, opt):
-        out = _C.distortion(tree, rays, opt)
-        ctx.tree = tree
-        ctx.rays = rays
-        ctx.opt = opt
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        if ctx.needs_input_grad[0]:
-            return _C.distortion_backward(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous()), None, None, None
-        return None, None, None, None
+            grad = ctx.bwd(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous(), *ctx.lead)
+        return (grad,) + (None,) * (5 + len(ctx.lead))
 
 
 class VolumeRenderer(nn.Module):
@@ -352,8 +337,8 @@ class VolumeRenderer(nn.Module):
             raise ValueError(f"at must be 'entry' or 'mid', not {at!r}")
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
         rspec.need_grad = _will_differentiate(features)
-        return _DepthMomentsFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
-                                           0 if at == "entry" else 1)
+        return _RaySweepFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
+                                       _C.depth_moments, _C.depth_moments_backward, 0 if at == "entry" else 1)
 
     def render_expected_depth(self, features, rays: Rays, *, at="entry", cuda=True, fast=False, image_shape=None,
                               sort_rays=None, eps=1e-10):
@@ -380,7 +365,8 @@ class VolumeRenderer(nn.Module):
         self._require_gpu(cuda, "render_distortion")
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
         rspec.need_grad = _will_differentiate(features)
-        return _DistortionFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast))
+        return _RaySweepFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
+                                       _C.distortion, _C.distortion_backward)
 
     def distortion_loss(self, features, rays: Rays, *, reduction="mean", cuda=True, fast=False, image_shape=None,
                         sort_rays=None):

@@ -10,6 +10,7 @@ import svox_t_amd.csrc as _C
 from oracle import oracle as O
 from svox_t_amd import synth
 from svox_t_amd.renderer import _make_camera_spec
+from tests import depth_restate as DR
 from tests import distortion_restate as R
 from tests.util import Case, assert_grads_close, assert_outputs_close
 
@@ -292,6 +293,56 @@ def test_backward_after_the_features_changed_marches(gpu, monkeypatch):
     assert_grads_close(stale, marched, scale)
     assert_grads_close(stale, R.distortion_grad(ot, c.rays_np(), oopt, g.cpu().numpy()), scale)
     assert (stale != 0).sum() > 500
+
+
+def test_both_operators_recorded_on_one_spec(gpu):
+    """render_depth_moments(at="mid") and render_distortion share their forward, backward and plan code: recorded one
+    after the other on ONE rays spec, each keeps a plan of its own, and the backwards -- taken in the opposite order --
+    give what each operator gives on a fresh spec.  Through csrc, not the renderer: VolumeRenderer builds a fresh spec for
+    every call, so only this level can put two plans on one spec.  The plan assertions are what catches a collision (a
+    backward whose plan does not match marches, and still agrees); one Rays object through the renderer follows, for the
+    autograd Function both operators share."""
+    c, ot, rays = built("d5_rgba4")
+    tree = c.tree(gpu)
+    spec, opt = tree._spec(tree.features), svox.VolumeRenderer(tree)._get_options()
+    rg = c.rays_gpu(gpu)
+    g3 = synth.grad_output(c.Q, 3, seed=20).to(gpu)
+    g2 = torch.from_numpy(grad_outputs(c.Q, "all", seed=21)).to(gpu)
+
+    def rspec():
+        s = svox.renderer._rays_spec_from_rays(rg, None, None)
+        s.need_grad = True
+        return s
+
+    rs = rspec()
+    _C.depth_moments(spec, rs, opt, "mid")
+    _C.distortion(spec, rs, opt)
+    for plan in (rs._svoxt_depth_plan, rs._svoxt_distortion_plan):
+        assert plan is not None and plan[2] is not None and plan[3] > 0
+    assert rs._svoxt_depth_plan[2].data_ptr() != rs._svoxt_distortion_plan[2].data_ptr()
+    ds = _C.distortion_backward(spec, rs, opt, g2).cpu().numpy()
+    dm = _C.depth_moments_backward(spec, rs, opt, g3, "mid").cpu().numpy()
+    own = rspec()
+    _C.distortion(spec, own, opt)
+    ds_own = _C.distortion_backward(spec, own, opt, g2).cpu().numpy()
+    own = rspec()
+    _C.depth_moments(spec, own, opt, "mid")
+    dm_own = _C.depth_moments_backward(spec, own, opt, g3, "mid").cpu().numpy()
+    oopt = c.oracle_opts()
+    assert_grads_close(ds, ds_own, R.distortion_grad_scale(ot, rays, oopt, g2.cpu().numpy()))
+    assert_grads_close(dm, dm_own, DR.moments_grad_scale(ot, rays, oopt, "mid", g3.cpu().numpy()))
+    assert (ds != 0).sum() > 500 and (dm != 0).sum() > 500
+    r = svox.VolumeRenderer(tree)
+    out_dm = r.render_depth_moments(tree.features, rg, at="mid")
+    out_ds = r.render_distortion(tree.features, rg)
+    tree.features.grad = None
+    out_ds.backward(g2)
+    ds_r = tree.features.grad.cpu().numpy()
+    tree.features.grad = None
+    out_dm.backward(g3)
+    dm_r = tree.features.grad.cpu().numpy()
+    assert_grads_close(ds_r, ds_own, R.distortion_grad_scale(ot, rays, oopt, g2.cpu().numpy()))
+    assert_grads_close(dm_r, dm_own, DR.moments_grad_scale(ot, rays, oopt, "mid", g3.cpu().numpy()))
 
 
 # the loss, the camera form ------------------------------------------------------------------------------------------
