@@ -1181,7 +1181,7 @@ from ._extras import assign_leaves, leaf_corners, snap_points  # noqa: E402,F401
 from ._extras import OPTIM_KINDS, OPTIM_STATES, optim_step  # noqa: E402,F401
 from ._extras import (frontier_diam, frontier_nodes, frontier_reduce, frontier_reduce_backward,  # noqa: E402,F401
                       merge_tree)
-from ._extras import subdivide_tree, unshare_rows  # noqa: E402,F401
+from ._extras import slot_decision, subdivide_tree, unshare_rows  # noqa: E402,F401
 from ._extras import TVPlan, leaf_neighbors, tv_plan, tv_rows  # noqa: E402,F401
 from ._extras import depth_moments, depth_moments_backward  # noqa: E402,F401
 from ._extras import distortion, distortion_backward  # noqa: E402,F401

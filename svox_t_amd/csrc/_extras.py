@@ -302,6 +302,64 @@ def construct_tree(tree: TreeSpec, indices: torch.Tensor) -> None:
     _drop_accel(tree.child)
 
 
+def _workspace(dev, nbytes, refusal):
+    """The workspace a *_workspace_bytes query asks for; the query's -1 (extents out of range) is refused with `refusal`."""
+    if nbytes < 0:
+        raise RuntimeError(refusal)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
+
+def _count(dev, nbytes, refusal, n_counts, call):
+    """The first half of a count / emit pipeline: the workspace, the counts on the device, `call(workspace pointer,
+    nbytes, counts pointer)`, and the one host read that sizes the outputs.  Returns (workspace, [counts as ints])."""
+    ws = _workspace(dev, nbytes, refusal)
+    counts = torch.empty((n_counts,), dtype=torch.int64, device=dev)
+    call(_ptr(ws), nbytes, _ptr(counts))
+    return ws, [int(v) for v in counts.tolist()]
+
+
+def _new_tables(rows, N, used, empty_index, dev):
+    """child / data / parent_depth of `rows` rows: the first `used` left for the caller to write, the rows behind them
+    initialised like unused rows of an N3Tree."""
+    child = torch.empty((rows, N, N, N), dtype=torch.int32, device=dev)
+    data = torch.empty((rows, N, N, N, 1), dtype=torch.int32, device=dev)
+    parent_depth = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+    if rows > used:
+        child[used:].zero_()
+        data[used:].fill_(int(empty_index))
+        parent_depth[used:].zero_()
+    return child, data, parent_depth
+
+
+def slot_decision(child, name, mask, weights, threshold, required):
+    """The caller's decision over the slots of child: a bool / uint8 mask (the argument called `name`), or float32 weights
+    with a threshold, or -- unless `required` -- neither: every slot.  Returns ({argument name: the tensor given}, the
+    threshold for the call); devices are checked with the tables (_check_on_device_of_child)."""
+    if required and (mask is None) == (weights is None):
+        raise RuntimeError(f"exactly one of {name} / weights must be given")
+    if mask is not None and weights is not None:
+        raise RuntimeError(f"at most one of {name} / weights may be given")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tuple(child.shape):
+            raise RuntimeError(f"{name} must be a bool or uint8 tensor with the shape of child")
+        if threshold is not None:
+            raise RuntimeError(f"threshold goes with weights, not with {name}")
+        given, thr = {name: mask}, 0.0
+    elif weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(child.shape):
+            raise RuntimeError("weights must be a float32 tensor with the shape of child")
+        if threshold is None or float(threshold) != float(threshold):
+            raise RuntimeError("weights needs a threshold (not NaN)")
+        given, thr = {"weights": weights}, float(threshold)
+    else:
+        if threshold is not None:
+            raise RuntimeError("threshold goes with weights")
+        given, thr = {}, 0.0
+    if any(v.device != child.device for v in given.values()):
+        raise RuntimeError(f"{name} / weights must be on the device of child")
+    return given, thr
+
+
 def build_octree(points: torch.Tensor, offset: torch.Tensor, scaling: torch.Tensor, depth: int,
                  empty_index: int, reserve: int = 0):
     """Octree of a point cloud in one pipeline (not an entry of the reference's
@@ -320,21 +378,9 @@ def build_octree(points: torch.Tensor, offset: torch.Tensor, scaling: torch.Tens
     P = points.shape[0]
     with _on(dev):
         nbytes = _lib.svoxt_build_workspace_bytes(int(depth))
-        if nbytes < 0:
-            raise RuntimeError("build_octree: depth must be in [1, 10]")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        count = torch.empty((1,), dtype=torch.int64, device=dev)
-        _call("svoxt_build_count", _ptr(points), P, _ptr(offset), _ptr(scaling), int(depth),
-              _ptr(ws), nbytes, _ptr(count), _stream(dev))
-        n = int(count.item())                 # the one host read: sizes the tables
-        rows = n + int(reserve)
-        child = torch.empty((rows, 2, 2, 2), dtype=torch.int32, device=dev)
-        data = torch.empty((rows, 2, 2, 2, 1), dtype=torch.int32, device=dev)
-        parent_depth = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-        if reserve > 0:
-            child[n:].zero_()
-            data[n:].fill_(int(empty_index))
-            parent_depth[n:].zero_()
+        ws, (n,) = _count(dev, nbytes, "build_octree: depth must be in [1, 10]", 1, lambda w, b, c: _call(
+            "svoxt_build_count", _ptr(points), P, _ptr(offset), _ptr(scaling), int(depth), w, b, c, _stream(dev)))
+        child, data, parent_depth = _new_tables(n + int(reserve), 2, n, empty_index, dev)
         _call("svoxt_build_emit", _ptr(points), P, _ptr(offset), _ptr(scaling), int(depth),
               _ptr(ws), nbytes, _ptr(child), _ptr(data), _ptr(parent_depth), n, int(empty_index),
               _stream(dev))
@@ -353,62 +399,20 @@ def prune_tree(child: torch.Tensor, data: torch.Tensor, parent_depth: torch.Tens
     rows of an N3Tree; row_map int64 [M'] = the old row of every new feature row (None without compact_features);
     with return_dropped a sixth value, the number of leaves that held a feature row and were not kept.
     One host read (the counts that size the outputs)."""
-    for nm, x in (("child", child), ("data", data), ("parent_depth", parent_depth)):
-        _check_input(x, nm)
-        if x.dtype != torch.int32:
-            raise RuntimeError(f"{nm} must be int32")
-        if x.device != child.device:
-            raise RuntimeError(f"{nm} must be on the device of child")
-    if child.dim() != 4 or child.shape[1] < 2 or child.shape[1] > 16 or child.shape[2] != child.shape[1] \
-            or child.shape[3] != child.shape[1]:
-        raise RuntimeError("child must be int32 [cap, N, N, N] with N in [2, 16]")
-    cap, N = child.shape[0], child.shape[1]
-    if data.numel() != child.numel() or data.shape[0] != cap:
-        raise RuntimeError("data must be int32 [cap, N, N, N, 1] matching child")
-    if parent_depth.dim() != 2 or tuple(parent_depth.shape) != (cap, 2):
-        raise RuntimeError("parent_depth must be int32 [cap, 2]")
-    n, M, reserve = int(n_internal), int(M), int(reserve)
-    if n < 1 or n > cap:
-        raise RuntimeError("n_internal must be in [1, cap]")
+    _, N, n = _check_tables(child, data, parent_depth, n_internal)
+    M, reserve = int(M), int(reserve)
     if M < 0 or reserve < 0:
         raise RuntimeError("M and reserve must be >= 0")
-    if (keep is None) == (weights is None):
-        raise RuntimeError("exactly one of keep / weights must be given")
-    if keep is not None:
-        _check_input(keep, "keep")
-        if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != tuple(child.shape):
-            raise RuntimeError("keep must be a bool or uint8 tensor with the shape of child")
-        if threshold is not None:
-            raise RuntimeError("threshold goes with weights, not with keep")
-        decision, thr = keep, 0.0
-    else:
-        _check_input(weights, "weights")
-        if weights.dtype != torch.float32 or tuple(weights.shape) != tuple(child.shape):
-            raise RuntimeError("weights must be a float32 tensor with the shape of child")
-        if threshold is None or float(threshold) != float(threshold):
-            raise RuntimeError("weights needs a threshold (not NaN)")
-        decision, thr = weights, float(threshold)
-    if decision.device != child.device:
-        raise RuntimeError("keep / weights must be on the device of child")
+    given, thr = slot_decision(child, "keep", keep, weights, threshold, required=True)
+    _check_on_device_of_child(child, data=data, parent_depth=parent_depth, **given)
     dev = child.device
-    kp, wp = (_ptr(keep), None) if keep is not None else (None, _ptr(weights))
+    kp, wp = _ptr(keep), _ptr(weights)
     with _on(dev):
         nbytes = _lib.svoxt_prune_workspace_bytes(n, M)
-        if nbytes < 0:
-            raise RuntimeError("prune_tree: n_internal and M must be below 2^31")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((3,), dtype=torch.int64, device=dev)
-        _call("svoxt_prune_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, kp, wp, thr, int(bool(collapse)),
-              int(bool(compact_features)), _ptr(ws), nbytes, _ptr(counts), _stream(dev))
-        new_n, new_M, dropped = (int(v) for v in counts.tolist())      # the one host read: sizes the outputs
-        rows = new_n + reserve
-        child_out = torch.empty((rows, N, N, N), dtype=torch.int32, device=dev)
-        data_out = torch.empty((rows, N, N, N, 1), dtype=torch.int32, device=dev)
-        pd_out = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-        if reserve > 0:
-            child_out[new_n:].zero_()
-            data_out[new_n:].fill_(int(empty_index))
-            pd_out[new_n:].zero_()
+        ws, (new_n, new_M, dropped) = _count(dev, nbytes, "prune_tree: n_internal and M must be below 2^31", 3, lambda w, b, c: _call(
+            "svoxt_prune_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, kp, wp, thr, int(bool(collapse)),
+            int(bool(compact_features)), w, b, c, _stream(dev)))
+        child_out, data_out, pd_out = _new_tables(new_n + reserve, N, new_n, empty_index, dev)
         row_map = torch.empty((new_M,), dtype=torch.int64, device=dev) if compact_features else None
         _call("svoxt_prune_emit", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, kp, wp, thr, int(bool(compact_features)),
               _ptr(ws), nbytes, new_n, new_M, int(empty_index), _ptr(child_out), _ptr(data_out), _ptr(pd_out), _ptr(row_map),
@@ -436,10 +440,7 @@ def gather_rows(src: torch.Tensor, row_map: torch.Tensor) -> torch.Tensor:
 def _grown_tables(child, data, parent_depth, rows, empty_index):
     """The three tables with `rows` rows: the old ones copied, the rows behind them initialised like unused rows of an N3Tree."""
     cap, N = child.shape[0], child.shape[1]
-    dev = child.device
-    child2 = torch.zeros((rows, N, N, N), dtype=torch.int32, device=dev)
-    data2 = torch.full((rows, N, N, N, 1), int(empty_index), dtype=torch.int32, device=dev)
-    pd2 = torch.zeros((rows, 2), dtype=torch.int32, device=dev)
+    child2, data2, pd2 = _new_tables(rows, N, cap, empty_index, child.device)
     child2[:cap], data2[:cap], pd2[:cap] = child, data.reshape(cap, N, N, N, 1), parent_depth
     return child2, data2, pd2
 
@@ -463,38 +464,16 @@ def subdivide_tree(child: torch.Tensor, data: torch.Tensor, parent_depth: torch.
     M = int(M)
     if M < 0:
         raise RuntimeError("M must be >= 0")
-    if sel is not None and weights is not None:
-        raise RuntimeError("at most one of sel / weights may be given")
-    if sel is not None:
-        if not isinstance(sel, torch.Tensor) or sel.dtype not in (torch.bool, torch.uint8) or tuple(sel.shape) != tuple(child.shape):
-            raise RuntimeError("sel must be a bool or uint8 tensor with the shape of child")
-        if threshold is not None:
-            raise RuntimeError("threshold goes with weights, not with sel")
-    thr = 0.0
-    if weights is not None:
-        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(child.shape):
-            raise RuntimeError("weights must be a float32 tensor with the shape of child")
-        if threshold is None or float(threshold) != float(threshold):
-            raise RuntimeError("weights needs a threshold (not NaN)")
-        thr = float(threshold)
-    elif threshold is not None and sel is None:
-        raise RuntimeError("threshold goes with weights")
-    extra = {k: v for k, v in (("sel", sel), ("weights", weights)) if v is not None}
-    if any(isinstance(v, torch.Tensor) and v.device != child.device for v in extra.values()):
-        raise RuntimeError("sel / weights must be on the device of child")
+    extra, thr = slot_decision(child, "sel", sel, weights, threshold, required=False)
     _check_on_device_of_child(child, data=data, parent_depth=parent_depth, **extra)
     dev = child.device
     n3 = N ** 3
     limit = max(-0x80000000, min(0x7fffffff, int(depth_limit)))
     with _on(dev):
         nbytes = _lib.svoxt_subdivide_workspace_bytes(n, N, M)
-        if nbytes < 0:
-            raise RuntimeError("subdivide_tree: n_internal * N^3 and M must be below 2^31")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((2,), dtype=torch.int64, device=dev)
-        _call("svoxt_subdivide_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(sel), _ptr(weights), thr, limit,
-              int(bool(split_empty)), int(bool(own_rows)), _ptr(ws), nbytes, _ptr(counts), _stream(dev))
-        added, rows_added = (int(v) for v in counts.tolist())         # the one host read: sizes the outputs
+        ws, (added, rows_added) = _count(dev, nbytes, "subdivide_tree: n_internal * N^3 and M must be below 2^31", 2, lambda w, b, c: _call(
+            "svoxt_subdivide_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(sel), _ptr(weights), thr, limit,
+            int(bool(split_empty)), int(bool(own_rows)), w, b, c, _stream(dev)))
         if (n + added) * n3 >= int(slot_limit):
             raise RuntimeError(f"subdivide_tree: {n} + {added} nodes of {n3} slots do not fit 32-bit slot indices "
                                f"((n_internal + nodes_added) * N^3 must be < {int(slot_limit)})")
@@ -530,12 +509,8 @@ def unshare_rows(child: torch.Tensor, data: torch.Tensor, n_internal: int, M: in
     dev = child.device
     with _on(dev):
         nbytes = _lib.svoxt_subdivide_workspace_bytes(n, N, M)
-        if nbytes < 0:
-            raise RuntimeError("unshare_rows: n_internal * N^3 and M must be below 2^31")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        count = torch.empty((1,), dtype=torch.int64, device=dev)
-        _call("svoxt_unshare_count", _ptr(child), _ptr(data), n, N, M, _ptr(ws), nbytes, _ptr(count), _stream(dev))
-        rows_added = int(count.item())                                  # the one host read: sizes row_map
+        ws, (rows_added,) = _count(dev, nbytes, "unshare_rows: n_internal * N^3 and M must be below 2^31", 1, lambda w, b, c: _call(
+            "svoxt_unshare_count", _ptr(child), _ptr(data), n, N, M, w, b, c, _stream(dev)))
         if M + rows_added >= int(empty_index):
             raise RuntimeError(f"unshare_rows: {M} + {rows_added} feature rows reach the empty index {int(empty_index)}")
         row_map = torch.empty((M + rows_added,), dtype=torch.int64, device=dev)
@@ -585,10 +560,8 @@ def frontier_nodes(child: torch.Tensor, n_internal: int) -> torch.Tensor:
     dev = child.device
     with _on(dev):
         nbytes = _lib.svoxt_frontier_workspace_bytes(n)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        count = torch.empty((1,), dtype=torch.int64, device=dev)
-        _call("svoxt_frontier_count", _ptr(child), n, N, _ptr(ws), nbytes, _ptr(count), _stream(dev))
-        F = int(count.item())                     # the one host read
+        ws, (F,) = _count(dev, nbytes, "frontier_nodes: n_internal must be below 2^31", 1, lambda w, b, c: _call(
+            "svoxt_frontier_count", _ptr(child), n, N, w, b, c, _stream(dev)))
         out = torch.empty((F,), dtype=torch.int64, device=dev)
         _call("svoxt_frontier_emit", _ptr(ws), nbytes, n, F, _ptr(out), _stream(dev))
     return out
@@ -697,21 +670,9 @@ def merge_tree(child, data, parent_depth, n_internal, features, selected, op="me
     compact = int(bool(compact_features))
     with _on(dev):
         nbytes = _lib.svoxt_merge_workspace_bytes(n, M)
-        if nbytes < 0:
-            raise RuntimeError("merge_tree: n_internal and M must be below 2^31")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        counts = torch.empty((3,), dtype=torch.int64, device=dev)
-        _call("svoxt_merge_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(selected), compact, _ptr(ws), nbytes,
-              _ptr(counts), _stream(dev))
-        new_n, carried, added = (int(v) for v in counts.tolist())      # the one host read: sizes the outputs
-        rows = new_n + reserve
-        child_out = torch.empty((rows, N, N, N), dtype=torch.int32, device=dev)
-        data_out = torch.empty((rows, N, N, N, 1), dtype=torch.int32, device=dev)
-        pd_out = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-        if reserve > 0:
-            child_out[new_n:].zero_()
-            data_out[new_n:].fill_(int(empty_index))
-            pd_out[new_n:].zero_()
+        ws, (new_n, carried, added) = _count(dev, nbytes, "merge_tree: n_internal and M must be below 2^31", 3, lambda w, b, c: _call(
+            "svoxt_merge_count", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(selected), compact, w, b, c, _stream(dev)))
+        child_out, data_out, pd_out = _new_tables(new_n + reserve, N, new_n, empty_index, dev)
         row_map = torch.empty((carried,), dtype=torch.int64, device=dev) if compact else None
         new_nodes = torch.empty((added,), dtype=torch.int64, device=dev)
         _call("svoxt_merge_emit", _ptr(child), _ptr(data), _ptr(parent_depth), n, N, M, _ptr(selected), compact, _ptr(ws), nbytes,
@@ -1096,9 +1057,7 @@ def leaf_neighbors(child: torch.Tensor, parent_depth: torch.Tensor, n_internal: 
     dev = child.device
     with _on(dev):
         nbytes = _lib.svoxt_neighbors_workspace_bytes(n, N)
-        if nbytes < 0:
-            raise RuntimeError("leaf_neighbors: n_internal * N^3 must be below 2^31")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws = _workspace(dev, nbytes, "leaf_neighbors: n_internal * N^3 must be below 2^31")
         out = torch.empty((L, 6), dtype=torch.int32, device=dev)
         _call("svoxt_leaf_neighbors", _ptr(child), _ptr(parent_depth), n, N, max_depth, L, _ptr(out), _ptr(ws), nbytes, _stream(dev))
     return out
@@ -1140,10 +1099,8 @@ def tv_plan(neighbors: torch.Tensor, depths: torch.Tensor, rows: torch.Tensor, M
     dev = neighbors.device
     with _on(dev):
         mbytes = _lib.svoxt_tv_plan_workspace_bytes(L, -1)
-        marks = torch.empty((mbytes,), dtype=torch.uint8, device=dev)
-        count = torch.empty((1,), dtype=torch.int64, device=dev)
-        _call("svoxt_tv_plan_count", _ptr(neighbors), _ptr(depths), _ptr(rows), L, M, _ptr(marks), mbytes, _ptr(count), _stream(dev))
-        E = int(count.item())                                           # the one host read: sizes the plan
+        marks, (E,) = _count(dev, mbytes, "tv_plan: 12 * L must be below 2^31", 1, lambda w, b, c: _call(
+            "svoxt_tv_plan_count", _ptr(neighbors), _ptr(depths), _ptr(rows), L, M, w, b, c, _stream(dev)))
         row_ptr = torch.empty((M + 1,), dtype=torch.int32, device=dev)
         other = torch.empty((2 * E,), dtype=torch.int32, device=dev)
         meta = torch.empty((2 * E,), dtype=torch.uint8, device=dev)

@@ -32,18 +32,16 @@
 
 #include "svoxt_host.h"
 #include "svoxt_sort.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
-constexpr int kAssignBlock = 256;
+constexpr int kAssignBlock = kLaunchBlock;
 constexpr int kMaxWalk = 128;            // levels a corner walk follows before it gives up (NaN): a malformed table
 enum { AS_LAST = SVOXT_ASSIGN_LAST, AS_SUM = SVOXT_ASSIGN_SUM, AS_MEAN = SVOXT_ASSIGN_MEAN, AS_MAX = SVOXT_ASSIGN_MAX,
        AS_MIN = SVOXT_ASSIGN_MIN };
 
 typedef float float4a __attribute__((ext_vector_type(4)));
-
-static size_t assign_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static unsigned assign_blocks(int64_t n) { return (unsigned)((n + kAssignBlock - 1) / kAssignBlock); }
 
 // workspace of "last": [row i32[Q]] [winner i32[M]]
 // of the others:       [keys u32[Q + 1]] x 2 [vals u32[Q + 1]] x 2 [counts] [starts] [chunk sums] [heads u32[Q]]; after
@@ -56,23 +54,20 @@ struct AssignSpace {
 
 static AssignSpace assign_carve(void* workspace, int64_t Q, int64_t M, int32_t reduce) {
     AssignSpace sp = {};
-    char* w = static_cast<char*>(workspace);
-    size_t o = 0;
+    Carver w(workspace);
     if (reduce == AS_LAST) {
-        sp.row = reinterpret_cast<int32_t*>(w + o); o += assign_align(sizeof(int32_t) * (size_t)Q);
-        sp.winner = reinterpret_cast<int32_t*>(w + o); o += assign_align(sizeof(int32_t) * (size_t)M);
+        sp.row = w.take<int32_t>((size_t)Q);
+        sp.winner = w.take<int32_t>((size_t)M);
     } else {
-        const size_t qq = assign_align(sizeof(uint32_t) * ((size_t)Q + 1));
         const size_t cc = (size_t)256 * sort_blocks((uint64_t)Q);
-        for (int i = 0; i < 2; ++i) { sp.keys[i] = reinterpret_cast<uint32_t*>(w + o); o += qq; }
-        for (int i = 0; i < 2; ++i) { sp.vals[i] = reinterpret_cast<uint32_t*>(w + o); o += qq; }
-        sp.counts = reinterpret_cast<uint32_t*>(w + o); o += assign_align(sizeof(uint32_t) * cc);
-        sp.starts = reinterpret_cast<uint32_t*>(w + o); o += assign_align(sizeof(uint32_t) * cc);
-        sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-        o += assign_align(sizeof(uint32_t) * exclusive_scan_chunks(cc > (size_t)Q + 1 ? cc : (size_t)Q + 1));
-        sp.heads = reinterpret_cast<uint32_t*>(w + o); o += qq;
+        for (int i = 0; i < 2; ++i) sp.keys[i] = w.take<uint32_t>((size_t)Q + 1);
+        for (int i = 0; i < 2; ++i) sp.vals[i] = w.take<uint32_t>((size_t)Q + 1);
+        sp.counts = w.take<uint32_t>(cc);
+        sp.starts = w.take<uint32_t>(cc);
+        sp.chunks = w.take<uint32_t>(exclusive_scan_chunks(cc > (size_t)Q + 1 ? cc : (size_t)Q + 1));
+        sp.heads = w.take<uint32_t>((size_t)Q + 1);            // (Q words are used: the piece is as long as the keys')
     }
-    sp.bytes = o + 256;
+    sp.bytes = w.bytes() + 256;
     return sp;
 }
 
@@ -121,12 +116,6 @@ assign_flag_kernel(const uint32_t* __restrict__ keys, int64_t Q, uint32_t M, uin
         head = k < M && (i == 0 || keys[i - 1] != k);
     }
     flag[i] = head ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(kAssignBlock)
-assign_heads_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank, int64_t Q, uint32_t* __restrict__ heads) {
-    const int64_t i = (int64_t)blockIdx.x * kAssignBlock + threadIdx.x;
-    if (i < Q && flag[i] != 0u && (int64_t)rank[i] < Q) heads[rank[i]] = (uint32_t)i;
 }
 
 // ------------------------------------------------------------------------------------------------------------ reduce
@@ -256,9 +245,9 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
     if (M > 0 && table == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: table is NULL", fn);
     if (Q > 0 && (points == nullptr || values == nullptr)) return set_error(SVOXT_ERR_INVALID, "%s: points / values is NULL", fn);
     if (Q > 0 && M > 0) {
-        if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-        if (workspace_bytes < svoxt_assign_workspace_bytes(Q, M, reduce))
-            return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_assign_workspace_bytes(Q, M, reduce)", fn);
+        if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_assign_workspace_bytes(Q, M, reduce),
+                                  "svoxt_assign_workspace_bytes(Q, M, reduce)")))
+            return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
@@ -274,10 +263,10 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
     if (reduce == AS_LAST) {
         e = hipMemsetAsync(sp.winner, 0xff, sizeof(int32_t) * (size_t)M, st);        // -1: below every point index
         if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-        hipLaunchKernelGGL((n2 ? assign_locate_kernel<true, false> : assign_locate_kernel<false, false>), dim3(assign_blocks(Q)),
+        hipLaunchKernelGGL((n2 ? assign_locate_kernel<true, false> : assign_locate_kernel<false, false>), dim3(launch_blocks(Q)),
                            dim3(kAssignBlock), 0, st, tr, points, Q, sp.row, sp.winner, (uint32_t*)nullptr, row_count);
         if ((rc = check_launch(fn))) return rc;
-        const dim3 grid(assign_blocks(Q * lpr));
+        const dim3 grid(launch_blocks(Q * lpr));
         if (vec)
             hipLaunchKernelGGL(assign_copy_kernel<float4a>, grid, dim3(kAssignBlock), 0, st, sp.row, sp.winner, Q, lpr,
                                reinterpret_cast<const float4a*>(values), reinterpret_cast<float4a*>(table));
@@ -285,7 +274,7 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
             hipLaunchKernelGGL(assign_copy_kernel<float>, grid, dim3(kAssignBlock), 0, st, sp.row, sp.winner, Q, lpr, values, table);
         return check_launch(fn);
     }
-    hipLaunchKernelGGL((n2 ? assign_locate_kernel<true, true> : assign_locate_kernel<false, true>), dim3(assign_blocks(Q)),
+    hipLaunchKernelGGL((n2 ? assign_locate_kernel<true, true> : assign_locate_kernel<false, true>), dim3(launch_blocks(Q)),
                        dim3(kAssignBlock), 0, st, tr, points, Q, (int32_t*)nullptr, (int32_t*)nullptr, sp.keys[0], row_count);
     if ((rc = check_launch(fn))) return rc;
     // the keys are in [0, M]: sort over the bits of M, in passes of at most 8 bits, all of (nearly) the same width
@@ -301,12 +290,12 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
         cur ^= 1;
     }
     uint32_t *flag = sp.keys[cur ^ 1], *rank = sp.vals[cur ^ 1];
-    hipLaunchKernelGGL(assign_flag_kernel, dim3(assign_blocks(Q + 1)), dim3(kAssignBlock), 0, st, sp.keys[cur], Q, (uint32_t)M, flag);
+    hipLaunchKernelGGL(assign_flag_kernel, dim3(launch_blocks(Q + 1)), dim3(kAssignBlock), 0, st, sp.keys[cur], Q, (uint32_t)M, flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(flag, (size_t)Q + 1, sp.chunks, rank, st, fn))) return rc;
-    hipLaunchKernelGGL(assign_heads_kernel, dim3(assign_blocks(Q)), dim3(kAssignBlock), 0, st, flag, rank, Q, sp.heads);
+    hipLaunchKernelGGL(scatter_ranked_kernel<uint32_t>, dim3(launch_blocks(Q)), dim3(kLaunchBlock), 0, st, flag, rank, Q, Q, sp.heads);
     if ((rc = check_launch(fn))) return rc;
     const int64_t groups = Q < M ? Q : M;                          // an upper bound: the kernel reads the number itself
-    const dim3 grid(assign_blocks(groups * lpr));
+    const dim3 grid(launch_blocks(groups * lpr));
     if (vec)
         hipLaunchKernelGGL(assign_reduce_kernel<float4a>, grid, dim3(kAssignBlock), 0, st, sp.keys[cur], sp.vals[cur], sp.heads, rank, Q,
                            (uint32_t)M, lpr, (int)reduce, reinterpret_cast<const float4a*>(values), reinterpret_cast<float4a*>(table));
@@ -319,14 +308,13 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
 int svoxt_leaf_corners(const int32_t* parent_depth, int64_t n_internal, int32_t N, const int64_t* leaf_node, int64_t Q,
                        float* corners, void* stream) {
     const char* fn = "svoxt_leaf_corners";
-    if (N < 2 || N > 16) return set_error(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
-    if (n_internal < 1 || (double)n_internal * N * N * N >= 2147483648.0)
-        return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be >= 1 with n_internal * N^3 < 2^31", fn);
+    int rc;
+    if ((rc = tree_extents_check(fn, n_internal, N, 0))) return rc;
     if (Q < 0 || Q >= (int64_t)kAssignBlock * 2147483647LL) return set_error(SVOXT_ERR_INVALID, "%s: bad leaf count", fn);
     if (Q == 0) return SVOXT_OK;
     if (parent_depth == nullptr || leaf_node == nullptr || corners == nullptr)
         return set_error(SVOXT_ERR_INVALID, "%s: parent_depth / leaf_node / corners is NULL", fn);
-    hipLaunchKernelGGL(leaf_corners_kernel, dim3(assign_blocks(Q)), dim3(kAssignBlock), 0, (hipStream_t)stream, parent_depth, n_internal, N,
+    hipLaunchKernelGGL(leaf_corners_kernel, dim3(launch_blocks(Q)), dim3(kAssignBlock), 0, (hipStream_t)stream, parent_depth, n_internal, N,
                        leaf_node, Q, corners);
     return check_launch(fn);
 }
@@ -341,7 +329,7 @@ int svoxt_snap_points(const svoxt_tree* tree, const int32_t* parent_depth, const
     if (Q == 0) return SVOXT_OK;
     if (parent_depth == nullptr || points == nullptr || corners == nullptr)
         return set_error(SVOXT_ERR_INVALID, "%s: parent_depth / points / corners is NULL", fn);
-    hipLaunchKernelGGL(tree->N == 2 ? snap_kernel<true> : snap_kernel<false>, dim3(assign_blocks(Q)), dim3(kAssignBlock), 0,
+    hipLaunchKernelGGL(tree->N == 2 ? snap_kernel<true> : snap_kernel<false>, dim3(launch_blocks(Q)), dim3(kAssignBlock), 0,
                        (hipStream_t)stream, to_dev(tree), parent_depth, tree->n_internal, points, Q, corners);
     return check_launch(fn);
 }

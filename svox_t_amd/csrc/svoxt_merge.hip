@@ -33,22 +33,21 @@
 // Every output word of merge is a function of the input alone.  The emit kernel is a sibling of prune_emit_kernel, not
 // shared with it: the two differ in every branch but the parent_depth row (a slot decision there, a node decision and
 // a third rank here), and prune's is measured as it stands (profiles/prune_timing.txt); what they share -- the scan,
-// the row gather, the layout rules -- is used, not copied (exclusive_scan, svoxt_prune_gather_rows).
+// the row gather, the parent_depth row, the ranked scatter and the totals behind the scans, the workspace carver and
+// the extents / workspace checks -- is used, not copied (exclusive_scan, svoxt_prune_gather_rows, svoxt_workspace.h).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
-constexpr int kMergeBlock = 256;
+constexpr int kMergeBlock = kLaunchBlock;
 enum { OP_MEAN = SVOXT_REDUCE_MEAN, OP_SUM = SVOXT_REDUCE_SUM, OP_MAX = SVOXT_REDUCE_MAX, OP_MIN = SVOXT_REDUCE_MIN };
 
 typedef float float4v __attribute__((ext_vector_type(4)));
-
-static size_t merge_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static unsigned merge_blocks(int64_t n) { return (unsigned)((n + kMergeBlock - 1) / kMergeBlock); }
 
 // ---------------------------------------------------------------------------------------------------------- frontier
 // workspace: [flag u32[n + 1]] [rank u32[n + 1]] [chunk sums]
@@ -59,12 +58,11 @@ struct FrontierSpace {
 
 static FrontierSpace frontier_carve(void* workspace, int64_t n) {
     FrontierSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t nn = merge_align(sizeof(uint32_t) * ((size_t)n + 1));
-    sp.flag = reinterpret_cast<uint32_t*>(w);
-    sp.rank = reinterpret_cast<uint32_t*>(w + nn);
-    sp.chunks = reinterpret_cast<uint32_t*>(w + 2 * nn);
-    sp.bytes = 2 * nn + merge_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)n + 1));
+    Carver w(workspace);
+    sp.flag = w.take<uint32_t>((size_t)n + 1);
+    sp.rank = w.take<uint32_t>((size_t)n + 1);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)n + 1));
+    sp.bytes = w.bytes();
     return sp;
 }
 
@@ -80,18 +78,6 @@ frontier_flag_kernel(const int32_t* __restrict__ child, int32_t n, int32_t n3, u
     const int32_t i = (int32_t)(blockIdx.x * kMergeBlock + threadIdx.x);
     if (i > n) return;
     flag[i] = (i > 0 && i < n && all_leaves(child, i, n3)) ? 1u : 0u;        // (flag[n] = 0: the scan reads n + 1 words)
-}
-
-__global__ void __launch_bounds__(64)
-frontier_count_kernel(const uint32_t* __restrict__ rank, int32_t n, int64_t* __restrict__ count) {
-    if (threadIdx.x == 0) count[0] = (int64_t)rank[n];
-}
-
-__global__ void __launch_bounds__(kMergeBlock)
-frontier_emit_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank, int32_t n, int64_t F,
-                     int64_t* __restrict__ frontier) {
-    const int32_t i = (int32_t)(blockIdx.x * kMergeBlock + threadIdx.x);
-    if (i < n && flag[i] != 0u && (int64_t)rank[i] < F) frontier[rank[i]] = (int64_t)i;
 }
 
 // ------------------------------------------------------------------------------------------------------------ reduce
@@ -301,20 +287,17 @@ struct MergeSpace {
 
 static MergeSpace merge_carve(void* workspace, int64_t n, int64_t M) {
     MergeSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t nn = merge_align(sizeof(uint32_t) * ((size_t)n + 1)), mm = merge_align(sizeof(uint32_t) * ((size_t)M + 1));
-    size_t o = 0;
-    sp.node_flag = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.new_flag = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.row_flag = reinterpret_cast<uint32_t*>(w + o); o += mm;
-    sp.clear_bytes = o;
-    sp.word = reinterpret_cast<int32_t*>(w + o); o += nn;
-    sp.node_rank = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.new_rank = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.row_rank = reinterpret_cast<uint32_t*>(w + o); o += mm;
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-    o += merge_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)(n > M ? n : M) + 1));
-    sp.bytes = o;
+    Carver w(workspace);
+    sp.node_flag = w.take<uint32_t>((size_t)n + 1);
+    sp.new_flag = w.take<uint32_t>((size_t)n + 1);
+    sp.row_flag = w.take<uint32_t>((size_t)M + 1);
+    sp.clear_bytes = w.bytes();
+    sp.word = w.take<int32_t>((size_t)n + 1);                  // (n words are used: the piece is as long as the flags')
+    sp.node_rank = w.take<uint32_t>((size_t)n + 1);
+    sp.new_rank = w.take<uint32_t>((size_t)n + 1);
+    sp.row_rank = w.take<uint32_t>((size_t)M + 1);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)(n > M ? n : M) + 1));
+    sp.bytes = w.bytes();
     return sp;
 }
 
@@ -346,17 +329,6 @@ merge_mark_kernel(MergeIn in, uint32_t* __restrict__ node_flag, uint32_t* __rest
     }
 }
 
-// counts[0] = nodes that remain, counts[1] = old feature rows carried, counts[2] = new rows
-__global__ void __launch_bounds__(64)
-merge_counts_kernel(const uint32_t* __restrict__ node_rank, const uint32_t* __restrict__ new_rank, int32_t n,
-                    const uint32_t* __restrict__ row_rank, uint32_t M, bool rows, int64_t* __restrict__ counts) {
-    if (threadIdx.x == 0) {
-        counts[0] = (int64_t)node_rank[n];
-        counts[1] = rows ? (int64_t)row_rank[M] : (int64_t)M;
-        counts[2] = (int64_t)new_rank[n];
-    }
-}
-
 __global__ void __launch_bounds__(kMergeBlock)
 merge_emit_kernel(MergeIn in, MergeSpace sp, int32_t new_n, int64_t carried, int32_t empty_index, int32_t* __restrict__ child_out,
                   int32_t* __restrict__ data_out, int32_t* __restrict__ pd_out) {
@@ -385,16 +357,7 @@ merge_emit_kernel(MergeIn in, MergeSpace sp, int32_t new_n, int64_t carried, int
     const int64_t at = (int64_t)id * in.n3 + k;
     child_out[at] = c;
     data_out[at] = d;
-    if (k == 0) {
-        const int32_t packed = in.parent_depth[2 * (int64_t)node];
-        int32_t p = packed;                                      // the root's row is carried
-        if (node != 0) {
-            const int32_t up = packed / in.n3;
-            p = (up >= 0 && up < in.n) ? (int32_t)sp.node_rank[up] * in.n3 + (packed - up * in.n3) : packed;
-        }
-        pd_out[2 * (int64_t)id] = p;
-        pd_out[2 * (int64_t)id + 1] = in.parent_depth[2 * (int64_t)node + 1];
-    }
+    if (k == 0) emit_renumbered_parent_depth(in.parent_depth, node, in.n, in.n3, sp.node_rank, id, pd_out);
 }
 
 // row_map[rank] = old row, new_nodes[rank] = merged node that gets a new row
@@ -407,19 +370,11 @@ merge_lists_kernel(MergeSpace sp, int32_t n, uint32_t M, bool rows, int64_t carr
 }
 
 // ------------------------------------------------------------------------------------------------- argument checks
-static int tables_check(const char* fn, int64_t n, int32_t N, int64_t M) {
-    if (N < 2 || N > 16) return set_error(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
-    if (n < 1 || (double)n * N * N * N >= 2147483648.0)
-        return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be >= 1 with n_internal * N^3 < 2^31", fn);
-    if (M < 0 || M > 0x7fffffff) return set_error(SVOXT_ERR_INVALID, "%s: the number of feature rows must be in [0, 2^31)", fn);
-    return SVOXT_OK;
-}
-
 static int reduce_check(const char* fn, const float* features, int64_t M, int32_t K, const int32_t* data, int64_t n, int32_t N,
                         const int64_t* nodes, int64_t F, const int32_t* cols, int32_t n_cols, int32_t op, int32_t empty_mode,
                         ReduceIn& in) {
     int rc;
-    if ((rc = tables_check(fn, n, N, M))) return rc;
+    if ((rc = tree_extents_check(fn, n, N, M))) return rc;
     if (K < 1) return set_error(SVOXT_ERR_INVALID, "%s: K must be >= 1", fn);
     if (F < 0 || n_cols < 0) return set_error(SVOXT_ERR_INVALID, "%s: F and n_cols must be >= 0", fn);
     if (op < OP_MEAN || op > OP_MIN) return set_error(SVOXT_ERR_INVALID, "%s: op must be one of SVOXT_REDUCE_MEAN / SUM / MAX / MIN", fn);
@@ -446,12 +401,12 @@ static int merge_check(const char* fn, const int32_t* child, const int32_t* data
                        int64_t M, const uint8_t* sel, int32_t compact_features, const void* workspace,
                        int64_t workspace_bytes, MergeIn& in) {
     int rc;
-    if ((rc = tables_check(fn, n, N, M))) return rc;
+    if ((rc = tree_extents_check(fn, n, N, M))) return rc;
     if (child == nullptr || data == nullptr || parent_depth == nullptr || sel == nullptr)
         return set_error(SVOXT_ERR_INVALID, "%s: child / data / parent_depth / selected is NULL", fn);
-    if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-    if (workspace_bytes < svoxt_merge_workspace_bytes(n, M))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_merge_workspace_bytes(n_internal, M)", fn);
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_merge_workspace_bytes(n, M),
+                              "svoxt_merge_workspace_bytes(n_internal, M)")))
+        return rc;
     in.child = child; in.data = data; in.parent_depth = parent_depth; in.sel = sel;
     in.n = (int32_t)n; in.n3 = N * N * N; in.M = (uint32_t)M; in.slots = (int32_t)(n * in.n3);
     in.rows = compact_features != 0;
@@ -473,16 +428,17 @@ int svoxt_frontier_count(const int32_t* child, int64_t n_internal, int32_t N, vo
                          int64_t* count, void* stream) {
     const char* fn = "svoxt_frontier_count";
     int rc;
-    if ((rc = tables_check(fn, n_internal, N, 0))) return rc;
+    if ((rc = tree_extents_check(fn, n_internal, N, 0))) return rc;
     if (child == nullptr || count == nullptr || workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: child / count / workspace is NULL", fn);
-    if (workspace_bytes < svoxt_frontier_workspace_bytes(n_internal))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_frontier_workspace_bytes(n_internal)", fn);
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_frontier_workspace_bytes(n_internal),
+                              "svoxt_frontier_workspace_bytes(n_internal)")))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const FrontierSpace sp = frontier_carve(workspace, n_internal);
-    hipLaunchKernelGGL(frontier_flag_kernel, dim3(merge_blocks(n_internal + 1)), dim3(kMergeBlock), 0, st, child, (int32_t)n_internal,
+    hipLaunchKernelGGL(frontier_flag_kernel, dim3(launch_blocks(n_internal + 1)), dim3(kMergeBlock), 0, st, child, (int32_t)n_internal,
                        N * N * N, sp.flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.flag, (size_t)n_internal + 1, sp.chunks, sp.rank, st, fn))) return rc;
-    hipLaunchKernelGGL(frontier_count_kernel, dim3(1), dim3(64), 0, st, sp.rank, (int32_t)n_internal, count);
+    hipLaunchKernelGGL(rank_totals_kernel<1>, dim3(1), dim3(64), 0, st, RankTotals<1>{{sp.rank}, {n_internal}}, count);
     return check_launch(fn);
 }
 
@@ -490,14 +446,15 @@ int svoxt_frontier_emit(const void* workspace, int64_t workspace_bytes, int64_t 
     const char* fn = "svoxt_frontier_emit";
     if (n_internal < 1 || n_internal > 0x7fffffff) return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be in [1, 2^31)", fn);
     if (F < 0 || F > n_internal - 1) return set_error(SVOXT_ERR_INVALID, "%s: F must be in [0, n_internal)", fn);
-    if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-    if (workspace_bytes < svoxt_frontier_workspace_bytes(n_internal))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_frontier_workspace_bytes(n_internal)", fn);
+    int rc;
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_frontier_workspace_bytes(n_internal),
+                              "svoxt_frontier_workspace_bytes(n_internal)")))
+        return rc;
     if (F == 0) return SVOXT_OK;
     if (frontier == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: frontier is NULL", fn);
     const FrontierSpace sp = frontier_carve(const_cast<void*>(workspace), n_internal);
-    hipLaunchKernelGGL(frontier_emit_kernel, dim3(merge_blocks(n_internal)), dim3(kMergeBlock), 0, (hipStream_t)stream, sp.flag, sp.rank,
-                       (int32_t)n_internal, F, frontier);
+    hipLaunchKernelGGL(scatter_ranked_kernel<int64_t>, dim3(launch_blocks(n_internal)), dim3(kLaunchBlock), 0, (hipStream_t)stream, sp.flag,
+                       sp.rank, n_internal, F, frontier);
     return check_launch(fn);
 }
 
@@ -511,8 +468,8 @@ int svoxt_frontier_reduce(const float* features, int64_t M, int32_t K, const int
     if (F == 0) return SVOXT_OK;
     if (out == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: out is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
-    if (rows8(in, out, true)) hipLaunchKernelGGL(reduce_rows8_kernel, dim3(merge_blocks(F * 8)), dim3(kMergeBlock), 0, st, in, out);
-    else hipLaunchKernelGGL(reduce_generic_kernel, dim3(merge_blocks(F * in.Kc)), dim3(kMergeBlock), 0, st, in, out);
+    if (rows8(in, out, true)) hipLaunchKernelGGL(reduce_rows8_kernel, dim3(launch_blocks(F * 8)), dim3(kMergeBlock), 0, st, in, out);
+    else hipLaunchKernelGGL(reduce_generic_kernel, dim3(launch_blocks(F * in.Kc)), dim3(kMergeBlock), 0, st, in, out);
     return check_launch(fn);
 }
 
@@ -531,7 +488,7 @@ int svoxt_frontier_reduce_bwd(const float* features, int64_t M, int32_t K, const
         if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
     }
     if (F == 0 || M == 0) return SVOXT_OK;
-    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(merge_blocks(F * in.Kc)), dim3(kMergeBlock), 0, st, in, grad_out, grad_features);
+    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(launch_blocks(F * in.Kc)), dim3(kMergeBlock), 0, st, in, grad_out, grad_features);
     return check_launch(fn);
 }
 
@@ -546,8 +503,8 @@ int svoxt_frontier_diam(const float* features, int64_t M, int32_t K, const int32
     if (F == 0) return SVOXT_OK;
     if (out == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: out is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
-    if (rows8(in, out, false)) hipLaunchKernelGGL(diam_rows8_kernel, dim3(merge_blocks(F * 8)), dim3(kMergeBlock), 0, st, in, scale, out);
-    else hipLaunchKernelGGL(diam_generic_kernel, dim3(merge_blocks(F)), dim3(kMergeBlock), 0, st, in, scale, out);
+    if (rows8(in, out, false)) hipLaunchKernelGGL(diam_rows8_kernel, dim3(launch_blocks(F * 8)), dim3(kMergeBlock), 0, st, in, scale, out);
+    else hipLaunchKernelGGL(diam_generic_kernel, dim3(launch_blocks(F)), dim3(kMergeBlock), 0, st, in, scale, out);
     return check_launch(fn);
 }
 
@@ -570,13 +527,15 @@ int svoxt_merge_count(const int32_t* child, const int32_t* data, const int32_t* 
     const MergeSpace sp = merge_carve(workspace, n_internal, M);
     const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
     if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(merge_mark_kernel, dim3(merge_blocks(n_internal)), dim3(kMergeBlock), 0, st, in, sp.node_flag, sp.new_flag,
+    hipLaunchKernelGGL(merge_mark_kernel, dim3(launch_blocks(n_internal)), dim3(kMergeBlock), 0, st, in, sp.node_flag, sp.new_flag,
                        sp.row_flag, sp.word);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.node_flag, (size_t)n_internal + 1, sp.chunks, sp.node_rank, st, fn)) ||
         (rc = exclusive_scan(sp.new_flag, (size_t)n_internal + 1, sp.chunks, sp.new_rank, st, fn)))
         return rc;
     if (in.rows && (rc = exclusive_scan(sp.row_flag, (size_t)M + 1, sp.chunks, sp.row_rank, st, fn))) return rc;
-    hipLaunchKernelGGL(merge_counts_kernel, dim3(1), dim3(64), 0, st, sp.node_rank, sp.new_rank, in.n, sp.row_rank, in.M, in.rows, counts);
+    // counts[0] = nodes that remain, counts[1] = old feature rows carried (all M where rows are not compacted), counts[2] = new rows
+    const RankTotals<3> totals = {{sp.node_rank, in.rows ? sp.row_rank : nullptr, sp.new_rank}, {n_internal, M, n_internal}};
+    hipLaunchKernelGGL(rank_totals_kernel<3>, dim3(1), dim3(64), 0, st, totals, counts);
     return check_launch(fn);
 }
 
@@ -606,10 +565,10 @@ int svoxt_merge_emit(const int32_t* child, const int32_t* data, const int32_t* p
     if (rows_added > 0 && new_row_nodes == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: new_row_nodes is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const MergeSpace sp = merge_carve(const_cast<void*>(workspace), n_internal, M);
-    hipLaunchKernelGGL(merge_emit_kernel, dim3(merge_blocks(in.slots)), dim3(kMergeBlock), 0, st, in, sp, (int32_t)new_n_internal, carried,
+    hipLaunchKernelGGL(merge_emit_kernel, dim3(launch_blocks(in.slots)), dim3(kMergeBlock), 0, st, in, sp, (int32_t)new_n_internal, carried,
                        empty_index, child_out, data_out, parent_depth_out);
     if ((in.rows && carried > 0) || rows_added > 0)
-        hipLaunchKernelGGL(merge_lists_kernel, dim3(merge_blocks((M > n_internal ? M : n_internal))), dim3(kMergeBlock), 0, st, sp, in.n,
+        hipLaunchKernelGGL(merge_lists_kernel, dim3(launch_blocks((M > n_internal ? M : n_internal))), dim3(kMergeBlock), 0, st, sp, in.n,
                            in.M, in.rows && carried > 0, carried, rows_added, row_map, new_row_nodes);
     return check_launch(fn);
 }

@@ -27,20 +27,13 @@
 
 #include "svoxt_host.h"
 #include "svoxt_sort.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
-constexpr int kNbBlock = 256;
-constexpr int kNbBlocksMax = 2048;           // the per-slot passes stride over the slots
+constexpr int kNbBlock = kLaunchBlock;       // (the per-slot passes stride over the slots: stride_blocks)
 constexpr int kTvBlock = 256;                // the loss tree's shape: part of the definition
 enum { TV_LOSS = SVOXT_TV_LOSS, TV_LOSS_GRAD = SVOXT_TV_LOSS_GRAD, TV_ACCUMULATE = SVOXT_TV_ACCUMULATE };
-
-static size_t nb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static unsigned nb_blocks(int64_t n) { return (unsigned)((n + kNbBlock - 1) / kNbBlock); }
-static unsigned nb_stride_blocks(int64_t n) {
-    const unsigned need = nb_blocks(n);
-    return need < (unsigned)kNbBlocksMax ? need : (unsigned)kNbBlocksMax;
-}
 
 // workspace of leaf_neighbors: [flag u32[slots + 1]] [rank u32[slots + 1]] [chunk sums]
 struct NbSpace {
@@ -49,14 +42,11 @@ struct NbSpace {
 };
 static NbSpace nb_carve(void* workspace, int64_t slots) {
     NbSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t ss = nb_align(sizeof(uint32_t) * ((size_t)slots + 1));
-    size_t o = 0;
-    sp.flag = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.rank = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-    o += nb_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)slots + 1));
-    sp.bytes = o;
+    Carver w(workspace);
+    sp.flag = w.take<uint32_t>((size_t)slots + 1);
+    sp.rank = w.take<uint32_t>((size_t)slots + 1);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)slots + 1));
+    sp.bytes = w.bytes();
     return sp;
 }
 
@@ -69,17 +59,16 @@ struct PlanSpace {
     size_t bytes;
 };
 static PlanSpace plan_carve(void* workspace, int64_t E) {
-    PlanSpace sp = {};
-    char* w = static_cast<char*>(workspace);
-    const size_t qq = nb_align(sizeof(uint32_t) * (2 * (size_t)E)), cc = (size_t)256 * sort_blocks(2 * (uint64_t)E);
-    size_t o = 0;
-    for (int i = 0; i < 2; ++i) { sp.keys[i] = reinterpret_cast<uint32_t*>(w + o); o += qq; }
-    for (int i = 0; i < 2; ++i) { sp.vals[i] = reinterpret_cast<uint32_t*>(w + o); o += qq; }
-    sp.counts = reinterpret_cast<uint32_t*>(w + o); o += nb_align(sizeof(uint32_t) * cc);
-    sp.starts = reinterpret_cast<uint32_t*>(w + o); o += nb_align(sizeof(uint32_t) * cc);
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o); o += nb_align(sizeof(uint32_t) * exclusive_scan_chunks(cc));
-    sp.list = reinterpret_cast<uint32_t*>(w + o); o += nb_align(sizeof(uint32_t) * (size_t)E);
-    sp.bytes = o + 256;
+    PlanSpace sp;
+    Carver w(workspace);
+    const size_t cc = (size_t)256 * sort_blocks(2 * (uint64_t)E);
+    for (int i = 0; i < 2; ++i) sp.keys[i] = w.take<uint32_t>(2 * (size_t)E);
+    for (int i = 0; i < 2; ++i) sp.vals[i] = w.take<uint32_t>(2 * (size_t)E);
+    sp.counts = w.take<uint32_t>(cc);
+    sp.starts = w.take<uint32_t>(cc);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks(cc));
+    sp.list = w.take<uint32_t>((size_t)E);
+    sp.bytes = w.bytes() + 256;
     return sp;
 }
 
@@ -167,11 +156,6 @@ tv_mark_kernel(const int32_t* __restrict__ neighbors, const int32_t* __restrict_
                int64_t M, uint32_t* __restrict__ flag) {
     for (int64_t e = (int64_t)blockIdx.x * kNbBlock + threadIdx.x; e <= 6 * L; e += (int64_t)gridDim.x * kNbBlock)
         flag[e] = (e < 6 * L && tv_is_edge(neighbors, depths, rows, L, M, e)) ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(64)
-tv_count_kernel(const uint32_t* __restrict__ rank, int64_t L6, int64_t* __restrict__ count) {
-    if (threadIdx.x == 0) count[0] = (int64_t)rank[L6];
 }
 
 // edge number r (slot e) -> incidences 2 r (row_i's) and 2 r + 1 (row_j's): their keys, and the slot for the emit
@@ -307,14 +291,6 @@ static void tv_launch(unsigned blocks, hipStream_t st, const float* f, int64_t M
                        divisor, scale, partials, G);
 }
 
-// The extents of the tree tables.  Nothing here touches HIP.
-static int nb_check_tables(const char* fn, int64_t n, int32_t N) {
-    if (N < 2 || N > 16) return set_error(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
-    if (n < 1 || (double)n * N * N * N >= 2147483648.0)
-        return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be >= 1 with n_internal * N^3 < 2^31", fn);
-    return SVOXT_OK;
-}
-
 static int plan_check(const char* fn, const int32_t* neighbors, const int32_t* depths, const int64_t* rows, int64_t L, int64_t M) {
     if (L < 0 || 12 * (double)L >= 2147483648.0) return set_error(SVOXT_ERR_INVALID, "%s: the number of leaves must be >= 0 with 12 * L < 2^31", fn);
     if (M < 0 || M > 0x7fffffff) return set_error(SVOXT_ERR_INVALID, "%s: the number of feature rows must be in [0, 2^31)", fn);
@@ -338,7 +314,7 @@ int svoxt_leaf_neighbors(const int32_t* child, const int32_t* parent_depth, int6
                          int32_t* neighbors, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "svoxt_leaf_neighbors";
     int rc;
-    if ((rc = nb_check_tables(fn, n_internal, N))) return rc;
+    if ((rc = tree_extents_check(fn, n_internal, N, 0))) return rc;
     double side = N;
     for (int32_t l = 0; l < max_depth && side < 4294967296.0; ++l) side *= N;
     if (max_depth < 0 || side >= 2147483648.0)
@@ -348,15 +324,15 @@ int svoxt_leaf_neighbors(const int32_t* child, const int32_t* parent_depth, int6
         return set_error(SVOXT_ERR_INVALID, "%s: the number of leaves must be in [0, n_internal * N^3] with 12 * L < 2^31", fn);
     if (child == nullptr || parent_depth == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: child / parent_depth is NULL", fn);
     if (L > 0 && neighbors == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: neighbors is NULL", fn);
-    if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-    if (workspace_bytes < svoxt_neighbors_workspace_bytes(n_internal, N))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_neighbors_workspace_bytes(n_internal, N)", fn);
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_neighbors_workspace_bytes(n_internal, N),
+                              "svoxt_neighbors_workspace_bytes(n_internal, N)")))
+        return rc;
     if (L == 0) return SVOXT_OK;
     hipStream_t st = (hipStream_t)stream;
     const NbSpace sp = nb_carve(workspace, slots);
-    hipLaunchKernelGGL(leaf_flag_kernel, dim3(nb_stride_blocks(slots + 1)), dim3(kNbBlock), 0, st, child, (int32_t)slots, sp.flag);
+    hipLaunchKernelGGL(leaf_flag_kernel, dim3(stride_blocks(slots + 1)), dim3(kNbBlock), 0, st, child, (int32_t)slots, sp.flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.flag, (size_t)slots + 1, sp.chunks, sp.rank, st, fn))) return rc;
-    hipLaunchKernelGGL(leaf_neighbors_kernel, dim3(nb_stride_blocks(slots)), dim3(kNbBlock), 0, st, child, parent_depth,
+    hipLaunchKernelGGL(leaf_neighbors_kernel, dim3(stride_blocks(slots)), dim3(kNbBlock), 0, st, child, parent_depth,
                        (int32_t)n_internal, N, N * N * N, (int32_t)slots, max_depth, sp.rank, L, neighbors);
     return check_launch(fn);
 }
@@ -377,9 +353,9 @@ int svoxt_tv_plan_count(const int32_t* neighbors, const int32_t* depths, const i
     if (count == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: count is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const NbSpace sp = marks_carve(marks, L);
-    hipLaunchKernelGGL(tv_mark_kernel, dim3(nb_stride_blocks(6 * L + 1)), dim3(kNbBlock), 0, st, neighbors, depths, rows, L, M, sp.flag);
+    hipLaunchKernelGGL(tv_mark_kernel, dim3(stride_blocks(6 * L + 1)), dim3(kNbBlock), 0, st, neighbors, depths, rows, L, M, sp.flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.flag, (size_t)(6 * L) + 1, sp.chunks, sp.rank, st, fn))) return rc;
-    hipLaunchKernelGGL(tv_count_kernel, dim3(1), dim3(64), 0, st, sp.rank, 6 * L, count);
+    hipLaunchKernelGGL(rank_totals_kernel<1>, dim3(1), dim3(64), 0, st, RankTotals<1>{{sp.rank}, {6 * L}}, count);
     return check_launch(fn);
 }
 
@@ -397,9 +373,8 @@ int svoxt_tv_plan_emit(const int32_t* neighbors, const int32_t* depths, const in
     if (row_ptr == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: row_ptr is NULL", fn);
     if (E > 0) {
         if (other == nullptr || meta == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: other / meta is NULL", fn);
-        if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-        if (workspace_bytes < svoxt_tv_plan_workspace_bytes(L, E))
-            return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_tv_plan_workspace_bytes(L, E)", fn);
+        if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_tv_plan_workspace_bytes(L, E), "svoxt_tv_plan_workspace_bytes(L, E)")))
+            return rc;
     }
     hipStream_t st = (hipStream_t)stream;
     if (E == 0) {
@@ -409,7 +384,7 @@ int svoxt_tv_plan_emit(const int32_t* neighbors, const int32_t* depths, const in
     }
     const NbSpace mk = marks_carve(const_cast<void*>(marks), L);
     const PlanSpace sp = plan_carve(workspace, E);
-    hipLaunchKernelGGL(tv_fill_kernel, dim3(nb_stride_blocks(6 * L)), dim3(kNbBlock), 0, st, neighbors, rows, L, mk.flag, mk.rank, E,
+    hipLaunchKernelGGL(tv_fill_kernel, dim3(stride_blocks(6 * L)), dim3(kNbBlock), 0, st, neighbors, rows, L, mk.flag, mk.rank, E,
                        sp.keys[0], sp.list);
     if ((rc = check_launch(fn))) return rc;
     // the keys are rows in [0, M): sort over the bits of M - 1, in passes of at most 8 bits, all of (nearly) the same width
@@ -424,15 +399,15 @@ int svoxt_tv_plan_emit(const int32_t* neighbors, const int32_t* depths, const in
             return rc;
         cur ^= 1;
     }
-    hipLaunchKernelGGL(tv_emit_kernel, dim3(nb_blocks(2 * E)), dim3(kNbBlock), 0, st, neighbors, depths, rows, L, M, sp.vals[cur], sp.list,
+    hipLaunchKernelGGL(tv_emit_kernel, dim3(launch_blocks(2 * E)), dim3(kNbBlock), 0, st, neighbors, depths, rows, L, M, sp.vals[cur], sp.list,
                        E, other, meta);
-    hipLaunchKernelGGL(tv_row_ptr_kernel, dim3(nb_blocks(M + 1)), dim3(kNbBlock), 0, st, sp.keys[cur], 2 * E, M, row_ptr);
+    hipLaunchKernelGGL(tv_row_ptr_kernel, dim3(launch_blocks(M + 1)), dim3(kNbBlock), 0, st, sp.keys[cur], 2 * E, M, row_ptr);
     return check_launch(fn);
 }
 
 int64_t svoxt_tv_workspace_bytes(int64_t M, int32_t n_cols) {
     if (M < 0 || M > 0x7fffffff || n_cols < 1 || (double)M * n_cols >= 274877906944.0) return -1;
-    return (int64_t)nb_align(sizeof(float) * (size_t)((M * n_cols + kTvBlock - 1) / kTvBlock)) + 256;
+    return (int64_t)align256(sizeof(float) * (size_t)((M * n_cols + kTvBlock - 1) / kTvBlock)) + 256;
 }
 
 int svoxt_tv_rows(const float* features, int64_t M, int32_t K, const int32_t* row_ptr, const int32_t* other, const uint8_t* meta,
@@ -458,9 +433,9 @@ int svoxt_tv_rows(const float* features, int64_t M, int32_t K, const int32_t* ro
         if (features == nullptr || row_ptr == nullptr || other == nullptr || meta == nullptr)
             return set_error(SVOXT_ERR_INVALID, "%s: features / row_ptr / other / meta is NULL", fn);
         if (wants_loss) {
-            if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-            if (workspace_bytes < svoxt_tv_workspace_bytes(M, Kc))
-                return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_tv_workspace_bytes(M, columns)", fn);
+            int rc;
+            if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_tv_workspace_bytes(M, Kc), "svoxt_tv_workspace_bytes(M, columns)")))
+                return rc;
         }
     }
     hipStream_t st = (hipStream_t)stream;

@@ -31,6 +31,7 @@
 
 #include "svoxt_host.h"
 #include "svoxt_sort.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
@@ -261,8 +262,6 @@ p2v_backward_kernel(const float* __restrict__ gout, const float* __restrict__ pt
     }
 }
 
-static size_t p2v_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Argument checks shared by the three entry points; fills the geometry.  Nothing here touches HIP.
 static int p2v_setup(int64_t P, int32_t F, const float* corner, const float* size, int32_t n, float kr, float cr,
                      P2VGeom& g, const char* fn) {
@@ -303,14 +302,17 @@ static int p2v_setup(int64_t P, int32_t F, const float* corner, const float* siz
     return SVOXT_OK;
 }
 
-struct P2VPlan {
+struct P2VSpace {
     uint32_t nblocks, bits;                  // sort workgroups, key bits
     size_t max_items, max_slots, scan_words;
-    size_t off_keys[2], off_vals[2], off_rec, off_win, off_counts, off_bins, off_items, off_item_tile, off_sort_counts,
-           off_sort_starts, off_chunks, off_partial, bytes;
+    uint32_t *keys[2], *vals[2], *counts, *bins, *items, *item_tile, *sort_counts, *sort_starts, *chunks;
+    float4* rec;
+    uint2* win;
+    float* partial;
+    size_t bytes;
 };
 
-static bool p2v_plan(int64_t P, const P2VGeom& g, P2VPlan& p) {
+static bool p2v_carve(void* workspace, int64_t P, const P2VGeom& g, P2VSpace& p) {
     // candidates over all tiles: every point at most once per tile of its apron.  One tile has at most P of them (< 2^31);
     // what has to fit 32 bits is the number of work items, tiles + candidates / kP2VChunk (checked below)
     const double cand = (double)P * (g.ax + 1) * (g.ay + 1) * (g.az + 1);
@@ -322,21 +324,20 @@ static bool p2v_plan(int64_t P, const P2VGeom& g, P2VPlan& p) {
     if ((double)g.nt + cand / kP2VChunk + 2.0 >= 4294967296.0) return false;
     const size_t tiles = (size_t)g.nt + 1, sortw = (size_t)256 * p.nblocks;
     p.scan_words = exclusive_scan_chunks(tiles > sortw ? tiles : sortw);
-    const size_t u = sizeof(uint32_t), n = (size_t)P;
-    size_t o = 0;
-    auto take = [&](size_t b) { const size_t at = o; o += p2v_align(b); return at; };
-    for (int b = 0; b < 2; ++b) { p.off_keys[b] = take(u * n); p.off_vals[b] = take(u * n); }
-    p.off_rec = take(sizeof(float4) * n);
-    p.off_win = take(sizeof(uint2) * n);
-    p.off_counts = take(u * tiles);
-    p.off_bins = take(u * tiles);
-    p.off_items = take(u * tiles);
-    p.off_item_tile = take(u * p.max_items);
-    p.off_sort_counts = take(u * sortw);
-    p.off_sort_starts = take(u * sortw);
-    p.off_chunks = take(u * p.scan_words);
-    p.off_partial = take(sizeof(float) * 64 * p.max_slots);
-    p.bytes = o;
+    const size_t n = (size_t)P;
+    Carver w(workspace);
+    for (int b = 0; b < 2; ++b) { p.keys[b] = w.take<uint32_t>(n); p.vals[b] = w.take<uint32_t>(n); }
+    p.rec = w.take<float4>(n);
+    p.win = w.take<uint2>(n);
+    p.counts = w.take<uint32_t>(tiles);
+    p.bins = w.take<uint32_t>(tiles);
+    p.items = w.take<uint32_t>(tiles);
+    p.item_tile = w.take<uint32_t>(p.max_items);
+    p.sort_counts = w.take<uint32_t>(sortw);
+    p.sort_starts = w.take<uint32_t>(sortw);
+    p.chunks = w.take<uint32_t>(p.scan_words);
+    p.partial = w.take<float>(64 * p.max_slots);
+    p.bytes = w.bytes();
     return true;
 }
 
@@ -349,10 +350,10 @@ extern "C" {
 int64_t svoxt_p2v_workspace_bytes(int64_t P, int32_t n_voxels, const float* volume_corner, const float* volume_size,
                                   float conv_radius) {
     P2VGeom g;
-    P2VPlan p;
+    P2VSpace p;
     // the same setup and plan as the forward's (the apron's rounding bound depends on the corner)
     if (p2v_setup(P, 1, volume_corner, volume_size, n_voxels, 1.f, conv_radius, g, "svoxt_p2v_workspace_bytes") != SVOXT_OK) return -1;
-    if (!p2v_plan(P, g, p)) return -1;
+    if (!p2v_carve(nullptr, P, g, p)) return -1;
     return (int64_t)p.bytes;
 }
 
@@ -363,8 +364,8 @@ int svoxt_p2v_fwd(const float* points, const float* point_features, int64_t P, i
     P2VGeom g;
     int rc;
     if ((rc = p2v_setup(P, F, volume_corner, volume_size, n_voxels, kernel_radius, conv_radius, g, fn))) return rc;
-    P2VPlan p;
-    if (!p2v_plan(P, g, p)) return set_error(SVOXT_ERR_UNSUPPORTED, "%s: conv_radius spans too many tiles for this many points", fn);
+    P2VSpace p;
+    if (!p2v_carve(workspace, P, g, p)) return set_error(SVOXT_ERR_UNSUPPORTED, "%s: conv_radius spans too many tiles for this many points", fn);
     if (P > 0 && workspace_bytes < (int64_t)p.bytes) return set_error(SVOXT_ERR_INVALID, "%s: workspace too small", fn);
     if (P > 0 && workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
     if (voxels == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: voxels is NULL", fn);
@@ -375,39 +376,30 @@ int svoxt_p2v_fwd(const float* points, const float* point_features, int64_t P, i
         const hipError_t e = hipMemsetAsync(voxels, 0, sizeof(float) * nvox, st);
         return e == hipSuccess ? SVOXT_OK : set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
     }
-    char* w = static_cast<char*>(workspace);
-    auto U = [&](size_t off) { return reinterpret_cast<uint32_t*>(w + off); };
-    uint32_t* keys[2] = {U(p.off_keys[0]), U(p.off_keys[1])};
-    uint32_t* vals[2] = {U(p.off_vals[0]), U(p.off_vals[1])};
-    uint32_t *counts = U(p.off_counts), *bins = U(p.off_bins), *items = U(p.off_items), *item_tile = U(p.off_item_tile);
-    uint32_t *sort_counts = U(p.off_sort_counts), *sort_starts = U(p.off_sort_starts), *chunks = U(p.off_chunks);
-    float4* rec = reinterpret_cast<float4*>(w + p.off_rec);
-    uint2* win = reinterpret_cast<uint2*>(w + p.off_win);
-    float* partial = reinterpret_cast<float*>(w + p.off_partial);
     const uint32_t n = (uint32_t)P, tiles = g.nt + 1;
     const unsigned nb = (n + kP2VBlock - 1) / kP2VBlock, waves = kP2VBlock / 64;
 
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * tiles, st);
+    hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(uint32_t) * tiles, st);
     if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(p2v_key_kernel, dim3(nb), dim3(kP2VBlock), 0, st, points, n, g, keys[0], counts);
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(counts, tiles, chunks, bins, st, fn))) return rc;
+    hipLaunchKernelGGL(p2v_key_kernel, dim3(nb), dim3(kP2VBlock), 0, st, points, n, g, p.keys[0], p.counts);
+    if ((rc = check_launch(fn)) || (rc = exclusive_scan(p.counts, tiles, p.chunks, p.bins, st, fn))) return rc;
     // stable LSD radix sort of (key, point index)
     int cur = 0;
     for (uint32_t shift = 0; shift < p.bits; shift += 8) {
         const int bits = (int)(p.bits - shift < 8 ? p.bits - shift : 8);
-        if ((rc = sort_pass(keys[cur], shift == 0 ? nullptr : vals[cur], n, (int)shift, bits, sort_counts, sort_starts, chunks,
-                            keys[cur ^ 1], vals[cur ^ 1], st, fn))) return rc;
+        if ((rc = sort_pass(p.keys[cur], shift == 0 ? nullptr : p.vals[cur], n, (int)shift, bits, p.sort_counts, p.sort_starts, p.chunks,
+                            p.keys[cur ^ 1], p.vals[cur ^ 1], st, fn))) return rc;
         cur ^= 1;
     }
-    const uint32_t* sorted = vals[cur];
-    hipLaunchKernelGGL(p2v_records_kernel, dim3(nb), dim3(kP2VBlock), 0, st, points, point_features, (int)F, sorted, bins, g, rec, win);
-    hipLaunchKernelGGL(p2v_tile_items_kernel, dim3((tiles + kP2VBlock - 1) / kP2VBlock), dim3(kP2VBlock), 0, st, bins, g, counts);
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(counts, tiles, chunks, items, st, fn))) return rc;
-    hipLaunchKernelGGL(p2v_item_list_kernel, dim3((g.nt + kP2VBlock - 1) / kP2VBlock), dim3(kP2VBlock), 0, st, items, g.nt, item_tile);
+    const uint32_t* sorted = p.vals[cur];
+    hipLaunchKernelGGL(p2v_records_kernel, dim3(nb), dim3(kP2VBlock), 0, st, points, point_features, (int)F, sorted, p.bins, g, p.rec, p.win);
+    hipLaunchKernelGGL(p2v_tile_items_kernel, dim3((tiles + kP2VBlock - 1) / kP2VBlock), dim3(kP2VBlock), 0, st, p.bins, g, p.counts);
+    if ((rc = check_launch(fn)) || (rc = exclusive_scan(p.counts, tiles, p.chunks, p.items, st, fn))) return rc;
+    hipLaunchKernelGGL(p2v_item_list_kernel, dim3((g.nt + kP2VBlock - 1) / kP2VBlock), dim3(kP2VBlock), 0, st, p.items, g.nt, p.item_tile);
     const size_t gather_blocks = (p.max_items + waves - 1) / waves;
-    hipLaunchKernelGGL(p2v_gather_kernel, dim3((unsigned)(gather_blocks < kGatherBlocksMax ? gather_blocks : kGatherBlocksMax)), dim3(kP2VBlock), 0, st, rec, win, bins,
-                       items, item_tile, g, voxels, partial);
-    hipLaunchKernelGGL(p2v_reduce_kernel, dim3((g.nt + waves - 1) / waves), dim3(kP2VBlock), 0, st, items, g, voxels, partial);
+    hipLaunchKernelGGL(p2v_gather_kernel, dim3((unsigned)(gather_blocks < kGatherBlocksMax ? gather_blocks : kGatherBlocksMax)), dim3(kP2VBlock), 0, st, p.rec, p.win, p.bins,
+                       p.items, p.item_tile, g, voxels, p.partial);
+    hipLaunchKernelGGL(p2v_reduce_kernel, dim3((g.nt + waves - 1) / waves), dim3(kP2VBlock), 0, st, p.items, g, voxels, p.partial);
     if ((rc = check_launch(fn))) return rc;
     if (order != nullptr) {
         e = hipMemcpyAsync(order, sorted, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st);

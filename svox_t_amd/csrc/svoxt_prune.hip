@@ -18,6 +18,7 @@
 //   emit     a thread per slot of a flagged node writes its child / data word at the node's new place (a child whose
 //            node is gone becomes an empty leaf; inner slots get the empty index instead of their stale word); the
 //            first slot's thread writes the parent_depth row; a thread per flagged feature row writes row_map
+//            (scatter_ranked_kernel, svoxt_workspace.h)
 //   gather   new feature table = old rows in row_map's order, 16 bytes a thread (svoxt_prune_gather_rows)
 // Every output word is a function of the input alone: two runs give the same bytes.
 // HBM traffic: child, data and the decision read twice (mark, emit), parent_depth's first column chased by the walks
@@ -31,19 +32,18 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
-constexpr int kPruneBlock = 256;
-constexpr int kMarkBlocksMax = 2048;     // the mark pass strides over the slots: a count of dropped leaves per workgroup, no atomics
+constexpr int kPruneBlock = kLaunchBlock;
+constexpr int kMarkBlocksMax = kStrideBlocksMax;   // the mark pass strides over the slots: a count of dropped leaves per workgroup, no atomics
 
 struct PruneIn {
     const int32_t* child;
     const int32_t* data;
     const int32_t* parent_depth;
-    const uint8_t* keep;                 // one of keep / weights
-    const float* weights;
-    float threshold;
+    SlotDecision kept;                   // one of mask / weights (prune_check refuses neither)
     int32_t n;                           // internal nodes
     int32_t n3;                          // slots per node
     uint32_t M;                          // feature rows: unsigned data >= M is an empty leaf
@@ -58,27 +58,18 @@ struct PruneSpace {
     size_t clear_bytes, bytes;
 };
 
-static size_t prune_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static PruneSpace prune_carve(void* workspace, int64_t n, int64_t M) {
     PruneSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t nn = prune_align(sizeof(uint32_t) * ((size_t)n + 1)), mm = prune_align(sizeof(uint32_t) * ((size_t)M + 1));
-    size_t o = 0;
-    sp.dropped = reinterpret_cast<uint32_t*>(w + o); o += prune_align(sizeof(uint32_t) * kMarkBlocksMax);
-    sp.node_flag = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.row_flag = reinterpret_cast<uint32_t*>(w + o); o += mm;
-    sp.clear_bytes = o;
-    sp.node_rank = reinterpret_cast<uint32_t*>(w + o); o += nn;
-    sp.row_rank = reinterpret_cast<uint32_t*>(w + o); o += mm;
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-    o += prune_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)(n > M ? n : M) + 1));
-    sp.bytes = o;
+    Carver w(workspace);
+    sp.dropped = w.take<uint32_t>(kMarkBlocksMax);
+    sp.node_flag = w.take<uint32_t>((size_t)n + 1);
+    sp.row_flag = w.take<uint32_t>((size_t)M + 1);
+    sp.clear_bytes = w.bytes();
+    sp.node_rank = w.take<uint32_t>((size_t)n + 1);
+    sp.row_rank = w.take<uint32_t>((size_t)M + 1);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)(n > M ? n : M) + 1));
+    sp.bytes = w.bytes();
     return sp;
-}
-
-__device__ __forceinline__ bool prune_kept(const PruneIn& in, int32_t s) {
-    return in.keep != nullptr ? in.keep[s] != 0 : in.weights[s] >= in.threshold;      // (a NaN weight: not kept)
 }
 
 __global__ void __launch_bounds__(kPruneBlock)
@@ -93,7 +84,7 @@ prune_mark_kernel(PruneIn in, bool collapse, bool rows, uint32_t* __restrict__ n
         if (in.child[s] != 0) continue;
         const uint32_t d = (uint32_t)in.data[s];
         if (d >= in.M) continue;
-        if (!prune_kept(in, s)) { ++drops; continue; }
+        if (!in.kept(s)) { ++drops; continue; }
         if (rows) row_flag[d] = 1u;
         if (!collapse) continue;
         // at most one step per level: a flagged node ends the walk, and every step flags one
@@ -147,28 +138,12 @@ prune_emit_kernel(PruneIn in, bool rows, const uint32_t* __restrict__ node_flag,
     } else {
         const int32_t old = in.data[s];
         if ((uint32_t)old >= in.M) d = old;                      // an empty leaf keeps its word
-        else if (prune_kept(in, s)) d = rows ? (int32_t)row_rank[(uint32_t)old] : old;
+        else if (in.kept(s)) d = rows ? (int32_t)row_rank[(uint32_t)old] : old;
     }
     const int64_t at = (int64_t)id * in.n3 + k;
     child_out[at] = c;
     data_out[at] = d;
-    if (k == 0) {
-        const int32_t packed = in.parent_depth[2 * (int64_t)node];
-        int32_t p = packed;                                      // the root's row is carried
-        if (node != 0) {
-            const int32_t up = packed / in.n3;
-            p = (up >= 0 && up < in.n) ? (int32_t)node_rank[up] * in.n3 + (packed - up * in.n3) : packed;
-        }
-        pd_out[2 * (int64_t)id] = p;
-        pd_out[2 * (int64_t)id + 1] = in.parent_depth[2 * (int64_t)node + 1];
-    }
-}
-
-__global__ void __launch_bounds__(kPruneBlock)
-prune_row_map_kernel(const uint32_t* __restrict__ row_flag, const uint32_t* __restrict__ row_rank, uint32_t M, int64_t new_M,
-                     int64_t* __restrict__ row_map) {
-    const uint32_t r = blockIdx.x * kPruneBlock + threadIdx.x;
-    if (r < M && row_flag[r] != 0u && (int64_t)row_rank[r] < new_M) row_map[row_rank[r]] = (int64_t)r;
+    if (k == 0) emit_renumbered_parent_depth(in.parent_depth, node, in.n, in.n3, node_rank, id, pd_out);
 }
 
 // dst[i, :] = src[row_map[i], :], a thread per V floats of a row (V = 4: 16-byte loads and stores; a 128-byte row is 8 lanes)
@@ -190,24 +165,20 @@ prune_gather_rows_kernel(const float* __restrict__ src, const int64_t* __restric
 static int prune_check(const char* fn, const int32_t* child, const int32_t* data, const int32_t* parent_depth, int64_t n, int32_t N,
                        int64_t M, const uint8_t* keep, const float* weights, float threshold, const void* workspace,
                        int64_t workspace_bytes, PruneIn& in) {
-    if (N < 2 || N > 16) return set_error(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
-    if (n < 1 || (double)n * N * N * N >= 2147483648.0)
-        return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be >= 1 with n_internal * N^3 < 2^31", fn);
-    if (M < 0 || M > 0x7fffffff) return set_error(SVOXT_ERR_INVALID, "%s: the number of feature rows must be in [0, 2^31)", fn);
+    int rc;
+    if ((rc = tree_extents_check(fn, n, N, M))) return rc;
     if (child == nullptr || data == nullptr || parent_depth == nullptr)
         return set_error(SVOXT_ERR_INVALID, "%s: child / data / parent_depth is NULL", fn);
     if ((keep == nullptr) == (weights == nullptr)) return set_error(SVOXT_ERR_INVALID, "%s: exactly one of keep / weights must be given", fn);
     if (weights != nullptr && threshold != threshold) return set_error(SVOXT_ERR_INVALID, "%s: threshold is NaN", fn);
-    if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-    if (workspace_bytes < svoxt_prune_workspace_bytes(n, M))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_prune_workspace_bytes(n_internal, M)", fn);
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_prune_workspace_bytes(n, M),
+                              "svoxt_prune_workspace_bytes(n_internal, M)")))
+        return rc;
     in.child = child; in.data = data; in.parent_depth = parent_depth;
-    in.keep = keep; in.weights = weights; in.threshold = threshold;
+    in.kept = SlotDecision{keep, weights, threshold};
     in.n = (int32_t)n; in.n3 = N * N * N; in.M = (uint32_t)M; in.slots = (int32_t)(n * in.n3);
     return SVOXT_OK;
 }
-
-static unsigned prune_blocks(int64_t n) { return (unsigned)((n + kPruneBlock - 1) / kPruneBlock); }
 
 }  // namespace svoxt
 
@@ -234,7 +205,7 @@ int svoxt_prune_count(const int32_t* child, const int32_t* data, const int32_t* 
     const bool rows = compact_features != 0;
     const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
     if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    const unsigned need = prune_blocks(in.slots), mark_blocks = need < (unsigned)kMarkBlocksMax ? need : (unsigned)kMarkBlocksMax;
+    const unsigned mark_blocks = stride_blocks(in.slots);
     hipLaunchKernelGGL(prune_mark_kernel, dim3(mark_blocks), dim3(kPruneBlock), 0, st, in, collapse != 0, rows,
                        sp.node_flag, sp.row_flag, sp.dropped);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.node_flag, (size_t)n_internal + 1, sp.chunks, sp.node_rank, st, fn))) return rc;
@@ -264,11 +235,11 @@ int svoxt_prune_emit(const int32_t* child, const int32_t* data, const int32_t* p
     if (rows && new_M > 0 && row_map == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: row_map is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const PruneSpace sp = prune_carve(const_cast<void*>(workspace), n_internal, M);
-    hipLaunchKernelGGL(prune_emit_kernel, dim3(prune_blocks(in.slots)), dim3(kPruneBlock), 0, st, in, rows, sp.node_flag, sp.node_rank,
+    hipLaunchKernelGGL(prune_emit_kernel, dim3(launch_blocks(in.slots)), dim3(kPruneBlock), 0, st, in, rows, sp.node_flag, sp.node_rank,
                        sp.row_rank, (int32_t)new_n_internal, empty_index, child_out, data_out, parent_depth_out);
     if (rows && new_M > 0)
-        hipLaunchKernelGGL(prune_row_map_kernel, dim3(prune_blocks(M)), dim3(kPruneBlock), 0, st, sp.row_flag, sp.row_rank, in.M, new_M,
-                           row_map);
+        hipLaunchKernelGGL(scatter_ranked_kernel<int64_t>, dim3(launch_blocks(M)), dim3(kLaunchBlock), 0, st, sp.row_flag, sp.row_rank, M,
+                           new_M, row_map);
     return check_launch(fn);
 }
 
@@ -282,7 +253,7 @@ int svoxt_prune_gather_rows(const float* src, int64_t src_rows, const int64_t* r
     const bool wide = cols % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 16 == 0;
     const int per_row = wide ? cols / 4 : cols;
     if ((double)n * per_row >= 2147483648.0 * kPruneBlock) return set_error(SVOXT_ERR_INVALID, "%s: too many rows for one launch (2^39 threads)", fn);
-    const unsigned nb = prune_blocks(n * per_row);
+    const unsigned nb = launch_blocks(n * per_row);
     if (wide) hipLaunchKernelGGL(prune_gather_rows_kernel<4>, dim3(nb), dim3(kPruneBlock), 0, st, src, row_map, dst, n, per_row, src_rows);
     else hipLaunchKernelGGL(prune_gather_rows_kernel<1>, dim3(nb), dim3(kPruneBlock), 0, st, src, row_map, dst, n, per_row, src_rows);
     return check_launch(fn);

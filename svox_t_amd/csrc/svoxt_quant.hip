@@ -27,6 +27,7 @@
 
 #include "svoxt_host.h"
 #include "svoxt_sort.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
@@ -288,12 +289,12 @@ q_remap_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_
     out[i] = (uint32_t)w < M ? map[(uint32_t)w] : w;
 }
 
-static size_t q_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct QuantPlan {
+struct QuantSpace {
     uint32_t n_chunks;                       // workgroups of the weight scan
-    size_t off_keys[2], off_vals[2], off_pos_seg, off_seg_start[2], off_n_seg, off_seg_col, off_counts, off_slots, off_cut,
-           off_ext, off_sort_counts, off_sort_starts, off_chunks, off_local, off_agg_v, off_agg_f, bytes;
+    uint32_t *keys[2], *vals[2], *pos_seg, *seg_start[2], *n_seg, *seg_col, *counts, *slots, *cut, *ext, *sort_counts, *sort_starts,
+             *chunks, *agg_f;
+    double *local, *agg_v;                   // (the three pieces of the weight scan: empty unless weighted)
+    size_t bytes;
 };
 
 static int q_check(int64_t M, int32_t K, int32_t order, const char* fn) {
@@ -304,28 +305,29 @@ static int q_check(int64_t M, int32_t K, int32_t order, const char* fn) {
     return SVOXT_OK;
 }
 
-static void q_plan(int64_t M, int32_t K, int32_t order, bool weighted, QuantPlan& p) {
-    const size_t n = (size_t)M, S = (size_t)1 << order, u = sizeof(uint32_t);
+static QuantSpace q_carve(void* workspace, int64_t M, int32_t K, int32_t order, bool weighted) {
+    QuantSpace sp;
+    Carver w(workspace);
+    const size_t n = (size_t)M, S = (size_t)1 << order;
     const size_t sortw = (size_t)256 * sort_blocks((uint64_t)M);
-    p.n_chunks = (uint32_t)((n + kQBlock - 1) / kQBlock);
-    size_t o = 0;
-    auto take = [&](size_t b) { const size_t at = o; o += q_align(b); return at; };
-    for (int b = 0; b < 2; ++b) { p.off_keys[b] = take(u * n); p.off_vals[b] = take(u * n); }
-    p.off_pos_seg = take(u * n);
-    for (int b = 0; b < 2; ++b) p.off_seg_start[b] = take(u * (S + 1));
-    p.off_n_seg = take(u * 2);
-    p.off_seg_col = take(u * S);
-    p.off_counts = take(u * (S + 1));
-    p.off_slots = take(u * (S + 1));
-    p.off_cut = take(u * S);
-    p.off_ext = take(u * 2 * S * (size_t)K);
-    p.off_sort_counts = take(u * sortw);
-    p.off_sort_starts = take(u * sortw);
-    p.off_chunks = take(u * exclusive_scan_chunks(sortw > S + 1 ? sortw : S + 1));
-    p.off_local = take(weighted ? sizeof(double) * n : 0);
-    p.off_agg_v = take(weighted ? sizeof(double) * p.n_chunks : 0);
-    p.off_agg_f = take(weighted ? u * p.n_chunks : 0);
-    p.bytes = o;
+    sp.n_chunks = (uint32_t)((n + kQBlock - 1) / kQBlock);
+    for (int b = 0; b < 2; ++b) { sp.keys[b] = w.take<uint32_t>(n); sp.vals[b] = w.take<uint32_t>(n); }
+    sp.pos_seg = w.take<uint32_t>(n);
+    for (int b = 0; b < 2; ++b) sp.seg_start[b] = w.take<uint32_t>(S + 1);
+    sp.n_seg = w.take<uint32_t>(2);
+    sp.seg_col = w.take<uint32_t>(S);
+    sp.counts = w.take<uint32_t>(S + 1);
+    sp.slots = w.take<uint32_t>(S + 1);
+    sp.cut = w.take<uint32_t>(S);
+    sp.ext = w.take<uint32_t>(2 * S * (size_t)K);
+    sp.sort_counts = w.take<uint32_t>(sortw);
+    sp.sort_starts = w.take<uint32_t>(sortw);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks(sortw > S + 1 ? sortw : S + 1));
+    sp.local = w.take<double>(weighted ? n : 0);
+    sp.agg_v = w.take<double>(weighted ? sp.n_chunks : 0);
+    sp.agg_f = w.take<uint32_t>(weighted ? sp.n_chunks : 0);
+    sp.bytes = w.bytes();
+    return sp;
 }
 
 }  // namespace svoxt
@@ -336,9 +338,7 @@ extern "C" {
 
 int64_t svoxt_quantize_workspace_bytes(int64_t M, int32_t K, int32_t order, int32_t weighted) {
     if (q_check(M, K, order, "svoxt_quantize_workspace_bytes") != SVOXT_OK) return -1;
-    QuantPlan p;
-    q_plan(M, K, order, weighted != 0, p);
-    return (int64_t)p.bytes;
+    return (int64_t)q_carve(nullptr, M, K, order, weighted != 0).bytes;
 }
 
 int svoxt_quantize_median_cut(const float* data, int64_t M, int32_t K, const float* weights, int32_t order, float* colors,
@@ -350,19 +350,9 @@ int svoxt_quantize_median_cut(const float* data, int64_t M, int32_t K, const flo
     if (colors == nullptr || color_id_map == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: colors / color_id_map is NULL", fn);
     if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
     const bool weighted = weights != nullptr;
-    QuantPlan p;
-    q_plan(M, K, order, weighted, p);
-    if (workspace_bytes < (int64_t)p.bytes) return set_error(SVOXT_ERR_INVALID, "%s: workspace too small", fn);
+    const QuantSpace sp = q_carve(workspace, M, K, order, weighted);
+    if (workspace_bytes < (int64_t)sp.bytes) return set_error(SVOXT_ERR_INVALID, "%s: workspace too small", fn);
     hipStream_t st = (hipStream_t)stream;
-    char* w = static_cast<char*>(workspace);
-    auto U = [&](size_t off) { return reinterpret_cast<uint32_t*>(w + off); };
-    uint32_t* keys[2] = {U(p.off_keys[0]), U(p.off_keys[1])};
-    uint32_t* vals[2] = {U(p.off_vals[0]), U(p.off_vals[1])};
-    uint32_t* seg_start[2] = {U(p.off_seg_start[0]), U(p.off_seg_start[1])};
-    uint32_t *pos_seg = U(p.off_pos_seg), *n_seg = U(p.off_n_seg), *seg_col = U(p.off_seg_col), *counts = U(p.off_counts);
-    uint32_t *slots = U(p.off_slots), *cut = U(p.off_cut), *ext = U(p.off_ext), *sort_counts = U(p.off_sort_counts);
-    uint32_t *sort_starts = U(p.off_sort_starts), *chunks = U(p.off_chunks), *agg_f = U(p.off_agg_f);
-    double *local = reinterpret_cast<double*>(w + p.off_local), *agg_v = reinterpret_cast<double*>(w + p.off_agg_v);
     uint32_t* row_seg = reinterpret_cast<uint32_t*>(color_id_map);
     const uint32_t n = (uint32_t)M, S = 1u << order;
     const unsigned nb = (n + kQBlock - 1) / kQBlock;
@@ -370,58 +360,58 @@ int svoxt_quantize_median_cut(const float* data, int64_t M, int32_t K, const flo
 
     hipError_t e = hipMemsetAsync(colors, 0, sizeof(float) * (size_t)S * K, st);
     if (e == hipSuccess) e = hipMemsetAsync(row_seg, 0, sizeof(uint32_t) * (size_t)n, st);
-    if (e == hipSuccess) e = hipMemsetAsync(pos_seg, 0, sizeof(uint32_t) * (size_t)n, st);
+    if (e == hipSuccess) e = hipMemsetAsync(sp.pos_seg, 0, sizeof(uint32_t) * (size_t)n, st);
     if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(q_init_kernel, dim3(1), dim3(64), 0, st, seg_start[0], n_seg, n);
+    hipLaunchKernelGGL(q_init_kernel, dim3(1), dim3(64), 0, st, sp.seg_start[0], sp.n_seg, n);
     if ((rc = check_launch(fn))) return rc;
 
     const uint32_t* perm = nullptr;          // the identity before the first sort
     int cur = 0, tab = 0;                    // the sort's current buffers; the current segment table
     for (int level = 0; level < order; ++level) {
         const uint32_t bound = 1u << level;  // segments at this level, at most
-        hipLaunchKernelGGL(q_ext_init_kernel, blocks((size_t)bound * K), dim3(kQBlock), 0, st, reinterpret_cast<uint2*>(ext), (size_t)bound * K);
-        hipLaunchKernelGGL(q_extremes_kernel, dim3(nb), dim3(kQBlock), 0, st, data, (int)K, n, perm, pos_seg, ext);
-        hipLaunchKernelGGL(q_choose_kernel, blocks((size_t)bound + 1), dim3(kQBlock), 0, st, ext, (int)K, seg_start[tab], n_seg + tab, bound, seg_col,
-                           counts, cut);
-        hipLaunchKernelGGL(q_key_kernel, dim3(nb), dim3(kQBlock), 0, st, data, (int)K, n, row_seg, seg_col, keys[cur]);
+        hipLaunchKernelGGL(q_ext_init_kernel, blocks((size_t)bound * K), dim3(kQBlock), 0, st, reinterpret_cast<uint2*>(sp.ext), (size_t)bound * K);
+        hipLaunchKernelGGL(q_extremes_kernel, dim3(nb), dim3(kQBlock), 0, st, data, (int)K, n, perm, sp.pos_seg, sp.ext);
+        hipLaunchKernelGGL(q_choose_kernel, blocks((size_t)bound + 1), dim3(kQBlock), 0, st, sp.ext, (int)K, sp.seg_start[tab], sp.n_seg + tab, bound, sp.seg_col,
+                           sp.counts, sp.cut);
+        hipLaunchKernelGGL(q_key_kernel, dim3(nb), dim3(kQBlock), 0, st, data, (int)K, n, row_seg, sp.seg_col, sp.keys[cur]);
         if ((rc = check_launch(fn))) return rc;
         for (int shift = 0; shift < 32; shift += 8) {
-            if ((rc = sort_pass(keys[cur], shift == 0 ? nullptr : vals[cur], n, shift, 8, sort_counts, sort_starts, chunks, keys[cur ^ 1],
-                                vals[cur ^ 1], st, fn))) return rc;
+            if ((rc = sort_pass(sp.keys[cur], shift == 0 ? nullptr : sp.vals[cur], n, shift, 8, sp.sort_counts, sp.sort_starts, sp.chunks, sp.keys[cur ^ 1],
+                                sp.vals[cur ^ 1], st, fn))) return rc;
             cur ^= 1;
         }
         if (level > 0) {
-            hipLaunchKernelGGL(q_seg_key_kernel, dim3(nb), dim3(kQBlock), 0, st, row_seg, vals[cur], n, keys[cur]);
+            hipLaunchKernelGGL(q_seg_key_kernel, dim3(nb), dim3(kQBlock), 0, st, row_seg, sp.vals[cur], n, sp.keys[cur]);
             if ((rc = check_launch(fn))) return rc;
             for (int shift = 0; shift < level; shift += 8) {
-                if ((rc = sort_pass(keys[cur], vals[cur], n, shift, level - shift < 8 ? level - shift : 8, sort_counts, sort_starts, chunks,
-                                    keys[cur ^ 1], vals[cur ^ 1], st, fn))) return rc;
+                if ((rc = sort_pass(sp.keys[cur], sp.vals[cur], n, shift, level - shift < 8 ? level - shift : 8, sp.sort_counts, sp.sort_starts, sp.chunks,
+                                    sp.keys[cur ^ 1], sp.vals[cur ^ 1], st, fn))) return rc;
                 cur ^= 1;
             }
         }
-        perm = vals[cur];
+        perm = sp.vals[cur];
         if (weighted) {
-            hipLaunchKernelGGL(q_wscan_local_kernel, dim3(p.n_chunks), dim3(kQBlock), 0, st, weights, perm, pos_seg, seg_start[tab], n, local,
-                               agg_v, agg_f);
-            hipLaunchKernelGGL(q_wscan_chunks_kernel, dim3(1), dim3(kQBlock), 0, st, agg_v, agg_f, p.n_chunks);
-            hipLaunchKernelGGL(q_wcut_kernel, dim3(nb), dim3(kQBlock), 0, st, local, agg_v, pos_seg, seg_start[tab], n, cut);
+            hipLaunchKernelGGL(q_wscan_local_kernel, dim3(sp.n_chunks), dim3(kQBlock), 0, st, weights, perm, sp.pos_seg, sp.seg_start[tab], n, sp.local,
+                               sp.agg_v, sp.agg_f);
+            hipLaunchKernelGGL(q_wscan_chunks_kernel, dim3(1), dim3(kQBlock), 0, st, sp.agg_v, sp.agg_f, sp.n_chunks);
+            hipLaunchKernelGGL(q_wcut_kernel, dim3(nb), dim3(kQBlock), 0, st, sp.local, sp.agg_v, sp.pos_seg, sp.seg_start[tab], n, sp.cut);
             if ((rc = check_launch(fn))) return rc;
         }
-        if ((rc = exclusive_scan(counts, (size_t)bound + 1, chunks, slots, st, fn))) return rc;
-        hipLaunchKernelGGL(q_split_kernel, blocks(bound), dim3(kQBlock), 0, st, seg_start[tab], n_seg + tab, slots, cut, weighted ? 1 : 0, n,
-                           seg_start[tab ^ 1], n_seg + (tab ^ 1));
-        hipLaunchKernelGGL(q_rewrite_kernel, dim3(nb), dim3(kQBlock), 0, st, seg_start[tab], slots, seg_start[tab ^ 1], perm, n, pos_seg, row_seg);
+        if ((rc = exclusive_scan(sp.counts, (size_t)bound + 1, sp.chunks, sp.slots, st, fn))) return rc;
+        hipLaunchKernelGGL(q_split_kernel, blocks(bound), dim3(kQBlock), 0, st, sp.seg_start[tab], sp.n_seg + tab, sp.slots, sp.cut, weighted ? 1 : 0, n,
+                           sp.seg_start[tab ^ 1], sp.n_seg + (tab ^ 1));
+        hipLaunchKernelGGL(q_rewrite_kernel, dim3(nb), dim3(kQBlock), 0, st, sp.seg_start[tab], sp.slots, sp.seg_start[tab ^ 1], perm, n, sp.pos_seg, row_seg);
         if ((rc = check_launch(fn))) return rc;
         tab ^= 1;
     }
     // big segments (few of them) get a workgroup per column, small ones a wavefront per column
     if ((n >> order) >= 2048) {
         hipLaunchKernelGGL(q_color_kernel<kQBlock>, dim3(S, (unsigned)(K < 1024 ? K : 1024)), dim3(kQBlock), 0, st, data, (int)K, weights, perm,
-                           seg_start[tab], n_seg + tab, colors);
+                           sp.seg_start[tab], sp.n_seg + tab, colors);
     } else {
         const int groups = (K + 3) / 4;
         hipLaunchKernelGGL(q_color_kernel<64>, dim3(S, (unsigned)(groups < 1024 ? groups : 1024)), dim3(kQBlock), 0, st, data, (int)K, weights,
-                           perm, seg_start[tab], n_seg + tab, colors);
+                           perm, sp.seg_start[tab], sp.n_seg + tab, colors);
     }
     return check_launch(fn);
 }

@@ -46,20 +46,18 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_workspace.h"
 
 namespace svoxt {
 
-constexpr int kSubBlock = 256;
-constexpr int kSubMarkBlocksMax = 2048;      // the per-slot passes stride over the slots
+constexpr int kSubBlock = kLaunchBlock;      // (the per-slot passes stride over the slots: stride_blocks)
 constexpr uint32_t kSubBringsBit = 0x80000000u;
 
 struct SubIn {
     const int32_t* child;
     const int32_t* data;
     const int32_t* parent_depth;
-    const uint8_t* sel;                      // at most one of sel / weights; neither: every leaf is selected
-    const float* weights;
-    float threshold;
+    SlotDecision selected;                   // at most one of mask / weights; neither: every leaf is selected
     int32_t depth_limit;                     // a slot splits iff its node's depth is below this
     int32_t n;                               // internal nodes
     int32_t n3;                              // slots per node
@@ -78,44 +76,29 @@ struct UnshareSpace {
     size_t owner_bytes, bytes;
 };
 
-static size_t sub_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static SubSpace sub_carve(void* workspace, int64_t slots) {
     SubSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t ss = sub_align(sizeof(uint32_t) * ((size_t)slots + 1));
-    size_t o = 0;
-    sp.split_flag = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.rows_flag = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.split_rank = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.rows_rank = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.list = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-    o += sub_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)slots + 1));
-    sp.bytes = o;
+    Carver w(workspace);
+    sp.split_flag = w.take<uint32_t>((size_t)slots + 1);
+    sp.rows_flag = w.take<uint32_t>((size_t)slots + 1);
+    sp.split_rank = w.take<uint32_t>((size_t)slots + 1);
+    sp.rows_rank = w.take<uint32_t>((size_t)slots + 1);
+    sp.list = w.take<uint32_t>((size_t)slots + 1);             // (slots words are used: the piece is as long as the flags')
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)slots + 1));
+    sp.bytes = w.bytes();
     return sp;
 }
 
 static UnshareSpace unshare_carve(void* workspace, int64_t slots, int64_t M) {
     UnshareSpace sp;
-    char* w = static_cast<char*>(workspace);
-    const size_t ss = sub_align(sizeof(uint32_t) * ((size_t)slots + 1));
-    size_t o = 0;
-    sp.flag = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.rank = reinterpret_cast<uint32_t*>(w + o); o += ss;
-    sp.owner = reinterpret_cast<uint32_t*>(w + o);
+    Carver w(workspace);
+    sp.flag = w.take<uint32_t>((size_t)slots + 1);
+    sp.rank = w.take<uint32_t>((size_t)slots + 1);
+    sp.owner = w.take<uint32_t>((size_t)M);
     sp.owner_bytes = sizeof(uint32_t) * (size_t)M;
-    o += sub_align(sp.owner_bytes);
-    sp.chunks = reinterpret_cast<uint32_t*>(w + o);
-    o += sub_align(sizeof(uint32_t) * exclusive_scan_chunks((size_t)slots + 1));
-    sp.bytes = o;
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)slots + 1));
+    sp.bytes = w.bytes();
     return sp;
-}
-
-__device__ __forceinline__ bool sub_selected(const SubIn& in, int32_t s) {
-    if (in.sel != nullptr) return in.sel[s] != 0;
-    if (in.weights != nullptr) return in.weights[s] >= in.threshold;                    // (a NaN weight: not selected)
-    return true;
 }
 
 __global__ void __launch_bounds__(kSubBlock)
@@ -123,7 +106,7 @@ subdivide_mark_kernel(SubIn in, bool split_empty, bool own_rows, uint32_t* __res
     for (int64_t s64 = (int64_t)blockIdx.x * kSubBlock + threadIdx.x; s64 <= in.slots; s64 += (int64_t)gridDim.x * kSubBlock) {
         const int32_t s = (int32_t)s64;
         uint32_t split = 0u, rows = 0u;
-        if (s < in.slots && in.child[s] == 0 && sub_selected(in, s)) {                  // (s == slots: the scans' extra element)
+        if (s < in.slots && in.child[s] == 0 && in.selected(s)) {                  // (s == slots: the scans' extra element)
             const int32_t node = s / in.n3;
             const bool full = (uint32_t)in.data[s] < in.M;
             if (in.parent_depth[2 * (int64_t)node + 1] < in.depth_limit && (full || split_empty)) {
@@ -216,11 +199,6 @@ unshare_mark_kernel(const int32_t* __restrict__ child, const int32_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(64)
-unshare_counts_kernel(const uint32_t* __restrict__ rank, int32_t slots, int64_t* __restrict__ counts) {
-    if (threadIdx.x == 0) counts[0] = (int64_t)rank[slots];
-}
-
 __global__ void __launch_bounds__(kSubBlock)
 unshare_emit_kernel(int32_t slots, uint32_t M, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
                     int64_t rows_added, int32_t* data, int64_t* __restrict__ row_map) {
@@ -234,20 +212,10 @@ unshare_emit_kernel(int32_t slots, uint32_t M, const uint32_t* __restrict__ flag
 
 // The extents every entry point shares.  Nothing here touches HIP.
 static int sub_check_extents(const char* fn, int64_t n, int32_t N, int64_t M, const void* workspace, int64_t workspace_bytes) {
-    if (N < 2 || N > 16) return set_error(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
-    if (n < 1 || (double)n * N * N * N >= 2147483648.0)
-        return set_error(SVOXT_ERR_INVALID, "%s: n_internal must be >= 1 with n_internal * N^3 < 2^31", fn);
-    if (M < 0 || M > 0x7fffffff) return set_error(SVOXT_ERR_INVALID, "%s: the number of feature rows must be in [0, 2^31)", fn);
-    if (workspace == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: workspace is NULL", fn);
-    if (workspace_bytes < svoxt_subdivide_workspace_bytes(n, N, M))
-        return set_error(SVOXT_ERR_INVALID, "%s: workspace smaller than svoxt_subdivide_workspace_bytes(n_internal, N, M)", fn);
-    return SVOXT_OK;
-}
-
-static unsigned sub_blocks(int64_t n) { return (unsigned)((n + kSubBlock - 1) / kSubBlock); }
-static unsigned sub_stride_blocks(int64_t n) {
-    const unsigned need = sub_blocks(n);
-    return need < (unsigned)kSubMarkBlocksMax ? need : (unsigned)kSubMarkBlocksMax;
+    int rc;
+    if ((rc = tree_extents_check(fn, n, N, M))) return rc;
+    return workspace_check(fn, workspace, workspace_bytes, svoxt_subdivide_workspace_bytes(n, N, M),
+                           "svoxt_subdivide_workspace_bytes(n_internal, N, M)");
 }
 
 }  // namespace svoxt
@@ -276,17 +244,17 @@ int svoxt_subdivide_count(const int32_t* child, const int32_t* data, const int32
     if (weights != nullptr && threshold != threshold) return set_error(SVOXT_ERR_INVALID, "%s: threshold is NaN", fn);
     if (counts == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: counts is NULL", fn);
     SubIn in;
-    in.child = child; in.data = data; in.parent_depth = parent_depth; in.sel = sel; in.weights = weights; in.threshold = threshold;
+    in.child = child; in.data = data; in.parent_depth = parent_depth; in.selected = SlotDecision{sel, weights, threshold};
     in.depth_limit = depth_limit; in.n = (int32_t)n_internal; in.n3 = N * N * N; in.M = (uint32_t)M;
     in.slots = (int32_t)(n_internal * in.n3);
     hipStream_t st = (hipStream_t)stream;
     const SubSpace sp = sub_carve(workspace, in.slots);
-    hipLaunchKernelGGL(subdivide_mark_kernel, dim3(sub_stride_blocks((int64_t)in.slots + 1)), dim3(kSubBlock), 0, st, in,
+    hipLaunchKernelGGL(subdivide_mark_kernel, dim3(stride_blocks((int64_t)in.slots + 1)), dim3(kSubBlock), 0, st, in,
                        split_empty != 0, own_rows != 0, sp.split_flag, sp.rows_flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.split_flag, (size_t)in.slots + 1, sp.chunks, sp.split_rank, st, fn)) ||
         (rc = exclusive_scan(sp.rows_flag, (size_t)in.slots + 1, sp.chunks, sp.rows_rank, st, fn)))
         return rc;
-    hipLaunchKernelGGL(subdivide_list_kernel, dim3(sub_stride_blocks(in.slots)), dim3(kSubBlock), 0, st, sp.split_flag, sp.rows_flag,
+    hipLaunchKernelGGL(subdivide_list_kernel, dim3(stride_blocks(in.slots)), dim3(kSubBlock), 0, st, sp.split_flag, sp.rows_flag,
                        sp.split_rank, in.slots, sp.list);
     hipLaunchKernelGGL(subdivide_counts_kernel, dim3(1), dim3(64), 0, st, sp.split_rank, sp.rows_rank, in.slots, in.n3, counts);
     return check_launch(fn);
@@ -313,9 +281,9 @@ int svoxt_subdivide_emit(int32_t* child, int32_t* data, int32_t* parent_depth, i
     if (own_rows != 0 && M + rows_added > 0 && row_map == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: row_map is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const SubSpace sp = sub_carve(const_cast<void*>(workspace), slots);
-    if (own_rows != 0 && M > 0) hipLaunchKernelGGL(row_map_head_kernel, dim3(sub_blocks(M)), dim3(kSubBlock), 0, st, M, row_map);
+    if (own_rows != 0 && M > 0) hipLaunchKernelGGL(row_map_head_kernel, dim3(launch_blocks(M)), dim3(kSubBlock), 0, st, M, row_map);
     if (nodes_added > 0)
-        hipLaunchKernelGGL(subdivide_emit_kernel, dim3(sub_blocks(nodes_added * n3)), dim3(kSubBlock), 0, st, (int32_t)n_internal,
+        hipLaunchKernelGGL(subdivide_emit_kernel, dim3(launch_blocks(nodes_added * n3)), dim3(kSubBlock), 0, st, (int32_t)n_internal,
                            (int32_t)n3, (uint32_t)M, (int32_t)slots, own_rows != 0, sp.list, sp.split_rank, sp.rows_rank, nodes_added,
                            M + rows_added, empty_index, child, data, parent_depth, row_map);
     return check_launch(fn);
@@ -334,13 +302,13 @@ int svoxt_unshare_count(const int32_t* child, const int32_t* data, int64_t n_int
     if (M > 0) {
         const hipError_t e = hipMemsetAsync(sp.owner, 0xff, sp.owner_bytes, st);
         if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-        hipLaunchKernelGGL(unshare_owner_kernel, dim3(sub_stride_blocks(slots)), dim3(kSubBlock), 0, st, child, data, slots, (uint32_t)M,
+        hipLaunchKernelGGL(unshare_owner_kernel, dim3(stride_blocks(slots)), dim3(kSubBlock), 0, st, child, data, slots, (uint32_t)M,
                            sp.owner);
     }
-    hipLaunchKernelGGL(unshare_mark_kernel, dim3(sub_stride_blocks((int64_t)slots + 1)), dim3(kSubBlock), 0, st, child, data, slots,
+    hipLaunchKernelGGL(unshare_mark_kernel, dim3(stride_blocks((int64_t)slots + 1)), dim3(kSubBlock), 0, st, child, data, slots,
                        (uint32_t)M, sp.owner, sp.flag);
     if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.flag, (size_t)slots + 1, sp.chunks, sp.rank, st, fn))) return rc;
-    hipLaunchKernelGGL(unshare_counts_kernel, dim3(1), dim3(64), 0, st, sp.rank, slots, counts);
+    hipLaunchKernelGGL(rank_totals_kernel<1>, dim3(1), dim3(64), 0, st, RankTotals<1>{{sp.rank}, {(int64_t)slots}}, counts);
     return check_launch(fn);
 }
 
@@ -357,9 +325,9 @@ int svoxt_unshare_emit(int32_t* data, int64_t n_internal, int32_t N, int64_t M, 
     if (M + rows_added > 0 && row_map == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: row_map is NULL", fn);
     hipStream_t st = (hipStream_t)stream;
     const UnshareSpace sp = unshare_carve(const_cast<void*>(workspace), slots, M);
-    if (M > 0) hipLaunchKernelGGL(row_map_head_kernel, dim3(sub_blocks(M)), dim3(kSubBlock), 0, st, M, row_map);
+    if (M > 0) hipLaunchKernelGGL(row_map_head_kernel, dim3(launch_blocks(M)), dim3(kSubBlock), 0, st, M, row_map);
     if (rows_added > 0)
-        hipLaunchKernelGGL(unshare_emit_kernel, dim3(sub_blocks(slots)), dim3(kSubBlock), 0, st, (int32_t)slots, (uint32_t)M, sp.flag,
+        hipLaunchKernelGGL(unshare_emit_kernel, dim3(launch_blocks(slots)), dim3(kSubBlock), 0, st, (int32_t)slots, (uint32_t)M, sp.flag,
                            sp.rank, rows_added, data, row_map);
     return check_launch(fn);
 }

@@ -516,12 +516,9 @@ class N3Tree(nn.Module):
                 self.child, self.data, self.parent_depth, before, self.features.shape[0], keep, weights, threshold,
                 collapse, compact_features, reserve, EMPTY_INDEX, return_dropped=True)
             _C.invalidate_caches(self.child)         # the old tables' acceleration grid goes now, not with the tensor
-            self.child, self.data, self.parent_depth = child, data, parent_depth
+            self._install_tables(child, data, parent_depth, n)
             if row_map is not None:
-                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
-                                             requires_grad=self.features.requires_grad)
-            self._n_internal.fill_(n)
-            self.filled = n
+                self._replace_features(row_map=row_map)
             self._invalidate()
         return PruneResult(n, before - n, dropped, row_map)
 
@@ -554,19 +551,7 @@ class N3Tree(nn.Module):
                  every new feature row (arange(M), then each r N^3 - 1 times), None without `own_rows`"""
         if self._lock_tree_structure:
             raise RuntimeError("Tree locked")
-        if sel is not None and weights is not None:
-            raise RuntimeError("subdivide: at most one of sel / weights may be given")
-        if weights is not None and threshold is None:
-            raise RuntimeError("subdivide: weights needs a threshold")
-        if weights is None and threshold is not None:
-            raise RuntimeError("subdivide: threshold goes with weights")
-        for nm, x, dtypes in (("sel", sel, (torch.bool, torch.uint8)), ("weights", weights, (torch.float32,))):
-            if x is None:
-                continue
-            if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or tuple(x.shape) != tuple(self.child.shape):
-                raise RuntimeError(f"subdivide: {nm} must be a {' / '.join(str(d) for d in dtypes)} tensor with the shape of child")
-            if x.device != self.child.device:
-                raise RuntimeError(f"subdivide: {nm} must be on the device of the tree")
+        _C.slot_decision(self.child, "sel", sel, weights, threshold, required=False)     # a bad decision is refused on a CPU tree too
         if not self.data.is_cuda:
             raise RuntimeError("subdivide: only the GPU (HIP) path exists; move the tree to a GPU")
         limit = self.depth_limit if max_depth is None else min(self.depth_limit, int(max_depth))
@@ -585,12 +570,9 @@ class N3Tree(nn.Module):
             if added == 0:
                 return SubdivideResult(before, 0, 0, row_map)
             _C.invalidate_caches(old_child, child, data)   # what was cached of the old words goes now
-            self.child, self.data, self.parent_depth = child, data, parent_depth
+            self._install_tables(child, data, parent_depth, before + added)
             if rows_added > 0:
-                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
-                                             requires_grad=self.features.requires_grad)
-            self._n_internal.fill_(before + added)
-            self.filled = before + added
+                self._replace_features(row_map=row_map)
             self._invalidate()
         return SubdivideResult(self.filled, added, rows_added, row_map)
 
@@ -614,8 +596,7 @@ class N3Tree(nn.Module):
             rows_added, row_map = _C.unshare_rows(self.child, self.data, self.filled, self.features.shape[0], EMPTY_INDEX)
             if rows_added > 0:
                 _C.invalidate_caches(self.child, self.data)
-                self.features = nn.Parameter(_C.gather_rows(self.features.detach().contiguous(), row_map),
-                                             requires_grad=self.features.requires_grad)
+                self._replace_features(row_map=row_map)
                 self._invalidate()
         return UnshareResult(rows_added, row_map)
 
@@ -655,7 +636,7 @@ class N3Tree(nn.Module):
             data = _C.remap_index(self.data.contiguous(), color_id_map)
             _C.invalidate_caches(self.child, self.data)     # what was cached of the old data words goes now
             self.data = data
-            self.features = nn.Parameter(colors, requires_grad=self.features.requires_grad)
+            self._replace_features(table=colors)
             self._invalidate()
         return QuantizeResult(colors, color_id_map)
 
@@ -928,10 +909,8 @@ class N3Tree(nn.Module):
                 self.child, self.data, self.parent_depth, before, self.features.detach().contiguous(), selected, op, empty,
                 compact_features, reserve, EMPTY_INDEX)
             _C.invalidate_caches(self.child)         # the old tables' acceleration grid goes now, not with the tensor
-            self.child, self.data, self.parent_depth = child, data, parent_depth
-            self.features = nn.Parameter(table, requires_grad=self.features.requires_grad)
-            self._n_internal.fill_(n)
-            self.filled = n
+            self._install_tables(child, data, parent_depth, n)
+            self._replace_features(table=table)
             self._invalidate()
         return MergeResult(n, before - n, row_map, added)
 
@@ -1035,6 +1014,20 @@ class N3Tree(nn.Module):
 
     def tree2world(self, indices):
         return (indices - self.offset) / self.invradius
+
+    def _install_tables(self, child, data, parent_depth, n):
+        """New tables and their node count; the caller drops what was cached of the old ones (invalidate_caches) before
+        and calls _invalidate() after."""
+        self.child, self.data, self.parent_depth = child, data, parent_depth
+        self._n_internal.fill_(n)
+        self.filled = n
+
+    def _replace_features(self, table=None, row_map=None):
+        """`self.features` becomes a NEW nn.Parameter -- `table`, or the old rows gathered through `row_map` -- that
+        requires a gradient iff the old one did."""
+        if table is None:
+            table = _C.gather_rows(self.features.detach().contiguous(), row_map)
+        self.features = nn.Parameter(table, requires_grad=self.features.requires_grad)
 
     def _invalidate(self):
         self._ver += 1

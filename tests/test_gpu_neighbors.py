@@ -119,6 +119,20 @@ def test_neighbors_equal_the_restatement_and_the_float_descent(gpu, name):
     np.testing.assert_array_equal(ids.cpu().numpy(), slots[want[i, k]])
 
 
+def test_neighbors_of_a_tree_above_the_stride_bound_equal_the_restatement(gpu):
+    """synth.shell_tree(8) has 990 728 slots: more than 2048 workgroups of 256, so the flag pass and the neighbour walk
+    stride (the trees above stay below the bound).  One case, the table alone."""
+    from svox_t_amd import synth
+    st = synth.shell_tree(8)
+    child, pd, n = st.child, st.parent_depth, st.n_internal
+    N = child.shape[1]
+    assert n * N ** 3 > 2048 * 256
+    want = R.leaf_neighbors(child, pd, n, N)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu)      # noqa: E731
+    got = _C.leaf_neighbors(dev(child), dev(pd), n, want.shape[0], int(pd[:n, 1].max()))
+    assert got.dtype == torch.int32 and same_bits(got.cpu().numpy(), want)
+
+
 CASES = [("shell_d5", 4, None), ("shell_d5", 28, -1), ("shell_d5", 28, slice(0, 3)), ("built_refined", 28, [5, 2]),
          ("deep_next_to_coarse", 65, None), ("deep_next_to_coarse", 1, None), ("deep_next_to_coarse", 28, [5, 2]),
          ("topology_full_n3_l2.npz", 4, -1), ("topology_points_a.npz", 65, slice(0, 3)), ("topology_points_b.npz", 1, -1),

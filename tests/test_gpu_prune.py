@@ -62,8 +62,8 @@ def hip_prune(gpu, child, data, pd, n, M, **kw):
     for k in ("keep", "weights"):
         if k in kw:
             kw[k] = t(kw[k])
-    c, d, p, n2, row_map = _C.prune_tree(t(child), t(data), t(pd), n, M, **kw)
-    return c.cpu().numpy(), d.cpu().numpy(), p.cpu().numpy(), n2, None if row_map is None else row_map.cpu().numpy()
+    c, d, p, n2, row_map, *dropped = _C.prune_tree(t(child), t(data), t(pd), n, M, **kw)
+    return (c.cpu().numpy(), d.cpu().numpy(), p.cpu().numpy(), n2, None if row_map is None else row_map.cpu().numpy(), *dropped)
 
 
 def assert_same(got, want):
@@ -98,6 +98,20 @@ def test_tables_and_row_map_equal_the_restatement(gpu, name, mask):
     assert_same(again, first)
     for a, b in zip(again[:3], first[:3]):
         assert a.tobytes() == b.tobytes()
+
+
+def test_a_tree_above_the_stride_bound_equals_the_restatement(gpu):
+    """synth.shell_tree(8) has 990 728 slots: more than 2048 workgroups of 256, so the mark pass strides and sums its
+    drop counts over all 2048 workgroups (shell_d6 and the fixtures stay below the bound).  One case."""
+    st = synth.shell_tree(8)
+    child, data, pd, n, M = st.child, st.data, st.parent_depth, st.n_internal, st.n_features
+    assert n * child.shape[1] ** 3 > 2048 * 256
+    kw = dict(keep=mask_of("half", child, data, M, seed=8), collapse=True, compact_features=True)
+    want = R.prune(child, data, pd, n, M, **kw)
+    got = hip_prune(gpu, child, data, pd, n, M, return_dropped=True, **kw)
+    assert_same(got, want)
+    assert got[5] == want[5]
+    R.integrity(got[0], got[1], got[2], got[3], child.shape[1], len(got[4]), collapsed=True)
 
 
 @pytest.mark.parametrize("name", ["shell_d5", "built_refined", "topology_full_n3_l2.npz"])

@@ -103,6 +103,31 @@ def test_tables_and_row_map_equal_the_restatement(gpu, name, mask):
         np.testing.assert_array_equal(got[5], np.arange(M))
 
 
+def test_trees_above_the_stride_bound_equal_the_restatement(gpu):
+    """synth.shell_tree(8) has 990 728 slots: more than 2048 workgroups of 256, so the per-slot passes of subdivide (mark,
+    list) and of unshare (owner, mark) stride (shell_d6 and the fixtures stay below the bound).  One case each."""
+    st = synth.shell_tree(8)
+    child, data, pd, n, M = st.child, st.data, st.parent_depth, st.n_internal, st.n_features
+    N = child.shape[1]
+    assert n * N ** 3 > 2048 * 256
+    sel = np.random.default_rng(8).random(child.shape) < 0.1
+    want = R.subdivide(child, data, pd, n, M, sel=sel, own_rows=True)
+    got = hip_subdivide(gpu, child, data, pd, n, M, sel=sel, own_rows=True)
+    assert want[3] > 0 and want[4] > 0
+    assert_same(got, want)
+    R.integrity(got[0], got[1], got[2], n + got[3], N, M + got[4], n_before=n, own_rows=True, row_map=got[5], M_before=M)
+    # unshare: the row words divided by 3, so that up to three leaves name a row
+    words = data.astype(np.int64) & 0xFFFFFFFF
+    shared = np.where(words < M, words // 3, words).astype(np.uint32).view(np.int32).reshape(data.shape)
+    want_data, want_rows, want_map = R.unshare(child, shared, n, M)
+    assert want_rows > 0
+    d = T(shared, gpu)
+    rows_added, row_map = _C.unshare_rows(T(child, gpu), d, n, M)
+    assert rows_added == want_rows
+    np.testing.assert_array_equal(row_map.cpu().numpy(), want_map)
+    np.testing.assert_array_equal(d.cpu().numpy(), want_data)
+
+
 @pytest.mark.parametrize("name", ["shell_d5", "built_refined", "topology_full_n3_l2.npz"])
 def test_weights_and_threshold(gpu, name):
     child, data, pd, n, M = tables_of(name, gpu)
