@@ -1203,6 +1203,55 @@ int svoxt_distortion_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const s
                          const float* grad_out, float* grad, int32_t gstride,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- per-sample interface (svoxt_samples.hip; not in the reference) -------------------------------
+ * A ray batch's leaf crossings as CSR lists, and the two primitives that turn per-sample values back into per-ray
+ * values: march -> samples -> weights from density -> accumulate along rays.
+ *
+ * A SAMPLE is a leaf crossing of the shared march whose data word names a feature row; with min_sigma (a HOST pointer;
+ * NULL: no filter; NaN is refused) only crossings with features[row, data_dim - 1] > *min_sigma -- 0.0 gives the set the
+ * backwards walk, sigma > 0.  Rays are walked as every per-ray operator walks them (8 x 8 tiles of a declared image,
+ * rays.order, plain batches); the lists come out in ray-index order whatever the walk was.
+ *   svoxt_ray_samples_count   marches, scans the per-ray counts and writes offsets int64 [Q + 1] (device, 8-byte
+ *                             aligned): ray q's samples are offsets[q] .. offsets[q + 1] - 1, offsets[Q] = T is a 64-bit
+ *                             total of its own.  T >= 2^31 has to be refused by the caller after reading offsets[Q]:
+ *                             the per-ray starts are 32-bit sums and wrap there, the total does not.
+ *                             workspace: svoxt_ray_samples_workspace_bytes(Q) device bytes (8-byte aligned; -1: Q negative
+ *                             or 2^31 and more; 0 for Q = 0).
+ *   svoxt_ray_samples_emit    marches again with the same arguments and writes, at offsets[q] + k in march order,
+ *                             row int32 (the feature row), ray int32 (q), depth float32 = delta_scale * t (the ENTRY z of
+ *                             the depth moments) and length float32 = delta_t * delta_scale, each [T].  Nothing is written
+ *                             at or behind offsets[q + 1].  No float sum: bit-identical from run to run.
+ * The per-sample primitives need no tree.  offsets int64 [Q + 1], Q and T below 2^31; segments are clipped to [0, T).
+ *   svoxt_sample_weights_fwd  per ray, in list order, float32 without contraction, T = 1 at the start:
+ *                                 sigma > 0:  att = exp(-(length * sigma));  w = T * (1 - att);  T *= att
+ *                                 sigma <= 0 (or NaN): w = 0, T unchanged
+ *                             w float32 [T], alpha float32 [Q] = 1 - T_end.  No thresholds, no early stop.  With
+ *                             sigma = features[row, data_dim - 1] alpha has the bits of svoxt_opacity_render_fwd at
+ *                             thresholds 0.
+ *   svoxt_sample_weights_bwd  grad_sigma float32 [T] (written, one entry per sample, no atomics) for grad_w [T] and
+ *                             grad_alpha [Q] (either may be NULL: zeros):
+ *                                 length_k (grad_w_k T_{k+1} - sum_{j>k} grad_w_j w_j + grad_alpha T_end),  0 where sigma <= 0
+ *                             in two forward-running sweeps: sweep 1 forms total = sum_j grad_w_j * w_j and T_end; sweep 2
+ *                             per sample: total -= grad_w * w;  length * ((grad_w * T_after - total) + grad_alpha * T_end).
+ *   svoxt_sample_accumulate_fwd   out float32 [Q, C]: out[q, c] = sum_k w[k] * values[k, c] over the ray's samples,
+ *                             acc += w * v in list order.  values float32 [T, C], or NULL with C = 1 (or T = 0): the plain sum of w.
+ *   svoxt_sample_accumulate_bwd   one pass over values: grad_w[k] = sum_c grad_out[ray[k], c] * values[k, c] in ascending
+ *                             c, grad_values[k, c] = w[k] * grad_out[ray[k], c]; either output may be NULL (not wanted).
+ * Q = 0 is a valid no-op everywhere.  No allocation, no synchronisation. */
+int64_t svoxt_ray_samples_workspace_bytes(int64_t Q);
+int svoxt_ray_samples_count(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                            int64_t* offsets, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_ray_samples_emit(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                           const int64_t* offsets, int32_t* row, int32_t* ray, float* depth, float* length, void* stream);
+int svoxt_sample_weights_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* length, const float* sigma, float* w,
+                             float* alpha, void* stream);
+int svoxt_sample_weights_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float* length, const float* sigma,
+                             const float* grad_w, const float* grad_alpha, float* grad_sigma, void* stream);
+int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
+                                float* out, void* stream);
+int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
+                                const float* grad_out, float* grad_w, float* grad_values, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

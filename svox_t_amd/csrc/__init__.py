@@ -1185,4 +1185,6 @@ from ._extras import slot_decision, subdivide_tree, unshare_rows  # noqa: E402,F
 from ._extras import TVPlan, leaf_neighbors, tv_plan, tv_rows  # noqa: E402,F401
 from ._extras import depth_moments, depth_moments_backward  # noqa: E402,F401
 from ._extras import distortion, distortion_backward  # noqa: E402,F401
+from ._extras import (ray_samples, sample_accumulate, sample_accumulate_backward, sample_weights,  # noqa: E402,F401
+                      sample_weights_backward)
 from . import _extras  # noqa: E402,F401

@@ -199,6 +199,13 @@ EXPORTS = {
     "svoxt_distortion_workspace_bytes": (_i64, [_i64, _i64]),
     "svoxt_distortion_fwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _i64, _vp]),
     "svoxt_distortion_bwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_ray_samples_workspace_bytes": (_i64, [_i64]),
+    "svoxt_ray_samples_count": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _P(ctypes.c_float), _vp, _vp, _i64, _vp]),
+    "svoxt_ray_samples_emit": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _P(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_sample_weights_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_sample_weights_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_sample_accumulate_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "svoxt_sample_accumulate_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

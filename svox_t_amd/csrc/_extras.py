@@ -1338,3 +1338,141 @@ def distortion_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: t
     gradient at thresholds 0 (include/svoxt.h, svoxt_distortion_bwd).  Reads what the forward of the same spec objects
     recorded if nothing it depends on has changed since; marches otherwise."""
     return _raysweep_backward(_DISTORTION, tree, rays, opt, grad_output)
+
+
+# ---------------------------------------------------------------------------
+# Per-sample interface (svoxt_samples.hip; not in the reference; DESIGN.md 4.20)
+# ---------------------------------------------------------------------------
+def ray_samples(tree: TreeSpec, rays, opt: RenderOptions, min_sigma=None):
+    """The leaf crossings of a ray batch as CSR lists (include/svoxt.h, svoxt_ray_samples_count / _emit): returns
+    (offsets int64 [Q + 1], row int32 [T], ray int32 [T], depth float32 [T], length float32 [T], T).  `rays`: a RaysSpec
+    or a CameraSpec, walked as depth_moments walks them; the lists are in ray-index order.  min_sigma None: every crossing
+    with a feature row; a number: only those with features[row, -1] > min_sigma.  One host read (T); T >= 2^31 raises."""
+    import svox_t_amd.csrc as csrc
+    ms = None
+    if min_sigma is not None:
+        ms = float(min_sigma)
+        if ms != ms:
+            raise RuntimeError("min_sigma is NaN")
+        ms = ctypes.byref(ctypes.c_float(ms))
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    Q = cr.Q
+    with _on(dev):
+        if Q == 0:
+            T, offsets = 0, torch.zeros((1,), dtype=torch.int64, device=dev)
+        else:
+            offsets = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+            ws = _workspace(dev, _lib.svoxt_ray_samples_workspace_bytes(Q), "ray_samples: the batch must have fewer than 2^31 rays")
+            _call("svoxt_ray_samples_count", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), ms, _ptr(offsets), _ptr(ws),
+                  ws.numel(), _stream(dev))
+            T = int(offsets[Q].item())                  # the one host read
+            if T >= 1 << 31:
+                raise RuntimeError(f"ray_samples: {T} samples; a batch's lists hold fewer than 2^31 (split the batch)")
+        row = torch.empty((T,), dtype=torch.int32, device=dev)
+        ray = torch.empty((T,), dtype=torch.int32, device=dev)
+        depth = torch.empty((T,), dtype=torch.float32, device=dev)
+        length = torch.empty((T,), dtype=torch.float32, device=dev)
+        if T > 0:
+            _call("svoxt_ray_samples_emit", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), ms, _ptr(offsets), _ptr(row),
+                  _ptr(ray), _ptr(depth), _ptr(length), _stream(dev))
+    return offsets, row, ray, depth, length, T
+
+
+def _check_csr(offsets, T) -> int:
+    """The checks of a CSR pair (offsets int64 [Q + 1], T samples); returns Q."""
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1:
+        raise RuntimeError("offsets must be int64 [Q + 1]")
+    _check_input(offsets, "offsets")
+    Q = offsets.shape[0] - 1
+    if Q >= 1 << 31 or T >= 1 << 31:
+        raise RuntimeError("Q and T must be below 2^31")
+    return Q
+
+
+def _check_per_sample(x, name, T, dev, cols=None, dtype=torch.float32):
+    shape = (T,) if cols is None else (T, cols)
+    if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape:
+        raise RuntimeError(f"{name} must be {str(dtype).split('.')[-1]} {'[T]' if cols is None else '[T, C]'} with T = {T} samples")
+    _check_input(x, name)
+    if x.device != dev:
+        raise RuntimeError(f"{name} must be on the device of offsets")
+
+
+def sample_weights(offsets, length, sigma):
+    """(w float32 [T], alpha float32 [Q]) of svoxt_sample_weights_fwd for offsets int64 [Q + 1], length and sigma [T]."""
+    if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or sigma.dim() != 1:
+        raise RuntimeError("sigma must be float32 [T]")
+    T = sigma.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(length, "length", T, dev)
+    _check_per_sample(sigma, "sigma", T, dev)
+    with _on(dev):
+        w = torch.empty((T,), dtype=torch.float32, device=dev)
+        alpha = torch.empty((Q,), dtype=torch.float32, device=dev)
+        _call("svoxt_sample_weights_fwd", _ptr(offsets), Q, T, _ptr(length), _ptr(sigma), _ptr(w), _ptr(alpha), _stream(dev))
+    return w, alpha
+
+
+def sample_weights_backward(offsets, length, sigma, grad_w, grad_alpha):
+    """grad_sigma float32 [T] of svoxt_sample_weights_bwd; grad_w [T] / grad_alpha [Q] may be None (zeros)."""
+    T = sigma.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(length, "length", T, dev)
+    _check_per_sample(sigma, "sigma", T, dev)
+    if grad_w is not None:
+        _check_per_sample(grad_w, "grad_w", T, dev)
+    if grad_alpha is not None:
+        _check_input(grad_alpha, "grad_alpha")
+        if grad_alpha.dtype != torch.float32 or tuple(grad_alpha.shape) != (Q,) or grad_alpha.device != dev:
+            raise RuntimeError("grad_alpha must be float32 [Q] on the device of offsets")
+    with _on(dev):
+        gs = torch.empty((T,), dtype=torch.float32, device=dev)
+        # (a NULL gradient of an array that has elements: zeros, said by the pointer alone)
+        _call("svoxt_sample_weights_bwd", _ptr(offsets), Q, T, _ptr(length), _ptr(sigma), _ptr(grad_w), _ptr(grad_alpha), _ptr(gs),
+              _stream(dev))
+    return gs
+
+
+def sample_accumulate(offsets, w, values=None):
+    """out float32 [Q, C] (or [Q] without values) of svoxt_sample_accumulate_fwd for w [T] and values [T, C]."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1:
+        raise RuntimeError("w must be float32 [T]")
+    T = w.shape[0]
+    if values is not None and (not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2
+                               or values.shape[0] != T or values.shape[1] < 1):
+        raise RuntimeError(f"values must be float32 [T, C] with T = {T} samples and C >= 1")
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(w, "w", T, dev)
+    C = 1 if values is None else values.shape[1]
+    if values is not None:
+        _check_per_sample(values, "values", T, dev, C)
+    with _on(dev):
+        out = torch.empty((Q,) if values is None else (Q, C), dtype=torch.float32, device=dev)
+        _call("svoxt_sample_accumulate_fwd", _ptr(offsets), Q, T, _ptr(w), _ptr(values), C, _ptr(out), _stream(dev))
+    return out
+
+
+def sample_accumulate_backward(ray, Q, w, values, grad_out, need_w=True, need_values=True):
+    """(grad_w [T] or None, grad_values [T, C] or None) of svoxt_sample_accumulate_bwd for grad_out [Q, C] ([Q] without
+    values) and ray int32 [T], the ray index of every sample."""
+    T = w.shape[0]
+    dev = w.device
+    _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+    _check_per_sample(w, "w", T, dev)
+    C = 1 if values is None else values.shape[1]
+    if values is not None:
+        _check_per_sample(values, "values", T, dev, C)
+    _check_input(grad_out, "grad_out")
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != ((Q,) if values is None else (Q, C)) or grad_out.device != dev:
+        raise RuntimeError("grad_out must be float32 with the shape of the output, on the device of w")
+    need_values = bool(need_values and values is not None)
+    with _on(dev):
+        gw = torch.empty((T,), dtype=torch.float32, device=dev) if need_w else None
+        gv = torch.empty((T, C), dtype=torch.float32, device=dev) if need_values else None
+        _call("svoxt_sample_accumulate_bwd", _ptr(ray), Q, T, _ptr(w), _ptr(values), C, _ptr(grad_out), _ptr(gw), _ptr(gv), _stream(dev))
+    return gw, gv

@@ -1,0 +1,373 @@
+// svoxt_samples.hip -- the per-sample interface (not in the reference): a ray batch's leaf crossings as
+// CSR lists, and the two primitives that turn per-sample values back into per-ray values.
+//
+//   ray_samples      count -> scan -> emit.  Both kernels run the shared march (setup_ray / march_step / march_advance of
+//                    svoxt_device.h), one lane per ray by ray_of_thread, exactly as raysweep_fwd_kernel walks it.  The count
+//                    kernel writes counts[q] at the ray's own index and adds each wavefront's count to one 64-bit total;
+//                    exclusive_scan (svoxt_host.h) turns the counts into starts, widened to int64 offsets[Q + 1] with the
+//                    64-bit total at offsets[Q].  The emit kernel marches again and writes (row, ray, depth, length) at
+//                    offsets[q] + k, never at or behind offsets[q + 1]: the lists are in ray-index order whatever the lane
+//                    assignment was.  No float sum anywhere: bit-identical from run to run.
+//                        depth = delta_scale * t         (the `entry` z of the depth moments, this operand order)
+//                        length = delta_t * delta_scale  (the d of the sweeps)
+//   sample_weights   one lane per ray walks its segment in list order, float32, no contraction:
+//                        sigma > 0:  att = pexpf(-(length * sigma));  w = T * (1 - att);  T *= att      else: w = 0
+//                    alpha = 1 - T_end.  Backward, two forward-running sweeps over the same products ("subtract down from
+//                    the total", as raysweep_bwd_kernel): sweep 1 forms total = sum_j gw_j w_j and T_end; sweep 2 per
+//                    sample: total -= gw * w;  grad_sigma = length * ((gw * T_after - total) + ga * T_end); 0 where
+//                    sigma <= 0.  One entry per sample, no atomics.
+//   accumulate       a lane per (ray, channel): acc += w * v in list order.  Backward: a lane per sample, one pass over
+//                    values: grad_w = sum_c g[ray, c] * v[c] in ascending c, grad_values[c] = w * g[ray, c].
+// C ABI: svoxt_ray_samples_* / svoxt_sample_weights_* / svoxt_sample_accumulate_* (include/svoxt.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "svoxt_device.h"
+#include "svoxt_host.h"
+#include "svoxt_launch.h"
+#include "svoxt_workspace.h"
+
+#pragma clang fp contract(off)
+
+namespace svoxt {
+
+// workspace of svoxt_ray_samples_count: [total u64] [counts u32[Q]] [starts u32[Q]] [chunk sums]; the total is cleared
+struct SamplesSpace {
+    unsigned long long* total;
+    uint32_t *counts, *starts, *chunks;
+    size_t clear_bytes, bytes;
+};
+static SamplesSpace samples_carve(void* workspace, int64_t Q) {
+    SamplesSpace sp;
+    Carver w(workspace);
+    sp.total = w.take<unsigned long long>(1);
+    sp.clear_bytes = w.bytes();
+    sp.counts = w.take<uint32_t>((size_t)Q);
+    sp.starts = w.take<uint32_t>((size_t)Q);
+    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)Q));
+    sp.bytes = w.bytes();
+    return sp;
+}
+
+// The samples of ray q in march order: f(row, depth, length) per leaf crossing whose data word names a feature row
+// (FILTER: and whose sigma exceeds min_sigma).
+template <bool N2, bool FILTER, class F>
+__device__ __forceinline__ void walk_samples(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float min_sigma, int64_t q, F&& f) {
+    Ray r;
+    if (!setup_ray(tr, rays, opt, q, r)) return;
+    const int K = tr.K;
+    float t = r.tmin;
+    while (t < r.tmax) {
+        Sample s;
+        march_step<N2>(tr, r, opt.step_size, t, s);
+        if (s.valid) {
+            bool take = true;
+            if constexpr (FILTER) take = tr.features[(int64_t)s.idx * K + (K - 1)] > min_sigma;
+            if (take) f(s.idx, r.delta_scale * t, s.delta_t * r.delta_scale);
+        }
+        t = march_advance(t, s.delta_t);
+    }
+}
+
+template <bool N2, bool FILTER>
+__global__ void __launch_bounds__(kBlock)
+samples_count_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, uint32_t* __restrict__ counts,
+                     unsigned long long* __restrict__ total) {
+    const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t q = ray_of_thread(rays, tid);
+    uint32_t n = 0;
+    if (q < rays.Q) {
+        walk_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t, float, float) { ++n; });
+        counts[q] = n;
+    }
+    uint32_t sum = n;                                            // (a wavefront's 64 counts: far below 2^32)
+    for (int off = 32; off > 0; off >>= 1) sum += (uint32_t)__shfl_xor((int)sum, off, 64);
+    if ((threadIdx.x & 63) == 0 && sum != 0u) atomicAdd(total, (unsigned long long)sum);
+}
+
+__global__ void __launch_bounds__(kLaunchBlock)
+samples_offsets_kernel(const uint32_t* __restrict__ starts, const unsigned long long* __restrict__ total, int64_t Q,
+                       int64_t* __restrict__ offsets) {
+    const int64_t i = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (i < Q) offsets[i] = (int64_t)starts[i];
+    else if (i == Q) offsets[Q] = (int64_t)total[0];
+}
+
+template <bool N2, bool FILTER>
+__global__ void __launch_bounds__(kBlock)
+samples_emit_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, const int64_t* __restrict__ offsets,
+                    int32_t* __restrict__ row, int32_t* __restrict__ ray, float* __restrict__ depth, float* __restrict__ length) {
+    const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t q = ray_of_thread(rays, tid);
+    if (q >= rays.Q) return;
+    int64_t at = offsets[q];
+    const int64_t end = offsets[q + 1];
+    if (at < 0) return;
+    walk_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t idx, float z, float d) {
+        if (at < end) {                                          // (the count's march found as many: never past the ray's own segment)
+            row[at] = idx;
+            ray[at] = (int32_t)q;
+            depth[at] = z;
+            length[at] = d;
+            ++at;
+        }
+    });
+}
+
+// ----------------------------------------------------------------------------------------------------- sample_weights
+__global__ void __launch_bounds__(kLaunchBlock)
+sample_weights_fwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ length,
+                          const float* __restrict__ sigma, float* __restrict__ w, float* __restrict__ alpha) {
+    const int64_t q = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (q >= Q) return;
+    const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+    float light = 1.f;
+    for (int64_t k = b; k < e; ++k) {
+        const float sg = sigma[k];
+        float wk = 0.f;
+        if (sg > 0.f) {
+            const float att = pexpf(-(length[k] * sg));
+            wk = light * (1.f - att);
+            light *= att;
+        }
+        w[k] = wk;
+    }
+    alpha[q] = 1.f - light;
+}
+
+__global__ void __launch_bounds__(kLaunchBlock)
+sample_weights_bwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ length,
+                          const float* __restrict__ sigma, const float* __restrict__ grad_w, const float* __restrict__ grad_alpha,
+                          float* __restrict__ grad_sigma) {
+    const int64_t q = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (q >= Q) return;
+    const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+    // sweep 1: the ray's total and final transmittance
+    float light = 1.f, total = 0.f;
+    for (int64_t k = b; k < e; ++k) {
+        const float sg = sigma[k];
+        if (sg > 0.f) {
+            const float att = pexpf(-(length[k] * sg));
+            const float wk = light * (1.f - att);
+            light *= att;
+            if (grad_w != nullptr) total += grad_w[k] * wk;
+        }
+    }
+    const float tail = (grad_alpha != nullptr ? grad_alpha[q] : 0.f) * light;
+    // sweep 2: subtract down
+    light = 1.f;
+    for (int64_t k = b; k < e; ++k) {
+        const float sg = sigma[k];
+        float gs = 0.f;
+        if (sg > 0.f) {
+            const float d = length[k];
+            const float att = pexpf(-(d * sg));
+            const float wk = light * (1.f - att);
+            light *= att;
+            const float gw = grad_w != nullptr ? grad_w[k] : 0.f;
+            total -= gw * wk;
+            gs = d * ((gw * light - total) + tail);
+        }
+        grad_sigma[k] = gs;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- accumulate
+// lane t = q * C + c
+__global__ void __launch_bounds__(kLaunchBlock)
+sample_accumulate_fwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ w,
+                             const float* __restrict__ values, int C, float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t q = t / C;
+    if (q >= Q) return;
+    const int c = (int)(t - q * C);
+    const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+    float acc = 0.f;
+    if (values != nullptr) {
+        for (int64_t k = b; k < e; ++k) acc += w[k] * values[k * C + c];
+    } else {
+        for (int64_t k = b; k < e; ++k) acc += w[k];
+    }
+    out[t] = acc;
+}
+
+// a lane per sample
+__global__ void __launch_bounds__(kLaunchBlock)
+sample_accumulate_bwd_kernel(const int32_t* __restrict__ ray, int64_t Q, int64_t T, const float* __restrict__ w,
+                             const float* __restrict__ values, int C, const float* __restrict__ grad_out,
+                             float* __restrict__ grad_w, float* __restrict__ grad_values) {
+    const int64_t k = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (k >= T) return;
+    const int64_t q = ray[k];
+    const bool in = q >= 0 && q < Q;
+    const float* __restrict__ g = grad_out + (in ? q : 0) * C;
+    const float wk = grad_values != nullptr ? w[k] : 0.f;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float gc = in ? g[c] : 0.f;
+        if (values != nullptr) s += gc * values[k * C + c];
+        else s += gc;
+        if (grad_values != nullptr) grad_values[k * C + c] = wk * gc;
+    }
+    if (grad_w != nullptr) grad_w[k] = s;
+}
+
+// ------------------------------------------------------------------------------------------------------------- checks
+static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+
+static int ray_samples_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                             const int64_t* offsets, const char* fn) {
+    int rc;
+    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, false))) return rc;
+    if (rays->Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: too many rays (ray indices are int32)", fn);
+    if (min_sigma != nullptr && *min_sigma != *min_sigma) return fail(SVOXT_ERR_INVALID, "%s: min_sigma is NaN", fn);
+    if (rays->Q > 0 && offsets == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets is NULL", fn);
+    if (misaligned(offsets, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets is not 8-byte aligned", fn);
+    return SVOXT_OK;
+}
+
+// the CSR arguments of the four per-sample entry points: Q rays, T samples, both below 2^31
+static int csr_check(int64_t Q, int64_t T, const char* fn) {
+    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
+    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
+    return SVOXT_OK;
+}
+
+}  // namespace svoxt
+
+using namespace svoxt;
+
+extern "C" {
+
+int64_t svoxt_ray_samples_workspace_bytes(int64_t Q) {
+    if (Q < 0 || Q > 0x7fffffffLL) return -1;
+    if (Q == 0) return 0;
+    return (int64_t)samples_carve(nullptr, Q).bytes;
+}
+
+int svoxt_ray_samples_count(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                            int64_t* offsets, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_ray_samples_count";
+    int rc;
+    if ((rc = ray_samples_check(tree, rays, opt, min_sigma, offsets, fn))) return rc;
+    const int64_t Q = rays->Q;
+    if (Q == 0) return SVOXT_OK;
+    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
+    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_ray_samples_workspace_bytes(Q), "svoxt_ray_samples_workspace_bytes(Q)")))
+        return rc;
+    const SamplesSpace sp = samples_carve(workspace, Q);
+    const TreeDev tr = to_dev(tree);
+    const RaysDev rd = to_dev(rays, tree);
+    const Opts od = to_dev(opt);
+    const float ms = min_sigma != nullptr ? *min_sigma : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
+    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+    with_bool(tree->N == 2, [&](auto N2) {
+        return with_bool(min_sigma != nullptr, [&](auto FILTER) {
+            hipLaunchKernelGGL((samples_count_kernel<N2.value, FILTER.value>), dim3(nblocks(Q)), dim3(kBlock), 0, st, tr, rd, od, ms,
+                               sp.counts, sp.total);
+            return true;
+        });
+    });
+    if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.counts, (size_t)Q, sp.chunks, sp.starts, st, fn))) return rc;
+    hipLaunchKernelGGL(samples_offsets_kernel, dim3(launch_blocks(Q + 1)), dim3(kLaunchBlock), 0, st, sp.starts, sp.total, Q, offsets);
+    return check_launch(fn);
+}
+
+int svoxt_ray_samples_emit(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                           const int64_t* offsets, int32_t* row, int32_t* ray, float* depth, float* length, void* stream) {
+    const char* fn = "svoxt_ray_samples_emit";
+    int rc;
+    if ((rc = ray_samples_check(tree, rays, opt, min_sigma, offsets, fn))) return rc;
+    const int64_t Q = rays->Q;
+    if (Q == 0) return SVOXT_OK;
+    if (row == nullptr || ray == nullptr || depth == nullptr || length == nullptr)
+        return fail(SVOXT_ERR_INVALID, "%s: row / ray / depth / length is NULL", fn);
+    if (misaligned(row, 4) || misaligned(ray, 4) || misaligned(depth, 4) || misaligned(length, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: row / ray / depth / length is not 4-byte aligned", fn);
+    const TreeDev tr = to_dev(tree);
+    const RaysDev rd = to_dev(rays, tree);
+    const Opts od = to_dev(opt);
+    const float ms = min_sigma != nullptr ? *min_sigma : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    with_bool(tree->N == 2, [&](auto N2) {
+        return with_bool(min_sigma != nullptr, [&](auto FILTER) {
+            hipLaunchKernelGGL((samples_emit_kernel<N2.value, FILTER.value>), dim3(nblocks(Q)), dim3(kBlock), 0, st, tr, rd, od, ms,
+                               offsets, row, ray, depth, length);
+            return true;
+        });
+    });
+    return check_launch(fn);
+}
+
+int svoxt_sample_weights_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* length, const float* sigma, float* w,
+                             float* alpha, void* stream) {
+    const char* fn = "svoxt_sample_weights_fwd";
+    int rc;
+    if ((rc = csr_check(Q, T, fn))) return rc;
+    if (Q == 0) return SVOXT_OK;
+    if (offsets == nullptr || alpha == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets / alpha is NULL", fn);
+    if (T > 0 && (length == nullptr || sigma == nullptr || w == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: length / sigma / w is NULL", fn);
+    if (misaligned(offsets, 8) || misaligned(length, 4) || misaligned(sigma, 4) || misaligned(w, 4) || misaligned(alpha, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets: 8 bytes, the float arrays: 4)", fn);
+    hipLaunchKernelGGL(sample_weights_fwd_kernel, dim3(launch_blocks(Q)), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T,
+                       length, sigma, w, alpha);
+    return check_launch(fn);
+}
+
+int svoxt_sample_weights_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float* length, const float* sigma,
+                             const float* grad_w, const float* grad_alpha, float* grad_sigma, void* stream) {
+    const char* fn = "svoxt_sample_weights_bwd";
+    int rc;
+    if ((rc = csr_check(Q, T, fn))) return rc;
+    if (Q == 0 || T == 0) return SVOXT_OK;
+    if (offsets == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets is NULL", fn);
+    if (length == nullptr || sigma == nullptr || grad_sigma == nullptr) return fail(SVOXT_ERR_INVALID, "%s: length / sigma / grad_sigma is NULL", fn);
+    if (misaligned(offsets, 8) || misaligned(length, 4) || misaligned(sigma, 4) || misaligned(grad_w, 4) || misaligned(grad_alpha, 4) ||
+        misaligned(grad_sigma, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets: 8 bytes, the float arrays: 4)", fn);
+    hipLaunchKernelGGL(sample_weights_bwd_kernel, dim3(launch_blocks(Q)), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T,
+                       length, sigma, grad_w, grad_alpha, grad_sigma);
+    return check_launch(fn);
+}
+
+int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
+                                float* out, void* stream) {
+    const char* fn = "svoxt_sample_accumulate_fwd";
+    int rc;
+    if ((rc = csr_check(Q, T, fn))) return rc;
+    if (C < 1 || (double)Q * C >= 274877906944.0 || (double)T * C >= 274877906944.0)
+        return fail(SVOXT_ERR_INVALID, "%s: C must be >= 1 with Q * C and T * C below 2^38", fn);
+    if (values == nullptr && C != 1 && T > 0) return fail(SVOXT_ERR_INVALID, "%s: values is NULL: C must be 1 (the plain sum of w)", fn);
+    if (Q == 0) return SVOXT_OK;
+    if (offsets == nullptr || out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets / out is NULL", fn);
+    if (T > 0 && w == nullptr) return fail(SVOXT_ERR_INVALID, "%s: w is NULL", fn);
+    if (misaligned(offsets, 8) || misaligned(w, 4) || misaligned(values, 4) || misaligned(out, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets: 8 bytes, the float arrays: 4)", fn);
+    hipLaunchKernelGGL(sample_accumulate_fwd_kernel, dim3(launch_blocks(Q * C)), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T,
+                       w, values, (int)C, out);
+    return check_launch(fn);
+}
+
+int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
+                                const float* grad_out, float* grad_w, float* grad_values, void* stream) {
+    const char* fn = "svoxt_sample_accumulate_bwd";
+    int rc;
+    if ((rc = csr_check(Q, T, fn))) return rc;
+    if (C < 1 || (double)Q * C >= 274877906944.0 || (double)T * C >= 274877906944.0)
+        return fail(SVOXT_ERR_INVALID, "%s: C must be >= 1 with Q * C and T * C below 2^38", fn);
+    if (values == nullptr && T > 0 && (C != 1 || grad_values != nullptr))
+        return fail(SVOXT_ERR_INVALID, "%s: values is NULL: C must be 1 and grad_values NULL", fn);
+    if (Q == 0 || T == 0 || (grad_w == nullptr && grad_values == nullptr)) return SVOXT_OK;
+    if (ray == nullptr || grad_out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: ray / grad_out is NULL", fn);
+    if (grad_values != nullptr && w == nullptr) return fail(SVOXT_ERR_INVALID, "%s: w is NULL", fn);
+    if (misaligned(ray, 4) || misaligned(w, 4) || misaligned(values, 4) || misaligned(grad_out, 4) || misaligned(grad_w, 4) ||
+        misaligned(grad_values, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    hipLaunchKernelGGL(sample_accumulate_bwd_kernel, dim3(launch_blocks(T)), dim3(kLaunchBlock), 0, (hipStream_t)stream, ray, Q, T, w,
+                       values, (int)C, grad_out, grad_w, grad_values);
+    return check_launch(fn);
+}
+
+}  // extern "C"
