@@ -1252,6 +1252,86 @@ int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, co
 int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
                                 const float* grad_out, float* grad_w, float* grad_values, void* stream);
 
+/* ---- samples to feature rows and back (svoxt_rows.hip; not in the reference) ----------------------
+ * The row side of the per-sample interface: a gather of table rows by sample, and its inverse, a reduction of
+ * per-sample values by feature row over a fixed-order plan.  Gather only: no atomics on floats anywhere, every result
+ * bit-identical from run to run.  Entry points added under ABI v22.
+ *
+ * THE ROW PLAN inverts row int32 [T] (svoxt_ray_samples_emit's, or any other): for every feature row r < M the samples
+ * that name it, in ascending sample index.  key = row where 0 <= row < M, M for anything else: samples whose row lies
+ * outside [0, M) are not an error, they sort behind row_ptr[M] and take no part in anything.
+ *   row_ptr  int32 [M + 1]   row r's samples are perm[row_ptr[r]] .. perm[row_ptr[r + 1] - 1]
+ *   perm     int32 [T]       the sample indices sorted stably by key
+ *   info     int64 [4]       n_outside = T - row_ptr[M];  the longest segment;  n_long, the rows with more than
+ *                            SVOXT_ROW_CHUNK samples;  n_chunks, the sum of ceil(n / SVOXT_ROW_CHUNK) over them
+ *   svoxt_row_plan_build   writes the three (all device; info 8-byte aligned): key -> stable LSD radix sort over the bits
+ *                          of M -> a binary search per row -> per-row marks and two scans.  The caller reads info (the one
+ *                          host read).  workspace: svoxt_row_plan_workspace_bytes(T, M) device bytes (-1: T or M negative
+ *                          or 2^31 and more; 0 for T = 0), 4-byte aligned.  T = 0: row_ptr and info are zeroed, the
+ *                          workspace is not needed.
+ *                          Checked before any HIP call, in this order: T, M in [0, 2^31); row_ptr, info not NULL; with
+ *                          T > 0 row, perm not NULL; alignment (row / row_ptr / perm 4 bytes, info 8); with T > 0 the
+ *                          workspace: alignment, not NULL, at least the query's size.
+ *   svoxt_row_plan_long    with info's n_long and n_chunks and the SAME workspace, unchanged since the build: writes
+ *                          long_rows int32 [n_long] (ascending), long_chunk_ptr int32 [n_long + 1] (the first chunk of
+ *                          every long row; [n_long] = n_chunks) and chunk_long int32 [n_chunks] (the index into
+ *                          long_rows of every chunk).  n_long = 0: long_chunk_ptr[0] = 0, the workspace is not read.
+ *                          Checked: T, M; n_long in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]; n_chunks in
+ *                          [2 n_long, T / SVOXT_ROW_CHUNK + n_long]; long_chunk_ptr not NULL; with n_long > 0 row_ptr,
+ *                          long_rows, chunk_long not NULL; alignment (4 bytes); with n_long > 0 the workspace as above.
+ *
+ *   svoxt_gather_rows      out float32 [T, C]: out[k, j] = table[row[k], cols[j]] (cols int32 [n_cols] distinct columns,
+ *                          or NULL / 0: all K, C = K).  A sample whose row is outside [0, M) gets zeros and the table is
+ *                          not read for it.  One kernel; 16 bytes per lane where all columns are taken, K is a multiple
+ *                          of 4 and table and out are 16-byte aligned.  T = 0: a no-op.
+ *                          Checked: T, M; K >= 1; cols / n_cols NULL / 0 or n_cols in [1, K]; T * C and M * K below
+ *                          2^38; with T > 0: row, out not NULL, table not NULL when M > 0, alignment (4 bytes).
+ *
+ *   svoxt_reduce_rows      out float32 [M, K] from values float32 [T, C] over a plan.  Without cols (NULL / 0) C = K and
+ *                          out[r, c] is the reduction of column c; with cols C = n_cols, out[r, cols[j]] is the
+ *                          reduction of column j and every other element of out is 0: every element written (the
+ *                          gradient of svoxt_gather_rows with respect to the table is this with op = SVOXT_ROWS_SUM).
+ *                          The order below is part of the definition.  Every operation is a separate float32 operation
+ *                          without contraction.  For row r with the n samples k_0 < k_1 < ... < k_{n-1}
+ *                          (perm[row_ptr[r] : row_ptr[r + 1]]) and column c:
+ *                            sum         chunk j covers k_{256 j} ... k_{min(256 j + 255, n - 1)}.  The chunk's partial is
+ *                                        p_j = ((0 + v[k_first]) + v[k_next]) + ... in ascending order.  The row's value
+ *                                        is (p_0 + p_1) + p_2 + ... in ascending j.  With n <= 256 this is the plain
+ *                                        sequential sum.
+ *                            mean        that sum, divided once by (float) n.
+ *                            max / min   the largest or smallest value, NaN as soon as any value of the row is NaN.
+ *                            n = 0       `empty`, for every op.
+ *                          (256 is SVOXT_ROW_CHUNK.)  A lane per (row, column) for the rows of at most 256 samples; for
+ *                          the long rows a lane per (chunk, column) writes partials to the workspace and a lane per
+ *                          (long row, column) joins them.  workspace: svoxt_reduce_rows_workspace_bytes(n_chunks, C)
+ *                          device bytes (-1: n_chunks negative or 2^31 and more, C < 1, n_chunks * C from 2^38; 0 for
+ *                          n_chunks = 0), 4-byte aligned.  M = 0: a no-op; T = 0: `empty` everywhere (cols: at the
+ *                          selected columns).
+ *                          Checked: T, M; C, K >= 1; cols / n_cols; C = n_cols (or K without cols); op among the
+ *                          constants; T * C and M * K below 2^38; n_long and n_chunks as above; with M > 0: out, row_ptr
+ *                          not NULL; with T > 0 values, perm not NULL; with n_long > 0 long_rows, long_chunk_ptr,
+ *                          chunk_long not NULL; alignment (4 bytes); with n_long > 0 the workspace not NULL and at least
+ *                          the query's size.  `empty` may be anything.
+ * No allocation, no synchronisation. */
+#define SVOXT_ROW_CHUNK 256
+#define SVOXT_ROWS_SUM 0
+#define SVOXT_ROWS_MEAN 1
+#define SVOXT_ROWS_MAX 2
+#define SVOXT_ROWS_MIN 3
+int64_t svoxt_row_plan_workspace_bytes(int64_t T, int64_t M);
+int svoxt_row_plan_build(const int32_t* row, int64_t T, int64_t M, int32_t* row_ptr, int32_t* perm, int64_t* info,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_row_plan_long(const int32_t* row_ptr, int64_t T, int64_t M, int64_t n_long, int64_t n_chunks,
+                        const void* workspace, int64_t workspace_bytes, int32_t* long_rows, int32_t* long_chunk_ptr,
+                        int32_t* chunk_long, void* stream);
+int svoxt_gather_rows(const float* table, int64_t M, int32_t K, const int32_t* row, int64_t T, const int32_t* cols,
+                      int32_t n_cols, float* out, void* stream);
+int64_t svoxt_reduce_rows_workspace_bytes(int64_t n_chunks, int32_t C);
+int svoxt_reduce_rows(const float* values, int64_t T, int32_t C, const int32_t* row_ptr, const int32_t* perm, int64_t M,
+                      const int32_t* long_rows, const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long,
+                      int64_t n_chunks, const int32_t* cols, int32_t n_cols, int32_t K, int32_t op, float empty,
+                      float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

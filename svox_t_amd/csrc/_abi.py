@@ -206,6 +206,13 @@ EXPORTS = {
     "svoxt_sample_weights_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_sample_accumulate_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
     "svoxt_sample_accumulate_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "svoxt_row_plan_workspace_bytes": (_i64, [_i64, _i64]),
+    "svoxt_row_plan_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_row_plan_long": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "svoxt_gather_rows": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "svoxt_reduce_rows_workspace_bytes": (_i64, [_i64, _i32]),
+    "svoxt_reduce_rows": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32,
+                                         ctypes.c_float, _vp, _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -1476,3 +1476,120 @@ def sample_accumulate_backward(ray, Q, w, values, grad_out, need_w=True, need_va
         gv = torch.empty((T, C), dtype=torch.float32, device=dev) if need_values else None
         _call("svoxt_sample_accumulate_bwd", _ptr(ray), Q, T, _ptr(w), _ptr(values), C, _ptr(grad_out), _ptr(gw), _ptr(gv), _stream(dev))
     return gw, gv
+
+
+# ---------------------------------------------------------------------------
+# Samples to feature rows and back (svoxt_rows.hip; not in the reference)
+# ---------------------------------------------------------------------------
+ROW_CHUNK = 256                                                   # SVOXT_ROW_CHUNK (include/svoxt.h)
+ROWS_OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3}              # SVOXT_ROWS_* (include/svoxt.h)
+ROW_PLAN_BUILDS = 0           # plans built so far (tests count them: RaySamples caches its plans)
+
+
+class RowPlanArrays(NamedTuple):
+    """What svoxt_row_plan_build / svoxt_row_plan_long write (include/svoxt.h)."""
+    row_ptr: torch.Tensor          # int32 [M + 1]
+    perm: torch.Tensor             # int32 [T]
+    long_rows: torch.Tensor        # int32 [n_long]
+    long_chunk_ptr: torch.Tensor   # int32 [n_long + 1]
+    chunk_long: torch.Tensor       # int32 [n_chunks]
+    T: int
+    M: int
+    n_outside: int
+    longest: int
+
+
+def _check_rows_extent(M, what) -> int:
+    if isinstance(M, bool) or not isinstance(M, int) or M < 0 or M >= 1 << 31:
+        raise RuntimeError(f"{what}: M must be an int in [0, 2^31)")
+    return M
+
+
+def row_plan(row: torch.Tensor, M: int) -> RowPlanArrays:
+    """The row plan of row int32 [T] for a table of M rows: svoxt_row_plan_build, one host read (the info record),
+    svoxt_row_plan_long."""
+    global ROW_PLAN_BUILDS
+    if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
+        raise RuntimeError("row must be int32 [T]")
+    M = _check_rows_extent(M, "row_plan")
+    _check_input(row, "row")
+    T, dev = row.shape[0], row.device
+    if T >= 1 << 31:
+        raise RuntimeError("row_plan: T must be below 2^31")
+    with _on(dev):
+        nbytes = _lib.svoxt_row_plan_workspace_bytes(T, M)
+        ws = _workspace(dev, nbytes, "row_plan: T and M must be below 2^31")
+        row_ptr = torch.empty((M + 1,), dtype=torch.int32, device=dev)
+        perm = torch.empty((T,), dtype=torch.int32, device=dev)
+        info = torch.empty((4,), dtype=torch.int64, device=dev)
+        _call("svoxt_row_plan_build", _ptr(row), T, M, _ptr(row_ptr), _ptr(perm), _ptr(info), _ptr(ws), nbytes, _stream(dev))
+        n_outside, longest, n_long, n_chunks = (int(v) for v in info.tolist())         # the one host read
+        long_rows = torch.empty((n_long,), dtype=torch.int32, device=dev)
+        long_chunk_ptr = torch.empty((n_long + 1,), dtype=torch.int32, device=dev)
+        chunk_long = torch.empty((n_chunks,), dtype=torch.int32, device=dev)
+        _call("svoxt_row_plan_long", _ptr(row_ptr), T, M, n_long, n_chunks, _ptr(ws), nbytes, _ptr(long_rows), _ptr(long_chunk_ptr),
+              _ptr(chunk_long), _stream(dev))
+    ROW_PLAN_BUILDS += 1
+    return RowPlanArrays(row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_outside, longest)
+
+
+def _check_cols(cols, K, dev):
+    """cols: None or int32 [K'] with 1 <= K' <= K on `dev`; returns the number of selected columns."""
+    if cols is None:
+        return K
+    if not isinstance(cols, torch.Tensor) or cols.dtype != torch.int32 or cols.dim() != 1 or cols.numel() == 0 or cols.shape[0] > K:
+        raise RuntimeError("cols must be int32 [K'] distinct columns, 1 <= K' <= K")
+    _check_input(cols, "cols")
+    if cols.device != dev:
+        raise RuntimeError("cols must be on the device of the table")
+    return cols.shape[0]
+
+
+def sample_gather_rows(table: torch.Tensor, row: torch.Tensor, cols=None) -> torch.Tensor:
+    """out float32 [T, C] of svoxt_gather_rows: out[k, j] = table[row[k], cols[j]], zeros where row[k] is outside [0, M).
+    table float32 [M, K] contiguous, row int32 [T], cols int32 [C] or None (all K)."""
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError("table must be float32 [M, K], K >= 1")
+    if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
+        raise RuntimeError("row must be int32 [T]")
+    _check_input(table, "table")
+    _check_input(row, "row")
+    dev = table.device
+    if row.device != dev:
+        raise RuntimeError("row must be on the device of the table")
+    (M, K), T = table.shape, row.shape[0]
+    C = _check_cols(cols, K, dev)
+    with _on(dev):
+        out = torch.empty((T, C), dtype=torch.float32, device=dev)
+        _call("svoxt_gather_rows", _ptr(table), M, K, _ptr(row), T, _ptr(cols), 0 if cols is None else C, _ptr(out), _stream(dev))
+    return out
+
+
+def sample_reduce_rows(values: torch.Tensor, plan: RowPlanArrays, op: str = "sum", empty: float = 0.0, cols=None, K=None) -> torch.Tensor:
+    """out float32 [M, K] of svoxt_reduce_rows for values float32 [T, C] over a plan.  Without cols K = C; with cols
+    (int32 [C] distinct columns of a table of K columns) column j lands in out[:, cols[j]], everything else is 0."""
+    if op not in ROWS_OPS:
+        raise RuntimeError(f"op must be one of {sorted(ROWS_OPS)}")
+    if not isinstance(plan, RowPlanArrays):
+        raise RuntimeError("plan must be a row plan")
+    T, M = plan.T, plan.M
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != T or values.shape[1] < 1:
+        raise RuntimeError(f"values must be float32 [T, C] with T = {T} samples and C >= 1")
+    _check_input(values, "values")
+    dev = values.device
+    if plan.row_ptr.device != dev:
+        raise RuntimeError("values must be on the device of the plan")
+    C = values.shape[1]
+    if cols is None:
+        K = C
+    elif _check_cols(cols, int(K), dev) != C:
+        raise RuntimeError("values must have one column per selected column")
+    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
+    with _on(dev):
+        out = torch.empty((M, K), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_reduce_rows_workspace_bytes(n_chunks, C)
+        ws = _workspace(dev, nbytes, "reduce_rows: chunks * C must be below 2^38")
+        _call("svoxt_reduce_rows", _ptr(values), T, C, _ptr(plan.row_ptr), _ptr(plan.perm), M, _ptr(plan.long_rows),
+              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(cols), 0 if cols is None else C, int(K),
+              ROWS_OPS[op], float(empty), _ptr(out), _ptr(ws), nbytes, _stream(dev))
+    return out

@@ -1,13 +1,15 @@
 """The per-sample interface: march -> samples -> weights from density -> accumulate along rays.
 
     samples = renderer.ray_samples(rays, min_sigma=0.0)            # RaySamples: CSR lists of the leaf crossings
-    sigma = features[samples.row.long(), -1]                       # any per-sample density, through torch indexing
-    w, alpha = sample_weights(samples, sigma)                      # w_k = T_k (1 - exp(-length_k sigma_k)), alpha = 1 - T_end
+    f = gather_rows(samples, features)                             # [T, K]: the feature row of every sample
+    w, alpha = sample_weights(samples, f[:, -1])                   # w_k = T_k (1 - exp(-length_k sigma_k)), alpha = 1 - T_end
     out = accumulate(samples, w, values)                           # out[q] = sum_k w_k values_k over ray q's samples
-    out, alpha, w = composite(samples, sigma, values)              # the two chained
+    out, alpha, w = composite(samples, f[:, -1], values)           # the two chained
+    wmax = reduce_rows(samples, w.detach(), M, "max")              # [M]: a per-row statistic of per-sample values
 
-Every per-sample loss is then a few lines of torch around three HIP operators; a per-leaf statistic is
-`torch.zeros(M).index_reduce_(0, samples.row.long(), w, "amax")`.  There is no CPU path.
+Every per-sample loss is then a few lines of torch around HIP operators whose results, gradients included, have the same
+bits in every run: the gradient of gather_rows reaches the table through reduce_rows' fixed-order row plan (DESIGN.md
+4.21), not through float atomics.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -51,6 +53,39 @@ class RaySamples:
     def counts(self):
         """int64 [Q]: the number of samples of every ray."""
         return self.offsets[1:] - self.offsets[:-1]
+
+    def row_plan(self, M: int) -> "RowPlan":
+        """The RowPlan of these lists for a feature table of M rows: for every row the samples that name it, in
+        ascending sample index.  Built on the GPU with one host read and cached on this object per M: the tensors of
+        a RaySamples are not meant to be edited -- a plan built before an edit of `row` describes the old rows."""
+        M = _C._extras._check_rows_extent(M, "row_plan")
+        if not self.row.is_cuda:
+            raise RuntimeError("row_plan: only the GPU (HIP) path exists; the samples must be on the GPU")
+        plans = self.__dict__.setdefault("_row_plans", {})
+        if M not in plans:
+            plans[M] = RowPlan(_C.row_plan(self.row.contiguous(), M))
+        return plans[M]
+
+
+class RowPlan:
+    """The inverse of a RaySamples' `row` list for a table of M rows (include/svoxt.h, "the row plan").
+
+    row_ptr   int32 [M + 1]   row r's samples are perm[row_ptr[r]] .. perm[row_ptr[r + 1] - 1], in ascending sample index
+    perm      int32 [T]       the sample indices sorted stably by key: `row` where 0 <= row < M, M for anything else
+    n_outside, longest        the samples whose row lies outside [0, M) (they sort behind row_ptr[M] and take no part in
+                              anything), and the length of the longest segment
+    Rows of more than 256 samples are listed (long_rows, long_chunk_ptr, chunk_long): reduce_rows sums them in chunks."""
+
+    def __init__(self, arrays):
+        self.arrays = arrays
+        self.row_ptr, self.perm, self.M, self.T = arrays.row_ptr, arrays.perm, arrays.M, arrays.T
+        self.n_outside, self.longest = arrays.n_outside, arrays.longest
+        self.long_rows, self.long_chunk_ptr, self.chunk_long = arrays.long_rows, arrays.long_chunk_ptr, arrays.chunk_long
+
+    @property
+    def counts(self):
+        """int32 [M]: the number of samples of every row."""
+        return self.row_ptr[1:] - self.row_ptr[:-1]
 
 
 def _ray_samples(self, rays: Rays, *, features=None, min_sigma=None, image_shape=None, sort_rays=None) -> RaySamples:
@@ -157,3 +192,93 @@ def composite(samples: RaySamples, sigma, values=None):
     """(out, alpha, w): accumulate(samples, w, values) with (w, alpha) = sample_weights(samples, sigma)."""
     w, alpha = sample_weights(samples, sigma)
     return accumulate(samples, w, values), alpha, w
+
+
+# ----------------------------------------------------------------------------------------- samples to rows and back
+def _columns(dim, K, dev, what):
+    """`dim` (None, int, slice, list or tensor, N3Tree.tv's convention) -> int32 distinct columns on `dev`, None for all."""
+    if dim is None:
+        return None
+    if isinstance(dim, torch.Tensor):
+        dim = dim.cpu()
+    try:
+        picked = torch.arange(K)[dim].reshape(-1)
+    except (IndexError, TypeError) as e:
+        raise RuntimeError(f"{what}: dim does not select columns of a table of {K}: {e}") from None
+    if picked.numel() == 0:
+        raise RuntimeError(f"{what}: dim selects no column")
+    if picked.unique().numel() != picked.numel():
+        raise RuntimeError(f"{what}: dim selects a column twice")
+    return picked.to(device=dev, dtype=torch.int32)
+
+
+class _GatherRowsFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, table, samples, cols):
+        ctx.samples, ctx.cols, ctx.shape = samples, cols, tuple(table.shape)
+        return _C.sample_gather_rows(table.contiguous(), samples.row, cols)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        M, K = ctx.shape
+        plan = ctx.samples.row_plan(M)
+        return _C.sample_reduce_rows(grad_out.contiguous(), plan.arrays, "sum", 0.0, ctx.cols, K), None, None
+
+
+class _ReduceRowsFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, values, samples, M, op, empty):
+        plan = samples.row_plan(M)
+        ctx.samples, ctx.plan, ctx.op = samples, plan, op
+        return _C.sample_reduce_rows(values.contiguous(), plan.arrays, op, empty)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g = grad_out
+        if ctx.op == "mean":                                    # (rows without a sample are gathered by no one)
+            g = g / ctx.plan.counts.clamp(min=1).to(torch.float32)[:, None]
+        return _C.sample_gather_rows(g.contiguous(), ctx.samples.row, None), None, None, None, None
+
+
+def gather_rows(samples: RaySamples, table, dim=None):
+    """out float32 [T, C]: out[k, j] = table[samples.row[k], cols[j]] -- the feature row of every sample.  `dim` selects
+    the columns as N3Tree.tv's does (int, slice, list or tensor of distinct columns; None: all K); the column axis is
+    kept, gather_rows(s, features, dim=-1)[:, 0] is sigma.  A sample whose row is outside [0, M) gets zeros.
+
+    Differentiable in `table`: the gradient is a full [M, K] table, reduce_rows(op="sum") of the upstream gradient at
+    the selected columns and 0 everywhere else, summed per row in the fixed order of include/svoxt.h over the cached
+    row plan -- no atomics, the same bits in every run."""
+    _require_gpu("gather_rows", samples, table if isinstance(table, torch.Tensor) else None)
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError("gather_rows: table must be float32 [M, K], K >= 1")
+    cols = _columns(dim, table.shape[1], table.device, "gather_rows")
+    return _GatherRowsFunction.apply(table, samples, cols)
+
+
+def reduce_rows(samples: RaySamples, values, M: int, op: str = "sum", empty: float = 0.0):
+    """out float32 [M, C] from per-sample values float32 [T, C] ([T]: the result is [M]): per feature row the "sum",
+    "mean", "max" or "min" over the samples that name it, `empty` for rows without a sample.  Gather only, in the order
+    include/svoxt.h defines: samples in ascending index; a sum in chunks of 256 samples, each added sequentially from
+    0, the chunks' partials added in chunk order (the plain sequential sum up to 256 samples); the mean divides that
+    sum once by the count; max / min are NaN as soon as one value of the row is.  Samples whose row is outside [0, M)
+    take no part.  "sum" and "mean" are differentiable in `values` (the gradient is gather_rows of the upstream
+    gradient, divided by the row's count for the mean); "max" and "min" return a tensor without gradient."""
+    _require_gpu("reduce_rows", samples, values if isinstance(values, torch.Tensor) else None)
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() not in (1, 2) \
+            or values.shape[0] != len(samples) or (values.dim() == 2 and values.shape[1] < 1):
+        raise RuntimeError("reduce_rows: values must be float32 [T] or [T, C], one row per sample, C >= 1")
+    if op not in _C._extras.ROWS_OPS:
+        raise RuntimeError(f"reduce_rows: op must be one of {sorted(_C._extras.ROWS_OPS)}")
+    M = _C._extras._check_rows_extent(M, "reduce_rows")
+    empty = float(empty)
+    flat = values.dim() == 1
+    v = values[:, None] if flat else values
+    if op in ("max", "min"):
+        out = _C.sample_reduce_rows(v.detach().contiguous(), samples.row_plan(M).arrays, op, empty)
+    else:
+        out = _ReduceRowsFunction.apply(v, samples, M, op, empty)
+    return out[:, 0] if flat else out

@@ -576,6 +576,23 @@ class N3Tree(nn.Module):
             self._invalidate()
         return SubdivideResult(self.filled, added, rows_added, row_map)
 
+    def spread_rows(self, per_row, empty=0.0):
+        """A per-row statistic (float32 [M'], e.g. reduce_rows(samples, w, M, "max")) as a per-slot map, float32 with
+        the shape of `child` -- what prune(weights=) and subdivide(weights=) take: a leaf slot whose data word names a
+        row below per_row.shape[0] holds per_row[word], every other slot holds `empty`.  Torch ops, under no_grad."""
+        if not isinstance(per_row, torch.Tensor) or per_row.dtype != torch.float32 or per_row.dim() != 1:
+            raise RuntimeError("spread_rows: per_row must be float32 [M], one entry per feature row")
+        if per_row.device != self.data.device:
+            raise RuntimeError("spread_rows: per_row must be on the device of the tree")
+        with torch.no_grad():
+            n = per_row.shape[0]
+            words = self.data[..., 0].long()
+            named = (self.child == 0) & (words >= 0) & (words < n)
+            out = torch.full(self.child.shape, float(empty), dtype=torch.float32, device=self.data.device)
+            if n > 0:
+                out[named] = per_row[words[named]]
+        return out
+
     def unshare(self):
         """Give every non-empty leaf a feature row of its own (csrc/svoxt_subdivide.hip): of the leaf slots that name
         one row the slot with the smallest flat index keeps it (an integer atomicMin per row: the same result in every
