@@ -1332,6 +1332,71 @@ int svoxt_reduce_rows(const float* values, int64_t T, int32_t C, const int32_t* 
                       int64_t n_chunks, const int32_t* cols, int32_t n_cols, int32_t K, int32_t op, float empty,
                       float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The deterministic render backward: sums by the row plan, not atomics (not in the reference) ------
+ * The gradient of svoxt_volume_render_fwd / svoxt_opacity_render_fwd with respect to the feature table,
+ *   grad[r, j] = the sum, over the samples that name row r, of the sample's contribution to column j,
+ * the same function of (tree, features, rays in index order, options, grad_out) in every run: it does not depend on the
+ * assignment of rays to lanes (rays.order, the image hint), on a pool or a previous call, or on the device's size.
+ *   The samples      the leaf crossings with a feature row and sigma > 0.f: no threshold, no early stop, whatever the
+ *                    options say (the convention of svoxt_volume_render_bwd).
+ *   A contribution   float32, no contraction, the operations of the reference's trace_ray_backward (rt_kernel.cu:331-496)
+ *                    one by one: att = expf(-delta_t * sigma * delta_scale); weight = light * (1 - att); per channel c
+ *                    tmp = sum over i = min_comp .. max_comp of basis[i] * row[c * basis_dim + i] from 0.f (RGBA: row[c]),
+ *                    sig = (float)(1.0 / (1.0 + (double)expf(-tmp))), gsig = (float)((double)sig * (1.0 - (double)sig));
+ *                    colour column (c, i): weight * basis[i] * gsig * g[c]  (RGBA column j: weight * sig * (1.f - sig) *
+ *                    g[j]); sigma column: delta_t * delta_scale * (total_color * light - accum) + delta_t * delta_scale *
+ *                    g[C] * light_ray, accum and total_color as the reference's two passes form them.
+ *   The order        svoxt_reduce_rows' rule, word for word: a row's samples run in ascending sample index (ray index
+ *                    first, then march order within the ray); chunks of SVOXT_ROW_CHUNK = 256 are each added sequentially
+ *                    from 0.f; the chunk partials are added in chunk order.
+ *   Every element of grad [M, K] is written: the caller need not clear it.  Columns outside [min_comp, max_comp] of a
+ *   channel, columns between C * basis_dim and K - 1, and rows no sample names are exactly 0.f.  With a row stride
+ *   above K the floats between the rows are not touched.
+ * grad_out is float32 [Q, grad_cols], grad_cols = C + 1 = svoxt_out_data_dim, or 1: the opacity backward (C = 0).
+ * tree.xform (transformation_matrices) is not served: SVOXT_ERR_INVALID.  The five steps, in this order, each on `stream`:
+ *   svoxt_render_grad_rows_count    offsets int64 [Q + 1] (device) of the sample lists: svoxt_ray_samples_count with
+ *                                   min_sigma = 0 and its workspace, svoxt_ray_samples_workspace_bytes(Q).  The caller
+ *                                   reads T = offsets[Q] (the one host read; from 2^31 on: split the batch).
+ *   svoxt_render_grad_rows_emit     marches again and leaves per sample row, ray and delta_t, per ray its basis values
+ *                                   and delta_scale, in the workspace: svoxt_render_grad_rows_workspace_bytes(Q, T, M, K,
+ *                                   C, basis_dim) device bytes, 8-byte aligned, the same workspace for every step
+ *                                   (basis_dim: the options' for SH / SG / ASG with C > 0, else 0; -1: an argument
+ *                                   negative or from 2^31, K < 1, C outside [0, K), basis_dim above 25, T * (C + 1) or
+ *                                   M * K from 2^38; 0 for T = 0).  Per sample it holds 4 * (C + 4) bytes (row, ray,
+ *                                   weight, the sigma contribution, C channel values) and the plan's perm, per ray
+ *                                   basis_dim + 1 floats, the plan's own arrays and svoxt_row_plan_build's workspace.
+ *                                   No [T, K] array exists at any point.
+ *   svoxt_render_grad_rows_plan     svoxt_row_plan_build over the emitted rows; info int64 [4] (device) as there: the
+ *                                   caller reads n_long = info[2] and n_chunks = info[3] (the plan's one host read).
+ *   svoxt_render_grad_rows_sweep    AFTER the plan and ONCE per emit (it overwrites row, delta_t and what the plan's sort
+ *                                   left behind: a plan built after it, or a second sweep, gives wrong sums silently): a lane per (sample, channel) shades, a lane per sample
+ *                                   forms its total_color the two ways the reference's passes do, a lane per ray runs the
+ *                                   two passes; leaves per sample the weight, the sigma contribution and per channel gsig
+ *                                   (RGBA: sig).  It may be queued before info is read.
+ *   svoxt_render_grad_rows_reduce   after the sweep: svoxt_row_plan_long, then a lane per (row, column) sums the row's
+ *                                   contributions, formed on the fly, into grad (row stride grad_stride floats, 0: K).
+ *                                   T = 0: zeros, the workspace may be NULL and no other step is needed.
+ * Checked: the tree, rays and options as svoxt_volume_render_bwd checks them; tree.xform NULL; Q, M, T below 2^31;
+ * grad_cols >= 1 and, above 1, equal to svoxt_out_data_dim; offsets / grad_out not NULL with Q > 0; info / grad not NULL;
+ * grad_stride 0 or >= K; n_long / n_chunks as svoxt_row_plan_long; the workspace's size.  No allocation, no
+ * synchronisation. */
+int64_t svoxt_render_grad_rows_workspace_bytes(int64_t Q, int64_t T, int64_t M, int32_t K, int32_t C, int32_t basis_dim);
+int svoxt_render_grad_rows_count(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int64_t* offsets,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_render_grad_rows_emit(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                const int64_t* offsets, int64_t T, const float* grad_out, int32_t grad_cols,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_render_grad_rows_plan(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                const int64_t* offsets, int64_t T, const float* grad_out, int32_t grad_cols, int64_t* info,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_render_grad_rows_sweep(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                 const int64_t* offsets, int64_t T, const float* grad_out, int32_t grad_cols,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                  const int64_t* offsets, int64_t T, const float* grad_out, int32_t grad_cols,
+                                  int64_t n_long, int64_t n_chunks, float* grad, int32_t grad_stride, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

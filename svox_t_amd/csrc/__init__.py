@@ -1188,4 +1188,5 @@ from ._extras import distortion, distortion_backward  # noqa: E402,F401
 from ._extras import (ray_samples, sample_accumulate, sample_accumulate_backward, sample_weights,  # noqa: E402,F401
                       sample_weights_backward)
 from ._extras import RowPlanArrays, row_plan, sample_gather_rows, sample_reduce_rows  # noqa: E402,F401
+from ._extras import volume_render_backward_rows  # noqa: E402,F401
 from . import _extras  # noqa: E402,F401

@@ -213,6 +213,13 @@ EXPORTS = {
     "svoxt_reduce_rows_workspace_bytes": (_i64, [_i64, _i32]),
     "svoxt_reduce_rows": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _i32,
                                          ctypes.c_float, _vp, _vp, _i64, _vp]),
+    "svoxt_render_grad_rows_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "svoxt_render_grad_rows_count": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _i64, _vp]),
+    "svoxt_render_grad_rows_emit": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_render_grad_rows_plan": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "svoxt_render_grad_rows_sweep": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_render_grad_rows_reduce": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32,
+                                                     _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

@@ -11,7 +11,7 @@ import torch
 
 from ._abi import _CMotion, _COptimHyper, _CRays, _CTree, _lib
 from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _check_quantize, _numel, _pack_opts, _pack_rays,
-                       _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
+                       get_out_data_dim, _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
 
 def _check_indices(indices):
     """check_indices (svox_kernel.cu:36-40)."""
@@ -1593,3 +1593,80 @@ def sample_reduce_rows(values: torch.Tensor, plan: RowPlanArrays, op: str = "sum
               _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(cols), 0 if cols is None else C, int(K),
               ROWS_OPS[op], float(empty), _ptr(out), _ptr(ws), nbytes, _stream(dev))
     return out
+
+
+# ---------------------------------------------------------------------------
+# The deterministic render backward (svoxt_rowgrad.hip; not in the reference; DESIGN.md 4.22)
+# ---------------------------------------------------------------------------
+ROWGRAD_LAST = {}             # what the last call allocated and found: Q, T, bytes, per-sample bytes, n_long, n_chunks, longest
+
+
+def volume_render_backward_rows(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions, grad_output: torch.Tensor, grad=None,
+                                timers=None) -> torch.Tensor:
+    """[M, K] gradient of volume_render (grad_output [Q, C + 1]) or opacity_render (grad_output [Q, 1]) with respect to
+    the feature table, bit-identical from run to run: every sample's contribution has the arithmetic of
+    volume_render_backward's generic kernel, and a table entry is their sum in svoxt_reduce_rows' order over the row plan
+    of the batch's sample lists (include/svoxt.h, svoxt_render_grad_rows_*).  The bits depend on the tree, the features,
+    the rays in index order, the options and grad_output -- not on RaysSpec.sort, an image hint, list capacities or pools.
+    Two host reads (the number of samples, the plan's info record); 2^31 samples or more raise before anything is
+    allocated for them.  transformation_matrices are not served.  `grad`: a float32 [M, >= K] buffer to write into (its
+    first K columns; the rest is not touched) instead of a new tensor.  `timers`: a function called with a step's name
+    before each of the five steps (measurement scripts)."""
+    import svox_t_amd.csrc as csrc
+    if _numel(tree.transformation_matrices):
+        raise RuntimeError("volume_render_backward_rows: transformation_matrices are not served by the deterministic backward "
+                           "(deterministic=True); use the default backward")
+    _check_input(grad_output, "grad_output")
+    Q = _spec_ray_count(rays)
+    if grad_output.dtype != torch.float32 or grad_output.dim() != 2 or grad_output.shape[0] != Q:
+        raise RuntimeError(f"grad_output must be float32 [Q, C + 1] (or [Q, 1]) with Q = {Q} rays")
+    cols = grad_output.shape[1]
+    M, K = tree.features.shape
+    want = get_out_data_dim(opt, K)
+    if cols != 1 and cols != want:
+        raise RuntimeError(f"grad_output must have {want} columns (get_out_data_dim), or 1 for the opacity backward")
+    C = cols - 1
+    bd = int(opt.basis_dim) if (int(opt.format) != 0 and C > 0) else 0
+    # (any walk gives the same lists: the coherent one marches fastest)
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    tick = timers if timers is not None else (lambda _name: None)
+    with _on(dev):
+        stride = 0
+        if grad is None:
+            grad = torch.empty((M, K), dtype=torch.float32, device=dev)
+        else:
+            if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or grad.dim() != 2 or grad.shape[0] != M \
+                    or grad.shape[1] < K or not grad.is_contiguous() or grad.device != dev:
+                raise RuntimeError("grad must be a contiguous float32 [M, >= K] tensor on the device of the features")
+            stride = grad.shape[1]
+        T = 0
+        offsets = None
+        tick("count")
+        if Q > 0:
+            offsets = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+            cws = _workspace(dev, _lib.svoxt_ray_samples_workspace_bytes(Q), "deterministic backward: the batch must have fewer than 2^31 rays")
+            _call("svoxt_render_grad_rows_count", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(offsets), _ptr(cws),
+                  cws.numel(), _stream(dev))
+            T = int(offsets[Q].item())                  # host read 1
+            if T >= 1 << 31:
+                raise RuntimeError(f"deterministic backward: {T} samples; a batch's lists hold fewer than 2^31 (split the batch)")
+        nbytes = _lib.svoxt_render_grad_rows_workspace_bytes(Q, T, M, K, C, bd)
+        ws = _workspace(dev, nbytes, "deterministic backward: T * (C + 1) and M * K must be below 2^38") if T > 0 else None
+        args = (ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(offsets), T, _ptr(grad_output), cols)
+        n_long = n_chunks = longest = 0
+        if T > 0:
+            tick("emit")
+            _call("svoxt_render_grad_rows_emit", *args, _ptr(ws), nbytes, _stream(dev))
+            tick("plan")
+            info = torch.empty((4,), dtype=torch.int64, device=dev)
+            _call("svoxt_render_grad_rows_plan", *args, _ptr(info), _ptr(ws), nbytes, _stream(dev))
+            tick("sweep")
+            _call("svoxt_render_grad_rows_sweep", *args, _ptr(ws), nbytes, _stream(dev))      # (queued in front of the read)
+            _, longest, n_long, n_chunks = (int(v) for v in info.tolist())        # host read 2
+        tick("reduce")
+        _call("svoxt_render_grad_rows_reduce", *args, n_long, n_chunks, _ptr(grad), stride, _ptr(ws), nbytes, _stream(dev))
+        tick(None)
+    ROWGRAD_LAST.update(Q=Q, T=T, bytes=int(nbytes), n_long=n_long, n_chunks=n_chunks, longest=longest)
+    return grad

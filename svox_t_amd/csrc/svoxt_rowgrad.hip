@@ -1,0 +1,414 @@
+// svoxt_rowgrad.hip -- the deterministic render backward (not in the reference): the gradient of
+// volume_render / opacity_render with respect to the feature table, every sample's contribution formed with the
+// arithmetic of render_bwd_generic_kernel (the reference's trace_ray_backward, rt_kernel.cu:331-496), operation for
+// operation, and summed per table entry over the row plan in svoxt_reduce_rows' order -- no float atomic anywhere.
+//
+//   count     svoxt_ray_samples_count with min_sigma = 0: the crossings with sigma > 0.f, as CSR offsets in ray-index order
+//   emit      rowgrad_record_kernel   a lane per ray on the shared march: row, ray and delta_t at offsets[q] + k, the
+//                                     ray's basis values and delta_scale once
+//   plan      svoxt_row_plan_build over the emitted rows (its one host read: the info record)
+//   sweep     rowgrad_shade_kernel    a lane per (sample, channel): e = pexpf(-sum_i basis[i] * row[off + i]) (RGBA:
+//                                     pexpf(-row[j])); the lane behind a sample's channels: att = pexpf(-delta_t * sigma *
+//                                     delta_scale).  The row reads of a sample's lanes fall into the same cache lines.
+//             rowgrad_totals_kernel   a lane per sample over its channels in order: total_color as pass 1 sums it (float)
+//                                     and as pass 2 does (through double), and gsig (RGBA: sig) in the place of e.  The
+//                                     two totals go where `row` was (the plan is built, the rows are shaded) and into a
+//                                     sort buffer of the plan's workspace that its build has left free.
+//             rowgrad_sweep_kernel    a lane per ray over its list, the generic kernel's two passes over four floats a
+//                                     sample: pass 1 forms accum and the ray's final light, pass 2 leaves per sample the
+//                                     weight and the sigma contribution in the places of delta_t and att
+//   reduce    svoxt_row_plan_long and the row kernels of svoxt_rowwalk.h, a lane per (row, column), the value of sample k
+//             at column j formed on the fly (GradValues): a colour column weight[k] * basis[ray[k], i] * gsig[k, c] *
+//             g[ray[k], c] (RGBA: weight[k] * sig * (1.f - sig) * g[ray[k], j]), the sigma column the stored contribution,
+//             every other column 0.f.  No [T, K] array exists at any point.
+// Per sample 4 * (C + 4) bytes (row, ray, weight, sigma contribution, C channel values) and the plan's perm; per ray
+// basis_dim + 1 floats.  C ABI: svoxt_render_grad_rows_* (include/svoxt.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "svoxt_device.h"
+#include "svoxt_host.h"
+#include "svoxt_launch.h"
+#include "svoxt_rowwalk.h"
+#include "svoxt_workspace.h"
+
+#pragma clang fp contract(off)
+
+namespace svoxt {
+
+// workspace: per ray [basis f32[Q * bd]] [dscale f32[Q]]; per sample [row] [ray] [wgt] [sigc] [chan f32[T * C]]; the plan
+// [perm] [row_ptr i32[M + 1]] [long_rows] [long_chunk_ptr] [chunk_long] [partials f32[chunks * K]] and svoxt_row_plan_build's
+// own workspace.  The long rows' pieces are sized by their bounds (T / 257 long rows, T / 256 + T / 257 chunks).
+struct RowGradSpace {
+    float *basis, *dscale;
+    int32_t *row, *ray;
+    float *wgt, *sigc, *chan;
+    int32_t *perm, *row_ptr, *long_rows, *long_chunk_ptr, *chunk_long;
+    float* partials;
+    void* plan;
+    int64_t plan_bytes, n_long_max, n_chunks_max;
+    size_t bytes;
+};
+static RowGradSpace rowgrad_carve(void* workspace, int64_t Q, int64_t T, int64_t M, int K, int C, int bd) {
+    RowGradSpace sp;
+    Carver w(workspace);
+    sp.n_long_max = T / (kRowChunk + 1);
+    sp.n_chunks_max = T / kRowChunk + sp.n_long_max;
+    sp.basis = w.take<float>((size_t)Q * (size_t)bd);
+    sp.dscale = w.take<float>((size_t)Q);
+    sp.row = w.take<int32_t>((size_t)T);
+    sp.ray = w.take<int32_t>((size_t)T);
+    sp.wgt = w.take<float>((size_t)T);
+    sp.sigc = w.take<float>((size_t)T);
+    sp.chan = w.take<float>((size_t)T * (size_t)C);
+    sp.perm = w.take<int32_t>((size_t)T);
+    sp.row_ptr = w.take<int32_t>((size_t)M + 1);
+    sp.long_rows = w.take<int32_t>((size_t)sp.n_long_max);
+    sp.long_chunk_ptr = w.take<int32_t>((size_t)sp.n_long_max + 1);
+    sp.chunk_long = w.take<int32_t>((size_t)sp.n_chunks_max);
+    sp.partials = w.take<float>((size_t)sp.n_chunks_max * (size_t)K);
+    sp.plan_bytes = svoxt_row_plan_workspace_bytes(T, M);
+    sp.plan = w.take<char>((size_t)sp.plan_bytes);
+    sp.bytes = w.bytes();
+    return sp;
+}
+
+// ------------------------------------------------------------------------------------------------------------- record
+// The crossings svoxt_ray_samples_count counted with min_sigma = 0 (valid, sigma > 0.f), in march order.
+template <bool N2>
+__global__ void __launch_bounds__(kBlock)
+rowgrad_record_kernel(TreeDev tr, RaysDev rays, Opts opt, int bd, const int64_t* __restrict__ offsets, int64_t T,
+                      int32_t* __restrict__ row, int32_t* __restrict__ ray, float* __restrict__ dt, float* __restrict__ basis,
+                      float* __restrict__ dscale) {
+    const int64_t q = ray_of_thread(rays, (int64_t)blockIdx.x * kBlock + threadIdx.x);
+    if (q >= rays.Q) return;
+    Ray r;
+    if (!setup_ray(tr, rays, opt, q, r)) return;                 // (no sample: nothing reads this ray's basis or scale)
+    int64_t at = offsets[q];
+    const int64_t end = min(offsets[q + 1], T);
+    if (at < 0 || at >= end) return;
+    dscale[q] = r.delta_scale;
+    if (bd > 0) {
+        float vd[3];
+        load_vdir(rays, q, vd);
+        precalc_basis<0>(opt.format, bd, tr, vd[0], vd[1], vd[2], basis + q * bd);
+    }
+    const int K = tr.K;
+    float t = r.tmin;
+    while (t < r.tmax) {
+        Sample s;
+        march_step<N2>(tr, r, opt.step_size, t, s);
+        if (s.valid && tr.features[(int64_t)s.idx * K + (K - 1)] > 0.f && at < end) {
+            row[at] = s.idx;
+            ray[at] = (int32_t)q;
+            dt[at] = s.delta_t;
+            ++at;
+        }
+        t = march_advance(t, s.delta_t);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------- shade
+// lane t = k * (C + 1) + c.  c < C: chan[k, c] = e of channel c; c == C: att[k]
+__global__ void __launch_bounds__(kLaunchBlock)
+rowgrad_shade_kernel(const float* __restrict__ features, int64_t M, int K, Opts opt, int C, int bd, int64_t Q, int64_t T,
+                     const int32_t* __restrict__ row, const int32_t* __restrict__ ray, const float* __restrict__ dt,
+                     const float* __restrict__ basis, const float* __restrict__ dscale, float* __restrict__ att,
+                     float* __restrict__ chan) {
+    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t k = t / (C + 1);
+    if (k >= T) return;
+    const int c = (int)(t - k * (C + 1));
+    const int64_t idx = row[k], q = ray[k];
+    if (idx < 0 || idx >= M || q < 0 || q >= Q) return;          // (the record kernel wrote both in range)
+    const float* __restrict__ frow = features + idx * K;
+    if (c == C) {
+        att[k] = pexpf(-dt[k] * frow[K - 1] * dscale[q]);
+        return;
+    }
+    float x;
+    if (opt.format != FMT_RGBA) {
+        const float* __restrict__ b = basis + q * bd;
+        const int off = c * bd;
+        float tmp = 0.f;
+        for (int i = opt.min_comp; i <= opt.max_comp; ++i) tmp += b[i] * frow[off + i];
+        x = tmp;
+    } else {
+        x = frow[c];
+    }
+    chan[k * C + c] = pexpf(-x);
+}
+
+// ------------------------------------------------------------------------------------------------------------- totals
+// A lane per sample over its channels in ascending order; in: chan = e.  out: chan = gsig (RGBA: sig), tc1 / tc2 = the
+// sample's total_color as the reference's pass 1 / pass 2 forms it.
+__global__ void __launch_bounds__(kLaunchBlock)
+rowgrad_totals_kernel(Opts opt, int C, int64_t Q, int64_t T, const int32_t* __restrict__ ray, const float* __restrict__ grad_out,
+                      float* __restrict__ chan, float* __restrict__ tc1, float* __restrict__ tc2) {
+    const int64_t k = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (k >= T) return;
+    const int64_t q = ray[k];
+    if (q < 0 || q >= Q) return;                                 // (the record kernel's own index: never)
+    const float* __restrict__ g = grad_out + q * (C + 1);
+    float* __restrict__ ch = chan + k * C;
+    const bool rgba = opt.format == FMT_RGBA;
+    float t1 = 0.f, t2 = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const double d = 1.0 / (1.0 + (double)ch[c]);
+        const float sig = (float)d;
+        t1 += sig * g[c];
+        t2 = (float)((double)t2 + d * (double)g[c]);
+        ch[c] = rgba ? sig : (float)((double)sig * (1.0 - (double)sig));
+    }
+    tc1[k] = t1;
+    tc2[k] = t2;
+}
+
+// -------------------------------------------------------------------------------------------------------------- sweep
+// A lane per ray over its list; in: wgt = delta_t, sigc = att.  out: wgt = weight, sigc = the sigma contribution.
+__global__ void __launch_bounds__(kBlock)
+rowgrad_sweep_kernel(Opts opt, int C, const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ grad_out,
+                     const float* __restrict__ dscale, const float* __restrict__ tc1, const float* __restrict__ tc2,
+                     float* __restrict__ wgt, float* __restrict__ sigc) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= Q) return;
+    const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+    if (b >= e) return;
+    const float* __restrict__ g = grad_out + q * (C + 1);
+    const float delta_scale = dscale[q];
+    float accum = 0.f;
+    float light_ray;
+    {   // pass 1
+        float light = 1.f;
+        for (int64_t k = b; k < e; ++k) {
+            const float att = sigc[k];
+            const float weight = light * (1.f - att);
+            const float total_color = tc1[k];
+            light *= att;
+            accum += weight * total_color;
+        }
+        float total_grad = 0.f;
+        for (int j = 0; j < C; ++j) total_grad += g[j];
+        accum += light * opt.background_brightness * total_grad;
+        light_ray = light;
+    }
+    {   // pass 2
+        float light = 1.f;
+        for (int64_t k = b; k < e; ++k) {
+            const float total_color = tc2[k];
+            const float att = sigc[k];
+            const float delta_t = wgt[k];
+            const float weight = light * (1.f - att);
+            light *= att;
+            accum -= weight * total_color;
+            const float toadd = delta_t * delta_scale * (total_color * light - accum)
+                              + delta_t * delta_scale * g[C] * light_ray;
+            wgt[k] = weight;
+            sigc[k] = toadd;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------- values
+// The contribution of sample k to column j of its row, for the row kernels of svoxt_rowwalk.h.
+struct GradValues {
+    const int32_t* __restrict__ ray;
+    const float* __restrict__ wgt;
+    const float* __restrict__ sigc;
+    const float* __restrict__ chan;
+    const float* __restrict__ basis;
+    const float* __restrict__ g;
+    int64_t T, Q;
+    int K, C, bd, min_comp, max_comp;
+    bool rgba;
+    enum { ZERO, SIGMA, BASIS, RGBA };
+    struct Col {
+        const int32_t* __restrict__ ray;
+        const float* __restrict__ wgt;
+        const float* __restrict__ v;       // SIGMA: sigc;  BASIS / RGBA: chan + c
+        const float* __restrict__ b;       // BASIS: basis + i
+        const float* __restrict__ g;       // grad_out + c
+        int64_t T, Q;
+        int mode, C, bd;
+        __device__ __forceinline__ float at(int64_t k) const {
+            if (mode == ZERO || k < 0 || k >= T) return 0.f;
+            if (mode == SIGMA) return v[k];
+            const int64_t q = ray[k];
+            if (q < 0 || q >= Q) return 0.f;                     // (the record kernel's own index: never)
+            const float gc = g[q * (C + 1)];
+            if (mode == BASIS) return wgt[k] * b[q * bd] * v[k * C] * gc;
+            const float sig = v[k * C];
+            return wgt[k] * sig * (1.f - sig) * gc;
+        }
+    };
+    __device__ __forceinline__ Col col(int j) const {
+        Col o{ray, wgt, sigc, basis, g, T, Q, ZERO, C, bd};
+        if (j == K - 1) {
+            o.mode = SIGMA;
+        } else if (rgba) {
+            if (j < C) { o.mode = RGBA; o.v = chan + j; o.g = g + j; }
+        } else if (C > 0 && j < C * bd) {
+            const int c = j / bd, i = j - c * bd;
+            if (i >= min_comp && i <= max_comp) { o.mode = BASIS; o.v = chan + c; o.b = basis + i; o.g = g + c; }
+        }
+        return o;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------- checks
+static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+
+// the basis values a ray keeps: none for RGBA rows and for the opacity backward
+static int basis_floats(const svoxt_options* opt, int C) { return (opt->format != SVOXT_FORMAT_RGBA && C > 0) ? opt->basis_dim : 0; }
+
+// What the steps share: the specs, grad_out [Q, C + 1], T samples in a workspace of the query's size.
+static int rowgrad_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets, int64_t T,
+                         const float* grad_out, int32_t grad_cols, const void* workspace, int64_t workspace_bytes, bool need_ws,
+                         const char* fn) {
+    int rc;
+    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, grad_cols > 1))) return rc;
+    if (tree->xform != nullptr) return fail(SVOXT_ERR_INVALID, "%s: transformation_matrices (tree.xform) are not served by the deterministic backward", fn);
+    if (rays->Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: too many rays (ray indices are int32)", fn);
+    if (tree->M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be below 2^31", fn);
+    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
+    const int C = grad_cols - 1;
+    if (C < 0) return fail(SVOXT_ERR_INVALID, "%s: grad_cols must be >= 1", fn);
+    if (C > 0 && svoxt_out_data_dim(opt, tree->K) != grad_cols)
+        return fail(SVOXT_ERR_INVALID, "%s: grad_out columns do not match get_out_data_dim (C + 1)", fn);
+    if ((double)T * (C + 1) >= 274877906944.0 || (double)tree->M * tree->K >= 274877906944.0)
+        return fail(SVOXT_ERR_INVALID, "%s: T * (C + 1) and M * K must be below 2^38", fn);
+    if (rays->Q > 0 && (offsets == nullptr || grad_out == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: offsets / grad_out is NULL", fn);
+    if (misaligned(offsets, 8) || misaligned(grad_out, 4)) return fail(SVOXT_ERR_INVALID, "%s: offsets (8 bytes) / grad_out (4 bytes) is misaligned", fn);
+    if (need_ws) {
+        if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
+        const int64_t need = svoxt_render_grad_rows_workspace_bytes(rays->Q, T, tree->M, tree->K, C, basis_floats(opt, C));
+        if ((rc = workspace_check(fn, workspace, workspace_bytes, need, "svoxt_render_grad_rows_workspace_bytes(Q, T, M, K, C, basis_dim)")))
+            return rc;
+    }
+    return SVOXT_OK;
+}
+
+}  // namespace svoxt
+
+using namespace svoxt;
+
+extern "C" {
+
+int64_t svoxt_render_grad_rows_workspace_bytes(int64_t Q, int64_t T, int64_t M, int32_t K, int32_t C, int32_t basis_dim) {
+    if (Q < 0 || Q > 0x7fffffffLL || T < 0 || T > 0x7fffffffLL || M < 0 || M > 0x7fffffffLL) return -1;
+    if (K < 1 || C < 0 || C >= K || basis_dim < 0 || basis_dim > 25) return -1;
+    if ((double)T * (C + 1) >= 274877906944.0 || (double)M * K >= 274877906944.0) return -1;
+    if (T == 0) return 0;
+    return (int64_t)rowgrad_carve(nullptr, Q, T, M, K, C, basis_dim).bytes;
+}
+
+int svoxt_render_grad_rows_count(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, int64_t* offsets,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_render_grad_rows_count";
+    if (tree != nullptr && tree->xform != nullptr)
+        return fail(SVOXT_ERR_INVALID, "%s: transformation_matrices (tree.xform) are not served by the deterministic backward", fn);
+    const float zero = 0.f;                                      // sigma > 0.f: the backward's sample set, whatever the thresholds say
+    return svoxt_ray_samples_count(tree, rays, opt, &zero, offsets, workspace, workspace_bytes, stream);
+}
+
+int svoxt_render_grad_rows_emit(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                int64_t T, const float* grad_out, int32_t grad_cols, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+    const char* fn = "svoxt_render_grad_rows_emit";
+    int rc;
+    if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, T > 0, fn))) return rc;
+    const int64_t Q = rays->Q;
+    if (Q == 0 || T == 0) return SVOXT_OK;
+    const int C = grad_cols - 1, bd = basis_floats(opt, C);
+    const RowGradSpace sp = rowgrad_carve(workspace, Q, T, tree->M, tree->K, C, bd);
+    const TreeDev tr = to_dev(tree);
+    const RaysDev rd = to_dev(rays, tree);
+    const Opts od = to_dev(opt);
+    hipStream_t st = (hipStream_t)stream;
+    with_bool(tree->N == 2, [&](auto N2) {
+        hipLaunchKernelGGL((rowgrad_record_kernel<N2.value>), dim3(nblocks(Q)), dim3(kBlock), 0, st, tr, rd, od, bd, offsets, T, sp.row, sp.ray,
+                           sp.wgt, sp.basis, sp.dscale);
+        return true;
+    });
+    return check_launch(fn);
+}
+
+int svoxt_render_grad_rows_plan(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                int64_t T, const float* grad_out, int32_t grad_cols, int64_t* info, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_render_grad_rows_plan";
+    int rc;
+    if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, T > 0, fn))) return rc;
+    if (info == nullptr || misaligned(info, 8)) return fail(SVOXT_ERR_INVALID, "%s: info is NULL or not 8-byte aligned", fn);
+    if (T == 0) {
+        const hipError_t e = hipMemsetAsync(info, 0, sizeof(int64_t) * 4, (hipStream_t)stream);
+        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+        return SVOXT_OK;
+    }
+    const int C = grad_cols - 1;
+    const RowGradSpace sp = rowgrad_carve(workspace, rays->Q, T, tree->M, tree->K, C, basis_floats(opt, C));
+    return svoxt_row_plan_build(sp.row, T, tree->M, sp.row_ptr, sp.perm, info, sp.plan, sp.plan_bytes, stream);
+}
+
+int svoxt_render_grad_rows_sweep(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                 int64_t T, const float* grad_out, int32_t grad_cols, void* workspace, int64_t workspace_bytes,
+                                 void* stream) {
+    const char* fn = "svoxt_render_grad_rows_sweep";
+    int rc;
+    if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, T > 0, fn))) return rc;
+    const int64_t Q = rays->Q;
+    if (Q == 0 || T == 0) return SVOXT_OK;
+    const int C = grad_cols - 1, bd = basis_floats(opt, C);
+    const RowGradSpace sp = rowgrad_carve(workspace, Q, T, tree->M, tree->K, C, bd);
+    const TreeDev tr = to_dev(tree);
+    const Opts od = to_dev(opt);
+    hipStream_t st = (hipStream_t)stream;
+    // the plan is built and the shade kernel is the last reader of `row`: the two totals of a sample go there and into the
+    // plan's free sort buffer
+    float* tc1 = reinterpret_cast<float*>(sp.row);
+    float* tc2 = reinterpret_cast<float*>(row_plan_sort_scratch(sp.plan, T, tree->M));
+    hipLaunchKernelGGL(rowgrad_shade_kernel, dim3(launch_blocks(T * (C + 1))), dim3(kLaunchBlock), 0, st, tr.features, tr.M, tr.K, od, C, bd, Q, T,
+                       sp.row, sp.ray, sp.wgt, sp.basis, sp.dscale, sp.sigc, sp.chan);
+    hipLaunchKernelGGL(rowgrad_totals_kernel, dim3(launch_blocks(T)), dim3(kLaunchBlock), 0, st, od, C, Q, T, sp.ray, grad_out, sp.chan, tc1, tc2);
+    hipLaunchKernelGGL(rowgrad_sweep_kernel, dim3(nblocks(Q)), dim3(kBlock), 0, st, od, C, offsets, Q, T, grad_out, sp.dscale, tc1, tc2, sp.wgt,
+                       sp.sigc);
+    return check_launch(fn);
+}
+
+int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                  int64_t T, const float* grad_out, int32_t grad_cols, int64_t n_long, int64_t n_chunks,
+                                  float* grad, int32_t grad_stride, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_render_grad_rows_reduce";
+    int rc;
+    if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, T > 0, fn))) return rc;
+    const int64_t M = tree->M;
+    const int K = tree->K;
+    const int gs = grad_stride > 0 ? grad_stride : K;
+    if (gs < K) return fail(SVOXT_ERR_INVALID, "%s: grad_stride smaller than data_dim", fn);
+    if ((double)M * gs >= 274877906944.0) return fail(SVOXT_ERR_INVALID, "%s: M * grad_stride must be below 2^38", fn);
+    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
+        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
+    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
+        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    if (M == 0) return SVOXT_OK;
+    if (grad == nullptr || misaligned(grad, 4)) return fail(SVOXT_ERR_INVALID, "%s: grad is NULL or not 4-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    if (T == 0) {                                                // no sample: zeros in the K columns of every row, the padding untouched
+        const hipError_t e = hipMemset2DAsync(grad, sizeof(float) * (size_t)gs, 0, sizeof(float) * (size_t)K, (size_t)M, st);
+        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemset2DAsync: %s", fn, hipGetErrorString(e));
+        return SVOXT_OK;
+    }
+    const int C = grad_cols - 1, bd = basis_floats(opt, C);
+    const RowGradSpace sp = rowgrad_carve(workspace, rays->Q, T, M, K, C, bd);
+    if ((rc = svoxt_row_plan_long(sp.row_ptr, T, M, n_long, n_chunks, sp.plan, sp.plan_bytes, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long,
+                                  stream)))
+        return rc;
+    const GradValues src{sp.ray, sp.wgt, sp.sigc, sp.chan, sp.basis, grad_out, T, rays->Q, K, C, bd, opt->min_comp, opt->max_comp,
+                         opt->format == SVOXT_FORMAT_RGBA};
+    // a lane per (row, column) over all K columns; the row stride stands where reduce_rows has its table's width
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, T, K, sp.row_ptr, sp.perm, M, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long, n_long, n_chunks,
+                                    nullptr, gs, 0.f, grad, sp.partials, st);
+    return check_launch(fn);
+}
+
+}  // extern "C"

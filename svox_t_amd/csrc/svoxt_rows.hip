@@ -15,22 +15,21 @@
 //                  (tv_rows_kernel's shape) for rows of at most SVOXT_ROW_CHUNK samples, and writes `empty` for rows
 //                  without one.  Long rows: rows_chunk_kernel, a lane per (chunk, column), leaves the chunk's partial in
 //                  the workspace; rows_join_kernel, a lane per (long row, column), joins them in chunk order.  The
-//                  order is part of the definition (include/svoxt.h; tests compare bits).
+//                  order is part of the definition (include/svoxt.h; tests compare bits).  The three kernels live in
+//                  svoxt_rowwalk.h, over any source of per-sample values; here the source is the [T, C] table.
 // C ABI: svoxt_row_plan_* / svoxt_gather_rows / svoxt_reduce_rows* (include/svoxt.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "svoxt_host.h"
 #include "svoxt_launch.h"
+#include "svoxt_rowwalk.h"
 #include "svoxt_sort.h"
 #include "svoxt_workspace.h"
 
 #pragma clang fp contract(off)
 
 namespace svoxt {
-
-constexpr int kRowChunk = SVOXT_ROW_CHUNK;
-enum { ROWS_SUM = SVOXT_ROWS_SUM, ROWS_MEAN = SVOXT_ROWS_MEAN, ROWS_MAX = SVOXT_ROWS_MAX, ROWS_MIN = SVOXT_ROWS_MIN };
 
 // workspace of the plan: [longest u32] (cleared) [keys u32[T]] x 2 [vals u32[T]] x 2 [counts] [starts] [chunk sums]
 // [flag u32[M + 1]] [rank] [nchunks] [cstart] [chunk sums]; svoxt_row_plan_long reads flag / rank / cstart
@@ -57,6 +56,13 @@ static RowPlanSpace row_plan_carve(void* workspace, int64_t T, int64_t M) {
     sp.bytes = w.bytes();
     return sp;
 }
+
+// (svoxt_rowwalk.h) INVARIANT the deterministic render backward (svoxt_rowgrad.hip) relies on: vals[0] is read and written by
+// the sort passes of svoxt_row_plan_build alone -- the last pass writes perm, row_ptr_kernel reads keys -- and
+// svoxt_row_plan_long reads flag / rank / cstart only.  From the build's last kernel on these T words are free, until the
+// next build over the same workspace.  Whoever changes the sort's buffers or what svoxt_row_plan_long reads keeps this true
+// or gives svoxt_rowgrad.hip a piece of its own.
+uint32_t* row_plan_sort_scratch(void* workspace, int64_t T, int64_t M) { return row_plan_carve(workspace, T, M).vals[0]; }
 
 // --------------------------------------------------------------------------------------------------------------- plan
 __global__ void __launch_bounds__(kLaunchBlock)
@@ -153,108 +159,6 @@ gather_rows4_kernel(const float4* __restrict__ table, int64_t M, int K4, const i
     const int j = (int)(t - k * K4);
     const int64_t r = row[k];
     out[t] = (r >= 0 && r < M) ? table[r * K4 + j] : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// ------------------------------------------------------------------------------------------------------------- reduce
-// One step of a row's walk.  SUM / MEAN: acc + v.  MAX / MIN: the larger / smaller, NaN as soon as either is.
-template <int OP>
-__device__ __forceinline__ float rows_step(float acc, float v) {
-    if constexpr (OP == ROWS_SUM || OP == ROWS_MEAN) return acc + v;
-    else if constexpr (OP == ROWS_MAX) return (v > acc || v != v) ? v : acc;
-    else return (v < acc || v != v) ? v : acc;
-}
-
-// the samples perm[b0 .. b1) of one chunk (or one short row) at column j of values [T, C]; b1 > b0
-template <int OP>
-__device__ __forceinline__ float rows_walk(const float* __restrict__ values, int64_t T, int C, int j, const int32_t* __restrict__ perm,
-                                           int32_t b0, int32_t b1) {
-    float acc = 0.f;
-    int32_t p = b0;
-    if constexpr (OP == ROWS_MAX || OP == ROWS_MIN) {
-        const int64_t k = perm[p++];
-        acc = (k >= 0 && k < T) ? values[k * C + j] : 0.f;
-    }
-#pragma unroll 4
-    for (; p < b1; ++p) {
-        const int64_t k = perm[p];
-        const float v = (k >= 0 && k < T) ? values[k * C + j] : 0.f;        // (a plan's perm is in range: never the zero)
-        acc = rows_step<OP>(acc, v);
-    }
-    return acc;
-}
-
-// out[r, c] for the rows of at most kRowChunk samples; lane t = r * C + j, c = cols[j] or j, out has K columns
-template <int OP>
-__global__ void __launch_bounds__(kLaunchBlock)
-rows_short_kernel(const float* __restrict__ values, int64_t T, int C, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ perm,
-                  int64_t M, const int32_t* __restrict__ cols, int K, float empty, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    const int64_t r = t / C;
-    if (r >= M) return;
-    const int j = (int)(t - r * C);
-    const int c = cols != nullptr ? cols[j] : j;
-    if (c < 0 || c >= K) return;
-    int32_t b0 = row_ptr[r], b1 = row_ptr[r + 1];
-    b0 = b0 < 0 ? 0 : b0;
-    b1 = (int64_t)b1 > T ? (int32_t)T : b1;
-    const int32_t n = b1 - b0;
-    if (n > kRowChunk) return;                                   // the long rows' kernels write it
-    float v = empty;
-    if (n > 0) {
-        v = rows_walk<OP>(values, T, C, j, perm, b0, b1);
-        if constexpr (OP == ROWS_MEAN) v = v / (float)n;
-    }
-    out[r * K + c] = v;
-}
-
-// partials[ch, j] for chunk ch of the long rows; lane t = ch * C + j
-template <int OP>
-__global__ void __launch_bounds__(kLaunchBlock)
-rows_chunk_kernel(const float* __restrict__ values, int64_t T, int C, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ perm,
-                  int64_t M, const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr,
-                  const int32_t* __restrict__ chunk_long, int64_t n_long, int64_t n_chunks, float* __restrict__ partials) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    const int64_t ch = t / C;
-    if (ch >= n_chunks) return;
-    const int j = (int)(t - ch * C);
-    float v = 0.f;
-    const int64_t li = chunk_long[ch];
-    if (li >= 0 && li < n_long) {
-        const int64_t r = long_rows[li];
-        const int64_t jc = ch - (int64_t)long_chunk_ptr[li];
-        if (r >= 0 && r < M && jc >= 0) {
-            int64_t b1 = row_ptr[r + 1];
-            b1 = b1 > T ? T : b1;
-            const int64_t c0 = (int64_t)row_ptr[r] + jc * kRowChunk;
-            const int64_t c1 = c0 + kRowChunk < b1 ? c0 + kRowChunk : b1;
-            if (c0 >= 0 && c1 > c0) v = rows_walk<OP>(values, T, C, j, perm, (int32_t)c0, (int32_t)c1);
-        }
-    }
-    partials[t] = v;
-}
-
-// out[r, c] = (p_0 + p_1) + p_2 ... over the long row's chunks, in chunk order; lane t = li * C + j
-template <int OP>
-__global__ void __launch_bounds__(kLaunchBlock)
-rows_join_kernel(const float* __restrict__ partials, int C, const int32_t* __restrict__ row_ptr, int64_t M,
-                 const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr, int64_t n_long, int64_t n_chunks,
-                 const int32_t* __restrict__ cols, int K, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    const int64_t li = t / C;
-    if (li >= n_long) return;
-    const int j = (int)(t - li * C);
-    const int c = cols != nullptr ? cols[j] : j;
-    const int64_t r = long_rows[li];
-    if (c < 0 || c >= K || r < 0 || r >= M) return;
-    int64_t q0 = long_chunk_ptr[li], q1 = long_chunk_ptr[li + 1];
-    q0 = q0 < 0 ? 0 : q0;
-    q1 = q1 > n_chunks ? n_chunks : q1;
-    if (q1 <= q0) return;
-    float acc = partials[q0 * C + j];
-#pragma unroll 4
-    for (int64_t q = q0 + 1; q < q1; ++q) acc = rows_step<OP>(acc, partials[q * C + j]);
-    if constexpr (OP == ROWS_MEAN) acc = acc / (float)(row_ptr[r + 1] - row_ptr[r]);
-    out[r * K + c] = acc;
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
@@ -426,14 +330,8 @@ int svoxt_reduce_rows(const float* values, int64_t T, int32_t C, const int32_t* 
     const bool ok = with_int(IntSet<ROWS_SUM, ROWS_MEAN, ROWS_MAX, ROWS_MIN>{}, op, [&](auto OP) {
         // the partials of a mean are the sum's; the division is the join's (and the short rows')
         constexpr int PART = OP.value == ROWS_MEAN ? (int)ROWS_SUM : OP.value;
-        hipLaunchKernelGGL((rows_short_kernel<OP.value>), dim3(launch_blocks(M * C)), dim3(kLaunchBlock), 0, st, values, T, (int)C, row_ptr, perm,
-                           M, cols, (int)K, empty, out);
-        if (n_long > 0) {
-            hipLaunchKernelGGL((rows_chunk_kernel<PART>), dim3(launch_blocks(n_chunks * C)), dim3(kLaunchBlock), 0, st, values, T, (int)C, row_ptr,
-                               perm, M, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks, partials);
-            hipLaunchKernelGGL((rows_join_kernel<OP.value>), dim3(launch_blocks(n_long * C)), dim3(kLaunchBlock), 0, st, partials, (int)C, row_ptr,
-                               M, long_rows, long_chunk_ptr, n_long, n_chunks, cols, (int)K, out);
-        }
+        rows_launch<OP.value, PART>(TableValues{values, T, (int)C}, T, (int)C, row_ptr, perm, M, long_rows, long_chunk_ptr, chunk_long, n_long,
+                                    n_chunks, cols, (int)K, empty, out, partials, st);
         return true;
     });
     if (!ok) return fail(SVOXT_ERR_INVALID, "%s: op must be one of SVOXT_ROWS_SUM / MEAN / MAX / MIN", fn);

@@ -178,6 +178,33 @@ class _OpacityRenderFunction(autograd.Function):
         return None, None, None, None
 
 
+class _DeterministicRenderFunction(autograd.Function):
+    """Not in the reference: volume_render / opacity_render (`fwd`, run exactly as the default route runs it) whose
+    backward is the deterministic one -- contributions summed over the row plan in a fixed order, no float atomics
+    (_C.volume_render_backward_rows).  That this route was asked for travels on the ctx."""
+
+    @staticmethod
+    def forward(ctx, data, tree, rays, opt, fwd):
+        out = fwd(tree, rays, opt)
+        ctx.tree = tree
+        ctx.rays = rays
+        ctx.opt = opt
+        ctx.deterministic = True
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad = None
+        if ctx.needs_input_grad[0]:
+            grad = _C.volume_render_backward_rows(ctx.tree, ctx.rays, ctx.opt, grad_out.contiguous())
+        return grad, None, None, None, None
+
+
+def _refuse_deterministic(what, why):
+    raise RuntimeError(f"VolumeRenderer.{what}: deterministic=True is not served: {why} "
+                       "(forward and opacity_render take it; see INTEGRATION.md)")
+
+
 class _RaySweepFunction(autograd.Function):
     """Not in the reference: the per-ray operators that are differentiable wrt the feature table's sigma column --
     depth moments (m1, m2, alpha) and distortion (distortion loss, alpha).  `fwd` / `bwd`: the operator's pair of _C,
@@ -236,7 +263,7 @@ class VolumeRenderer(nn.Module):
                                "(the reference asserts on its non-CUDA branch too)")
 
     def forward(self, features, rays: Rays, transformation_matrices=None, cuda=True, fast=False,
-                image_shape=None, sort_rays=None):
+                image_shape=None, sort_rays=None, deterministic=False):
         """Render a ray batch; differentiable wrt `features`.
 
         :param features: float32 [M, data_dim] leaf feature table (on the GPU)
@@ -250,10 +277,21 @@ class VolumeRenderer(nn.Module):
                a wavefront cross the same leaves; every ray's result is unchanged and comes
                back at the ray's own position.  None: from 16 384 rays on (svox_t_amd.csrc
                SORT_RAYS; SVOXT_SORT_RAYS=0/1 overrides)
+        :param deterministic: (not in the reference) True: the gradient with respect to `features` is
+               bit-identical from run to run and across sort_rays / image_shape / fast / list and pool
+               settings: every sample's contribution is summed per table entry in a fixed order over
+               the row plan instead of with float atomics (slower).  The output is the
+               same bits either way.  Not with transformation_matrices
         :return: [Q, C+1]: C colour/feature channels then accumulated alpha
         """
         self._require_gpu(cuda, "forward")
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+        if deterministic:
+            if transformation_matrices is not None:
+                _refuse_deterministic("forward", "transformation_matrices are not served by the deterministic backward")
+            rspec.need_grad = False          # (its backward marches itself: the forward records nothing for it)
+            return _DeterministicRenderFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
+                                                      _C.volume_render)
         rspec.need_grad = _will_differentiate(features)
         return _VolumeRenderFunction.apply(
             features,
@@ -262,7 +300,7 @@ class VolumeRenderer(nn.Module):
             self._get_options(fast))
 
     def render_persp(self, features, c2w, width=800, height=800, fx=1111.111, fy=None,
-                     cuda=True, fast=False):
+                     cuda=True, fast=False, deterministic=False):
         """Render a perspective image; differentiable wrt `features`.
 
         Same signature and route as the reference (svox_t/renderer.py:310-366:
@@ -278,6 +316,8 @@ class VolumeRenderer(nn.Module):
         :return: (height, width, C+1)
         """
         self._require_gpu(cuda, "render_persp")
+        if deterministic:
+            _refuse_deterministic("render_persp", "camera batches keep the default backward")
         if fy is None:
             fy = fx
         c2w = c2w.to(device=self.tree.data.device, dtype=torch.float32).contiguous()
@@ -285,21 +325,25 @@ class VolumeRenderer(nn.Module):
         cam.need_grad = _will_differentiate(features)
         return _VolumeRenderImageFunction.apply(features, self.tree._spec(features), cam, self._get_options(fast))
 
-    def motion_render(self, features, rays: Rays, cuda=True, fast=False, image_shape=None):
+    def motion_render(self, features, rays: Rays, cuda=True, fast=False, image_shape=None, deterministic=False):
         """First sample with sigma > sigma_thresh per ray (svox_t/renderer.py:367-375):
         (distance to each joint position in tree.extra_data [Q, J], depth [Q, 1],
         hit_point [Q, 3], feature row index [Q, 1] int64); zeros where nothing is hit."""
+        if deterministic:
+            _refuse_deterministic("motion_render", "the motion operators keep the default backward")
         assert self.tree.extra_data is not None, "Need extra data to store skeleton position."
         self._require_gpu(cuda, "motion_render")
         return _C.motion_render(self.tree._spec(features), _rays_spec_from_rays(rays, image_shape),
                                 self._get_options(fast))
 
     def motion_feature_render(self, features, joint_features, skinning_weights, joint_index, rays: Rays,
-                              cuda=True, fast=False, image_shape=None):
+                              cuda=True, fast=False, image_shape=None, deterministic=False):
         """Composite, per ray, sigmoid(sum_j skinning_weights[row, j] * joint_features[joint_index[row, j]])
         over the samples (svox_t/renderer.py:384-396); [Q, joint_features.shape[1]],
         differentiable wrt `joint_features`."""
         self._require_gpu(cuda, "motion_feature_render")
+        if deterministic:
+            _refuse_deterministic("motion_feature_render", "the motion operators keep the default backward")
         return _MotionFeatureRenderFunction.apply(
             joint_features, self.tree._spec(features, joint_features, skinning_weights, joint_index),
             _rays_spec_from_rays(rays, image_shape), self._get_options(fast))
@@ -310,10 +354,15 @@ class VolumeRenderer(nn.Module):
         return _C.render_depth(self.tree._spec(features), _rays_spec_from_rays(rays, image_shape),
                                self._get_options(fast))
 
-    def opacity_render(self, features, rays: Rays, cuda=True, fast=False, image_shape=None, sort_rays=None):
-        """[Q, 1] accumulated alpha only; differentiable wrt `features` (sort_rays: see forward)."""
+    def opacity_render(self, features, rays: Rays, cuda=True, fast=False, image_shape=None, sort_rays=None,
+                       deterministic=False):
+        """[Q, 1] accumulated alpha only; differentiable wrt `features` (sort_rays, deterministic: see forward)."""
         self._require_gpu(cuda, "opacity_render")
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+        if deterministic:
+            rspec.need_grad = False
+            return _DeterministicRenderFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast),
+                                                      _C.opacity_render)
         rspec.need_grad = _will_differentiate(features)
         return _OpacityRenderFunction.apply(features, self.tree._spec(features), rspec, self._get_options(fast))
 
