@@ -503,27 +503,65 @@ march_rec_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L, uint4* __restri
 // tile inside the launch that marched it (fwd_roles_kernel).
 constexpr int kShadeP = 7;                       // list positions per round: one per wavefront but the first
 typedef float shade_v4f __attribute__((ext_vector_type(4)));
+// The tile's records, staged in LDS before the first round: a tile is shaded after its march has finished, so its whole
+// list lies in memory as whole 4 KB blocks whose ids the block table names -- every record can be requested at once
+// (behind the table, which arrives with the list lengths: in one trip with the ray set-up's loads), instead of one
+// round at a time in front of the round's row gather (a round was two dependent trips: record, then the row it
+// names).  A window of kShadeWin blocks (72 list positions), as a ring for
+// longer lists: block b lives in slot b % kShadeWin.  A slot is position-major, [k % 8][ray] (conflict-free ds_read_b64
+// of one position by 64 rays), the ray's column XORed with 8 * (k % 8 / 2) so that the 16-byte pieces of the block as
+// it lies in memory ([ray][k % 8]: two positions of one ray per piece, four pieces per ray) go in without conflicts too.
+// Nine blocks: 14 336 B of hand-over + 36 864 B here = 51 200 B, three workgroups in a CU's 160 KiB.
+// The kernels that shade from memory a finished launch left (shade_tile_kernel, fwd_finish_kernel) are throughput
+// work: they take six blocks, 14 336 + 24 576 B, and stay at four workgroups per CU.
+constexpr int kShadeWin = 9, kShadeWinSmall = 6;
+constexpr int kShadeStageRecs = kShadeWin * kRecBlock * 64, kShadeStageRecsSmall = kShadeWinSmall * kRecBlock * 64;      // uint2 each
+typedef unsigned int shade_v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ int shade_stage_at(int slot, int kk, int ray) {
+    return (slot * kRecBlock + kk) * 64 + (ray ^ ((kk >> 1) << 3));
+}
+// piece c (of 256) of a block: records 2 (c % 4), 2 (c % 4) + 1 of ray c / 4.  COH: from the L2 (sc1), and through a
+// buffer descriptor of exactly the block -- 16 bytes in one request is not an atomic load the language offers.
+template <bool COH>
+__device__ __forceinline__ shade_v4u shade_stage_load(const uint2* __restrict__ rec, int64_t blk, int c) {
+    const uint2* base = rec + (blk << 9);
+    if constexpr (COH) {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2*>(base), 0, 64 * kRecBlock * 8, 0x00020000);
+        return __builtin_bit_cast(shade_v4u, __builtin_amdgcn_raw_buffer_load_b128(rsrc, c * 16, 0, 16 /* sc1 */));
+    } else {
+        return __builtin_nontemporal_load(reinterpret_cast<const shade_v4u*>(base) + c);
+    }
+}
+__device__ __forceinline__ void shade_stage_store(uint2* __restrict__ stage, int slot, int c, shade_v4u v) {
+    const int ray = c >> 2, kk = (c & 3) * 2;
+    stage[shade_stage_at(slot, kk, ray)] = make_uint2(v.x, v.y);
+    stage[shade_stage_at(slot, kk + 1, ray)] = make_uint2(v.z, v.w);
+}
 // LOBES (FMT_SH instances): the basis values are those of opt.format = SG or ASG with BD lobes (precalc_lobes).
 // COH also: returns the XOR of rec_hash over the records this LANE loaded (its wavefront's list positions of its ray),
 // for the caller to combine per ray and compare with the march's checksum; what it loads is made harmless first (a block id
 // inside the pool, a row inside the table), so that a stale line costs a re-shade by the fallback launch, never a
 // fault; `stale_test`: (test only) treat the first record of every ray as if a stale line had been read.
-template <int FMT, int BD, bool XF, bool STOP, bool WTERMS, bool COH, bool LOBES = false>
+template <int FMT, int BD, bool XF, bool STOP, bool WTERMS, bool COH, bool LOBES = false, int NBW = kShadeWin>
 __device__ __forceinline__ uint32_t shade_tile_body(const TreeDev& tr, const RaysDev& rays, const Opts& opt, const RecLists& L,
                                                     uint4* __restrict__ aux, float* __restrict__ out, int64_t tile,
                                                     shade_v4f (*terms)[kShadeP][64] /* [2]: (att, e_0, e_1, e_2) of a list position, per ray */,
+                                                    uint2* __restrict__ stage /* [NBW * 512]: the ring of record blocks */,
                                                     bool stale_test = false, uint32_t* ax_used = nullptr /* COH: <- the aux.x this lane worked with */) {
     constexpr int C = 3, W = 8, P = kShadeP;
+    static_assert(NBW >= 4, "a refilled block is handed over rounds before its first use");
     static_assert(P == W - 1, "one wavefront runs along the rays");
     constexpr int K = (FMT == FMT_RGBA) ? (C + 1) : (C * BD + 1);
     constexpr int NB = (FMT == FMT_SH) ? BD : 1;
     typedef shade_v4f v4f;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (the wavefront's number as a scalar: its role, its list position and the staging's block numbers are uniform)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t q = ray_of_thread(rays, tile * 64 + lane);
     const bool inb = q < rays.Q;
     // (only the count lives through the rounds; wavefront 0 reads the entry again when it finalises the ray)
     uint32_t a_x = 0u;
     if (inb) a_x = COH ? aux_get_coherent(aux + q).x : aux[q].x;
+    const int32_t tabreg = rec_tab_reg<COH>(L, tile, lane);          // lane b holds block b (one trip, with the list lengths)
     int nrec = (int)(a_x & ~kRecOverflow);
     if constexpr (COH) {
         nrec = min(nrec, L.S);                       // (a stale count must not run the loops away)
@@ -533,7 +571,23 @@ __device__ __forceinline__ uint32_t shade_tile_body(const TreeDev& tr, const Ray
     for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
     maxn = __builtin_amdgcn_readfirstlane(maxn);     // what decides the barrier count is scalar
     const int nround = (maxn + P - 1) / P;           // the same in every wavefront of the workgroup
-    const int32_t tabreg = rec_tab_reg<COH>(L, tile, lane);
+    const int need = (maxn + kRecBlock - 1) >> 3;    // blocks the rounds will read: those the table names (pooled lists)
+    // All eight wavefronts stage, 16 bytes per lane and request: piece threadIdx.x % 256 of blocks 2 i + wave / 4.  The
+    // requests go out here, in front of the ray set-up's loads and in one trip with them; the registers are dead before
+    // the first round.
+    constexpr int NSV = (NBW * 256 + 511) / 512;
+    shade_v4u sv[NSV];
+    auto stage_block = [&](int b /* wavefront-uniform */) -> int64_t {
+        int64_t blk = rec_block_u(L, tabreg, tile, b);
+        if constexpr (COH) blk = min(max(blk, (int64_t)0), L.pool_blocks - 1);      // (a stale entry must stay inside the pool)
+        return blk;
+    };
+    const int nb0 = min(need, NBW);                  // blocks staged before round 0
+#pragma unroll
+    for (int i = 0; i < NSV; ++i) {
+        const int b = 2 * i + (wave >> 2);
+        if (b < nb0) sv[i] = shade_stage_load<COH>(L.rec, stage_block(b), (int)(threadIdx.x & 255));
+    }
     uint32_t cs = 0u;                                // COH: XOR of rec_hash over the records this lane loaded
 
     float delta_scale = 0.f;
@@ -551,14 +605,23 @@ __device__ __forceinline__ uint32_t shade_tile_body(const TreeDev& tr, const Ray
     }
     float light = 1.f, acc[C] = {0.f, 0.f, 0.f};
     bool stopped = false;
+#pragma unroll
+    for (int i = 0; i < NSV; ++i) {
+        const int b = 2 * i + (wave >> 2);
+        if (b < nb0) shade_stage_store(stage, b, (int)(threadIdx.x & 255), sv[i]);
+    }
+    // (said once, where everything requested so far is needed anyway: a piece "possibly still on its way" on the path
+    // that did not request it would otherwise put a wait for ALL of a round's traffic -- the previous round's hand-over
+    // store included -- in front of every round's LDS read)
+    __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0)
+    lds_barrier();
 
     for (int rd = 0; rd <= nround; ++rd) {
         if (wave > 0) {
             const int k = rd * P + (wave - 1);
             if (rd < nround && k < nrec) {
-                int64_t blk = rec_block_u(L, tabreg, tile, k >> 3);
-                if constexpr (COH) blk = min(max(blk, (int64_t)0), L.pool_blocks - 1);
-                uint2 e = COH ? rec_get_coherent(L.rec + rec_index_in(blk, lane, k)) : rec_get(L.rec + rec_index_in(blk, lane, k));
+                // the round's record: one LDS read, the row loads right behind it
+                uint2 e = stage[shade_stage_at((k >> 3) % NBW, k & 7, lane)];
                 if constexpr (COH) {
                     if (stale_test && k == 0) e.x ^= 1u;
                     if constexpr (SVOXT_ROLES_CSUM != 0) cs ^= rec_hash(k, e.x, e.y);
@@ -593,25 +656,46 @@ __device__ __forceinline__ uint32_t shade_tile_body(const TreeDev& tr, const Ray
                     typedef float v4g __attribute__((ext_vector_type(4)));
                     const float att_b = pexpf(-__uint_as_float(e.y) * row[K - 1] * delta_scale);
                     __builtin_nontemporal_store(v4g{att_b, tv.y, tv.z, tv.w},
-                                                reinterpret_cast<v4g*>(L.terms + terms_index_pm(blk, lane, k)));
+                                                reinterpret_cast<v4g*>(L.terms + terms_index_pm(stage_block(k >> 3), lane, k)));
                 }
             }
         } else if (rd > 0) {
-            const int kb = (rd - 1) * P;
+            // Lists longer than the window: rounds step by 7 positions and blocks by 8, so a round frees at most one
+            // block -- block d - 1 when the positions below 7 rd cover d = 7 rd / 8 blocks and those below 7 (rd - 1) did
+            // not.  This wavefront, which has no gather of its own, requests its successor d - 1 + kShadeWin then, runs
+            // its chain, and writes it behind the chain; the barrier below hands it over, rounds before its first use.
+            const int d = (rd * P) >> 3;
+            const bool refill = d > (((rd - 1) * P) >> 3) && d - 1 + NBW < need;      // (scalar)
+            auto chain = [&]() {
+                const int kb = (rd - 1) * P;
 #pragma unroll
-            for (int j = 0; j < P; ++j) {
-                if (kb + j < nrec && !stopped) {
-                    const v4f tv = terms[(rd - 1) & 1][j][lane];
-                    const float weight = light * (1.f - tv.x);
-                    acc[0] = (float)((double)acc[0] + (double)weight / (1.0 + (double)tv.y));
-                    acc[1] = (float)((double)acc[1] + (double)weight / (1.0 + (double)tv.z));
-                    acc[2] = (float)((double)acc[2] + (double)weight / (1.0 + (double)tv.w));
-                    light *= tv.x;
-                    // (the stop rule, rt_kernel.cu:313-319 -- also where the march did not apply it (!STOP: lists for a
-                    // backward, or a threshold of 0): it then ends the COMPOSITING here; at 0 it fires at T == 0 exactly,
-                    // where every later weight is 0 and the rescale is by 1)
-                    if (light <= opt.stop_thresh) stopped = true;
+                for (int j = 0; j < P; ++j) {
+                    if (kb + j < nrec && !stopped) {
+                        const v4f tv = terms[(rd - 1) & 1][j][lane];
+                        const float weight = light * (1.f - tv.x);
+                        acc[0] = (float)((double)acc[0] + (double)weight / (1.0 + (double)tv.y));
+                        acc[1] = (float)((double)acc[1] + (double)weight / (1.0 + (double)tv.z));
+                        acc[2] = (float)((double)acc[2] + (double)weight / (1.0 + (double)tv.w));
+                        light *= tv.x;
+                        // (the stop rule, rt_kernel.cu:313-319 -- also where the march did not apply it (!STOP: lists for a
+                        // backward, or a threshold of 0): it then ends the COMPOSITING here; at 0 it fires at T == 0 exactly,
+                        // where every later weight is 0 and the rescale is by 1)
+                        if (light <= opt.stop_thresh) stopped = true;
+                    }
                 }
+            };
+            if (refill) {                            // (a branch of its own: the four pieces live in this block alone, not through the rounds)
+                int rl = lane;
+                asm volatile("" : "+v"(rl));         // (... nor do their addresses)
+                const int64_t blk = stage_block(d - 1 + NBW);
+                shade_v4u rf[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) rf[j] = shade_stage_load<COH>(L.rec, blk, j * 64 + rl);
+                chain();
+#pragma unroll
+                for (int j = 0; j < 4; ++j) shade_stage_store(stage, (d - 1) % NBW, j * 64 + rl, rf[j]);
+            } else {
+                chain();
             }
         }
         lds_barrier();       // (the rounds hand over through LDS alone: the hand-over stores to memory stay in flight)
@@ -670,9 +754,10 @@ shade_tile_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L,
                   uint4* __restrict__ aux, float* __restrict__ out, const int32_t* __restrict__ tile_state = nullptr) {
     static_assert(!LOBES || (FMT == FMT_SH && !XF), "lobes stand in for an SH basis");
     __shared__ shade_v4f terms[2][kShadeP][64];
+    __shared__ uint2 stage[kShadeStageRecsSmall];
     const int64_t tile = (int64_t)blockIdx.x + rays.tile0;
     if (tile_state != nullptr && tile_state[tile] == kTileShaded) return;       // (uniform: one tile per workgroup)
-    shade_tile_body<FMT, BD, XF, STOP, WTERMS, false, LOBES>(tr, rays, opt, L, aux, out, tile, terms);
+    shade_tile_body<FMT, BD, XF, STOP, WTERMS, false, LOBES, kShadeWinSmall>(tr, rays, opt, L, aux, out, tile, terms, stage);
     if (tile_state != nullptr && threadIdx.x == 0)                              // (fallback of fwd_roles_kernel: counted)
         atomicAdd(const_cast<int32_t*>(tile_state) + roles_even(gridDim.x + rays.tile0) + kRoleCtrFallback, 1);
 }
@@ -688,6 +773,7 @@ __global__ void __launch_bounds__(512)
 fwd_finish_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L, uint4* __restrict__ aux, float* __restrict__ out,
                   int32_t* __restrict__ tile_state, int ntiles) {
     __shared__ shade_v4f terms[2][kShadeP][64];
+    __shared__ uint2 stage[kShadeStageRecsSmall];
     constexpr int CAP = 64;
     __shared__ int32_t s_list[CAP];
     __shared__ int32_t s_n;
@@ -708,13 +794,13 @@ fwd_finish_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L, uint4* __restr
     if (n > CAP) {                                           // more than the list holds: the run, tile by tile
         for (int tile = t0; tile < t1; ++tile) {
             if (tile_state[tile] == kTileShaded) continue;   // (uniform)
-            shade_tile_body<FMT, BD, XF, false, WTERMS, false, LOBES>(tr, rays, opt, L, aux, out, tile, terms);
+            shade_tile_body<FMT, BD, XF, false, WTERMS, false, LOBES, kShadeWinSmall>(tr, rays, opt, L, aux, out, tile, terms, stage);
             if (threadIdx.x == 0) atomicAdd(fallback_ctr, 1);
             __syncthreads();
         }
     } else {
         for (int j = 0; j < n; ++j) {
-            shade_tile_body<FMT, BD, XF, false, WTERMS, false, LOBES>(tr, rays, opt, L, aux, out, s_list[j], terms);
+            shade_tile_body<FMT, BD, XF, false, WTERMS, false, LOBES, kShadeWinSmall>(tr, rays, opt, L, aux, out, s_list[j], terms, stage);
             if (threadIdx.x == 0) atomicAdd(fallback_ctr, 1);
             __syncthreads();
         }
@@ -844,12 +930,16 @@ __host__ __device__ inline int64_t roles_group_of(const RolesMap& m, int b) {   
 // registers), and 0.80 -> 0.83 at 1024 x 1024 / depth 9 where the march is a kernel of its own at 64 -- runs of equal
 // levels are short on these trees, and every iteration pays two points and two requests.)
 template <int FMT, int BD, int ACC, bool WTERMS, bool LOBES = false, bool XF = false>
-__global__ void __launch_bounds__(512)
+// (SH up to 9 without view rotations: the register allocator is held to six wavefronts per SIMD -- three workgroups per
+// CU, 80 registers -- which these instances meet without scratch; 0: no such demand)
+__global__ void __launch_bounds__(512, (BD <= 9 && !XF) ? 6 : 0)
 fwd_roles_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L, uint4* __restrict__ aux, float* __restrict__ out,
                  const uint32_t* __restrict__ sigma_mask, int32_t* __restrict__ tile_state, int n_march, int ntiles,
                  int tflags /* kRoleTest* | kRoleAgentFence: 0 in production */, RolesMap map) {
     constexpr int kMarchBytes = 8 * (kRecBlock * 64 * (int)sizeof(uint2) + kMaxRecBlocks * (int)sizeof(int32_t));
-    constexpr int kShadeBytes = 2 * kShadeP * 64 * (int)sizeof(shade_v4f);
+    constexpr int kTermBytes = 2 * kShadeP * 64 * (int)sizeof(shade_v4f);
+    constexpr int kShadeBytes = kTermBytes + kShadeStageRecs * (int)sizeof(uint2);      // hand-over double buffer + the ring of record blocks
+    static_assert(kShadeBytes + 8 <= 53248, "three workgroups per CU: 160 KiB / 3, less the allocation granule");
     __shared__ __attribute__((aligned(16))) unsigned char lds[kMarchBytes > kShadeBytes ? kMarchBytes : kShadeBytes];
     __shared__ unsigned long long s_ent;
     const int wave = threadIdx.x >> 6;
@@ -910,7 +1000,7 @@ fwd_roles_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L, uint4* __restri
     uint32_t ax = 0u;
     static_assert(!XF || (FMT == FMT_SH && !LOBES && BD <= 9), "view rotations: SH rows");
     const uint32_t part = shade_tile_body<FMT, BD, XF, false, WTERMS, true, LOBES>(
-        tr, rays, opt, L, aux, out, tile, reinterpret_cast<shade_v4f (*)[kShadeP][64]>(lds), (tflags & kRoleTestStale) && tile % 5 == 0, &ax);
+        tr, rays, opt, L, aux, out, tile, reinterpret_cast<shade_v4f (*)[kShadeP][64]>(lds), reinterpret_cast<uint2*>(lds + kTermBytes), (tflags & kRoleTestStale) && tile % 5 == 0, &ax);
     // what this workgroup loaded, folded like the march folded what it wrote: per ray first (the eight wavefronts'
     // words of a lane; the shade's double buffer is free behind its last barrier), then over the tile
     uint32_t* s_part = reinterpret_cast<uint32_t*>(lds);
