@@ -1397,6 +1397,72 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
                                   int64_t n_long, int64_t n_chunks, float* grad, int32_t grad_stride, void* workspace,
                                   int64_t workspace_bytes, void* stream);
 
+/* ---- shade_samples: per-sample colours from feature rows (svoxt_shade.hip; not in the reference) ----
+ * The shading step of the per-sample interface: the basis of a sample's ray dotted into its feature row's coefficients,
+ * then the sigmoid -- and the gradient with respect to the feature table, summed over the row plan.  No [T, K] array
+ * exists at any point, no float atomic, every result bit-identical from run to run.  Entry points added under ABI v22.
+ *
+ *   svoxt_view_basis          basis float32 [Q, basis_dim]: the ray's basis values exactly as the render kernels form them
+ *                             from the view direction (rays.vdirs[q], or the pixel's direction in camera mode): SH 1 / 4 /
+ *                             9 / 16 / 25 in closed form, SG / ASG from tree.extra_data.  Components outside [min_comp,
+ *                             max_comp] are still written: the basis does not depend on the range.  RGBA (and Q = 0): a
+ *                             no-op, basis may be NULL.  A lane per ray, no march; rays.order and the image hint are not
+ *                             consulted.  Checked: the tree, rays and options as svoxt_volume_render_fwd checks them;
+ *                             tree.xform NULL; Q below 2^31; basis not NULL, 4-byte aligned.
+ *
+ *   svoxt_shade_samples_fwd   values float32 [T, C] and sigma float32 [T] for the samples (row int32 [T], ray int32 [T]) of
+ *                             a table features float32 [M, K].  C = svoxt_out_data_dim - 1: K - 1 for RGBA, (K - 1) /
+ *                             basis_dim otherwise.  basis is svoxt_view_basis' [Q, basis_dim] (RGBA: not read, may be
+ *                             NULL, as ray).  The definition is fixed operation for operation, in float32 without
+ *                             contraction.  For sample k with row r and ray q:
+ *                               tmp          = sum over i = min_comp .. max_comp of basis[q, i] * features[r, c * basis_dim
+ *                                              + i], summed from 0.f in ascending i.  For RGBA, tmp = features[r, c].
+ *                               values[k, c] = (float)(1.0 / (1.0 + (double)expf(-tmp))) with activate != 0 (expf: the
+ *                                              library's fixed operation sequence).  This is the value the backward's
+ *                                              pass 1 calls sig.  With activate == 0, values[k, c] = tmp.
+ *                               sigma[k]     = features[r, K - 1], the stored bits.
+ *                             A sample whose row is outside [0, M) gets values = 0, sigma = 0 and no gradient
+ *                             (svoxt_gather_rows' rule); so does, for its values, a sample whose ray is outside [0, Q).
+ *                             A lane per (sample, channel) plus one per sample for sigma; RGBA rows of K = 4 n floats in a
+ *                             16-byte aligned table: a lane per (sample, four columns), 16-byte loads.  T = 0: a no-op.
+ *                             Checked: options not NULL, the format, K >= 1, T, M, Q in [0, 2^31); with a basis basis_dim
+ *                             in [1, 25] and min_comp / max_comp inside [0, basis_dim); T * (C + 1) and M * K below 2^38;
+ *                             with T > 0: row, sigma, values (C > 0) not NULL, features not NULL when M > 0, with a basis
+ *                             ray and basis not NULL; alignment (4 bytes).
+ *
+ *   svoxt_shade_samples_bwd   grad float32 [M, K], the gradient with respect to features for grad_values [T, C] and
+ *                             grad_sigma [T] (either may be NULL: zeros, nothing is read for it).  Every element of grad
+ *                             is written.
+ *                               colour column (c, i), i in the component range: the sum over the row's samples of
+ *                                              (grad_values[k, c] * d[k, c]) * basis[ray[k], i].  With activate != 0 and a
+ *                                              basis, d = (float)((double)sig * (1.0 - (double)sig)); for RGBA, d = sig *
+ *                                              (1.f - sig) and there is no basis factor; sig = values[k, c], the forward's
+ *                                              own output.  With activate == 0 the factor is grad_values[k, c] alone.
+ *                               sigma column   the sum of grad_sigma[k].
+ *                               every other column, and rows no sample names: exactly 0.f.
+ *                             The sum order is svoxt_reduce_rows' rule: samples in ascending index over the plan (row_ptr,
+ *                             perm, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks: svoxt_row_plan_build /
+ *                             svoxt_row_plan_long of the same row array and M), chunks of SVOXT_ROW_CHUNK = 256 from 0.f,
+ *                             the partials in chunk order.  A lane per (row, column) over all K columns, the value of
+ *                             sample k at column j formed on the fly.  workspace: svoxt_shade_samples_bwd_workspace_bytes(
+ *                             n_chunks, K) device bytes (-1: n_chunks negative or from 2^31, K < 1, n_chunks * K from 2^38;
+ *                             0 for n_chunks = 0), 4-byte aligned.  M = 0: a no-op; T = 0: zeros everywhere.
+ *                             Checked: as the forward; n_long and n_chunks as svoxt_row_plan_long; with M > 0: grad,
+ *                             row_ptr not NULL; with T > 0 perm and what the given gradients make it read (values, ray,
+ *                             basis) not NULL; with n_long > 0 long_rows, long_chunk_ptr, chunk_long not NULL; alignment
+ *                             (4 bytes); with n_long > 0 the workspace not NULL and at least the query's size.
+ * No allocation, no synchronisation. */
+int svoxt_view_basis(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, float* basis, void* stream);
+int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const int32_t* row,
+                            const int32_t* ray, int64_t T, const float* basis, int64_t Q, int32_t activate, float* values,
+                            float* sigma, void* stream);
+int64_t svoxt_shade_samples_bwd_workspace_bytes(int64_t n_chunks, int32_t K);
+int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, const int32_t* ray, int64_t T, const float* basis,
+                            int64_t Q, int32_t activate, const float* values, const float* grad_values,
+                            const float* grad_sigma, const int32_t* row_ptr, const int32_t* perm, const int32_t* long_rows,
+                            const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks,
+                            float* grad, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

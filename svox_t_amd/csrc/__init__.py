@@ -1189,4 +1189,5 @@ from ._extras import (ray_samples, sample_accumulate, sample_accumulate_backward
                       sample_weights_backward)
 from ._extras import RowPlanArrays, row_plan, sample_gather_rows, sample_reduce_rows  # noqa: E402,F401
 from ._extras import volume_render_backward_rows  # noqa: E402,F401
+from ._extras import shade_samples_bwd, shade_samples_fwd, view_basis  # noqa: E402,F401
 from . import _extras  # noqa: E402,F401

@@ -220,6 +220,11 @@ EXPORTS = {
     "svoxt_render_grad_rows_sweep": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
     "svoxt_render_grad_rows_reduce": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32,
                                                      _vp, _i64, _vp]),
+    "svoxt_view_basis": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp]),
+    "svoxt_shade_samples_fwd": (ctypes.c_int, [_vp, _i64, _i32, _P(_COptions), _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "svoxt_shade_samples_bwd_workspace_bytes": (_i64, [_i64, _i32]),
+    "svoxt_shade_samples_bwd": (ctypes.c_int, [_P(_COptions), _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

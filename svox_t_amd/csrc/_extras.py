@@ -1670,3 +1670,98 @@ def volume_render_backward_rows(tree: TreeSpec, rays: RaysSpec, opt: RenderOptio
         tick(None)
     ROWGRAD_LAST.update(Q=Q, T=T, bytes=int(nbytes), n_long=n_long, n_chunks=n_chunks, longest=longest)
     return grad
+
+
+# ---------------------------------------------------------------------------
+# shade_samples: per-sample colours from feature rows (svoxt_shade.hip; not in the reference)
+# ---------------------------------------------------------------------------
+def view_basis(tree: TreeSpec, rays, opt: RenderOptions) -> torch.Tensor:
+    """basis float32 [Q, basis_dim] of svoxt_view_basis: every ray's basis values as the render kernels form them; [Q, 0]
+    for RGBA.  `rays`: a RaysSpec or a CameraSpec.  transformation_matrices are not served."""
+    if _numel(tree.transformation_matrices):
+        raise RuntimeError("view_basis: transformation_matrices are not served by shade_samples (the per-leaf rotation of "
+                           "the view direction); use forward")
+    ct, cr, co = _pack_tree(tree), _pack_rays(rays), _pack_opts(opt)
+    dev = tree.features.device
+    bd = 0 if int(opt.format) == 0 else int(opt.basis_dim)
+    with _on(dev):
+        basis = torch.empty((cr.Q, bd), dtype=torch.float32, device=dev)
+        _call("svoxt_view_basis", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(basis), _stream(dev))
+    return basis
+
+
+def _shade_dims(opt: RenderOptions, K: int):
+    """(C, basis_dim or 0 for RGBA) of a table of K columns under `opt`."""
+    C = get_out_data_dim(opt, K) - 1
+    return C, (0 if int(opt.format) == 0 else int(opt.basis_dim))
+
+
+def _check_shade(features, row, ray, basis, Q, opt):
+    """The checks the two directions of shade_samples share; returns (M, K, T, C, basis_dim, device)."""
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise RuntimeError("features must be float32 [M, K], K >= 1")
+    _check_input(features, "features")
+    dev = features.device
+    if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
+        raise RuntimeError("row must be int32 [T]")
+    T = row.shape[0]
+    _check_per_sample(row, "row", T, dev, dtype=torch.int32)
+    _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+    (M, K) = features.shape
+    C, bd = _shade_dims(opt, K)
+    if bd > 0:
+        if not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (Q, bd):
+            raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] (view_basis of the samples' rays)")
+        _check_input(basis, "basis")
+        if basis.device != dev:
+            raise RuntimeError("basis must be on the device of the features")
+    if M >= 1 << 31 or T >= 1 << 31 or Q >= 1 << 31:
+        raise RuntimeError("M, T and Q must be below 2^31")
+    return M, K, T, C, bd, dev
+
+
+def shade_samples_fwd(features, row, ray, basis, Q: int, opt: RenderOptions, activate: bool = True):
+    """(values float32 [T, C], sigma float32 [T]) of svoxt_shade_samples_fwd for features float32 [M, K], row / ray int32 [T]
+    and basis float32 [Q, basis_dim] (RGBA: not read, may be None)."""
+    M, K, T, C, bd, dev = _check_shade(features, row, ray, basis, Q, opt)
+    co = _pack_opts(opt)
+    with _on(dev):
+        values = torch.empty((T, C), dtype=torch.float32, device=dev)
+        sigma = torch.empty((T,), dtype=torch.float32, device=dev)
+        _call("svoxt_shade_samples_fwd", _ptr(features), M, K, ctypes.byref(co), _ptr(row), _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q,
+              1 if activate else 0, _ptr(values), _ptr(sigma), _stream(dev))
+    return values, sigma
+
+
+def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: bool, values, grad_values, grad_sigma,
+                      plan: RowPlanArrays) -> torch.Tensor:
+    """grad float32 [M, K] of svoxt_shade_samples_bwd for a table of `shape` = (M, K) over the samples' row plan; values is
+    the forward's output, grad_values [T, C] / grad_sigma [T] may be None (zeros)."""
+    if not isinstance(plan, RowPlanArrays):
+        raise RuntimeError("plan must be a row plan")
+    M, K = (int(v) for v in shape)
+    T = plan.T
+    if plan.M != M:
+        raise RuntimeError("the plan must be built for the table's M rows")
+    C, bd = _shade_dims(opt, K)
+    dev = plan.row_ptr.device
+    _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+    _check_per_sample(values, "values", T, dev, C)
+    if grad_values is not None:
+        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    if grad_sigma is not None:
+        _check_per_sample(grad_sigma, "grad_sigma", T, dev)
+    if bd > 0:
+        if not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (Q, bd) or basis.device != dev:
+            raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] on the device of the plan")
+        _check_input(basis, "basis")
+    co = _pack_opts(opt)
+    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
+    with _on(dev):
+        grad = torch.empty((M, K), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)
+        ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
+        _call("svoxt_shade_samples_bwd", ctypes.byref(co), M, K, _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q, 1 if activate else 0,
+              _ptr(values), _ptr(grad_values), _ptr(grad_sigma), _ptr(plan.row_ptr), _ptr(plan.perm), _ptr(plan.long_rows),
+              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(grad), _ptr(ws), nbytes, _stream(dev))
+    return grad

@@ -1,0 +1,273 @@
+// svoxt_shade.hip -- shade_samples (not in the reference): the colour of every sample of a RaySamples
+// list from its feature row and its ray's basis values, and the gradient with respect to the feature table summed per
+// table entry over the row plan in svoxt_reduce_rows' order -- no [T, K] array and no float atomic anywhere.
+//
+//   view_basis   view_basis_kernel        a lane per ray, no march: precalc_basis<0> of load_vdir into basis[q, :]
+//   forward      shade_fwd_kernel         a lane per (sample, channel) and one per sample behind them for sigma
+//                                         (rowgrad_shade_kernel's cut: a sample's lanes read the same feature row)
+//                shade_fwd_rgba4_kernel   RGBA rows of K = 4 K4 floats in a 16-byte aligned table: a lane per (sample,
+//                                         four columns), one 16-byte load each (gather_rows4_kernel's cut)
+//   backward     the row kernels of svoxt_rowwalk.h, a lane per (row, column) over all K columns, the value of sample k
+//                at column j formed on the fly (ShadeValues): a colour column (g_values[k, c] * d[k, c]) *
+//                basis[ray[k], i], the sigma column g_sigma[k], every other column 0.f.  sig is the forward's own output.
+// Per sample 4 * (C + 1) bytes out of the forward; the backward keeps values, basis and ray.  C ABI: svoxt_view_basis,
+// svoxt_shade_samples_* (include/svoxt.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "svoxt_device.h"
+#include "svoxt_host.h"
+#include "svoxt_launch.h"
+#include "svoxt_rowwalk.h"
+#include "svoxt_workspace.h"
+
+#pragma clang fp contract(off)
+
+namespace svoxt {
+
+// --------------------------------------------------------------------------------------------------------- view_basis
+// lane q: the basis values the render kernels form for ray q (every component, whatever the component range)
+__global__ void __launch_bounds__(kLaunchBlock)
+view_basis_kernel(TreeDev tr, RaysDev rays, int format, int bd, float* __restrict__ basis) {
+    const int64_t q = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (q >= rays.Q) return;
+    float vd[3];
+    load_vdir(rays, q, vd);
+    precalc_basis<0>(format, bd, tr, vd[0], vd[1], vd[2], basis + q * bd);
+}
+
+// ------------------------------------------------------------------------------------------------------------ forward
+// one channel's value from tmp: the backward's pass-1 sig, or tmp itself
+__device__ __forceinline__ float shade_value(float tmp, bool activate) {
+    return activate ? (float)(1.0 / (1.0 + (double)pexpf(-tmp))) : tmp;
+}
+
+// lane t = k * (C + 1) + c.  c < C: values[k, c]; c == C: sigma[k]
+__global__ void __launch_bounds__(kLaunchBlock)
+shade_fwd_kernel(const float* __restrict__ features, int64_t M, int K, int C, int bd, int min_comp, int max_comp, bool activate,
+                 int64_t Q, int64_t T, const int32_t* __restrict__ row, const int32_t* __restrict__ ray,
+                 const float* __restrict__ basis, float* __restrict__ values, float* __restrict__ sigma) {
+    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t k = t / (C + 1);
+    if (k >= T) return;
+    const int c = (int)(t - k * (C + 1));
+    const int64_t idx = row[k];
+    const bool inside = idx >= 0 && idx < M;
+    const float* __restrict__ frow = features + (inside ? idx : 0) * K;
+    if (c == C) {
+        sigma[k] = inside ? frow[K - 1] : 0.f;
+        return;
+    }
+    float v = 0.f;
+    if (inside) {
+        if (bd > 0) {
+            const int64_t q = ray[k];
+            if (q >= 0 && q < Q) {                               // (a ray outside [0, Q): zeros, as a row outside [0, M))
+                const float* __restrict__ b = basis + q * bd;
+                const int off = c * bd;
+                float tmp = 0.f;
+                for (int i = min_comp; i <= max_comp; ++i) tmp += b[i] * frow[off + i];
+                v = shade_value(tmp, activate);
+            }
+        } else {
+            v = shade_value(frow[c], activate);
+        }
+    }
+    values[k * C + c] = v;
+}
+
+// lane t = k * K4 + j: columns 4 j .. 4 j + 3 of sample k's RGBA row (K = 4 K4, C = K - 1, the table 16-byte aligned);
+// the last column of the last lane is sigma
+__global__ void __launch_bounds__(kLaunchBlock)
+shade_fwd_rgba4_kernel(const float4* __restrict__ features, int64_t M, int K4, bool activate, int64_t T,
+                       const int32_t* __restrict__ row, float* __restrict__ values, float* __restrict__ sigma) {
+    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t k = t / K4;
+    if (k >= T) return;
+    const int j = (int)(t - k * K4);
+    const int64_t idx = row[k];
+    const bool inside = idx >= 0 && idx < M;
+    const int C = 4 * K4 - 1;
+    const float4 x = inside ? features[idx * K4 + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* __restrict__ o = values + k * C + 4 * j;
+    o[0] = inside ? shade_value(x.x, activate) : 0.f;
+    o[1] = inside ? shade_value(x.y, activate) : 0.f;
+    o[2] = inside ? shade_value(x.z, activate) : 0.f;
+    if (j == K4 - 1) sigma[k] = x.w;
+    else o[3] = inside ? shade_value(x.w, activate) : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------- values
+// The contribution of sample k to column j of its row, for the row kernels of svoxt_rowwalk.h.  A NULL upstream gradient
+// is zeros: its columns are ZERO columns, nothing is read.
+struct ShadeValues {
+    const int32_t* __restrict__ ray;
+    const float* __restrict__ values;
+    const float* __restrict__ basis;
+    const float* __restrict__ gv;
+    const float* __restrict__ gs;
+    int64_t T, Q;
+    int K, C, bd, min_comp, max_comp;
+    bool activate;
+    enum { ZERO, SIGMA, BASIS, BASIS_LINEAR, RGBA, RGBA_LINEAR };
+    struct Col {
+        const int32_t* __restrict__ ray;
+        const float* __restrict__ v;       // BASIS / RGBA: values + c
+        const float* __restrict__ b;       // BASIS, BASIS_LINEAR: basis + i
+        const float* __restrict__ g;       // SIGMA: g_sigma;  the colour modes: g_values + c
+        int64_t T, Q;
+        int mode, C, bd;
+        __device__ __forceinline__ float at(int64_t k) const {
+            if (mode == ZERO || k < 0 || k >= T) return 0.f;
+            if (mode == SIGMA) return g[k];
+            const float gc = g[k * C];
+            if (mode == RGBA_LINEAR) return gc;
+            if (mode == RGBA) {
+                const float sig = v[k * C];
+                return gc * (sig * (1.f - sig));
+            }
+            const int64_t q = ray[k];
+            if (q < 0 || q >= Q) return 0.f;                     // (the forward gave this sample zeros)
+            if (mode == BASIS_LINEAR) return gc * b[q * bd];
+            const float sig = v[k * C];
+            const float d = (float)((double)sig * (1.0 - (double)sig));
+            return (gc * d) * b[q * bd];
+        }
+    };
+    __device__ __forceinline__ Col col(int j) const {
+        Col o{ray, values, basis, gs, T, Q, ZERO, C, bd};
+        if (j == K - 1) {
+            if (gs != nullptr) o.mode = SIGMA;
+        } else if (gv == nullptr) {
+            // (zeros upstream: every colour column is 0.f)
+        } else if (bd == 0) {
+            if (j < C) { o.mode = activate ? RGBA : RGBA_LINEAR; o.v = values + j; o.g = gv + j; }
+        } else if (j < C * bd) {
+            const int c = j / bd, i = j - c * bd;
+            if (i >= min_comp && i <= max_comp) {
+                o.mode = activate ? BASIS : BASIS_LINEAR;
+                o.v = values + c; o.b = basis + i; o.g = gv + c;
+            }
+        }
+        return o;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------- checks
+static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+
+// C and the basis values a ray has (0 for RGBA) for a table of K columns; what both directions check first
+static int shade_dims(const svoxt_options* opt, int64_t M, int32_t K, int64_t T, int64_t Q, int* C, int* bd, const char* fn) {
+    if (opt == nullptr) return fail(SVOXT_ERR_INVALID, "%s: options is NULL", fn);
+    if (opt->format < SVOXT_FORMAT_RGBA || opt->format > SVOXT_FORMAT_ASG) return fail(SVOXT_ERR_INVALID, "%s: unknown data format", fn);
+    if (K < 1) return fail(SVOXT_ERR_INVALID, "%s: K must be >= 1", fn);
+    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
+    if (M < 0 || M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be in [0, 2^31)", fn);
+    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
+    if (opt->format == SVOXT_FORMAT_RGBA) {
+        *bd = 0;
+        *C = K - 1;
+    } else {
+        if (opt->basis_dim < 1 || opt->basis_dim > 25) return fail(SVOXT_ERR_INVALID, "%s: basis_dim must be in [1, 25]", fn);
+        if (opt->min_comp < 0 || opt->max_comp >= opt->basis_dim)
+            return fail(SVOXT_ERR_INVALID, "%s: min_comp / max_comp outside [0, basis_dim)", fn);
+        *bd = opt->basis_dim;
+        *C = (K - 1) / opt->basis_dim;
+    }
+    if ((double)T * (*C + 1) >= 274877906944.0 || (double)M * K >= 274877906944.0)
+        return fail(SVOXT_ERR_INVALID, "%s: T * (C + 1) and M * K must be below 2^38", fn);
+    return SVOXT_OK;
+}
+
+}  // namespace svoxt
+
+using namespace svoxt;
+
+extern "C" {
+
+int svoxt_view_basis(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, float* basis, void* stream) {
+    const char* fn = "svoxt_view_basis";
+    int rc;
+    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, true))) return rc;
+    if (tree->xform != nullptr) return fail(SVOXT_ERR_INVALID, "%s: transformation_matrices (tree.xform) are not served by shade_samples", fn);
+    if (rays->Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: too many rays (ray indices are int32)", fn);
+    if (opt->format == SVOXT_FORMAT_RGBA || rays->Q == 0) return SVOXT_OK;     // [Q, 0]: nothing to write
+    if (basis == nullptr || misaligned(basis, 4)) return fail(SVOXT_ERR_INVALID, "%s: basis is NULL or not 4-byte aligned", fn);
+    const TreeDev tr = to_dev(tree);
+    const RaysDev rd = to_dev(rays, tree);
+    hipLaunchKernelGGL(view_basis_kernel, dim3(launch_blocks(rays->Q)), dim3(kLaunchBlock), 0, (hipStream_t)stream, tr, rd, (int)opt->format,
+                       (int)opt->basis_dim, basis);
+    return check_launch(fn);
+}
+
+int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const int32_t* row,
+                            const int32_t* ray, int64_t T, const float* basis, int64_t Q, int32_t activate, float* values,
+                            float* sigma, void* stream) {
+    const char* fn = "svoxt_shade_samples_fwd";
+    int rc, C, bd;
+    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn))) return rc;
+    if (T == 0) return SVOXT_OK;
+    if (row == nullptr || sigma == nullptr || (C > 0 && values == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: row / values / sigma is NULL", fn);
+    if (M > 0 && features == nullptr) return fail(SVOXT_ERR_INVALID, "%s: features is NULL", fn);
+    if (bd > 0 && C > 0 && (ray == nullptr || (Q > 0 && basis == nullptr))) return fail(SVOXT_ERR_INVALID, "%s: ray / basis is NULL", fn);
+    if (misaligned(features, 4) || misaligned(row, 4) || misaligned(ray, 4) || misaligned(basis, 4) || misaligned(values, 4) ||
+        misaligned(sigma, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    hipStream_t st = (hipStream_t)stream;
+    if (bd == 0 && K % 4 == 0 && !misaligned(features, 16)) {
+        const int K4 = K / 4;
+        hipLaunchKernelGGL(shade_fwd_rgba4_kernel, dim3(launch_blocks(T * K4)), dim3(kLaunchBlock), 0, st,
+                           reinterpret_cast<const float4*>(features), M, K4, activate != 0, T, row, values, sigma);
+    } else {
+        hipLaunchKernelGGL(shade_fwd_kernel, dim3(launch_blocks(T * (C + 1))), dim3(kLaunchBlock), 0, st, features, M, (int)K, C, bd,
+                           (int)opt->min_comp, (int)opt->max_comp, activate != 0, Q, T, row, ray, basis, values, sigma);
+    }
+    return check_launch(fn);
+}
+
+int64_t svoxt_shade_samples_bwd_workspace_bytes(int64_t n_chunks, int32_t K) {
+    if (n_chunks < 0 || n_chunks > 0x7fffffffLL || K < 1 || (double)n_chunks * K >= 274877906944.0) return -1;
+    if (n_chunks == 0) return 0;
+    Carver w(nullptr);
+    w.take<float>((size_t)n_chunks * (size_t)K);
+    return (int64_t)w.bytes();
+}
+
+int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, const int32_t* ray, int64_t T, const float* basis,
+                            int64_t Q, int32_t activate, const float* values, const float* grad_values,
+                            const float* grad_sigma, const int32_t* row_ptr, const int32_t* perm, const int32_t* long_rows,
+                            const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks,
+                            float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_shade_samples_bwd";
+    int rc, C, bd;
+    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn))) return rc;
+    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
+        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
+    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
+        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    if (M == 0) return SVOXT_OK;
+    if (grad == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad / row_ptr is NULL", fn);
+    if (C == 0) grad_values = nullptr;                           // (no colour column: nothing of it is read)
+    const bool reads_values = grad_values != nullptr && activate != 0;
+    const bool reads_basis = grad_values != nullptr && bd > 0;
+    if (T > 0 && (perm == nullptr || (reads_values && values == nullptr) || (reads_basis && (ray == nullptr || (Q > 0 && basis == nullptr)))))
+        return fail(SVOXT_ERR_INVALID, "%s: perm / values / ray / basis is NULL", fn);
+    if (n_long > 0 && (long_rows == nullptr || long_chunk_ptr == nullptr || chunk_long == nullptr))
+        return fail(SVOXT_ERR_INVALID, "%s: long_rows / long_chunk_ptr / chunk_long is NULL", fn);
+    if (misaligned(ray, 4) || misaligned(basis, 4) || misaligned(values, 4) || misaligned(grad_values, 4) || misaligned(grad_sigma, 4) ||
+        misaligned(row_ptr, 4) || misaligned(perm, 4) || misaligned(long_rows, 4) || misaligned(long_chunk_ptr, 4) ||
+        misaligned(chunk_long, 4) || misaligned(grad, 4) || misaligned(workspace, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K),
+                                            "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)")))
+        return rc;
+    Carver w(workspace);
+    float* partials = w.take<float>((size_t)n_chunks * (size_t)K);
+    const ShadeValues src{ray, values, basis, grad_values, grad_sigma, T, Q, (int)K, C, bd, (int)opt->min_comp, (int)opt->max_comp, activate != 0};
+    // a lane per (row, column) over all K columns: every element of grad is written
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, T, (int)K, row_ptr, perm, M, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks, nullptr, (int)K,
+                                    0.f, grad, partials, (hipStream_t)stream);
+    return check_launch(fn);
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
     out = accumulate(samples, w, values)                           # out[q] = sum_k w_k values_k over ray q's samples
     out, alpha, w = composite(samples, f[:, -1], values)           # the two chained
     wmax = reduce_rows(samples, w.detach(), M, "max")              # [M]: a per-row statistic of per-sample values
+    rgb, sigma = renderer.shade_samples(samples, features, rays)   # [T, C], [T]: the samples' colours and densities, no [T, K]
 
 Every per-sample loss is then a few lines of torch around HIP operators whose results, gradients included, have the same
 bits in every run: the gradient of gather_rows reaches the table through reduce_rows' fixed-order row plan (DESIGN.md
@@ -107,6 +108,98 @@ def _ray_samples(self, rays: Rays, *, features=None, min_sigma=None, image_shape
 
 
 VolumeRenderer.ray_samples = _ray_samples
+
+
+# ------------------------------------------------------------------------------------------------ shading the samples
+def _refuse_transformation_matrices(what):
+    raise RuntimeError(f"VolumeRenderer.{what}: transformation_matrices are not served: the per-leaf rotation of the view "
+                       "direction is out of scope here (forward takes them; see INTEGRATION.md)")
+
+
+def _view_basis(self, rays: Rays, *, image_shape=None, transformation_matrices=None):
+    """basis float32 [Q, basis_dim]: every ray's basis values exactly as the render kernels form them from its view
+    direction -- SH 1 / 4 / 9 / 16 / 25, SG / ASG from tree.extra_data -- every component, whatever [min_comp, max_comp]
+    says.  RGBA: an empty [Q, 0] tensor.  A lane per ray, no march; not differentiable.  `image_shape` is accepted as the
+    neighbours take it and changes nothing."""
+    if transformation_matrices is not None:
+        _refuse_transformation_matrices("view_basis")
+    self._require_gpu(True, "view_basis")
+    with torch.no_grad():
+        return _C.view_basis(self.tree._spec(self.tree.features.detach()), _rays_spec_from_rays(rays, image_shape), self._get_options())
+
+
+class _ShadeSamplesFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, features, samples, basis, opt, activate):
+        values, sigma = _C.shade_samples_fwd(features.contiguous(), samples.row, samples.ray, basis, samples.Q, opt, activate)
+        ctx.samples, ctx.opt, ctx.activate, ctx.shape = samples, opt, activate, tuple(features.shape)
+        ctx.has_basis = basis is not None
+        ctx.set_materialize_grads(False)                         # (a None upstream gradient stays None: the kernel's null pointer)
+        ctx.save_for_backward(*((values,) if basis is None else (values, basis)))  # (sig: the forward's own output)
+        return values, sigma
+
+    @staticmethod
+    def backward(ctx, grad_values, grad_sigma):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        values = ctx.saved_tensors[0]
+        basis = ctx.saved_tensors[1] if ctx.has_basis else None
+        s = ctx.samples
+        gv = None if grad_values is None else grad_values.contiguous()
+        gs = None if grad_sigma is None else grad_sigma.contiguous()
+        plan = s.row_plan(ctx.shape[0])
+        grad = _C.shade_samples_bwd(ctx.shape, s.ray, basis, s.Q, ctx.opt, ctx.activate, values, gv, gs, plan.arrays)
+        return grad, None, None, None, None
+
+
+def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True,
+                   transformation_matrices=None):
+    """(values float32 [T, C], sigma float32 [T]): the colour of every sample -- the basis of its ray's view direction
+    dotted into its feature row's coefficients over [min_comp, max_comp], then the sigmoid (activate=False: the dot
+    product itself) -- and its density features[row, -1].  C = out_data_dim - 1: K - 1 for RGBA, (K - 1) // basis_dim
+    otherwise.  The arithmetic is the render kernels', operation for operation (include/svoxt.h,
+    svoxt_shade_samples_fwd).  A sample whose row is outside [0, M) gets zeros and no gradient.
+
+    :param features: float32 [M, K] (default: the tree's own)
+    :param rays: the Rays the samples were marched from (view_basis is called), or
+    :param basis: what view_basis returned for them, float32 [Q, basis_dim]; RGBA needs neither
+    Differentiable in `features`: the gradient is a full [M, K] table, every element written, summed per entry over
+    samples.row_plan(M) in reduce_rows' fixed order -- no [T, K] tensor, no atomics, the same bits in every run."""
+    if transformation_matrices is not None:
+        _refuse_transformation_matrices("shade_samples")
+    if not isinstance(samples, RaySamples):
+        raise RuntimeError("shade_samples: samples must be a RaySamples")
+    if features is None:
+        features = self.tree.features
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise RuntimeError("shade_samples: features must be float32 [M, K], K >= 1")
+    opt = self._get_options()
+    if int(opt.format) == 0:
+        basis = None
+    elif basis is None:
+        if rays is None:
+            raise RuntimeError("shade_samples: a format with a basis needs `rays` or a `basis` from view_basis")
+    elif not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (samples.Q, int(opt.basis_dim)):
+        raise RuntimeError(f"shade_samples: basis must be float32 [Q, basis_dim] = [{samples.Q}, {int(opt.basis_dim)}], "
+                           "view_basis of the samples' rays")
+    self._require_gpu(True, "shade_samples")
+    _require_gpu("shade_samples", samples, features, basis)
+    if int(opt.format) != 0:
+        basis = self.view_basis(rays) if basis is None else basis.detach().contiguous()
+        if basis.shape[0] != samples.Q:
+            raise RuntimeError(f"shade_samples: `rays` holds {basis.shape[0]} rays, the samples were marched from {samples.Q}")
+    return _ShadeSamplesFunction.apply(features, samples, basis, opt, bool(activate))
+
+
+VolumeRenderer.view_basis = _view_basis
+VolumeRenderer.shade_samples = _shade_samples
+
+
+def shade_samples(renderer: VolumeRenderer, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True):
+    """renderer.shade_samples(samples, features, rays, basis=basis, activate=activate) as a function, beside gather_rows."""
+    if not isinstance(renderer, VolumeRenderer):
+        raise RuntimeError("shade_samples: the first argument must be the VolumeRenderer whose format shades the samples")
+    return renderer.shade_samples(samples, features, rays, basis=basis, activate=activate)
 
 
 def _require_gpu(what, samples, *tensors):
