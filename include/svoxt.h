@@ -59,6 +59,28 @@ enum {
     SVOXT_ERR_HIP = 3           /* HIP runtime / launch failure                   */
 };
 
+/* Alignment.  A device pointer is aligned to its element (4 bytes for float / int32, 8 for int64) unless its entry
+ * point asks for more; a tensor may start anywhere in a larger buffer (flat[1:], a slice of a checkpoint blob).
+ * No entry point issues a 16-byte access through a caller's pointer that is not 16-byte aligned:
+ *   - The entry points whose kernels read tree.features as 16-byte vectors when K % 4 == 0 -- the colour render
+ *     (svoxt_volume_render_fwd / _fwd_ws / _fwd_scratch / _fwd_record, svoxt_volume_render_bwd / _bwd_replay), the
+ *     svoxt_step_* calls of a payload that is not padded, and svoxt_exp_table_build -- REFUSE such a table (and a
+ *     tree.exp_table) that is not 16-byte aligned: SVOXT_ERR_INVALID before any launch, svoxt_last_error() names the
+ *     function and the 16-byte requirement.  K % 4 != 0: rows are read float by float, any 4-byte alignment will do.
+ *     This was undefined before and is an error now: the ABI version is unchanged.
+ *   - The operators that read sigma alone take 4-byte alignment for every K: opacity (forward, backward, replay), depth,
+ *     depth moments, distortion, svoxt_ray_samples_*, the row-plan backward (svoxt_render_grad_rows_*), query, count, the
+ *     sigma bitmask, and the motion operators (their joint-feature rows are 16-byte reads of the aligned workspace).
+ *   - The operators that move or write whole rows choose a 16-byte or a 4-byte route from the pointers they get and give
+ *     the same bits either way, writing nothing outside the table: svoxt_assign_leaves, svoxt_prune_gather_rows,
+ *     svoxt_gather_rows, svoxt_shade_samples_fwd, svoxt_frontier_reduce, svoxt_compact_rows, svoxt_optim_step.
+ *     svoxt_frontier_diam chooses likewise (from features AND data), but its two routes add a pair's squared differences
+ *     in different orders: results agree within float32 rounding of the sum, not bit for bit (the Python layer hands it
+ *     aligned copies of both, so that one table gives one result wherever it starts).
+ *   - Workspaces, sample lists and matrix_out of svoxt_warp_vertices state their own alignment where they are declared.
+ * The Python operator layer (svox_t_amd.csrc) accepts any contiguous tensor: its colour render hands over an aligned copy
+ * of a feature table with K % 4 == 0 that starts off a 16-byte boundary (one integer test per call for an aligned one). */
+
 /* enum DataFormat, svox_t/csrc/include/data_spec.hpp:45-50 */
 enum {
     SVOXT_FORMAT_RGBA = 0,
@@ -71,7 +93,8 @@ enum {
  * feature storage: it holds, per leaf slot, the row index into `features`; a
  * slot is empty iff its index >= M (rt_kernel.cu:269). */
 typedef struct svoxt_tree {
-    const float*   features;     /* device [M, K] row-major; row = colour/SH coeffs..., sigma last */
+    const float*   features;     /* device [M, K] row-major; row = colour/SH coeffs..., sigma last; 16-byte aligned where
+                                    K % 4 == 0 and the entry point reads whole rows ("Alignment" above) */
     int64_t        M;
     int32_t        K;            /* data_dim */
     int32_t        N;            /* branching factor per axis (2 = octree) */

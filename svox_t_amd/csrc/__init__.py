@@ -820,7 +820,7 @@ def _volume_render(tree, rays, opt, record):
     # SVOXT_ACCEL_BRICKS).
     bricks = _numel(tree._weight_accum) == 0 and (bool(record) or (int(opt.format) == FORMAT_RGBA and tree.features.shape[1] in (8, 16, 32)
                                                                     and FWD_SPLIT != "0"))
-    ct, cr, co = _pack_tree_accel(tree, bricks), _pack_rays(rays), _pack_opts(opt)
+    ct, cr, co = _pack_tree_accel(tree, bricks, vec_rows=True), _pack_rays(rays), _pack_opts(opt)
     dev = tree.features.device
     lists = None
     wide = co.format == FORMAT_RGBA and ct.K in (8, 16, 32)
@@ -977,7 +977,7 @@ def volume_render_backward(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions,
 
 def _volume_render_backward(tree, rays, opt, grad_output, lists, fwd_output):
     # (the grid the forward that recorded the lists went through: a backward with lists marches overflowed rays at most)
-    ct, cr, co = _pack_tree_accel(tree, bool(getattr(lists, "bricks", False))), _pack_rays(rays), _pack_opts(opt)
+    ct, cr, co = _pack_tree_accel(tree, bool(getattr(lists, "bricks", False)), vec_rows=True), _pack_rays(rays), _pack_opts(opt)
     _check_input(grad_output, "grad_output")
     if grad_output.dtype != torch.float32 or grad_output.dim() != 2 or grad_output.shape[0] != cr.Q:
         raise RuntimeError("grad_output must be float32 [Q, C+1]")

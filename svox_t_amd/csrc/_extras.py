@@ -10,7 +10,7 @@ from typing import NamedTuple
 import torch
 
 from ._abi import _CMotion, _COptimHyper, _CRays, _CTree, _lib
-from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _drop_accel, _call, _check_input, _check_quantize, _numel, _pack_opts, _pack_rays,
+from ._marshal import (CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _aligned16, _drop_accel, _call, _check_input, _check_quantize, _numel, _pack_opts, _pack_rays,
                        get_out_data_dim, _on, _pack_tree, _pack_tree_accel, _ptr, _stream)
 
 def _check_indices(indices):
@@ -638,6 +638,11 @@ def frontier_diam(features, data, n_internal, N, nodes, cols=None, empty="zero",
         raise RuntimeError("cols out of range")
     dev = features.device
     F = nodes.shape[0]
+    if cols is None and N == 2 and K % 4 == 0 and K <= 32:
+        # The library's 16-byte route (whole rows of an octree node, taken where features and data are 16-byte aligned)
+        # adds a pair's squared differences in another order than its 4-byte route: both inputs are only read, so a
+        # tensor that starts elsewhere goes in as an aligned copy -- the same route and the same bits wherever it starts.
+        features, data = _aligned16(features), _aligned16(data)
     with _on(dev):
         out = torch.empty((F,), dtype=torch.float32, device=dev)
         _call("svoxt_frontier_diam", _ptr(features), features.shape[0], K, _ptr(data), n, N, _ptr(nodes), F, _ptr(cols),

@@ -102,6 +102,19 @@ def _ptr(x):
     return None if (x is None or x.numel() == 0) else x.data_ptr()
 
 
+def _aligned16(x):
+    """x itself where its data starts on a 16-byte boundary (one integer test), else a fresh copy of it, which does:
+    same values, dtype and shape.  For tensors the kernels only READ as 16-byte vectors -- a contiguous view into a larger
+    buffer (`flat[1:].view(M, K)`, `grad[1:]`) is a legal input that starts anywhere (include/svoxt.h, "Alignment").
+    The caller keeps the copy alive for as long as the launch may run; nothing is cached, so nothing can go stale."""
+    if x.data_ptr() % 16 == 0:
+        return x
+    with torch.no_grad():
+        y = torch.empty_like(x, memory_format=torch.contiguous_format, requires_grad=False)
+        y.copy_(x)
+    return y
+
+
 def _check_quantize(data, weights, order):
     """The argument checks of quantize_median_cut, shapes and values before devices, all before any GPU work.
     Returns (weights or None, order)."""
@@ -135,8 +148,9 @@ def _check_quantize(data, weights, order):
     return weights, order
 
 
-def _pack_tree(tree: TreeSpec) -> _CTree:
-    """TreeSpec.check() (data_spec.hpp:85-110) + pointer extraction."""
+def _pack_tree(tree: TreeSpec, vec_rows: bool = False) -> _CTree:
+    """TreeSpec.check() (data_spec.hpp:85-110) + pointer extraction.  vec_rows: the call goes to an entry point whose
+    kernels read whole feature rows as 16-byte vectors (the colour render: what check_features_vec guards in the library)."""
     _check_input(tree.features, "features")
     _check_input(tree.data, "data")
     _check_input(tree.child, "child")
@@ -169,7 +183,14 @@ def _pack_tree(tree: TreeSpec) -> _CTree:
     if n_internal > tree.child.shape[0]:
         raise RuntimeError("n_internal exceeds the capacity of child")
     c = _CTree()
-    c.features = _ptr(tree.features)
+    # Rows of a multiple of 4 floats are read as 16-byte vectors by the colour render (svoxt_device.h, load_row): for it
+    # a table that starts off a 16-byte boundary goes in as an aligned copy, kept alive on the struct.  Everything that
+    # recognises a feature table (the sigma bitmask's and the exponentials table's cache, the plans) looks at
+    # tree.features, the caller's tensor; every other operator reads single floats and takes the table as it is.
+    f = tree.features
+    if vec_rows and f.shape[1] % 4 == 0:
+        f = c._keepalive_features = _aligned16(f)
+    c.features = _ptr(f)
     c.M, c.K = tree.features.shape
     c.N = tree.child.shape[1]
     c.data = tree.data.data_ptr()
@@ -382,10 +403,10 @@ def _drop_accel(child) -> None:
         _ACCEL_CACHE.pop((id(child), b), None)
 
 
-def _pack_tree_accel(tree: TreeSpec, bricks: bool = False) -> _CTree:
+def _pack_tree_accel(tree: TreeSpec, bricks: bool = False, vec_rows: bool = False) -> _CTree:
     """_pack_tree + the (cached) acceleration grid for the marching kernels; `bricks`: in the layout that pays where a
     kernel waits for the cell load alone (include/svoxt.h, SVOXT_ACCEL_BRICKS)."""
-    ct = _pack_tree(tree)
+    ct = _pack_tree(tree, vec_rows)
     cells, g = _accel_for(tree, ct, bricks)
     if cells is not None:
         ct.accel = cells.data_ptr()

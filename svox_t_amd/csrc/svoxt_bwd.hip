@@ -206,6 +206,8 @@ int bwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_optio
     if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) ||
         (rc = check_opts(opt, tree, fn, grad_cols > 1)))
         return rc;
+    // (the opacity backward, grad_cols == 1, reads sigma alone, float by float)
+    if (grad_cols > 1 && (rc = check_features_vec(tree, fn))) return rc;
     if (grad_features == nullptr && tree->M > 0) return fail(SVOXT_ERR_INVALID, "%s: grad_features is NULL", fn);
     if (rays->Q > 0 && grad_out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad_out is NULL", fn);
     const int C = grad_cols - 1;

@@ -801,8 +801,10 @@ __device__ __forceinline__ double sigmoid_d(float x) {
     return 1.0 / (1.0 + (double)pexpf<PIN>(-x));
 }
 
-// Feature row -> registers.  16-byte loads when the row stride allows it
-// (K % 4 == 0 and torch allocations are >= 16-byte aligned).
+// Feature row -> registers.  16-byte loads when K % 4 == 0: the table then has to start on a 16-byte boundary.  That is
+// the C ABI's contract (include/svoxt.h, "Alignment"), enforced before any launch by check_features_vec (svoxt_kernels.hip)
+// in every entry point that reaches a caller of this function; the Python boundary hands over an aligned copy of a table
+// that starts elsewhere (_marshal.py, _aligned16).  Rows read from the library's own workspaces are aligned by their carving.
 template <int K>
 __device__ __forceinline__ void load_row(const float* __restrict__ p, float (&row)[K]) {
     if constexpr (K % 4 == 0) {

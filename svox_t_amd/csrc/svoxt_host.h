@@ -50,6 +50,10 @@ int check_launch(const char* what);
 // Argument validation shared by every entry point (the TORCH_CHECKs of
 // data_spec.hpp:57-64, 85-110 for raw pointers); `fn` names the caller in the error text.
 int check_tree(const svoxt_tree* t, const char* fn);
+// ... and of the entry points whose kernels read tree.features (and tree.exp_table) as 16-byte vectors when K % 4 == 0
+// (load_row, the channel-row kernels, exp_table_kernel: the colour render forward and backwards, svoxt_step_*,
+// svoxt_exp_table_build): such a table must start on a 16-byte boundary.  Called next to check_tree, before any launch.
+int check_features_vec(const svoxt_tree* t, const char* fn);
 int check_rays(const svoxt_rays* r, const char* fn);
 int check_opts(const svoxt_options* o, const svoxt_tree* t, const char* fn, bool needs_basis);
 

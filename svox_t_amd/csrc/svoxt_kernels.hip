@@ -89,6 +89,16 @@ int check_tree(const svoxt_tree* t, const char* fn) {
     return SVOXT_OK;
 }
 
+int check_features_vec(const svoxt_tree* t, const char* fn) {
+    if (t->K % 4 != 0) return SVOXT_OK;             // rows that do not start on 16-byte boundaries are read float by float
+    if (((uintptr_t)t->features & 15u) != 0)
+        return fail(SVOXT_ERR_INVALID, "%s: tree.features is not 16-byte aligned: with K a multiple of 4 its rows are read as "
+                    "16-byte vectors (copy the table to an aligned buffer)", fn);
+    if (((uintptr_t)t->exp_table & 15u) != 0)
+        return fail(SVOXT_ERR_INVALID, "%s: tree.exp_table is not 16-byte aligned", fn);
+    return SVOXT_OK;
+}
+
 int check_rays(const svoxt_rays* r, const char* fn) {
     if (r == nullptr) return fail(SVOXT_ERR_INVALID, "%s: rays is NULL", fn);
     if (r->Q < 0) return fail(SVOXT_ERR_INVALID, "%s: negative ray count", fn);
@@ -470,7 +480,8 @@ static int fwd_common(const svoxt_tree* tree, const svoxt_rays* rays, const svox
                       void* workspace = nullptr, int64_t workspace_bytes = 0, int32_t flags = 0,
                       const svoxt_sample_lists* scratch = nullptr) {
     int rc;
-    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, true)))
+    if ((rc = check_tree(tree, fn)) || (rc = check_features_vec(tree, fn)) || (rc = check_rays(rays, fn)) ||
+        (rc = check_opts(opt, tree, fn, true)))
         return rc;
     if (lists != nullptr && (rc = check_lists(lists, opt, fn))) return rc;
     if (lists != nullptr && uses_xform(tree, opt) && !(full_comp(opt) && xform_special(tree, opt)))
@@ -635,12 +646,12 @@ int svoxt_sigma_mask_build_fill(const svoxt_tree* tree, float sigma_thresh, void
 int svoxt_exp_table_build(const svoxt_tree* tree, float sigma_thresh, void* mask, float* table, void* stream) {
     const char* fn = "svoxt_exp_table_build";
     int rc;
-    if ((rc = check_tree(tree, fn))) return rc;
+    if ((rc = check_tree(tree, fn)) || (rc = check_features_vec(tree, fn))) return rc;
     if (!chan_rows(tree->K))
         return fail(SVOXT_ERR_UNSUPPORTED, "%s: the table serves RGBA-style rows of 8, 16 or 32 floats", fn);
     if (tree->M == 0) return SVOXT_OK;
-    if (table == nullptr || ((uintptr_t)table & 15u) != 0 || ((uintptr_t)tree->features & 15u) != 0)
-        return fail(SVOXT_ERR_INVALID, "%s: table is NULL, or table / features not 16-byte aligned", fn);
+    if (table == nullptr || ((uintptr_t)table & 15u) != 0)
+        return fail(SVOXT_ERR_INVALID, "%s: table is NULL or not 16-byte aligned", fn);
     if (mask != nullptr && ((uintptr_t)mask & 7u) != 0) return fail(SVOXT_ERR_INVALID, "%s: mask not 8-byte aligned", fn);
     const int64_t threads = tree->M * (tree->K / 4);
     const dim3 grid((unsigned)((threads + 255) / 256));

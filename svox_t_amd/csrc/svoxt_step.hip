@@ -96,6 +96,8 @@ int svoxt_step_plan(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_
         padded_tree.K = pl.Kp;
         tree = &padded_tree;
         step->pad_K = pl.Kp; step->pad_real = pl.real; step->pad_dummy = pl.dummy; step->pad_w = pl.w;
+    } else if ((rc = check_features_vec(tree, fn))) {      // (a padded payload is rendered from its aligned copy in the workspace)
+        return rc;
     }
     const int64_t Q = rays->Q, M = tree->M, K = tree->K;
     const int cols = svoxt_out_data_dim(opt, tree->K);
@@ -176,6 +178,7 @@ int svoxt_step_forward(const svoxt_tree* tree, const svoxt_rays* rays, const svo
     if (step == nullptr || workspace == nullptr || tree == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: NULL argument", fn);
     if (((uintptr_t)workspace & 255u) != 0) return set_error(SVOXT_ERR_INVALID, "%s: workspace must be 256-byte aligned", fn);
     int rc;
+    if (!step->pad_K && (rc = check_features_vec(tree, fn))) return rc;
     svoxt_tree padded_tree;
     float* out_caller = out;
     const int cols_caller = opt != nullptr ? svoxt_out_data_dim(opt, tree->K) : 0;
@@ -226,6 +229,7 @@ int svoxt_step_backward(const svoxt_tree* tree, const svoxt_rays* rays, const sv
         return set_error(SVOXT_ERR_INVALID, "%s: NULL argument", fn);
     if (grad_features == nullptr && tree->M > 0) return set_error(SVOXT_ERR_INVALID, "%s: grad_features is NULL", fn);
     int rc;
+    if (!step->pad_K && (rc = check_features_vec(tree, fn))) return rc;
     svoxt_tree padded_tree;
     float* grad_caller = grad_features;
     const int32_t K_caller = tree->K;
