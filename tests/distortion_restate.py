@@ -10,9 +10,10 @@ in `dtype`: float32 reproduces the kernels' operation sequence, float64 is the y
 
     distortion(tree, rays, opt, dtype)          [Q, 2] (L, alpha)
     distortion_grad(tree, rays, opt, g)         [M, K] float64: autograd of sum(distortion * g) at thresholds 0
-    distortion_grad_scale(tree, rays, opt, g)   [M, K] float64: sum_k d_k (|gd| (|u_k| T_{k+1} + 2 L) + |ga| T_end), the
-                                                gradient's addends priced one by one, the suffix sum by the full sum 2 L
-                                                it is subtracted down from
+    distortion_grad_scale(tree, rays, opt, g)   [M, K] float64: sum_k d_k (|gd| (|u_k| T_{k+1} + 2 L + 2 E_0 + ETA V_k) +
+                                                |ga| T_end), the gradient's addends priced one by one, the suffix sum by
+                                                the full sum 2 L and E_k by the E_0 they are subtracted down from, and one
+                                                unit in the last place of every attenuation (the function's docstring)
     ray_samples(tree, rays, opt)                per ray: float64 arrays (w, s, d) of the samples with sigma > 0
 tree: O.Tree; rays: (origins, dirs, vdirs) numpy; opt: O.RenderOptions; g: [Q, 2] numpy.
 """
@@ -115,22 +116,61 @@ def _sweep(tree: O.Tree, rays, opt):
     return m, recs, L, light
 
 
+ETA = 2.0 ** -23 / 1e-5          # one unit in the last place of an attenuation, in units of the bound 1e-5 * scale
+
+
 def distortion_grad_scale(tree: O.Tree, rays, opt, grad_output):
     """[M, K] float64, non-zero in the sigma column only: sum over the samples of a row of
-    d_k (|gd| (|u_k| T_{k+1} + 2 L) + |ga| T_end), u_k = 2 (D_k + E_k) + (2/3) w_k d_k."""
+    d_k (|gd| (|u_k| T_{k+1} + 2 L + 2 E_0 + ETA V_k) + |ga| T_end), u_k = 2 (D_k + E_k) + (2/3) w_k d_k.
+
+    |u_k| T_{k+1} + 2 L prices the addends of u_k T_{k+1} - sum_{i>k} w_i u_i as they stand.  Two rounding errors of the
+    float32 sequence are proportional to neither, and the other two terms price them:
+
+    2 E_0.  Sweep 2 does not sum E_k = sum_{j>k} w_j (s_j - s_k), it subtracts it down from E_0 = sum_j w_j (s_j - s_0):
+        E_k = E_{k-1} - (A_tot - A_k)(s_k - s_{k-1}).  Every intermediate lies in [E_k, E_0], so E_k carries an error of
+        a few units in the last place of E_0 whatever its own size -- behind a thin first sample E_0 is the ray's whole
+        spread while E_k, u_k and 2 L = sum w_i u_i >= 2 w_0 E_0 are all small.  u_k = 2 (D_k + E_k) + ... moves by twice
+        that error; it enters the sample's value once through u_k T_{k+1} and once, times w_i for every i <= k, through
+        the suffix sum: 2 E_0 (T_{k+1} + sum_{i<=k} w_i) = 2 E_0.
+    ETA V_k, V_k = 2 sum_j T_j |s_k - s_j| + (2/3) d_k T_k.  att_j is a float32 exponential: it is off by up to one unit
+        in its last place, 2^-23 att_j at most, and so is w_j = T_j (1 - att_j) in absolute terms, by 2^-23 T_j -- of a thin
+        sample's weight, 1 - att_j ~ 1e-3, that is 1e-4, where the float64 yardstick has the exact exponential.  (T_j
+        itself is off by as much relative to T_j: that is priced with the addends it multiplies.)  u_k moves by
+        2 sum_j dw_j |s_k - s_j| + (2/3) d_k dw_k <= 2^-23 V_k, and reaches the value as 2 E_0 does, with total weight 1.
+        An error of fixed absolute size enters a scale that is multiplied by 1e-5 divided by 1e-5: ETA = 2^-23 / 1e-5.
+
+    On coherent camera rays over a shell (w_0 is no thinner than the rest) 2 L already covers both; on irregular trees
+    with sigma from 1e-2 to 1e4 along one ray it does not (tests/test_gpu_adversarial.py)."""
     m, recs, L, t_end = _sweep(tree, rays, opt)
     g = torch.as_tensor(np.asarray(grad_output), dtype=torch.float64).abs()
     Q = m.Q
-    after = torch.zeros(Q, dtype=torch.float64)                      # sum_{j>k} w_j
-    E = torch.zeros(Q, dtype=torch.float64)                          # sum_{j>k} w_j (s_j - s_k)
-    sn = torch.zeros(Q, dtype=torch.float64)                         # s_{k+1}
+    zeros = lambda: torch.zeros(Q, dtype=torch.float64)              # noqa: E731
+    # forward: E_0, and P_k = sum_{j<k} T_j (s_k - s_j) as D_k is formed, with T_j (in front of sample j) in the place of w_j
+    s0, E0, B, P, sp = zeros(), zeros(), zeros(), zeros(), zeros()
+    seen = torch.zeros(Q, dtype=torch.bool)
+    before = []
+    for a, ra, w, s, d, Dk, tn in recs:
+        s0[a] = torch.where(seen[a], s0[a], s)
+        seen[a] = True
+        E0[a] += w * (s - s0[a])
+        P[a] += B[a] * (s - sp[a])                                   # (the first sample: B == 0)
+        sp[a] = s
+        B[a] += tn + w
+        before.append(P[a].clone())
+    after = zeros()                                                  # sum_{j>k} w_j
+    E = zeros()                                                      # sum_{j>k} w_j (s_j - s_k)
+    C, R = zeros(), zeros()                                          # sum_{j>k} T_j and sum_{j>k} T_j (s_j - s_k)
+    sn = zeros()                                                     # s_{k+1}
     scale = np.zeros((tree.M, tree.K), dtype=np.float64)
-    for a, ra, w, s, d, Dk, tn in reversed(recs):
+    for (a, ra, w, s, d, Dk, tn), Pk in zip(reversed(recs), reversed(before)):
         E[a] += after[a] * (sn[a] - s)                               # (the last sample: after == 0)
+        R[a] += C[a] * (sn[a] - s)
         u = 2.0 * (Dk + E[a]) + (2.0 / 3.0) * w * d
+        V = 2.0 * (Pk + R[a]) + (2.0 / 3.0) * d * (tn + w)
         np.add.at(scale[:, tree.K - 1], ra.numpy(),
-                  (d * (g[a, 0] * (u.abs() * tn + 2.0 * L[a]) + g[a, 1] * t_end[a])).numpy())
+                  (d * (g[a, 0] * (u.abs() * tn + 2.0 * L[a] + 2.0 * E0[a] + ETA * V) + g[a, 1] * t_end[a])).numpy())
         after[a] += w
+        C[a] += tn + w
         sn[a] = s
     return scale
 
