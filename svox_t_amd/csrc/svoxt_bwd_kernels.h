@@ -1737,81 +1737,67 @@ render_bwd_generic_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
     float accum = 0.f;
     float light_ray;
     {   // pass 1
-        float light = 1.f, t = r.tmin;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float* row = tr.features + (int64_t)s.idx * K;
-                const float sigma = row[K - 1];
-                if (sigma > 0.f) {
-                    float* grow = grad + (int64_t)s.idx * gstride;
-                    // pass 1 re-evaluates the rotated basis; pass 2 keeps the last one
-                    if (tr.xform != nullptr) rotated_basis(tr, opt.format, opt.basis_dim, s.idx, vd, basis);
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    const float weight = light * (1.f - att);
-                    float total_color = 0.f;
-                    if (opt.format != FMT_RGBA) {
-                        for (int c = 0; c < C; ++c) {
-                            const int off = c * opt.basis_dim;
-                            float tmp = 0.f;
-                            for (int i = opt.min_comp; i <= opt.max_comp; ++i) tmp += basis[i] * row[off + i];
-                            const float sig = (float)(1.0 / (1.0 + (double)pexpf(-tmp)));
-                            const float gsig = (float)((double)sig * (1.0 - (double)sig));
-                            for (int i = opt.min_comp; i <= opt.max_comp; ++i)
-                                atomicAdd(grow + off + i, weight * basis[i] * gsig * g[c]);
-                            total_color += sig * g[c];
-                        }
-                    } else {
-                        for (int j = 0; j < C; ++j) {
-                            const float sig = (float)(1.0 / (1.0 + (double)pexpf(-row[j])));
-                            atomicAdd(grow + j, weight * sig * (1.f - sig) * g[j]);
-                            total_color += sig * g[j];
-                        }
-                    }
-                    light *= att;
-                    accum += weight * total_color;
+        float light = 1.f;
+        walk_samples<N2>(tr, r, opt.step_size, r.tmin, 0.f, [&](const Sample& s, float, float sigma) {
+            const float* row = tr.features + (int64_t)s.idx * K;
+            float* grow = grad + (int64_t)s.idx * gstride;
+            // pass 1 re-evaluates the rotated basis; pass 2 keeps the last one
+            if (tr.xform != nullptr) rotated_basis(tr, opt.format, opt.basis_dim, s.idx, vd, basis);
+            const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+            const float weight = light * (1.f - att);
+            float total_color = 0.f;
+            if (opt.format != FMT_RGBA) {
+                for (int c = 0; c < C; ++c) {
+                    const int off = c * opt.basis_dim;
+                    float tmp = 0.f;
+                    for (int i = opt.min_comp; i <= opt.max_comp; ++i) tmp += basis[i] * row[off + i];
+                    const float sig = (float)(1.0 / (1.0 + (double)pexpf(-tmp)));
+                    const float gsig = (float)((double)sig * (1.0 - (double)sig));
+                    for (int i = opt.min_comp; i <= opt.max_comp; ++i)
+                        atomicAdd(grow + off + i, weight * basis[i] * gsig * g[c]);
+                    total_color += sig * g[c];
+                }
+            } else {
+                for (int j = 0; j < C; ++j) {
+                    const float sig = (float)(1.0 / (1.0 + (double)pexpf(-row[j])));
+                    atomicAdd(grow + j, weight * sig * (1.f - sig) * g[j]);
+                    total_color += sig * g[j];
                 }
             }
-            t = march_advance(t, s.delta_t);
-        }
+            light *= att;
+            accum += weight * total_color;
+            return true;
+        });
         float total_grad = 0.f;
         for (int j = 0; j < C; ++j) total_grad += g[j];
         accum += light * opt.background_brightness * total_grad;
         light_ray = light;
     }
     {   // pass 2
-        float light = 1.f, t = r.tmin;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float* row = tr.features + (int64_t)s.idx * K;
-                const float sigma = row[K - 1];
-                if (sigma > 0.f) {
-                    float total_color = 0.f;
-                    if (opt.format != FMT_RGBA) {
-                        for (int c = 0; c < C; ++c) {
-                            const int off = c * opt.basis_dim;
-                            float tmp = 0.f;
-                            for (int i = opt.min_comp; i <= opt.max_comp; ++i) tmp += basis[i] * row[off + i];
-                            total_color = (float)((double)total_color + 1.0 / (1.0 + (double)pexpf(-tmp)) * (double)g[c]);
-                        }
-                    } else {
-                        for (int j = 0; j < C; ++j)
-                            total_color = (float)((double)total_color + 1.0 / (1.0 + (double)pexpf(-row[j])) * (double)g[j]);
-                    }
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    const float weight = light * (1.f - att);
-                    light *= att;
-                    accum -= weight * total_color;
-                    const float toadd = s.delta_t * r.delta_scale * (total_color * light - accum)
-                                      + s.delta_t * r.delta_scale * g[C] * light_ray;
-                    atomicAdd(grad + (int64_t)s.idx * gstride + (K - 1), toadd);
+        float light = 1.f;
+        walk_samples<N2>(tr, r, opt.step_size, r.tmin, 0.f, [&](const Sample& s, float, float sigma) {
+            const float* row = tr.features + (int64_t)s.idx * K;
+            float total_color = 0.f;
+            if (opt.format != FMT_RGBA) {
+                for (int c = 0; c < C; ++c) {
+                    const int off = c * opt.basis_dim;
+                    float tmp = 0.f;
+                    for (int i = opt.min_comp; i <= opt.max_comp; ++i) tmp += basis[i] * row[off + i];
+                    total_color = (float)((double)total_color + 1.0 / (1.0 + (double)pexpf(-tmp)) * (double)g[c]);
                 }
+            } else {
+                for (int j = 0; j < C; ++j)
+                    total_color = (float)((double)total_color + 1.0 / (1.0 + (double)pexpf(-row[j])) * (double)g[j]);
             }
-            t = march_advance(t, s.delta_t);
-        }
+            const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+            const float weight = light * (1.f - att);
+            light *= att;
+            accum -= weight * total_color;
+            const float toadd = s.delta_t * r.delta_scale * (total_color * light - accum)
+                              + s.delta_t * r.delta_scale * g[C] * light_ray;
+            atomicAdd(grad + (int64_t)s.idx * gstride + (K - 1), toadd);
+            return true;
+        });
     }
 }
 
@@ -1846,34 +1832,28 @@ render_bwd_generic_staged_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
     float accum = 0.f, light_ray = 1.f;
     if (alive) {
         precalc_basis<0>(opt.format, opt.basis_dim, tr, vd[0], vd[1], vd[2], basis);
-        float light = 1.f, t = r.tmin;
-        while (t < r.tmax) {                               // march 1 (rt_kernel.cu:365-437 minus the atomics)
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float* row = tr.features + (int64_t)s.idx * K;
-                const float sigma = row[K - 1];
-                if (sigma > 0.f) {
-                    if (tr.xform != nullptr) rotated_basis(tr, opt.format, opt.basis_dim, s.idx, vd, basis);
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    const float weight = light * (1.f - att);
-                    float total_color = 0.f;
-                    for (int c = 0; c < C; ++c) {
-                        float x;
-                        if (rgba) {
-                            x = row[c];
-                        } else {
-                            x = 0.f;
-                            for (int i = opt.min_comp; i <= opt.max_comp; ++i) x += basis[i] * row[c * opt.basis_dim + i];
-                        }
-                        total_color += (float)(1.0 / (1.0 + (double)pexpf(-x))) * g[c];
-                    }
-                    light *= att;
-                    accum += weight * total_color;
+        float light = 1.f;
+        // march 1 (rt_kernel.cu:365-437 minus the atomics)
+        walk_samples<N2>(tr, r, opt.step_size, r.tmin, 0.f, [&](const Sample& s, float, float sigma) {
+            const float* row = tr.features + (int64_t)s.idx * K;
+            if (tr.xform != nullptr) rotated_basis(tr, opt.format, opt.basis_dim, s.idx, vd, basis);
+            const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+            const float weight = light * (1.f - att);
+            float total_color = 0.f;
+            for (int c = 0; c < C; ++c) {
+                float x;
+                if (rgba) {
+                    x = row[c];
+                } else {
+                    x = 0.f;
+                    for (int i = opt.min_comp; i <= opt.max_comp; ++i) x += basis[i] * row[c * opt.basis_dim + i];
                 }
+                total_color += (float)(1.0 / (1.0 + (double)pexpf(-x))) * g[c];
             }
-            t = march_advance(t, s.delta_t);
-        }
+            light *= att;
+            accum += weight * total_color;
+            return true;
+        });
         float total_grad = 0.f;
         for (int j = 0; j < C; ++j) total_grad += g[j];
         accum += light * opt.background_brightness * total_grad;
@@ -1890,14 +1870,10 @@ render_bwd_generic_staged_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
         bool active = false;
         int32_t idx = -1;
         Sample s;
-        const float* row = nullptr;
-        if (t < tmax) {
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            t = march_advance(t, s.delta_t);
-            if (s.valid) {
-                row = tr.features + (int64_t)s.idx * K;
-                if (row[K - 1] > 0.f) { active = true; idx = s.idx; }
-            }
+        float sigma = 0.f;
+        if (t < tmax) {                                    // one crossing per round
+            next_crossing<N2>(tr, r, opt.step_size, t, s);
+            if (is_sample(tr, s, 0.f, sigma)) { active = true; idx = s.idx; }
         }
         const unsigned long long amask = __ballot(active);
         if (amask == 0ull) continue;
@@ -1907,7 +1883,7 @@ render_bwd_generic_staged_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
             sidx[slot] = idx;
             float* st = stage + slot * KS;
             for (int j = 0; j < K - 1; ++j) st[j] = 0.f;       // columns outside the component range stay 0
-            const float sigma = row[K - 1];
+            const float* row = tr.features + (int64_t)idx * K;
             if (tr.xform != nullptr) rotated_basis(tr, opt.format, opt.basis_dim, idx, vd, basis);
             const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
             const float weight = light * (1.f - att);

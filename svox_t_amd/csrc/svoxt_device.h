@@ -617,6 +617,63 @@ __device__ __forceinline__ float march_advance(float t, float delta_t) {
     return (tn > t) ? tn : __int_as_float(0x7f800000);
 }
 
+// The walk over a ray's samples, stated once for the per-ray operators: what a crossing is, what makes a crossing a
+// sample, and the loop.  Kernels that must agree crossing for crossing (a count and its emit, a recording forward and the
+// tails that resume from its t_resume, the passes of a backward) agree because they all come through here.
+//
+// A crossing: march_step at t, then t moves on -- by march_advance and nowhere else.  The Sample is the leaf at the t the
+// caller passed in (keep a copy where a payload wants it: the t a sample is "at", the t to resume a march from).
+template <bool N2, int ACC = -1, bool MARK = false>
+__device__ __forceinline__ void next_crossing(const TreeDev& tr, const Ray& r, float step_size, float& t, Sample& s,
+                                              uint8_t* mark = nullptr, uint32_t n_slots = 0) {
+    march_step<N2, ACC, MARK>(tr, r, step_size, t, s, mark, n_slots);
+    t = march_advance(t, s.delta_t);
+}
+
+// A sample: a crossing whose data word names a feature row (s.valid) with sigma > min_sigma -- written this way round,
+// so that a NaN sigma is never a sample.  Among the kernels that walk through here this is the one read of the sigma
+// column for the test; those that want the rest of the row read it through a pointer of their own.
+__device__ __forceinline__ bool is_sample(const TreeDev& tr, const Sample& s, float min_sigma, float& sigma) {
+    if (!s.valid) return false;
+    sigma = tr.features[(int64_t)s.idx * tr.K + (tr.K - 1)];
+    return sigma > min_sigma;
+}
+
+// The loop: f(s, t_at) for every crossing from t0 while t < r.tmax, t_at the t the crossing was marched at.  A false
+// return ends the walk.  The body is next_crossing's two calls with the payload between them, and that order is part
+// of the loop's shape: with t advanced first, a crossing that is no sample has nothing left to do, the compiler gives
+// that path a back edge -- an inner loop -- of its own, and the lanes that hold a sample idle until every lane of
+// the wavefront has found one (opacity forward at 800 x 800 / depth 8: 0.13 -> 0.53 ms; registers unchanged).  With the
+// advance at the single back edge the code is the hand-written loop's.
+template <bool N2, bool MARK = false, class F>
+__device__ __forceinline__ void walk_crossings(const TreeDev& tr, const Ray& r, float step_size, float t0, F&& f,
+                                               uint8_t* mark = nullptr, uint32_t n_slots = 0) {
+    float t = t0;
+    while (t < r.tmax) {
+        Sample s;
+        march_step<N2, -1, MARK>(tr, r, step_size, t, s, mark, n_slots);
+        if (!f(s, t)) break;
+        t = march_advance(t, s.delta_t);
+    }
+}
+
+// ... and f(s, t_at, sigma) for every sample among them.
+template <bool N2, class F>
+__device__ __forceinline__ void walk_samples(const TreeDev& tr, const Ray& r, float step_size, float t0, float min_sigma, F&& f) {
+    walk_crossings<N2>(tr, r, step_size, t0, [&](const Sample& s, float t_at) {
+        float sigma;
+        return !is_sample(tr, s, min_sigma, sigma) || f(s, t_at, sigma);
+    });
+}
+
+// Wavefront-synchronous kernels (a crossing or a sample per lane and round, then a flush by all lanes) call next_crossing
+// and is_sample themselves and keep their own cadence.  Not walked through here, on purpose: the tuned render path, whose
+// loops are shaped around their loads -- render_fwd_ray (the next descent is in flight while a sample is shaded),
+// march_rec_tile of march_rec_kernel and fwd_roles_kernel (sigma is looked at one crossing late), tail_chan_kernel (lanes
+// are channels), render_bwd_kernel and with it the list walkers grad_fused_kernel and grad_wide_kernel --,
+// render_fwd_generic_kernel (measured slower as a payload for wide rows: see there) and grid_weights_kernel
+// (svoxt_gridw.hip), which does not use march_step: its cell locate is its own.
+
 // SH constants, `const float` in the reference (rt_kernel.cu:54-84).
 __device__ __constant__ const float kC0 = 0.28209479177387814;
 __device__ __constant__ const float kC1 = 0.4886025119029199;

@@ -2,8 +2,9 @@
 // per cell, the largest compositing weight any ray gave it and the number of samples that landed in it (the
 // reference's grid_weight_render, svox_t/csrc/rt_kernel.cu:1240-1344, host :1454-1478).
 //
-// One ray (grid_trace_ray): the preamble every marching kernel here uses (setup_ray: camera ray, NDC warp, world ->
-// unit cube, direction normalised, invdir in double, slab test), then while t < tmax: pos = origin + t dir, clamped to
+// One ray (grid_trace_ray): the preamble of svoxt_device.h (setup_ray: camera ray, NDC warp, world -> unit cube,
+// direction normalised, invdir in double, slab test), then a loop of its own -- not the shared walk of svoxt_device.h,
+// whose crossing is a tree leaf found by march_step; here it is a cell of the volume: while t < tmax: pos = origin + t dir, clamped to
 // [0, 1 - 1e-6], times R, split into cell (u, v, w) and the cell-local point; delta_t = the cell's chord / R +
 // step_size (leaf_delta_t: _dda_unit on the local point, whose entry distance is 0); sigma = volume[cell]; if sigma >
 // sigma_thresh: att = pexpf(-delta_t delta_scale sigma), w = T (1 - att), T *= att, weight[cell] = max(.., w),

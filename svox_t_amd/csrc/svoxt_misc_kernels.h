@@ -39,44 +39,36 @@ opacity_fwd_kernel(TreeDev tr, RaysDev rays, Opts opt, float* __restrict__ out,
         if constexpr (REC) aux[q] = make_uint4(0u, 0u, __float_as_uint(1.f), 0u);
         return;
     }
-    const int K = tr.K;
-    float light = 1.f, t = r.tmin;
+    float light = 1.f;
     int nrec = 0;
     bool over = false, stopped = false;
     float t_resume = 0.f;
-    while (t < r.tmax) {
-        Sample s;
-        march_step<N2>(tr, r, opt.step_size, t, s);
-        if (s.valid) {
-            const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-            // (REC, r05: every sigma > 0 is recorded -- the backward's set, rt_kernel.cu:382 -- and composited only by the
-            // forward's own rules: sigma > sigma_thresh, not after T <= stop_thresh)
-            if (sigma > (REC ? 0.f : opt.sigma_thresh)) {
-                if constexpr (REC) {
-                    bool room = nrec < S;
-                    if (room && (nrec & 7) == 0) {
-                        cur_block = rec_block_begin(L, ltab, tid >> 6, nrec >> 3);
-                        room = cur_block >= 0;
-                    }
-                    if (room) {
-                        rec_stage_put(rstage, (int)threadIdx.x, L.rec, cur_block, nrec, (uint32_t)s.idx, s.delta_t);
-                        ++nrec;
-                    } else if (!over) {
-                        over = true;
-                        t_resume = t;
-                    }
-                }
-                if (!REC || (sigma > opt.sigma_thresh && !stopped)) {
-                    light *= pexpf(-s.delta_t * r.delta_scale * sigma);
-                    if (light <= opt.stop_thresh) {
-                        if constexpr (!REC) break;
-                        stopped = true;
-                    }
-                }
+    // (REC, r05: every sigma > 0 is recorded -- the backward's set, rt_kernel.cu:382 -- and composited only by the
+    // forward's own rules: sigma > sigma_thresh, not after T <= stop_thresh)
+    walk_samples<N2>(tr, r, opt.step_size, r.tmin, REC ? 0.f : opt.sigma_thresh, [&](const Sample& s, float t, float sigma) {
+        if constexpr (REC) {
+            bool room = nrec < S;
+            if (room && (nrec & 7) == 0) {
+                cur_block = rec_block_begin(L, ltab, tid >> 6, nrec >> 3);
+                room = cur_block >= 0;
+            }
+            if (room) {
+                rec_stage_put(rstage, (int)threadIdx.x, L.rec, cur_block, nrec, (uint32_t)s.idx, s.delta_t);
+                ++nrec;
+            } else if (!over) {
+                over = true;
+                t_resume = t;
             }
         }
-        t = march_advance(t, s.delta_t);
-    }
+        if (!REC || (sigma > opt.sigma_thresh && !stopped)) {
+            light *= pexpf(-s.delta_t * r.delta_scale * sigma);
+            if (light <= opt.stop_thresh) {
+                if constexpr (!REC) return false;
+                stopped = true;
+            }
+        }
+        return true;
+    });
     out[q] = 1.f - light;
     if constexpr (REC) {
         rec_stage_finish(rstage, (int)threadIdx.x, L.rec, cur_block, nrec);
@@ -146,19 +138,11 @@ opacity_walk_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
         const float t0 = __uint_as_float(a.y);
         for (int pass = 0; pass < 2; ++pass) {
             const float light_ray = light;                  // complete only in the second pass
-            float t = t0;
-            while (t < r.tmax) {
-                Sample s;
-                march_step<N2>(tr, r, opt.step_size, t, s);
-                if (s.valid) {
-                    const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                    if (sigma > 0.f) {
-                        if (pass == 0) light *= pexpf(-s.delta_t * sigma * r.delta_scale);
-                        else atomicAdd(grad + (int64_t)s.idx * gstride + (K - 1), s.delta_t * r.delta_scale * g * light_ray);
-                    }
-                }
-                t = march_advance(t, s.delta_t);
-            }
+            walk_samples<N2>(tr, r, opt.step_size, t0, 0.f, [&](const Sample& s, float, float sigma) {
+                if (pass == 0) light *= pexpf(-s.delta_t * sigma * r.delta_scale);
+                else atomicAdd(grad + (int64_t)s.idx * gstride + (K - 1), s.delta_t * r.delta_scale * g * light_ray);
+                return true;
+            });
         }
     }
     aux[q].w = __float_as_uint(light);
@@ -239,17 +223,10 @@ depth_kernel(TreeDev tr, RaysDev rays, Opts opt, float* __restrict__ depth) {
     Ray r;
     float d = 0.f;
     if (setup_ray(tr, rays, opt, q, r)) {
-        const int K = tr.K;
-        float t = r.tmin;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                if (sigma > opt.sigma_thresh) { d = r.delta_scale * t; break; }
-            }
-            t = march_advance(t, s.delta_t);
-        }
+        walk_samples<N2>(tr, r, opt.step_size, r.tmin, opt.sigma_thresh, [&](const Sample&, float t, float) {
+            d = r.delta_scale * t;                            // the first sample ends the walk
+            return false;
+        });
     }
     depth[q] = d;
 }
@@ -267,24 +244,19 @@ count_fwd_kernel(TreeDev tr, RaysDev rays, Opts opt, unsigned long long* __restr
     Ray r;
     if (q < rays.Q && setup_ray(tr, rays, opt, q, r)) {
         hit = 1;
-        const int K = tr.K;
-        float light = 1.f, t = r.tmin;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
+        float light = 1.f;
+        walk_crossings<N2>(tr, r, opt.step_size, r.tmin, [&](const Sample& s, float) {
             ++steps;
             levels += s.leaf.levels;
-            if (s.valid) {
-                ++valid;
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                if (sigma > opt.sigma_thresh) {
-                    ++active;
-                    light *= pexpf(-s.delta_t * r.delta_scale * sigma);
-                    if (light <= opt.stop_thresh) break;
-                }
+            if (s.valid) ++valid;
+            float sigma;
+            if (is_sample(tr, s, opt.sigma_thresh, sigma)) {
+                ++active;
+                light *= pexpf(-s.delta_t * r.delta_scale * sigma);
+                if (light <= opt.stop_thresh) return false;
             }
-            t = march_advance(t, s.delta_t);
-        }
+            return true;
+        });
     }
     hit = wave_sum(hit); steps = wave_sum(steps); levels = wave_sum(levels);
     valid = wave_sum(valid); active = wave_sum(active);
@@ -300,8 +272,9 @@ count_fwd_kernel(TreeDev tr, RaysDev rays, Opts opt, unsigned long long* __restr
 // What one forward march touches (svoxt_count_touched; for the roofline's compulsory bytes):
 // row_mask[idx] = 1 for every valid leaf's feature row (the forward reads it), row_mask[M + idx] = 1
 // if a sample there is composited (the backward reads the row again); tree_mask: grid cells and (child, data)
-// pairs with the acceleration grid, child and data words without (march_step<..., MARK>);
-// longest[0] = the most leaf crossings any ray makes.  The march is the real one.
+// pairs with the acceleration grid, child and data words without (walk_crossings<..., MARK>);
+// longest[0] = the most leaf crossings any ray makes.  The walk is the one every per-ray operator takes
+// (walk_crossings / is_sample, svoxt_device.h), like count_fwd_kernel's above.
 template <bool N2>
 __global__ void __launch_bounds__(kBlock)
 count_touched_kernel(TreeDev tr, RaysDev rays, Opts opt, uint8_t* __restrict__ row_mask,
@@ -310,23 +283,18 @@ count_touched_kernel(TreeDev tr, RaysDev rays, Opts opt, uint8_t* __restrict__ r
     unsigned long long steps = 0;
     Ray r;
     if (q < rays.Q && setup_ray(tr, rays, opt, q, r)) {
-        const int K = tr.K;
-        float light = 1.f, t = r.tmin;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2, -1, true>(tr, r, opt.step_size, t, s, tree_mask, n_slots);
+        float light = 1.f;
+        walk_crossings<N2, true>(tr, r, opt.step_size, r.tmin, [&](const Sample& s, float) {
             ++steps;
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                row_mask[s.idx] = 1;                      // (every writer stores the same value: no race to lose)
-                if (sigma > opt.sigma_thresh) {
-                    row_mask[tr.M + s.idx] = 1;
-                    light *= pexpf(-s.delta_t * r.delta_scale * sigma);
-                    if (light <= opt.stop_thresh) break;
-                }
+            if (s.valid) row_mask[s.idx] = 1;             // (every writer stores the same value: no race to lose)
+            float sigma;
+            if (is_sample(tr, s, opt.sigma_thresh, sigma)) {
+                row_mask[tr.M + s.idx] = 1;
+                light *= pexpf(-s.delta_t * r.delta_scale * sigma);
+                if (light <= opt.stop_thresh) return false;
             }
-            t = march_advance(t, s.delta_t);
-        }
+            return true;
+        }, tree_mask, n_slots);
     }
     for (int off = 32; off > 0; off >>= 1) steps = max(steps, (unsigned long long)__shfl_down(steps, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(longest, steps);

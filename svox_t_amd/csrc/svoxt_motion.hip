@@ -45,30 +45,25 @@ motion_render_kernel(TreeDev tr, RaysDev rays, Opts opt, int J, float* __restric
     data_idx[q] = 0;
     Ray r;
     if (!setup_ray(tr, rays, opt, q, r)) return;
-    const int K = tr.K;
-    float t = r.tmin;
-    while (t < r.tmax) {
-        Sample s;
-        march_step<N2>(tr, r, opt.step_size, t, s);
-        if (s.valid) {
-            const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-            if (sigma > opt.sigma_thresh) {
-                const float px = (s.leaf.lx - tr.offset[0]) / tr.scaling[0];
-                const float py = (s.leaf.ly - tr.offset[1]) / tr.scaling[1];
-                const float pz = (s.leaf.lz - tr.offset[2]) / tr.scaling[2];
-                hit_point[3 * q + 0] = px; hit_point[3 * q + 1] = py; hit_point[3 * q + 2] = pz;
-                depth[q] = t * r.delta_scale;
-                for (int i = 0; i < J; ++i) {
-                    const float* jp = tr.extra + (int64_t)i * tr.extra_cols;
-                    const float d0 = px - jp[0], d1 = py - jp[1], d2 = pz - jp[2];
-                    o[i] = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-                }
-                data_idx[q] = (int64_t)s.idx;
-                return;
-            }
-        }
-        t = march_advance(t, s.delta_t);
+    Sample s;
+    float t = 0.f;
+    bool hit = false;
+    walk_samples<N2>(tr, r, opt.step_size, r.tmin, opt.sigma_thresh, [&](const Sample& first, float t_at, float) {
+        s = first; t = t_at; hit = true;
+        return false;                                        // the first sample ends the walk
+    });
+    if (!hit) return;
+    const float px = (s.leaf.lx - tr.offset[0]) / tr.scaling[0];
+    const float py = (s.leaf.ly - tr.offset[1]) / tr.scaling[1];
+    const float pz = (s.leaf.lz - tr.offset[2]) / tr.scaling[2];
+    hit_point[3 * q + 0] = px; hit_point[3 * q + 1] = py; hit_point[3 * q + 2] = pz;
+    depth[q] = t * r.delta_scale;
+    for (int i = 0; i < J; ++i) {
+        const float* jp = tr.extra + (int64_t)i * tr.extra_cols;
+        const float d0 = px - jp[0], d1 = py - jp[1], d2 = pz - jp[2];
+        o[i] = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
     }
+    data_idx[q] = (int64_t)s.idx;
 }
 
 // pos_joint_feature (rt_kernel.cu:946-952) depends on the feature row alone, not on the
@@ -126,38 +121,28 @@ motion_feature_fwd_kernel(TreeDev tr, int F, const float* __restrict__ blended, 
         for (int j = 0; j < F; ++j) o[j] = 0.f;              // zeros, not the background (:913-919)
         return;
     }
-    const int K = tr.K;
     float acc[FMAX];
 #pragma unroll
     for (int k = 0; k < FMAX; ++k) acc[k] = 0.f;
     float light = 1.f;
-    float t = r.tmin;
     bool stopped = false;
-    while (t < r.tmax) {
-        Sample s;
-        march_step<N2>(tr, r, opt.step_size, t, s);
-        if (s.valid) {
-            const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-            if (sigma > opt.sigma_thresh) {
-                const float att = pexpf(-s.delta_t * r.delta_scale * sigma);
-                const float weight = light * (1.f - att);
-                float pjf[FMAX];
-                load_row<FMAX>(blended + (int64_t)s.idx * FMAX, pjf);
+    walk_samples<N2>(tr, r, opt.step_size, r.tmin, opt.sigma_thresh, [&](const Sample& s, float, float sigma) {
+        const float att = pexpf(-s.delta_t * r.delta_scale * sigma);
+        const float weight = light * (1.f - att);
+        float pjf[FMAX];
+        load_row<FMAX>(blended + (int64_t)s.idx * FMAX, pjf);
 #pragma unroll
-                for (int k = 0; k < FMAX; ++k)
-                    if (k < F) acc[k] = (float)((double)acc[k] + (double)weight / (1.0 + (double)pjf[k]));      // (pjf: exp(-value), MODE 1)
-                light *= att;
-                if (light <= opt.stop_thresh) {
-                    const float scale = (float)(1.0 / (1.0 - (double)light));
+        for (int k = 0; k < FMAX; ++k)
+            if (k < F) acc[k] = (float)((double)acc[k] + (double)weight / (1.0 + (double)pjf[k]));      // (pjf: exp(-value), MODE 1)
+        light *= att;
+        if (light <= opt.stop_thresh) {
+            const float scale = (float)(1.0 / (1.0 - (double)light));
 #pragma unroll
-                    for (int k = 0; k < FMAX; ++k) acc[k] *= scale;
-                    stopped = true;
-                    break;
-                }
-            }
+            for (int k = 0; k < FMAX; ++k) acc[k] *= scale;
+            stopped = true;
         }
-        t = march_advance(t, s.delta_t);
-    }
+        return !stopped;
+    });
 #pragma unroll
     for (int k = 0; k < FMAX; ++k)
         if (k < F) o[k] = stopped ? acc[k] : acc[k] + light * opt.background_brightness;
@@ -181,7 +166,6 @@ motion_feature_bwd_kernel(TreeDev tr, int F, const float* __restrict__ blended, 
     bool alive = q < rays.Q;
     if (alive) alive = setup_ray(tr, rays, opt, q, r);
     if (!__any(alive)) return;
-    const int K = tr.K;
     float g[FMAX];
 #pragma unroll
     for (int k = 0; k < FMAX; ++k) g[k] = (alive && k < F) ? grad_out[q * F + k] : 0.f;
@@ -192,19 +176,16 @@ motion_feature_bwd_kernel(TreeDev tr, int F, const float* __restrict__ blended, 
         bool active = false;
         int32_t idx = -1;
         float weight = 0.f;
-        if (t < tmax) {
+        if (t < tmax) {                                       // one crossing per round
             Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            t = march_advance(t, s.delta_t);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                if (sigma > 0.f) {                            // thresholds ignored, as in every backward of the reference
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    weight = light * (1.f - att);
-                    light *= att;
-                    active = true;
-                    idx = s.idx;
-                }
+            float sigma;
+            next_crossing<N2>(tr, r, opt.step_size, t, s);
+            if (is_sample(tr, s, 0.f, sigma)) {               // thresholds ignored, as in every backward of the reference
+                const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+                weight = light * (1.f - att);
+                light *= att;
+                active = true;
+                idx = s.idx;
             }
         }
         const unsigned long long amask = __ballot(active);

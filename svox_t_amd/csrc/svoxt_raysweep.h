@@ -1,7 +1,8 @@
 // svoxt_raysweep.h -- the loop of the per-ray operators with a sigma-only gradient (svoxt_depthmom.hip, svoxt_distort.hip;
 // DESIGN.md 4.17): one forward that composites a payload along each ray, one backward of two forward-running sweeps.
-// The march is the shared one (setup_ray / march_step / march_advance / pexpf of svoxt_device.h), walked exactly as
-// opacity_fwd_kernel walks it; lists and table are those of svoxt_raylists.h.  An operator is a payload P:
+// The march is the shared walk of svoxt_device.h (setup_ray, then walk_samples; the lock-step tail of sweep 2 takes
+// next_crossing / is_sample itself), so the forward, the tails that resume from its t_resume and every other per-ray
+// operator see the same samples; lists and table are those of svoxt_raylists.h.  An operator is a payload P:
 //
 //   P::kOut                      floats per ray of the output row (and of grad_out); the last one is alpha = 1 - T_end
 //   P::z(r, t, delta_t)          the distance of a sample: recorded, composited, handed to the sweeps
@@ -56,46 +57,36 @@ raysweep_fwd_kernel(TreeDev tr, RaysDev rays, Opts opt, float* __restrict__ out,
     float t_resume = 0.f;
     Ray r;
     if (setup_ray(tr, rays, opt, q, r)) {
-        const int K = tr.K;
         const int S = L.S;
-        float t = r.tmin;
         bool stopped = false;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                // (REC: every sigma > 0 is recorded, and composited only by the forward's own rules)
-                if (sigma > (REC ? 0.f : opt.sigma_thresh)) {
-                    const float z = P::z(r, t, s.delta_t);
-                    if constexpr (REC) {
-                        if (nrec < S) {
-                            const int64_t i = dm_index(tid >> 6, S, nrec, (int)threadIdx.x);
-                            L.row[i] = (uint32_t)s.idx;
-                            L.dt[i] = s.delta_t;
-                            L.z[i] = z;
-                            ++nrec;
-                        } else if (!over) {
-                            over = true;
-                            t_resume = t;
-                        }
-                    }
-                    if (!REC || (sigma > opt.sigma_thresh && !stopped)) {
-                        const float att = pexpf(-s.delta_t * r.delta_scale * sigma);
-                        const float w = light * (1.f - att);
-                        acc.add(w, z, s.delta_t * r.delta_scale);
-                        light *= att;
-                        if (light <= opt.stop_thresh) {          // as the colour forward scales its channels (rt_kernel.cu:313-319)
-                            acc.rescale((float)(1.0 / (1.0 - (double)light)));
-                            if constexpr (!REC) break;
-                            stopped = true;
-                        }
-                    }
-                    if (REC && over && stopped) break;           // nothing left to record or to composite
+        // (REC: every sigma > 0 is recorded, and composited only by the forward's own rules)
+        walk_samples<N2>(tr, r, opt.step_size, r.tmin, REC ? 0.f : opt.sigma_thresh, [&](const Sample& s, float t, float sigma) {
+            const float z = P::z(r, t, s.delta_t);
+            if constexpr (REC) {
+                if (nrec < S) {
+                    const int64_t i = dm_index(tid >> 6, S, nrec, (int)threadIdx.x);
+                    L.row[i] = (uint32_t)s.idx;
+                    L.dt[i] = s.delta_t;
+                    L.z[i] = z;
+                    ++nrec;
+                } else if (!over) {
+                    over = true;
+                    t_resume = t;
                 }
             }
-            t = march_advance(t, s.delta_t);
-        }
+            if (!REC || (sigma > opt.sigma_thresh && !stopped)) {
+                const float att = pexpf(-s.delta_t * r.delta_scale * sigma);
+                const float w = light * (1.f - att);
+                acc.add(w, z, s.delta_t * r.delta_scale);
+                light *= att;
+                if (light <= opt.stop_thresh) {                  // as the colour forward scales its channels (rt_kernel.cu:313-319)
+                    acc.rescale((float)(1.0 / (1.0 - (double)light)));
+                    if constexpr (!REC) return false;
+                    stopped = true;
+                }
+            }
+            return !(REC && over && stopped);                    // false: nothing left to record or to composite
+        });
     }
     acc.store(out + q * P::kOut, light);
     if constexpr (REC) L.aux[tid] = make_uint2((uint32_t)nrec | (over ? kDmOver : 0u), __float_as_uint(t_resume));
@@ -172,21 +163,13 @@ raysweep_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
         }
     }
     if (over) {
-        float t = t_tail;
-        while (t < r.tmax) {
-            Sample s;
-            march_step<N2>(tr, r, opt.step_size, t, s);
-            if (s.valid) {
-                const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                if (sigma > 0.f) {
-                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                    const float w = light * (1.f - att);
-                    light *= att;
-                    c.sweep1(w, light, P::z(r, t, s.delta_t), s.delta_t * r.delta_scale);
-                }
-            }
-            t = march_advance(t, s.delta_t);
-        }
+        walk_samples<N2>(tr, r, opt.step_size, t_tail, 0.f, [&](const Sample& s, float t, float sigma) {
+            const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+            const float w = light * (1.f - att);
+            light *= att;
+            c.sweep1(w, light, P::z(r, t, s.delta_t), s.delta_t * r.delta_scale);
+            return true;
+        });
     }
     const float light_ray = light;
     c.turn();
@@ -220,20 +203,18 @@ raysweep_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
         if (more) {
             bool found = false;
             while (!found && t < r.tmax) {
+                const float t_at = t;
                 Sample s;
-                march_step<N2>(tr, r, opt.step_size, t, s);
-                if (s.valid) {
-                    const float sigma = tr.features[(int64_t)s.idx * K + (K - 1)];
-                    if (sigma > 0.f) {
-                        const float d = s.delta_t * r.delta_scale;
-                        const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
-                        const float w = light * (1.f - att);
-                        light *= att;
-                        dm_table_put(keys, vals, s.idx, c.sweep2(w, light, P::z(r, t, s.delta_t), d) + d * ga * light_ray);
-                        found = true;
-                    }
+                float sigma;
+                next_crossing<N2>(tr, r, opt.step_size, t, s);
+                if (is_sample(tr, s, 0.f, sigma)) {
+                    const float d = s.delta_t * r.delta_scale;
+                    const float att = pexpf(-s.delta_t * sigma * r.delta_scale);
+                    const float w = light * (1.f - att);
+                    light *= att;
+                    dm_table_put(keys, vals, s.idx, c.sweep2(w, light, P::z(r, t_at, s.delta_t), d) + d * ga * light_ray);
+                    found = true;
                 }
-                t = march_advance(t, s.delta_t);
             }
             more = found;
         }

@@ -74,7 +74,8 @@ static RowGradSpace rowgrad_carve(void* workspace, int64_t Q, int64_t T, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------------------- record
-// The crossings svoxt_ray_samples_count counted with min_sigma = 0 (valid, sigma > 0.f), in march order.
+// The samples of walk_samples (svoxt_device.h) with min_sigma = 0, in march order: the walk svoxt_ray_samples_count
+// counted them with, so the two cannot disagree.
 template <bool N2>
 __global__ void __launch_bounds__(kBlock)
 rowgrad_record_kernel(TreeDev tr, RaysDev rays, Opts opt, int bd, const int64_t* __restrict__ offsets, int64_t T,
@@ -93,19 +94,15 @@ rowgrad_record_kernel(TreeDev tr, RaysDev rays, Opts opt, int bd, const int64_t*
         load_vdir(rays, q, vd);
         precalc_basis<0>(opt.format, bd, tr, vd[0], vd[1], vd[2], basis + q * bd);
     }
-    const int K = tr.K;
-    float t = r.tmin;
-    while (t < r.tmax) {
-        Sample s;
-        march_step<N2>(tr, r, opt.step_size, t, s);
-        if (s.valid && tr.features[(int64_t)s.idx * K + (K - 1)] > 0.f && at < end) {
+    walk_samples<N2>(tr, r, opt.step_size, r.tmin, 0.f, [&](const Sample& s, float, float) {
+        if (at < end) {
             row[at] = s.idx;
             ray[at] = (int32_t)q;
             dt[at] = s.delta_t;
             ++at;
         }
-        t = march_advance(t, s.delta_t);
-    }
+        return true;
+    });
 }
 
 // -------------------------------------------------------------------------------------------------------------- shade

@@ -1,8 +1,8 @@
 // svoxt_samples.hip -- the per-sample interface (not in the reference): a ray batch's leaf crossings as
 // CSR lists, and the two primitives that turn per-sample values back into per-ray values.
 //
-//   ray_samples      count -> scan -> emit.  Both kernels run the shared march (setup_ray / march_step / march_advance of
-//                    svoxt_device.h), one lane per ray by ray_of_thread, exactly as raysweep_fwd_kernel walks it.  The count
+//   ray_samples      count -> scan -> emit.  Both kernels take the shared walk (setup_ray, then walk_samples / walk_crossings
+//                    of svoxt_device.h), one lane per ray by ray_of_thread, through one adapter (ray_samples below).  The count
 //                    kernel writes counts[q] at the ray's own index and adds each wavefront's count to one 64-bit total;
 //                    exclusive_scan (svoxt_host.h) turns the counts into starts, widened to int64 offsets[Q + 1] with the
 //                    64-bit total at offsets[Q].  The emit kernel marches again and writes (row, ray, depth, length) at
@@ -49,24 +49,15 @@ static SamplesSpace samples_carve(void* workspace, int64_t Q) {
     return sp;
 }
 
-// The samples of ray q in march order: f(row, depth, length) per leaf crossing whose data word names a feature row
-// (FILTER: and whose sigma exceeds min_sigma).
+// The samples of ray q in march order: f(row, depth, length) per sample of the shared walk (svoxt_device.h); without
+// FILTER per crossing whose data word names a feature row -- the crossing layer: sigma is not read.
 template <bool N2, bool FILTER, class F>
-__device__ __forceinline__ void walk_samples(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float min_sigma, int64_t q, F&& f) {
+__device__ __forceinline__ void ray_samples(const TreeDev& tr, const RaysDev& rays, const Opts& opt, float min_sigma, int64_t q, F&& f) {
     Ray r;
     if (!setup_ray(tr, rays, opt, q, r)) return;
-    const int K = tr.K;
-    float t = r.tmin;
-    while (t < r.tmax) {
-        Sample s;
-        march_step<N2>(tr, r, opt.step_size, t, s);
-        if (s.valid) {
-            bool take = true;
-            if constexpr (FILTER) take = tr.features[(int64_t)s.idx * K + (K - 1)] > min_sigma;
-            if (take) f(s.idx, r.delta_scale * t, s.delta_t * r.delta_scale);
-        }
-        t = march_advance(t, s.delta_t);
-    }
+    auto emit = [&](const Sample& s, float t) { f(s.idx, r.delta_scale * t, s.delta_t * r.delta_scale); return true; };
+    if constexpr (FILTER) walk_samples<N2>(tr, r, opt.step_size, r.tmin, min_sigma, [&](const Sample& s, float t, float) { return emit(s, t); });
+    else walk_crossings<N2>(tr, r, opt.step_size, r.tmin, [&](const Sample& s, float t) { return !s.valid || emit(s, t); });
 }
 
 template <bool N2, bool FILTER>
@@ -77,7 +68,7 @@ samples_count_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, uint32
     const int64_t q = ray_of_thread(rays, tid);
     uint32_t n = 0;
     if (q < rays.Q) {
-        walk_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t, float, float) { ++n; });
+        ray_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t, float, float) { ++n; });
         counts[q] = n;
     }
     uint32_t sum = n;                                            // (a wavefront's 64 counts: far below 2^32)
@@ -103,7 +94,7 @@ samples_emit_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, const i
     int64_t at = offsets[q];
     const int64_t end = offsets[q + 1];
     if (at < 0) return;
-    walk_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t idx, float z, float d) {
+    ray_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t idx, float z, float d) {
         if (at < end) {                                          // (the count's march found as many: never past the ray's own segment)
             row[at] = idx;
             ray[at] = (int32_t)q;
