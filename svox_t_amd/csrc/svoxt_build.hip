@@ -41,6 +41,7 @@
 #include "../../include/svoxt.h"
 #include "svoxt_device.h"
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -220,7 +221,7 @@ build_segsum_kernel(BuildLevels lv, BuildSpace sp) {
     uint32_t c = 0;
     for (int i = threadIdx.x; i < kScanSeg; i += kBuildBlock)
         if (w0 + i < lv.words[l]) c += __popc(sp.bitmap[lv.word_off[l] + w0 + i]);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -234,11 +235,7 @@ build_segsum_kernel(BuildLevels lv, BuildSpace sp) {
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t mine, uint32_t* wsum /*[kBuildBlock/64 + 1]*/,
                                                          uint32_t* total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const uint32_t incl = wave_inclusive_scan(mine, lane);
     __syncthreads();                      // wsum may still be read from a previous call
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();

@@ -294,6 +294,7 @@ render_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ 
     const int lane = threadIdx.x & 63;
     float* stage = stage_all + (threadIdx.x >> 6) * (64 * KS);
     int32_t* sidx = sidx_all + (threadIdx.x >> 6) * 64;
+    // (not lane_rank at the two sites: 80 > 82 registers and 6 > 5 waves for GATHER rows of 8, + 2 registers for ONEPASS)
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t q = ray_of_thread(rays, tid);
@@ -335,9 +336,7 @@ render_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ 
     if constexpr (ONEPASS) {      // sweep 1 over the lists, all lanes of the wavefront in step
         int n1 = 0;
         if (alive) n1 = (int)(aux[q].x & ~kRecOverflow);
-        int maxn = n1;
-        for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-        maxn = __builtin_amdgcn_readfirstlane(maxn);
+        const int maxn = wave_uniform_max(n1);
         for (int k1 = 0; k1 < maxn; ++k1) {
             const bool active = k1 < n1;
             const unsigned long long amask = __ballot(active);
@@ -614,16 +613,11 @@ grad_merge_kernel(TreeDev tr, RaysDev rays, const float* __restrict__ grad_out, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* stage = stage_all + wave * 64 * KS;
     int32_t* seg = seg_all + wave * 64;
-    const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int64_t q = ray_of_thread(rays, (int64_t)blockIdx.x * 64 + lane);
     const bool alive = q < rays.Q;
     int nrec = 0;
     if (alive) nrec = (int)(aux[q].x & ~kRecOverflow);
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    // wavefront-uniform by construction; said so to the compiler, because everything that
-    // decides how many workgroup barriers a wavefront executes must be scalar control flow
-    maxn = __builtin_amdgcn_readfirstlane(maxn);
+    const int maxn = wave_uniform_max(nrec);
     if (maxn == 0) return;                       // the same in every wavefront of the workgroup
     if (wave == 0 && alive && nrec > 0) {
         if constexpr (FMT == FMT_SH && !XF) {
@@ -687,20 +681,14 @@ grad_merge_kernel(TreeDev tr, RaysDev rays, const float* __restrict__ grad_out, 
                 if (am == 0ull) continue;
                 uint32_t h = 0;
                 if (active) {
-                    const int32_t idx = (int32_t)e[u].x;
-                    h = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(T));
-                    while (true) {
-                        const int32_t old = atomicCAS(keys + h, -1, idx);
-                        if (old == -1 || old == idx) break;
-                        h = (h + 1u) & (uint32_t)(T - 1);
-                    }
+                    h = row_table_claim<T>(keys, (int32_t)e[u].x);
                     atomicAdd(cnt + h, 1);
                 }
                 int base = 0;
                 if (lane == 0) base = atomicAdd(&s_nb, __popcll(am));
                 base = __shfl(base, 0, 64);
                 if (active) {
-                    const int pos = base + __popcll(am & lane_lt);
+                    const int pos = base + lane_rank(am, lane);
                     r_sl[pos] = (uint16_t)((h << 6) | (uint32_t)lane);
                     r_sg[pos] = __uint_as_float(e[u].y);
                     r_w[pos] = c4[u].x; r_c[pos] = c4[u].y; r_c[R + pos] = c4[u].z; r_c[2 * R + pos] = c4[u].w;
@@ -711,20 +699,7 @@ grad_merge_kernel(TreeDev tr, RaysDev rays, const float* __restrict__ grad_out, 
         __syncthreads();
         // ---- sort: exclusive scan of the counters (wavefront 0), counting sort of the record numbers
         const int nb = __builtin_amdgcn_readfirstlane(s_nb);
-        if (wave == 0) {
-            constexpr int PER = T / 64;
-            int mine[PER], sum = 0;
-#pragma unroll
-            for (int j2 = 0; j2 < PER; ++j2) { mine[j2] = cnt[lane * PER + j2]; sum += mine[j2]; }
-            int incl = sum;
-            for (int off = 1; off < 64; off <<= 1) {
-                const int v = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += v;
-            }
-            int run = incl - sum;
-#pragma unroll
-            for (int j2 = 0; j2 < PER; ++j2) { cnt[lane * PER + j2] = run; run += mine[j2]; }
-        }
+        if (wave == 0) row_table_counts_scan<T>(cnt, lane);
         __syncthreads();
         for (int rr = threadIdx.x; rr < nb; rr += NT) {
             const int sl = (int)r_sl[rr] >> 6;
@@ -929,9 +904,7 @@ grad_fused_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ 
     if (!in_batch) a = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (XF) { if (a.x & kRecOverflow) a.x = 0u; }  // (done whole by the launch in front)
     const int nrec = (int)(a.x & ~kRecOverflow);
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);             // everything that decides barriers is scalar
+    const int maxn = wave_uniform_max(nrec);
     if (maxn == 0) return;                                   // the same in every wavefront of the workgroup
     if constexpr (CHECK) { if (threadIdx.x == 0) atomicAdd(counters + kChkBase + 29, 1ull); }    // (tiles this instance worked on)
 
@@ -1121,6 +1094,7 @@ grad_fused_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ 
     // of them).  With the fixed window of 14 positions the arrays were a third full on the headline workload
     // (~300 of 896 slots: lists are ragged), i.e. three times the scans, sorts, table clears and barriers, and a
     // feature row left the CU once per window instead of once per ~40 positions.
+    // (not lane_rank in the rounds: the COUNT instances' registers moved, 98 > 100 for RGBA, and SH9's scratch, 12 > 8 bytes)
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
     // one round: positions kb .. kb + P - 1 (kb uniform), records from slot `nslot` on; returns the round's records
     auto round = [&](int kb, int nslot, uint2& eq, float4& uq) -> int {
@@ -1195,13 +1169,7 @@ grad_fused_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ 
                 }
             }
             const int32_t idx = SVOXT_CHK((int32_t)e.x, tr.M, 6);
-            uint32_t h = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(T));
-            while (true) {
-                const int32_t old = atomicCAS(keys + h, -1, idx);
-                if (old == -1 || old == idx) break;
-                h = (h + 1u) & (uint32_t)(T - 1);
-            }
-            h = (uint32_t)SVOXT_CHK((int)h, T, 4);
+            const uint32_t h = (uint32_t)SVOXT_CHK((int)row_table_claim<T>(keys, idx), T, 4);
             atomicAdd(cnt + h, 1);
             r_sl[slot] = (h << 6) | (uint32_t)lane;
             r_w[slot] = att; r_sg[slot] = tc; r_dt[slot] = __uint_as_float(e.y);
@@ -1352,9 +1320,9 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
     uint4 a = make_uint4(0u, 0u, 0u, 0u);
     if (q < rays.Q) a = aux[q];
     const int nrec = (int)(a.x & ~kRecOverflow);
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);             // everything that decides barriers is scalar
+    int maxn = nrec;                                         // (wave_uniform_max, written out: the call cost the K = 16 instances
+    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));          // 12 > 16 bytes of scratch)
+    maxn = __builtin_amdgcn_readfirstlane(maxn);
     if (maxn == 0) return;                                   // the same in every wavefront of the workgroup
     if constexpr (CHECK) { if (threadIdx.x == 0) atomicAdd(counters + kChkBase + 29, 1ull); }    // (tiles this instance worked on)
 
@@ -1398,7 +1366,7 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
                         const int slot = (rd * W + wave) * 64 + lane;
                         r_sl[slot] = e[rd].x;
                         r_dt[slot] = __uint_as_float(e[rd].y);
-                        order[SVOXT_CHK(base + (int)__popcll(m & ((1ull << lane) - 1ull)), R, 17)] = (uint16_t)slot;
+                        order[SVOXT_CHK(base + lane_rank(m, lane), R, 17)] = (uint16_t)slot;
                     }
                 }
             }
@@ -1456,7 +1424,7 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
                     }
                 }
 #pragma unroll
-                for (int off = 1; off < G; off <<= 1) part += __shfl_xor(part, off, 64);
+                for (int off = 1; off < G; off <<= 1) part += __shfl_xor(part, off, 64);     // (as wave_group_sum<G>: scratch 60 > 48 bytes, K = 8)
                 if (on && gq == G - 1) {
                     r_w[slot] = nexpf(-r_dt[slot] * row[7] * dsl[ray]);
                     r_t1[slot] = part;
@@ -1573,13 +1541,7 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
             for (int rd = 0; rd < RPP; ++rd) {
                 if (have[rd]) {
                     const int32_t idx = SVOXT_CHK((int32_t)e[rd].x, tr.M, 19);
-                    uint32_t h32 = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(T));
-                    while (true) {
-                        const int32_t old = atomicCAS(keys + h32, -1, idx);
-                        if (old == -1 || old == idx) break;
-                        h32 = (h32 + 1u) & (uint32_t)(T - 1);
-                    }
-                    h32 = (uint32_t)SVOXT_CHK((int)h32, T, 20);
+                    const uint32_t h32 = (uint32_t)SVOXT_CHK((int)row_table_claim<T>(keys, idx), T, 20);
                     atomicAdd(cnt + h32, 1);
                     const int slot = (rd * W + wave) * 64 + lane;
                     r_sl[slot] = (h32 << 6) | (uint32_t)lane;
@@ -1616,6 +1578,7 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
             int mine[PER], sum = 0, used = 0;
 #pragma unroll
             for (int j2 = 0; j2 < PER; ++j2) { mine[j2] = cnt[lane * PER + j2]; sum += mine[j2]; used += mine[j2] > 0 ? 1 : 0; }
+            // (row_table_counts_scan with a second value; as two wave_inclusive_scan calls: scratch 56 > 52 bytes, K = 8 CHECK)
             int incl = sum, uincl = used;
             for (int off = 1; off < 64; off <<= 1) {
                 const int v = __shfl_up(incl, off, 64);
@@ -1685,9 +1648,7 @@ grad_wide_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict__ g
                     om = 1.f - sig;
                 }
                 float acc = 0.f;
-                int n_here = st.pes[u] - p, n_max = n_here;
-                for (int off = 32; off >= K; off >>= 1) n_max = max(n_max, __shfl_xor(n_max, off, 64));
-                n_max = __builtin_amdgcn_readfirstlane(n_max);
+                const int n_here = st.pes[u] - p, n_max = wave_uniform_max<K>(n_here);
                 for (int t = 0; t < n_max; ++t) {
                     if (t < n_here) {
                         float val;
@@ -1817,7 +1778,6 @@ render_bwd_generic_staged_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
     const int lane = threadIdx.x & 63;
     float* stage = dyn_lds + (threadIdx.x >> 6) * (64 * KS);
     int32_t* sidx = reinterpret_cast<int32_t*>(dyn_lds + (kBlock / 64) * 64 * KS) + (threadIdx.x >> 6) * 64;
-    const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int64_t q = ray_of_thread(rays, (int64_t)blockIdx.x * kBlock + threadIdx.x);
     Ray r;
     bool alive = q < rays.Q;
@@ -1879,7 +1839,7 @@ render_bwd_generic_staged_kernel(TreeDev tr, RaysDev rays, Opts opt, int C,
         if (amask == 0ull) continue;
         const int n = __popcll(amask);
         if (active) {
-            const int slot = __popcll(amask & lane_lt);
+            const int slot = lane_rank(amask, lane);
             sidx[slot] = idx;
             float* st = stage + slot * KS;
             for (int j = 0; j < K - 1; ++j) st[j] = 0.f;       // columns outside the component range stay 0

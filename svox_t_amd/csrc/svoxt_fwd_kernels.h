@@ -572,9 +572,7 @@ __device__ __forceinline__ uint32_t shade_tile_body(const TreeDev& tr, const Ray
         nrec = min(nrec, L.S);                       // (a stale count must not run the loops away)
         if (ax_used != nullptr) *ax_used = a_x;
     }
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);     // what decides the barrier count is scalar
+    const int maxn = wave_uniform_max(nrec);
     const int nround = (maxn + P - 1) / P;           // the same in every wavefront of the workgroup
     const int need = (maxn + kRecBlock - 1) >> 3;    // blocks the rounds will read: those the table names (pooled lists)
     // All eight wavefronts stage, 16 bytes per lane and request: piece threadIdx.x % 256 of blocks 2 i + wave / 4.  The
@@ -1084,9 +1082,7 @@ shade_chan_kernel(TreeDev tr, RaysDev rays, Opts opt, RecLists L,
     uint4 a = make_uint4(0u, 0u, 0u, 0u);
     if (inb) a = aux[q];
     const int nrec = (int)(a.x & ~kRecOverflow);
-    int maxn = nrec;
-    for (int off = 32; off >= K; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);
+    const int maxn = wave_uniform_max<K>(nrec);      // (over the wavefront's rays: lane / K)
     float ds = 0.f;
     if (nrec > 0) {
         Ray r;

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "svoxt_device.h"
+#include "svoxt_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -261,11 +262,6 @@ __device__ __forceinline__ uint32_t rec_hash(int k, uint32_t idx, uint32_t dt_bi
     const uint32_t kk = (uint32_t)k;
     return __builtin_rotateleft32(idx + kk * 0x9E3779u, kk & 31u) ^ __builtin_rotateleft32(dt_bits ^ kk, (5u * kk + 11u) & 31u);
 }
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v ^= (uint32_t)__shfl_xor((int)v, off, 64);
-    return v;
-}
 // (rays_xor: XOR of rec_hash over ALL records of this lane's ray; ax: the ray's aux.x; 0 / 0 for a lane without a ray.)
 // Per lane a bijection with full avalanche (murmur3's finalizer on the word offset by the lane): a first version that
 // only multiplied by an odd number of the lane let the SAME small difference in every lane -- which is what the test's
@@ -294,12 +290,6 @@ __device__ __forceinline__ I chk(I i, int64_t n, unsigned long long* __restrict_
         }
     }
     return i;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 }  // namespace svoxt

@@ -40,6 +40,7 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 namespace svoxt {
@@ -255,9 +256,7 @@ diam_rows8_kernel(ReduceIn in, float scale, float* __restrict__ out) {
         for (int b = a + 1; b < 8; ++b) {
             const float4v d = (r.x[a] - r.x[b]) * scale;
             float s = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-            s += __shfl_xor(s, 1, 64);
-            s += __shfl_xor(s, 2, 64);
-            s += __shfl_xor(s, 4, 64);
+            s = wave_group_sum<8>(s);
             const bool counts = !in.skip || (((has >> a) & (has >> b)) & 1u);
             best = (counts && s > best) ? s : best;
         }

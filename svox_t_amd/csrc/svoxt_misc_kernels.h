@@ -171,11 +171,9 @@ opacity_merge_kernel(RaysDev rays, RecLists L, const uint4* __restrict__ aux,
         nrec = (int)(a.x & ~kRecOverflow);
         t_ray = __uint_as_float(a.w);
     }
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);
+    const int maxn = wave_uniform_max(nrec);
     if (maxn == 0) return;
-    for (int i = threadIdx.x; i < T; i += NT) { keys[i] = -1; vals[i] = 0.f; }
+    row_values_clear<T, NT>(keys, vals, threadIdx.x);
     __syncthreads();
     for (int k0 = 0; k0 < maxn; k0 += RPP * kRound) {
 #pragma unroll 1
@@ -190,27 +188,12 @@ opacity_merge_kernel(RaysDev rays, RecLists L, const uint4* __restrict__ aux,
             }
 #pragma unroll
             for (int u = 0; u < kGroup; ++u) {
-                if (kb + u < nrec) {
-                    const int32_t idx = (int32_t)e[u].x;
-                    uint32_t h = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(T));
-                    while (true) {
-                        const int32_t old = atomicCAS(keys + h, -1, idx);
-                        if (old == -1 || old == idx) break;
-                        h = (h + 1u) & (uint32_t)(T - 1);
-                    }
-                    atomicAdd(vals + h, __uint_as_float(e[u].y) * t_ray);     // ((delta_t * ds) * g) * T_ray
-                }
+                if (kb + u < nrec)
+                    row_values_add<T>(keys, vals, (int32_t)e[u].x, __uint_as_float(e[u].y) * t_ray);   // ((delta_t * ds) * g) * T_ray
             }
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < T; i += NT) {
-            const int32_t key = keys[i];
-            if (key >= 0) {
-                atomicAdd(grad + (int64_t)key * gstride + col, vals[i]);
-                keys[i] = -1;
-                vals[i] = 0.f;
-            }
-        }
+        row_values_flush<T, NT>(keys, vals, threadIdx.x, grad, gstride, col);
         __syncthreads();
     }
 }
@@ -296,7 +279,7 @@ count_touched_kernel(TreeDev tr, RaysDev rays, Opts opt, uint8_t* __restrict__ r
             return true;
         }, tree_mask, n_slots);
     }
-    for (int off = 32; off > 0; off >>= 1) steps = max(steps, (unsigned long long)__shfl_down(steps, off, 64));
+    steps = wave_max(steps);
     if ((threadIdx.x & 63) == 0) atomicMax(longest, steps);
 }
 
@@ -383,7 +366,7 @@ leaves_count_kernel(const uint8_t* __restrict__ mask, int64_t n, int32_t* __rest
     const int64_t base = (int64_t)blockIdx.x * kSeg;
     int c = 0;
     for (int i = threadIdx.x; i < kSeg; i += kBlock) c += (base + i < n && mask[base + i]) ? 1 : 0;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -430,7 +413,7 @@ leaves_scatter_kernel(const uint8_t* __restrict__ mask, int64_t n, int N, const 
         int32_t before = 0, total = 0;
         for (int w = 0; w < kBlock / 64; ++w) { if (w < wave) before += wbase[w]; total += wbase[w]; }
         if (hit) {
-            const int64_t dst = running + before + __popcll(b & ((1ull << lane) - 1ull));
+            const int64_t dst = running + before + lane_rank(b, lane);
             int64_t tmp = i;
             const int64_t w3 = tmp % N; tmp /= N;
             const int64_t v3 = tmp % N; tmp /= N;

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -160,7 +161,6 @@ motion_feature_bwd_kernel(TreeDev tr, int F, const float* __restrict__ blended, 
     __shared__ float stage[64 * KS];
     __shared__ int32_t sidx[64];
     const int lane = threadIdx.x & 63;
-    const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int64_t q = ray_of_thread(rays, (int64_t)blockIdx.x * kMotionBlock + threadIdx.x);
     Ray r;
     bool alive = q < rays.Q;
@@ -193,7 +193,7 @@ motion_feature_bwd_kernel(TreeDev tr, int F, const float* __restrict__ blended, 
         if (active) {
             float pjf[FMAX];
             load_row<FMAX>(blended + (int64_t)idx * FMAX, pjf);
-            const int slot = __popcll(amask & lane_lt);
+            const int slot = lane_rank(amask, lane);
             sidx[slot] = idx;
             float* st = stage + slot * KS;
 #pragma unroll

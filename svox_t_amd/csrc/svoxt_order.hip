@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 
 namespace svoxt {
 
@@ -91,7 +92,6 @@ ray_key_kernel(TreeDev tr, RaysDev rays, Opts opt, uint32_t* __restrict__ keys, 
         }
     }
     const int lane = threadIdx.x & 63;
-    const unsigned long long lane_lt = (1ull << lane) - 1ull;
     // group the lanes by key first (no memory operation in the loop), then all group leaders send their
     // atomics in ONE instruction -- one round trip per wavefront instead of one per distinct key
     int my_leader = lane;
@@ -104,7 +104,7 @@ ray_key_kernel(TreeDev tr, RaysDev rays, Opts opt, uint32_t* __restrict__ keys, 
         const unsigned long long m = __ballot(mine);
         if (mine) {
             my_leader = leader;
-            my_rank = (uint32_t)__popcll(m & lane_lt);
+            my_rank = (uint32_t)lane_rank(m, lane);
             my_count = (uint32_t)__popcll(m);
         }
         todo &= ~m;
@@ -161,7 +161,7 @@ constexpr int kScanThreads = 256, kScanItems = 16, kScanChunk = kScanThreads * k
 constexpr size_t kScanChunks = (kOrderCells + kScanChunk - 1) / kScanChunk;
 
 __device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* lds /* [4] */) {
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+    v = wave_all_sum(v);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
     const uint32_t s = lds[0] + lds[1] + lds[2] + lds[3];
@@ -193,11 +193,7 @@ scan_chunks_kernel(const uint32_t* __restrict__ counts, size_t n, const uint32_t
     for (int j = 0; j < kScanItems; ++j) { v[j] = base + j < n ? counts[base + j] : 0u; mine += v[j]; }
     // exclusive scan of the threads' sums: within the wavefront, then over the four wavefronts
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += u;
-    }
+    const uint32_t incl = wave_inclusive_scan(mine, lane);
     if (lane == 63) lds[wave] = incl;
     __syncthreads();
     uint32_t run = offset + incl - mine;
@@ -254,10 +250,8 @@ __global__ void __launch_bounds__(64)
 image_probe_merge_kernel(int32_t* __restrict__ res, int32_t ticket) {
     const int b = (int)threadIdx.x;                          // kProbeBlocks == 64: a workgroup's partial per lane
     const int same = res[8 + 3 * b], f = res[9 + 3 * b], s2 = res[10 + 3 * b];
-    int first = f;
-    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
-    int second = f > first ? f : s2;                         // this workgroup's smallest jump past the batch's first
-    for (int off = 32; off > 0; off >>= 1) second = min(second, __shfl_xor(second, off, 64));
+    const int first = wave_all_min(f);
+    const int second = wave_all_min(f > first ? f : s2);     // (a workgroup's smallest jump past the batch's first)
     const unsigned long long all_same = __ballot(same != 0);
     if (b == 0) {
         res[0] = all_same == ~0ull ? 1 : 0;

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 namespace svoxt {
@@ -97,7 +98,7 @@ prune_mark_kernel(PruneIn in, bool collapse, bool rows, uint32_t* __restrict__ n
         }
     }
     // leaves dropped by this workgroup: one plain store (a same-address atomic per wavefront was 0.9 of the pass's 1.0 ms)
-    for (int off = 32; off > 0; off >>= 1) drops += (uint32_t)__shfl_xor((int)drops, off, 64);
+    drops = wave_all_sum(drops);
     if ((threadIdx.x & 63) == 0) wave_drops[threadIdx.x >> 6] = drops;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -113,7 +114,7 @@ prune_counts_kernel(const uint32_t* __restrict__ node_rank, int32_t n, const uin
                     const uint32_t* __restrict__ dropped, int mark_blocks, int64_t* __restrict__ counts) {
     unsigned long long t = 0;
     for (int b = threadIdx.x; b < mark_blocks; b += 64) t += dropped[b];
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    t = wave_all_sum(t);
     if (threadIdx.x == 0) {
         counts[0] = (int64_t)node_rank[n];
         counts[1] = rows ? (int64_t)row_rank[M] : (int64_t)M;

@@ -27,6 +27,7 @@
 
 #include "svoxt_host.h"
 #include "svoxt_sort.h"
+#include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 namespace svoxt {
@@ -264,11 +265,7 @@ q_color_kernel(const float* __restrict__ data, int K, const float* __restrict__ 
                     sw = sw + w;
                 }
             }
-        for (int off = 32; off > 0; off >>= 1) {
-            sx = sx + __shfl_down(sx, off, 64);
-            swx = swx + __shfl_down(swx, off, 64);
-            sw = sw + __shfl_down(sw, off, 64);
-        }
+        sx = wave_sum(sx); swx = wave_sum(swx); sw = wave_sum(sw);   // (each sum its own chain: the same bits as one loop over the three)
         if constexpr (T > 64) {
             if (lane == 0) { part[0][wave] = sx; part[1][wave] = swx; part[2][wave] = sw; }
             __syncthreads();

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "svoxt_launch.h"
+#include "svoxt_wave.h"
 
 namespace svoxt {
 
@@ -35,34 +36,16 @@ __device__ __forceinline__ int64_t dm_index(int64_t tile, int S, int k, int lane
     return ((tile * S + k) << 6) + lane;
 }
 
-// the table of one wavefront: keys[kDmTable], vals[kDmTable] in LDS
+// the table of one wavefront, keys[kDmTable], vals[kDmTable] in LDS: svoxt_wave.h's value table with the barriers of its phases
 __device__ __forceinline__ void dm_table_clear(int32_t* keys, float* vals, int lane) {
-    for (int i = lane; i < kDmTable; i += 64) { keys[i] = -1; vals[i] = 0.f; }
+    row_values_clear<kDmTable, 64>(keys, vals, lane);
     __syncthreads();
 }
-
-__device__ __forceinline__ void dm_table_put(int32_t* keys, float* vals, int32_t idx, float v) {
-    uint32_t h = ((uint32_t)idx * 0x9E3779B1u) >> (32 - __builtin_ctz(kDmTable));
-    while (true) {
-        const int32_t old = atomicCAS(keys + h, -1, idx);
-        if (old == -1 || old == idx) break;
-        h = (h + 1u) & (uint32_t)(kDmTable - 1);
-    }
-    atomicAdd(vals + h, v);
-}
-
+__device__ __forceinline__ void dm_table_put(int32_t* keys, float* vals, int32_t idx, float v) { row_values_add<kDmTable>(keys, vals, idx, v); }
 // adds every row's sum to column `col` of grad [M, gstride] and leaves the table empty
-__device__ __forceinline__ void dm_table_flush(int32_t* keys, float* vals, int lane, float* __restrict__ grad, int gstride,
-                                               int col) {
+__device__ __forceinline__ void dm_table_flush(int32_t* keys, float* vals, int lane, float* __restrict__ grad, int gstride, int col) {
     __syncthreads();
-    for (int i = lane; i < kDmTable; i += 64) {
-        const int32_t key = keys[i];
-        if (key >= 0) {
-            atomicAdd(grad + (int64_t)key * gstride + col, vals[i]);
-            keys[i] = -1;
-            vals[i] = 0.f;
-        }
-    }
+    row_values_flush<kDmTable, 64>(keys, vals, lane, grad, gstride, col);
     __syncthreads();
 }
 

@@ -123,9 +123,7 @@ raysweep_bwd_kernel(TreeDev tr, RaysDev rays, Opts opt, const float* __restrict_
         c.init(grad_out + q * P::kOut);
         ga = grad_out[q * P::kOut + (P::kOut - 1)];
     }
-    int maxn = nrec;
-    for (int off = 32; off > 0; off >>= 1) maxn = max(maxn, __shfl_xor(maxn, off, 64));
-    maxn = __builtin_amdgcn_readfirstlane(maxn);
+    const int maxn = wave_uniform_max(nrec);
     if (maxn == 0 && !__any(over)) return;
     dm_table_clear(keys, vals, lane);
 

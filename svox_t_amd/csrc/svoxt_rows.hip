@@ -25,6 +25,7 @@
 #include "svoxt_launch.h"
 #include "svoxt_rowwalk.h"
 #include "svoxt_sort.h"
+#include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 #pragma clang fp contract(off)
@@ -98,8 +99,7 @@ row_mark_kernel(const int32_t* __restrict__ row_ptr, int64_t M, uint32_t* __rest
         flag[r] = is_long ? 1u : 0u;
         nchunks[r] = is_long ? (n + (uint32_t)kRowChunk - 1u) / (uint32_t)kRowChunk : 0u;
     }
-    uint32_t m = n;                                              // (integers: the same in every run)
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    const uint32_t m = wave_all_max(n);                          // (integers: the same in every run)
     if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(longest, m);
 }
 

@@ -25,6 +25,7 @@
 #include "svoxt_device.h"
 #include "svoxt_host.h"
 #include "svoxt_launch.h"
+#include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 #pragma clang fp contract(off)
@@ -71,8 +72,7 @@ samples_count_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, uint32
         ray_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t, float, float) { ++n; });
         counts[q] = n;
     }
-    uint32_t sum = n;                                            // (a wavefront's 64 counts: far below 2^32)
-    for (int off = 32; off > 0; off >>= 1) sum += (uint32_t)__shfl_xor((int)sum, off, 64);
+    const uint32_t sum = wave_all_sum(n);                        // (a wavefront's 64 counts: far below 2^32)
     if ((threadIdx.x & 63) == 0 && sum != 0u) atomicAdd(total, (unsigned long long)sum);
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "svoxt_host.h"
+#include "svoxt_wave.h"
 
 namespace svoxt {
 
@@ -38,7 +39,6 @@ sort_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __rest
     const uint32_t radix = 1u << bits, lane = threadIdx.x;
     for (uint32_t d = lane; d < radix; d += 64) run[d] = starts[(size_t)d * nblocks + blockIdx.x];
     __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
     const uint32_t base = blockIdx.x * kSortSpan;
     for (int s = 0; s < kSortSteps; ++s) {
         const uint32_t idx = base + s * 64 + lane;
@@ -51,7 +51,7 @@ sort_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __rest
             const unsigned long long on = __ballot(bit);
             m &= bit ? on : ~on;
         }
-        const uint32_t rank = (uint32_t)__popcll(m & below);
+        const uint32_t rank = (uint32_t)lane_rank(m, lane);
         const uint32_t at = valid ? run[dig] : 0u;
         __syncthreads();                                     // every lane has read its digit's offset
         if (valid) {

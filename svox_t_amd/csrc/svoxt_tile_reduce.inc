@@ -1,5 +1,5 @@
 // svoxt_tile_reduce.inc -- the second half of a pass of the per-tile backwards, included INSIDE
-// grad_fused_kernel and grad_dense_kernel (textually: as a function with a dozen pointer parameters the same
+// grad_fused_kernel (textually: as a function with a dozen pointer parameters the same
 // code cost the SH9 instances 70-110 bytes of scratch spills per lane at their 128-register budget, r03).
 // In scope: lane, wave, NT, T, R, K, NB, BDS, HALF, NH, KS, C, FMT, COUNT, CHECK (SVOXT_CHK), XF (+ vds, tr); the LDS arrays keys, cnt, order, r_sl,
 // r_sg, r_w, r_c, bases, gl, stage, seg, s_nb; grad, gstride, counters; nscan = the records of the pass (slots 0 .. nscan - 1).
@@ -15,19 +15,8 @@
     // the last round (the counters are complete since the round's barrier) -- then the
     // counting sort of the record numbers
     if (wave == 1) {
-        constexpr int PER = T / 64;
-        int mine[PER], sum = 0;
-#pragma unroll
-        for (int j2 = 0; j2 < PER; ++j2) { mine[j2] = cnt[lane * PER + j2]; sum += mine[j2]; }
-        int incl = sum;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        int run = incl - sum;
-#pragma unroll
-        for (int j2 = 0; j2 < PER; ++j2) { cnt[lane * PER + j2] = run; run += mine[j2]; }
-        if (lane == 63) s_nb = incl;
+        const int total = row_table_counts_scan<T>(cnt, lane);
+        if (lane == 63) s_nb = total;
     }
     lds_barrier();       // (the phases of a pass hand over through LDS alone: the next round's request and the
                          // gradient atomics stay in flight across their barriers)
