@@ -1275,6 +1275,62 @@ int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, co
 int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
                                 const float* grad_out, float* grad_w, float* grad_values, void* stream);
 
+/* ---- scans, quantiles and subsets of the lists (svoxt_scan.hip; not in the reference) -------------
+ * The conventions of the per-sample primitives above: ray q's segment is max(offsets[q], 0) .. min(offsets[q + 1], T),
+ * Q and T below 2^31, float32, sequential in list order without contraction, no float atomic: the same bits in every run.
+ *   svoxt_ray_scan_fwd        out float32 [T, C] from values float32 [T, C] (C >= 1), per ray and channel, in list order or,
+ *                             with SVOXT_SCAN_REVERSE, from the ray's last sample to its first:
+ *                                 acc = 0 | 1 | -inf | +inf                          (SVOXT_SCAN_SUM | PROD | MAX | MIN)
+ *                                 new = acc + v | acc * v | (v > acc) ? v : acc | (v < acc) ? v : acc
+ *                                 out = new, or with SVOXT_SCAN_EXCLUSIVE acc from before the step;  acc = new
+ *                             (max / min never take a NaN; the first occurrence wins a tie).  Elements outside every
+ *                             segment are not written.  out must not overlap values.
+ *   svoxt_ray_scan_bwd        grad_values float32 [T, C] (every element written: 0 outside the segments; it must overlap
+ *                             neither grad_out nor values) for grad_out [T, C].  Positions j = 0 .. n-1 along the scan's
+ *                             direction, g = grad_out, v = values (NULL allowed for the sum only):
+ *                                 sum    the scan of g with the same EXCLUSIVE and the other direction
+ *                                 prod   sweep 1 against the direction:  S_j = g_j + v_{j+1} * S_{j+1},  S_{n-1} = g_{n-1}
+ *                                        (EXCLUSIVE: S_j = g_{j+1} + v_{j+1} * S_{j+1},  S_{n-1} = 0);
+ *                                        sweep 2 along it, P = 1:  grad_j = P * S_j;  P *= v_j      -- no division: zeros are safe
+ *                                 max / min   one sweep along the direction with the running argument a (none at first):
+ *                                        inclusive: a moves to j where v_j is taken, then grad_a += g_j; EXCLUSIVE:
+ *                                        grad_a += g_j (nowhere while there is no a), then a moves.  Every sum starts at 0
+ *                                        and adds in scan order.
+ *   svoxt_ray_quantile        per ray and target i < nq (q: device float32 [nq], values in [0, 1] -- the caller's check):
+ *                                 c = 0;  per sample with w > 0 (others -- 0, negative, NaN -- are passed over):  c = c + w
+ *                                 target = q_i * c_end (normalize != 0) or q_i
+ *                                 index[ray, i] = the list index k in [0, T) of the first such sample with c_k >= target,
+ *                                 frac[ray, i] = (target - c_{k-1}) / w_k clamped to [0, 1] (NaN: 0);  -1 and 0 where no
+ *                                 sample has w > 0 or the target is never reached.
+ *                             index int64 [Q, nq] (8-byte aligned), frac float32 [Q, nq].
+ *   svoxt_samples_select_*    the samples with keep[k] != 0 (keep: T bytes), in their old order, as new lists:
+ *       _workspace_bytes(T)   device bytes (8-byte aligned) shared by the pair; -1: T negative or 2^31 and more; 0 for T = 0
+ *       _count                flags, scans (pos = the number of kept samples before each, 32-bit, T + 1 entries) and writes
+ *                             offsets_out int64 [Q + 1] = pos[clamped offsets[q]] and total int64 [1] = pos[T] = T'
+ *                             (both device, 8-byte aligned).  T = 0: zeros, nothing else is read.
+ *       _emit                 with the same keep, T and workspace (unchanged since _count) and T_out = T' read back by the
+ *                             caller: ray / row / depth / length of every kept sample copied bit for bit to pos[k], and
+ *                             index int64 [T'] = k.  Nothing is written at or behind T_out.
+ * Q = 0 and T = 0 are valid no-ops.  No allocation, no synchronisation. */
+#define SVOXT_SCAN_SUM 0
+#define SVOXT_SCAN_PROD 1
+#define SVOXT_SCAN_MAX 2
+#define SVOXT_SCAN_MIN 3
+#define SVOXT_SCAN_EXCLUSIVE 1
+#define SVOXT_SCAN_REVERSE 2
+int svoxt_ray_scan_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* values, int32_t C, int32_t op, int32_t flags,
+                       float* out, void* stream);
+int svoxt_ray_scan_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float* values, int32_t C, int32_t op, int32_t flags,
+                       const float* grad_out, float* grad_values, void* stream);
+int svoxt_ray_quantile(const int64_t* offsets, int64_t Q, int64_t T, const float* w, const float* q, int32_t nq, int32_t normalize,
+                       int64_t* index, float* frac, void* stream);
+int64_t svoxt_samples_select_workspace_bytes(int64_t T);
+int svoxt_samples_select_count(const uint8_t* keep, const int64_t* offsets, int64_t Q, int64_t T, int64_t* offsets_out, int64_t* total,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_samples_select_emit(const uint8_t* keep, int64_t T, const void* workspace, int64_t workspace_bytes, const int32_t* ray,
+                              const int32_t* row, const float* depth, const float* length, int64_t T_out, int32_t* ray_out,
+                              int32_t* row_out, float* depth_out, float* length_out, int64_t* index, void* stream);
+
 /* ---- samples to feature rows and back (svoxt_rows.hip; not in the reference) ----------------------
  * The row side of the per-sample interface: a gather of table rows by sample, and its inverse, a reduction of
  * per-sample values by feature row over a fixed-order plan.  Gather only: no atomics on floats anywhere, every result

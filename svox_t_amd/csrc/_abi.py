@@ -206,6 +206,12 @@ EXPORTS = {
     "svoxt_sample_weights_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_sample_accumulate_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
     "svoxt_sample_accumulate_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "svoxt_ray_scan_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "svoxt_ray_scan_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "svoxt_ray_quantile": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "svoxt_samples_select_workspace_bytes": (_i64, [_i64]),
+    "svoxt_samples_select_count": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_samples_select_emit": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_row_plan_workspace_bytes": (_i64, [_i64, _i64]),
     "svoxt_row_plan_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_row_plan_long": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),

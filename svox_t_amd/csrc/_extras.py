@@ -1484,6 +1484,98 @@ def sample_accumulate_backward(ray, Q, w, values, grad_out, need_w=True, need_va
 
 
 # ---------------------------------------------------------------------------
+# Scans, quantiles and subsets of the lists (svoxt_scan.hip; not in the reference)
+# ---------------------------------------------------------------------------
+SCAN_OPS = {"sum": 0, "prod": 1, "max": 2, "min": 3}              # SVOXT_SCAN_* (include/svoxt.h)
+SCAN_EXCLUSIVE, SCAN_REVERSE = 1, 2
+
+
+def _scan_args(offsets, values, op, exclusive, reverse):
+    if op not in SCAN_OPS:
+        raise RuntimeError(f"op must be one of {sorted(SCAN_OPS)}")
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() != 2 or values.shape[1] < 1:
+        raise RuntimeError("values must be float32 [T, C], C >= 1")
+    T, C = values.shape
+    Q = _check_csr(offsets, T)
+    _check_per_sample(values, "values", T, offsets.device, C)
+    return Q, T, C, SCAN_OPS[op], (SCAN_EXCLUSIVE if exclusive else 0) | (SCAN_REVERSE if reverse else 0)
+
+
+def ray_scan(offsets, values, op="sum", exclusive=False, reverse=False):
+    """out float32 [T, C] of svoxt_ray_scan_fwd for offsets int64 [Q + 1] and values [T, C]; samples outside every
+    segment get 0."""
+    Q, T, C, opc, flags = _scan_args(offsets, values, op, exclusive, reverse)
+    dev = offsets.device
+    with _on(dev):
+        out = torch.zeros((T, C), dtype=torch.float32, device=dev)
+        _call("svoxt_ray_scan_fwd", _ptr(offsets), Q, T, _ptr(values), C, opc, flags, _ptr(out), _stream(dev))
+    return out
+
+
+def ray_scan_backward(offsets, values, op, exclusive, reverse, grad_out):
+    """grad_values float32 [T, C] of svoxt_ray_scan_bwd for grad_out [T, C]."""
+    Q, T, C, opc, flags = _scan_args(offsets, values, op, exclusive, reverse)
+    dev = offsets.device
+    _check_per_sample(grad_out, "grad_out", T, dev, C)
+    with _on(dev):
+        grad = torch.empty((T, C), dtype=torch.float32, device=dev)
+        _call("svoxt_ray_scan_bwd", _ptr(offsets), Q, T, None if opc == 0 else _ptr(values), C, opc, flags, _ptr(grad_out), _ptr(grad),
+              _stream(dev))
+    return grad
+
+
+def ray_quantile(offsets, w, q, normalize=True):
+    """(index int64 [Q, nq], frac float32 [Q, nq]) of svoxt_ray_quantile for w float32 [T] and q float32 [nq] on the
+    device (values in [0, 1]: the caller's check)."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1:
+        raise RuntimeError("w must be float32 [T]")
+    T = w.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(w, "w", T, dev)
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.float32 or q.dim() != 1 or q.shape[0] < 1:
+        raise RuntimeError("q must be float32 [nq], nq >= 1")
+    _check_input(q, "q")
+    if q.device != dev:
+        raise RuntimeError("q must be on the device of offsets")
+    nq = q.shape[0]
+    with _on(dev):
+        index = torch.empty((Q, nq), dtype=torch.int64, device=dev)
+        frac = torch.empty((Q, nq), dtype=torch.float32, device=dev)
+        _call("svoxt_ray_quantile", _ptr(offsets), Q, T, _ptr(w), _ptr(q), nq, 1 if normalize else 0, _ptr(index), _ptr(frac), _stream(dev))
+    return index, frac
+
+
+def samples_select(keep, offsets, ray, row, depth, length):
+    """(offsets' int64 [Q + 1], ray', row', depth', length', index int64 [T'], T') of svoxt_samples_select_count / _emit
+    for keep bool [T].  One host read (T')."""
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.dim() != 1:
+        raise RuntimeError("keep must be bool [T]")
+    T = keep.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(keep, "keep", T, dev, dtype=torch.bool)
+    for name, x, dt in (("ray", ray, torch.int32), ("row", row, torch.int32), ("depth", depth, torch.float32), ("length", length, torch.float32)):
+        _check_per_sample(x, name, T, dev, dtype=dt)
+    with _on(dev):
+        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+        total = torch.empty((1,), dtype=torch.int64, device=dev)
+        nbytes = _lib.svoxt_samples_select_workspace_bytes(T)
+        ws = _workspace(dev, nbytes, "select: T must be below 2^31")
+        _call("svoxt_samples_select_count", _ptr(keep), _ptr(offsets), Q, T, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
+        Tn = int(total.item())                          # the one host read
+        ray_o = torch.empty((Tn,), dtype=torch.int32, device=dev)
+        row_o = torch.empty((Tn,), dtype=torch.int32, device=dev)
+        depth_o = torch.empty((Tn,), dtype=torch.float32, device=dev)
+        length_o = torch.empty((Tn,), dtype=torch.float32, device=dev)
+        index = torch.empty((Tn,), dtype=torch.int64, device=dev)
+        if Tn > 0:
+            _call("svoxt_samples_select_emit", _ptr(keep), T, _ptr(ws), nbytes, _ptr(ray), _ptr(row), _ptr(depth), _ptr(length), Tn,
+                  _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o), _ptr(index), _stream(dev))
+    return offsets_out, ray_o, row_o, depth_o, length_o, index, Tn
+
+
+# ---------------------------------------------------------------------------
 # Samples to feature rows and back (svoxt_rows.hip; not in the reference; DESIGN.md 4.21)
 # ---------------------------------------------------------------------------
 ROW_CHUNK = 256                                                   # SVOXT_ROW_CHUNK (include/svoxt.h)

@@ -7,6 +7,9 @@
     out, alpha, w = composite(samples, f[:, -1], values)           # the two chained
     wmax = reduce_rows(samples, w.detach(), M, "max")              # [M]: a per-row statistic of per-sample values
     rgb, sigma = renderer.shade_samples(samples, features, rays)   # [T, C], [T]: the samples' colours and densities, no [T, K]
+    trans = ray_scan(samples, att, "prod", exclusive=True)         # running sum / prod / max / min along every ray
+    index, frac = ray_quantile(samples, w, [0.5])                  # where the running weight crosses q * total; quantile_depth: the depth
+    sub, index = samples.select(w > 1e-3)                          # the kept samples as a RaySamples of its own; values[index] follows
 
 Every per-sample loss is then a few lines of torch around HIP operators whose results, gradients included, have the same
 bits in every run: the gradient of gather_rows reaches the table through reduce_rows' fixed-order row plan (DESIGN.md
@@ -21,6 +24,7 @@ from svox_t_amd.helpers import _get_c_extension
 from svox_t_amd.renderer import Rays, VolumeRenderer, _rays_spec_from_rays
 
 _C = _get_c_extension()
+_X = _C._extras            # (ray_scan / ray_quantile / select's wrappers are reached here, not as csrc.* names)
 
 
 class RaySamples:
@@ -66,6 +70,21 @@ class RaySamples:
         if M not in plans:
             plans[M] = RowPlan(_C.row_plan(self.row.contiguous(), M))
         return plans[M]
+
+    def select(self, keep):
+        """(RaySamples, index int64 [T']): the samples with keep[k] set, in their old order, as lists of their own -- the
+        same Q rays (a ray may become empty), ray / row / depth / length copied bit for bit -- and every kept sample's
+        position in the old lists: values[index] carries any per-sample tensor over, gradients flow through torch's
+        indexing.  `keep` is torch.bool [T] on the samples' device.  Flag, scan, emit on the GPU with one host read (T');
+        the result holds no cached row plan."""
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != (len(self),):
+            raise RuntimeError("select: keep must be torch.bool [T], one entry per sample")
+        _require_gpu("select", self, keep)
+        with torch.no_grad():
+            offsets, ray, row, depth, length, index, _ = _X.samples_select(
+                keep.contiguous(), self.offsets.contiguous(), self.ray.contiguous(), self.row.contiguous(), self.depth.contiguous(),
+                self.length.contiguous())
+        return RaySamples(offsets, ray, row, depth, length), index
 
 
 class RowPlan:
@@ -285,6 +304,97 @@ def composite(samples: RaySamples, sigma, values=None):
     """(out, alpha, w): accumulate(samples, w, values) with (w, alpha) = sample_weights(samples, sigma)."""
     w, alpha = sample_weights(samples, sigma)
     return accumulate(samples, w, values), alpha, w
+
+
+# --------------------------------------------------------------------------------------- running values along a ray
+class _RayScanFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, values, samples, op, exclusive, reverse):
+        values = values.contiguous()
+        ctx.samples, ctx.op, ctx.exclusive, ctx.reverse = samples, op, exclusive, reverse
+        ctx.save_for_backward(values)
+        return _X.ray_scan(samples.offsets, values, op, exclusive, reverse)
+
+    @staticmethod
+    @autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        (values,) = ctx.saved_tensors
+        grad = _X.ray_scan_backward(ctx.samples.offsets, values, ctx.op, ctx.exclusive, ctx.reverse, grad_out.contiguous())
+        return grad, None, None, None, None
+
+
+def ray_scan(samples: RaySamples, values, op: str = "sum", *, exclusive: bool = False, reverse: bool = False):
+    """Running values along every ray, shaped like `values` (float32 [T] or [T, C]): per ray and channel, in list order
+    (reverse: from the ray's last sample to its first), float32, no contraction:
+
+        acc = 0 | 1 | -inf | +inf;   new = acc + v | acc * v | (v > acc) ? v : acc | (v < acc) ? v : acc     ("sum" | "prod" | "max" | "min")
+        out = new   (exclusive: acc from before the step);   acc = new
+
+    max / min never take a NaN and keep the first of equal values.  ray_scan(s, att, "prod", exclusive=True) is the
+    transmittance in front of every sample; the last inclusive "sum" of a ray is accumulate(s, w), bit for bit.
+    Differentiable in `values`, once: "sum" by the scan of the gradient in the other direction, "prod" by two sweeps
+    without a division (zeros among the values are safe), "max" / "min" by sending every position's gradient to the
+    sample that supplied its value -- fixed float32 sequences (include/svoxt.h), one entry per sample, no atomics."""
+    if not isinstance(samples, RaySamples):
+        raise RuntimeError("ray_scan: samples must be a RaySamples")
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.dim() not in (1, 2) \
+            or values.shape[0] != len(samples) or (values.dim() == 2 and values.shape[1] < 1):
+        raise RuntimeError("ray_scan: values must be float32 [T] or [T, C], one row per sample, C >= 1")
+    if op not in _X.SCAN_OPS:
+        raise RuntimeError(f"ray_scan: op must be one of {sorted(_X.SCAN_OPS)}")
+    _require_gpu("ray_scan", samples, values)
+    flat = values.dim() == 1
+    out = _RayScanFunction.apply(values[:, None] if flat else values, samples, op, bool(exclusive), bool(reverse))
+    return out[:, 0] if flat else out
+
+
+def _quantiles(q, dev):
+    """`q` (a number, a sequence or a tensor) -> float32 [nq] on `dev`, every value in [0, 1]."""
+    if isinstance(q, torch.Tensor):
+        if q.dtype != torch.float32:
+            raise RuntimeError("ray_quantile: q must be a sequence or a float32 tensor of values in [0, 1]")
+        t = q.detach()
+    else:
+        try:
+            t = torch.tensor(q, dtype=torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise RuntimeError("ray_quantile: q must be a sequence or a float32 tensor of values in [0, 1]") from None
+    if t.dim() == 0:
+        t = t.reshape(1)
+    if t.dim() != 1 or t.numel() < 1 or not bool(((t >= 0) & (t <= 1)).all()):
+        raise RuntimeError("ray_quantile: q must hold nq >= 1 values in [0, 1]")
+    return t.to(dev).contiguous()
+
+
+def ray_quantile(samples: RaySamples, w, q, *, normalize: bool = True):
+    """(index int64 [Q, nq], frac float32 [Q, nq]): where along every ray the running sum of `w` (float32 [T]) crosses
+    each target.  Per ray, in list order, float32: a sample with w > 0 adds c = c + w from 0, any other (zero, negative,
+    NaN) is passed over; target = q * c_end (normalize=False: q itself -- compositing weights, the mass 1 - alpha lying
+    behind the volume); index is the list index in [0, T) of the first sample with w > 0 and c >= target, frac =
+    (target - c_before) / w clamped to [0, 1], the position inside the crossing.  index = -1 and frac = 0 where the ray
+    has no positive weight or the target is never reached.  `q`: a sequence or float32 tensor of nq >= 1 values in [0, 1].
+    Not differentiable."""
+    if not isinstance(samples, RaySamples):
+        raise RuntimeError("ray_quantile: samples must be a RaySamples")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 1 or w.shape[0] != len(samples):
+        raise RuntimeError("ray_quantile: w must be float32 [T], one entry per sample")
+    qs = _quantiles(q, w.device)
+    _require_gpu("ray_quantile", samples, w)
+    with torch.no_grad():
+        return _X.ray_quantile(samples.offsets, w.detach().contiguous(), qs, bool(normalize))
+
+
+def quantile_depth(samples: RaySamples, w, q, *, normalize: bool = True, empty: float = float("nan")):
+    """depth float32 [Q, nq] at the quantiles of ray_quantile: depth[index] + frac * length[index], `empty` where
+    index < 0.  q = 0.5: the median depth."""
+    index, frac = ray_quantile(samples, w, q, normalize=normalize)
+    if len(samples) == 0:
+        return torch.full_like(frac, float(empty))
+    at = index.clamp(min=0)
+    z = samples.depth[at] + frac * samples.length[at]
+    return torch.where(index < 0, torch.full_like(z, float(empty)), z)
 
 
 # ----------------------------------------------------------------------------------------- samples to rows and back
