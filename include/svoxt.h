@@ -73,7 +73,8 @@ enum {
  *     sigma bitmask, and the motion operators (their joint-feature rows are 16-byte reads of the aligned workspace).
  *   - The operators that move or write whole rows choose a 16-byte or a 4-byte route from the pointers they get and give
  *     the same bits either way, writing nothing outside the table: svoxt_assign_leaves, svoxt_prune_gather_rows,
- *     svoxt_gather_rows, svoxt_shade_samples_fwd, svoxt_frontier_reduce, svoxt_compact_rows, svoxt_optim_step.
+ *     svoxt_gather_rows, svoxt_shade_samples_fwd, svoxt_frontier_reduce, svoxt_compact_rows, svoxt_optim_step,
+ *     svoxt_interp_stencil (its outputs), svoxt_interp_rows_fwd, svoxt_interp_points_bwd.
  *     svoxt_frontier_diam chooses likewise (from features AND data), but its two routes add a pair's squared differences
  *     in different orders: results agree within float32 rounding of the sum, not bit for bit (the Python layer hands it
  *     aligned copies of both, so that one table gives one result wherever it starts).
@@ -1541,6 +1542,85 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
                             const float* grad_sigma, const int32_t* row_ptr, const int32_t* perm, const int32_t* long_rows,
                             const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks,
                             float* grad, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- interp: a trilinear lookup over the leaves around a point (svoxt_interp.hip; not in the reference)
+ * A lookup that is continuous in position where svoxt_query_fwd is piecewise constant, with the gradients with respect
+ * to the table and to the point.  Gather only, a fixed float32 order, no float atomic: every result is bit-identical
+ * from run to run.  Entry points added under ABI v22.  Every float operation below is a separate float32 operation
+ * without contraction; everything else is integer arithmetic.  Finite points are the contract.
+ *
+ * THE STENCIL of a point p: eight feature rows and eight weights.
+ *   1. Locate     Transform, clamp and descend exactly as svoxt_query_fwd does (one shared function).  This gives the
+ *                 leaf slot, its depth d, cube_sz = N^(d + 1), the leaf-local coordinates l in [0, 1)^3 and the leaf's
+ *                 integer cell coordinate c in [0, N^(d + 1))^3: the digits of the descent, svoxt_leaf_neighbors'
+ *                 definition of a cell.
+ *   2. Per axis a u = l_a - 0.5f;  s_a = (u < 0) ? -1 : +1;  f_a = |u|;  g_a = 1.0f - f_a.
+ *   3. Corners    Corner j = 4 b_x + 2 b_y + b_z with b in {0, 1}^3.  Its cell is t = c + (b_x s_x, b_y s_y, b_z s_z) at
+ *                 the leaf's own level.  Its weight is w_j = (m_x * m_y) * m_z with m_a = b_a ? f_a : g_a.  Corner 0 is
+ *                 the leaf itself.
+ *   4. The row of corner j, t inside the cube: ONE integer descent from node 0 by the base-N digits of t for the levels
+ *                 0 .. d.  If it ends at a leaf of depth <= d, that leaf's data word is taken.  If the cell is still a
+ *                 node after level d, finer leaves cover it: the descent continues with the digits of the cell's centre
+ *                 -- for an even N digit N / 2 once and then digit 0, for an odd N digit (N - 1) / 2 at every level --
+ *                 until a leaf (at most 64 levels further).  By construction this is the leaf svoxt_query_fwd reports at
+ *                 the centre X_j of cell t_j:  interp(p) = sum over j of w_j * query(X_j).
+ *   5. Corners without a row: t outside the cube, a data word outside [0, M), a descent that leaves the tables.
+ *                 fill = SVOXT_INTERP_FILL_SELF: the corner takes the query leaf's own row (clamp to the edge: the hard
+ *                 silhouette of the piecewise-constant field stays).  SVOXT_INTERP_FILL_ZERO: it takes row -1.
+ *   6. An empty query leaf (its data word outside [0, M)): all eight rows are -1.  The weights are written as in 3.
+ *   Depth limits are svoxt_leaf_neighbors': where N^(d + 1) >= 2^31 the cell coordinate is not formed and the corners
+ *   1 .. 7 count as corners without a row.
+ * THE VALUE      out[q, jc] = sum over j = 0 .. 7 of w_j * table[rows[q, j], cols[jc]]:  acc = 0;  acc = acc + w_j * v_j in
+ *                ascending j; corners with a row outside [0, M) are skipped.
+ * THE TABLE GRADIENT  G[r, c] = the sum over the entries e = 8 q + j with rows[e] = r of w_e * g[e >> 3, c], in
+ *                svoxt_reduce_rows' order over the row plan of `rows` viewed as int32 [8 Q]: ascending e, chunks of
+ *                SVOXT_ROW_CHUNK from 0.f, the partials in chunk order.  Every element of [M, K] is written.
+ * THE POINT GRADIENT  D_j = sum over the selected columns jc, ascending, from 0.f, of g[q, jc] * v_{j, jc} (0 for a skipped
+ *                corner).  Per axis a: S_a = sum over j, ascending, from 0.f, of sigma_{j,a} * (m_a' * m_a'') * D_j, where
+ *                sigma_{j,a} = b_a ? +1 : -1 (a change of sign, exact) and a' < a'' are the other two axes.
+ *                grad_points[q, a] = ((S_a * s_a) * cube_sz) * scaling[a], and 0 on an axis whose coordinate the clamp
+ *                changed.  The exact derivative of the value as defined, inside a leaf.
+ * KNOWN PROPERTIES, stated and not hidden: the field is continuous inside leaves and across faces between leaves of
+ * equal depth; it is NOT continuous across a change of level.  No parity claim: the reference has no such operator.
+ *
+ *   svoxt_interp_stencil      rows int32 [Q, 8], weights float32 [Q, 8] for points float32 [Q, 3].  A lane per point, an
+ *                             N = 2 and a generic-N instance; 16-byte stores where rows and weights are 16-byte aligned.
+ *                             tree.features is not read (tree.M decides which data words name a row).  Q = 0: a no-op.
+ *                             Checked: the tree (as svoxt_query_fwd), N <= 16; Q in [0, 2^28) (8 Q < 2^31), M in
+ *                             [0, 2^31); fill among the constants; with Q > 0 points, rows, weights not NULL, 4-byte aligned.
+ *   svoxt_interp_rows_fwd     out float32 [Q, C] (C = n_cols, or K without cols) from table float32 [M, K].  The lanes of a
+ *                             point move its rows together; 16 bytes a lane where all columns are taken, K is a multiple
+ *                             of 4 and table and out are 16-byte aligned, else 4 ("Alignment" above): the same bits.
+ *                             Checked: Q, M; K >= 1; cols / n_cols NULL / 0 or n_cols in [1, K]; Q * C and M * K below
+ *                             2^38; with Q > 0: rows, weights, out not NULL, table not NULL when M > 0, alignment (4 bytes).
+ *   svoxt_interp_rows_bwd     grad float32 [M, K] from grad_out float32 [Q, C] over the plan (svoxt_row_plan_build /
+ *                             svoxt_row_plan_long of rows as int32 [8 Q] and M).  workspace:
+ *                             svoxt_interp_rows_bwd_workspace_bytes(n_chunks, C) device bytes (-1 / 0 as
+ *                             svoxt_reduce_rows_workspace_bytes), 4-byte aligned.  M = 0: a no-op.
+ *                             Checked: Q, M; K, cols / n_cols; C = n_cols (or K); Q * C and M * K below 2^38; n_long and
+ *                             n_chunks as svoxt_row_plan_long with T = 8 Q; with M > 0: grad, row_ptr not NULL; with Q > 0
+ *                             grad_out, weights, perm not NULL; with n_long > 0 the long-row arrays not NULL; alignment
+ *                             (4 bytes); with n_long > 0 the workspace not NULL and at least the query's size.
+ *   svoxt_interp_points_bwd   grad_points float32 [Q, 3]: locates again for s, f and cube_sz; eight lanes per point, lane j
+ *                             forms D_j (16-byte loads where all columns are taken, K is a multiple of 4 and table and
+ *                             grad_out are 16-byte aligned, else 4: the same order, the same bits).
+ *                             Checked: the tree, N <= 16; Q, M; K, cols / n_cols; the 2^38 bounds; with Q > 0 points, rows,
+ *                             grad_out, grad_points not NULL, table not NULL when M > 0; alignment (4 bytes).
+ * No allocation, no synchronisation. */
+#define SVOXT_INTERP_FILL_SELF 0
+#define SVOXT_INTERP_FILL_ZERO 1
+int svoxt_interp_stencil(const svoxt_tree* tree, const float* points, int64_t Q, int32_t fill, int32_t* rows, float* weights,
+                         void* stream);
+int svoxt_interp_rows_fwd(const float* table, int64_t M, int32_t K, const int32_t* rows, const float* weights, int64_t Q,
+                          const int32_t* cols, int32_t n_cols, float* out, void* stream);
+int64_t svoxt_interp_rows_bwd_workspace_bytes(int64_t n_chunks, int32_t C);
+int svoxt_interp_rows_bwd(const float* grad_out, const float* weights, int64_t Q, int32_t C, const int32_t* row_ptr,
+                          const int32_t* perm, int64_t M, const int32_t* long_rows, const int32_t* long_chunk_ptr,
+                          const int32_t* chunk_long, int64_t n_long, int64_t n_chunks, const int32_t* cols, int32_t n_cols,
+                          int32_t K, float* grad, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_interp_points_bwd(const svoxt_tree* tree, const float* points, int64_t Q, const int32_t* rows, const float* table,
+                            int64_t M, int32_t K, const int32_t* cols, int32_t n_cols, const float* grad_out,
+                            float* grad_points, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,8 +10,8 @@ Importing this package loads libsvoxt_hip.so; build it first with
 `python svox_t_amd/build.py` (there is no CPU fallback).
 """
 from svox_t_amd.helpers import DataFormat, LocalIndex, N3TreeView  # noqa: F401
-from svox_t_amd.svox import (N3Tree, blend_transformation_matrix, get_transformation_matrix,  # noqa: F401
-                            warp_vertices)
+from svox_t_amd.svox import (InterpStencil, N3Tree, blend_transformation_matrix, get_transformation_matrix,  # noqa: F401
+                            interp_rows, warp_vertices)
 from svox_t_amd.renderer import NDCConfig, Rays, VolumeRenderer  # noqa: F401
 from svox_t_amd.p2v import voxelize  # noqa: F401
 from svox_t_amd.gridw import GridWeights, grid_weights  # noqa: F401
@@ -25,4 +25,5 @@ __all__ = ["N3Tree", "N3TreeView", "VolumeRenderer", "Rays", "NDCConfig",
            "DataFormat", "LocalIndex", "get_transformation_matrix", "warp_vertices",
            "blend_transformation_matrix", "voxelize", "grid_weights", "GridWeights", "quantize_median_cut",
            "FeatureSGD", "FeatureRMSprop", "FeatureAdam", "RaySamples", "sample_weights", "accumulate", "composite",
-           "RowPlan", "gather_rows", "reduce_rows", "shade_samples", "ray_scan", "ray_quantile", "quantile_depth"]
+           "RowPlan", "gather_rows", "reduce_rows", "shade_samples", "ray_scan", "ray_quantile", "quantile_depth",
+           "InterpStencil", "interp_rows"]

@@ -231,6 +231,12 @@ EXPORTS = {
     "svoxt_shade_samples_bwd_workspace_bytes": (_i64, [_i64, _i32]),
     "svoxt_shade_samples_bwd": (ctypes.c_int, [_P(_COptions), _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "svoxt_interp_stencil": (ctypes.c_int, [_P(_CTree), _vp, _i64, _i32, _vp, _vp, _vp]),
+    "svoxt_interp_rows_fwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "svoxt_interp_rows_bwd_workspace_bytes": (_i64, [_i64, _i32]),
+    "svoxt_interp_rows_bwd": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp,
+                                             _i64, _vp]),
+    "svoxt_interp_points_bwd": (ctypes.c_int, [_P(_CTree), _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in EXPORTS.items():
     _fn = getattr(_lib, _name)       # AttributeError here = library/header mismatch

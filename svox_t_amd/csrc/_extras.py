@@ -1862,3 +1862,143 @@ def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: b
               _ptr(values), _ptr(grad_values), _ptr(grad_sigma), _ptr(plan.row_ptr), _ptr(plan.perm), _ptr(plan.long_rows),
               _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(grad), _ptr(ws), nbytes, _stream(dev))
     return grad
+
+
+# ---------------------------------------------------------------------------
+# interp: a trilinear lookup over the leaves around a point (svoxt_interp.hip; not in the reference)
+# ---------------------------------------------------------------------------
+INTERP_FILLS = {"self": 0, "zero": 1}                             # SVOXT_INTERP_FILL_* (include/svoxt.h)
+INTERP_MAX_Q = (1 << 28) - 1                                      # 8 Q < 2^31: the plan's entries are int32
+
+
+def _check_stencil(rows, weights, dev=None, shapes_only=False):
+    """rows int32 [Q, 8] and weights float32 [Q, 8] (shapes_only: that alone), contiguous, on one GPU (`dev` if given);
+    returns Q."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 8:
+        raise RuntimeError("rows must be int32 [Q, 8]")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(rows.shape):
+        raise RuntimeError("weights must be float32 [Q, 8], one entry per entry of rows")
+    if rows.shape[0] > INTERP_MAX_Q:
+        raise RuntimeError("interp: the number of points must be below 2^28 (8 Q < 2^31)")
+    if shapes_only:
+        return rows.shape[0]
+    _check_input(rows, "rows")
+    _check_input(weights, "weights")
+    if weights.device != rows.device or (dev is not None and rows.device != dev):
+        raise RuntimeError("rows and weights must be on one device, the table's")
+    return rows.shape[0]
+
+
+def _check_points(indices):
+    """indices float32 [Q, 3]: shape and dtype (checked before any device by the callers)."""
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.float32 or indices.dim() != 2 or indices.shape[1] != 3:
+        raise RuntimeError("indices must be float32 [Q, 3]")
+
+
+def _check_table(table, name="table"):
+    """table float32 [M, K], K >= 1: shape and dtype (checked before any device by the callers); returns (M, K)."""
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError(f"{name} must be float32 [M, K], K >= 1")
+    return table.shape
+
+
+def interp_stencil(tree: TreeSpec, indices: torch.Tensor, fill: str = "self"):
+    """(rows int32 [Q, 8], weights float32 [Q, 8]) of svoxt_interp_stencil for the points indices float32 [Q, 3]: per
+    point the feature rows of the eight cells around it at its leaf's level and their trilinear weights (include/svoxt.h,
+    "interp").  tree.features decides M alone: which data words name a row."""
+    if fill not in INTERP_FILLS:
+        raise RuntimeError(f"fill must be one of {sorted(INTERP_FILLS)}")
+    _check_points(indices)
+    if indices.shape[0] > INTERP_MAX_Q:
+        raise RuntimeError("interp: the number of points must be below 2^28 (8 Q < 2^31)")
+    _check_indices(indices)
+    ct = _pack_tree(tree)
+    dev = indices.device
+    if tree.features.device != dev:
+        raise RuntimeError("indices must be on the device of the tree")
+    Q = indices.shape[0]
+    with _on(dev):
+        rows = torch.empty((Q, 8), dtype=torch.int32, device=dev)
+        weights = torch.empty((Q, 8), dtype=torch.float32, device=dev)
+        _call("svoxt_interp_stencil", ctypes.byref(ct), _ptr(indices), Q, INTERP_FILLS[fill], _ptr(rows), _ptr(weights), _stream(dev))
+    return rows, weights
+
+
+def interp_rows_fwd(table: torch.Tensor, rows: torch.Tensor, weights: torch.Tensor, cols=None) -> torch.Tensor:
+    """out float32 [Q, C] of svoxt_interp_rows_fwd: out[q, jc] = sum_j weights[q, j] * table[rows[q, j], cols[jc]] in ascending
+    j, corners with a row outside [0, M) skipped."""
+    M, K = _check_table(table)
+    _check_stencil(rows, weights, shapes_only=True)
+    _check_input(table, "table")
+    dev = table.device
+    Q = _check_stencil(rows, weights, dev)
+    C = _check_cols(cols, K, dev)
+    with _on(dev):
+        out = torch.empty((Q, C), dtype=torch.float32, device=dev)
+        _call("svoxt_interp_rows_fwd", _ptr(table), M, K, _ptr(rows), _ptr(weights), Q, _ptr(cols), 0 if cols is None else C, _ptr(out),
+              _stream(dev))
+    return out
+
+
+def interp_rows_bwd(grad_out: torch.Tensor, weights: torch.Tensor, plan: RowPlanArrays, cols=None, K=None) -> torch.Tensor:
+    """grad float32 [M, K] of svoxt_interp_rows_bwd for grad_out float32 [Q, C] over the row plan of the stencil's rows
+    viewed as [8 Q]: every element written, reduce_rows' order, no [8 Q, C] tensor."""
+    if not isinstance(plan, RowPlanArrays):
+        raise RuntimeError("plan must be a row plan")
+    M = plan.M
+    dev = plan.row_ptr.device
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.dim() != 2 or weights.shape[1] != 8 \
+            or 8 * weights.shape[0] != plan.T:
+        raise RuntimeError("weights must be float32 [Q, 8] with 8 Q the entries of the plan")
+    Q = weights.shape[0]
+    if not isinstance(grad_out, torch.Tensor) or grad_out.dtype != torch.float32 or grad_out.dim() != 2 or grad_out.shape[0] != Q \
+            or grad_out.shape[1] < 1:
+        raise RuntimeError(f"grad_out must be float32 [Q, C] with Q = {Q} points and C >= 1")
+    _check_input(weights, "weights")
+    _check_input(grad_out, "grad_out")
+    if weights.device != dev or grad_out.device != dev:
+        raise RuntimeError("grad_out and weights must be on the device of the plan")
+    C = grad_out.shape[1]
+    if cols is None:
+        K = C
+    elif _check_cols(cols, int(K), dev) != C:
+        raise RuntimeError("grad_out must have one column per selected column")
+    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
+    with _on(dev):
+        grad = torch.empty((M, int(K)), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_interp_rows_bwd_workspace_bytes(n_chunks, C)
+        ws = _workspace(dev, nbytes, "interp: chunks * C must be below 2^38")
+        _call("svoxt_interp_rows_bwd", _ptr(grad_out), _ptr(weights), Q, C, _ptr(plan.row_ptr), _ptr(plan.perm), M, _ptr(plan.long_rows),
+              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(cols), 0 if cols is None else C, int(K), _ptr(grad),
+              _ptr(ws), nbytes, _stream(dev))
+    return grad
+
+
+def interp_points_bwd(tree: TreeSpec, indices: torch.Tensor, rows: torch.Tensor, table: torch.Tensor, grad_out: torch.Tensor,
+                      cols=None) -> torch.Tensor:
+    """grad_points float32 [Q, 3] of svoxt_interp_points_bwd: the derivative of interp_rows_fwd's value with respect to the
+    points the stencil `rows` was built for (the tree spec's coordinates), for the upstream gradient grad_out [Q, C]."""
+    _check_points(indices)
+    M, K = _check_table(table)
+    Q = indices.shape[0]
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or tuple(rows.shape) != (Q, 8):
+        raise RuntimeError("rows must be int32 [Q, 8], the stencil of indices")
+    C = K if cols is None else (cols.shape[0] if isinstance(cols, torch.Tensor) and cols.dim() == 1 else -1)
+    if not isinstance(grad_out, torch.Tensor) or grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (Q, C):
+        raise RuntimeError("grad_out must be float32 [Q, C], one column per selected column")
+    _check_indices(indices)
+    ct = _pack_tree(tree)
+    _check_input(table, "table")
+    dev = table.device
+    _check_input(rows, "rows")
+    _check_cols(cols, K, dev)
+    _check_input(grad_out, "grad_out")
+    if Q > INTERP_MAX_Q:
+        raise RuntimeError("interp: the number of points must be below 2^28 (8 Q < 2^31)")
+    if indices.device != dev or rows.device != dev or grad_out.device != dev or tree.features.device != dev:
+        raise RuntimeError("indices, rows, grad_out and the tree must be on the device of the table")
+    with _on(dev):
+        grad = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_interp_points_bwd", ctypes.byref(ct), _ptr(indices), Q, _ptr(rows), _ptr(table), M, K, _ptr(cols),
+              0 if cols is None else C, _ptr(grad_out), _ptr(grad), _stream(dev))
+    return grad

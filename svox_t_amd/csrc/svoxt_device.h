@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace svoxt {
@@ -276,11 +278,22 @@ struct Leaf {
     int levels;         // child words read
 };
 
+// A Leaf that also carries the INTEGER CELL COORDINATE of the descent: the slot digits it took, most significant first,
+// c in [0, side)^3 with side = N^levels cells per axis at the leaf's level -- svoxt_leaf_neighbors' definition of a cell.
+// The same descent, the same leaf: locate<N2, MARK, LeafCell> only writes the digits down (svoxt_interp.hip).
+struct LeafCell : Leaf {
+    uint32_t cx, cy, cz;
+    uint32_t side;      // N^levels where cell_ok
+    bool cell_ok;       // false: N^levels >= 2^31, deeper than int32 cell coordinates reach (svoxt_leaf_neighbors' limit)
+};
+
 // Generic-N continuation of the descent (common.cuh:74-99), starting at
-// `node` with node-local coordinates p in [0,1).
+// `node` with node-local coordinates p in [0,1).  L = LeafCell: lf.cx / cy / cz / side / cell_ok hold the digits so far.
+template <class L = Leaf>
 __device__ __forceinline__ void descend_generic(const TreeDev& tr, int32_t node,
                                                 float px, float py, float pz,
-                                                float cube_sz, int levels, Leaf& lf) {
+                                                float cube_sz, int levels, L& lf) {
+    constexpr bool CELL = std::is_same<L, LeafCell>::value;
     const int Ni = tr.N;
     const float N = (float)Ni;
     while (true) {
@@ -294,6 +307,14 @@ __device__ __forceinline__ void descend_generic(const TreeDev& tr, int32_t node,
         const uint32_t slot = (((uint32_t)node * Ni + u) * Ni + v) * Ni + w;
         const int32_t skip = tr.child[slot];
         ++levels;
+        if constexpr (CELL) {
+            if (lf.cell_ok && (uint64_t)lf.side * (uint32_t)Ni < 0x80000000ull) {
+                lf.cx = lf.cx * Ni + u; lf.cy = lf.cy * Ni + v; lf.cz = lf.cz * Ni + w;
+                lf.side *= Ni;
+            } else {
+                lf.cell_ok = false;
+            }
+        }
         if (skip == 0) {
             lf.slot = slot; lf.lx = px; lf.ly = py; lf.lz = pz;
             lf.cube_sz = cube_sz; lf.levels = levels;
@@ -308,12 +329,14 @@ constexpr int kFixBits = 22;   // integer descent handles up to 22 levels
 
 // query_single_from_root (common.cuh:63-100) for a tree-space point.
 // MARK (instrumentation, svoxt_count_touched): mark[slot] = 1 for every child word read
-template <bool N2, bool MARK = false>
-__device__ __forceinline__ void locate(const TreeDev& tr, float px, float py, float pz, Leaf& lf,
+template <bool N2, bool MARK = false, class L = Leaf>
+__device__ __forceinline__ void locate(const TreeDev& tr, float px, float py, float pz, L& lf,
                                        uint8_t* mark = nullptr) {
+    constexpr bool CELL = std::is_same<L, LeafCell>::value;
     px = fmaxf(0.f, fminf(kClampHi, px));
     py = fmaxf(0.f, fminf(kClampHi, py));
     pz = fmaxf(0.f, fminf(kClampHi, pz));
+    if constexpr (CELL) { lf.cx = lf.cy = lf.cz = 0u; lf.side = 1u; lf.cell_ok = true; }
     if constexpr (!N2) {
         descend_generic(tr, 0, px, py, pz, (float)tr.N, 0, lf);
     } else {
@@ -338,6 +361,10 @@ __device__ __forceinline__ void locate(const TreeDev& tr, float px, float py, fl
         const float sc = __int_as_float((127 + k) << 23);   // 2^k
         const float fx = px * sc, fy = py * sc, fz = pz * sc;
         const float lx = fx - floorf(fx), ly = fy - floorf(fy), lz = fz - floorf(fz);
+        if constexpr (CELL) {                               // the k bits the loop read, per axis
+            lf.cx = ux >> (kFixBits - k); lf.cy = uy >> (kFixBits - k); lf.cz = uz >> (kFixBits - k);
+            lf.side = 1u << k;
+        }
         if (skip == 0) {
             lf.slot = slot; lf.lx = lx; lf.ly = ly; lf.lz = lz;
             lf.cube_sz = sc; lf.levels = k;
@@ -350,15 +377,23 @@ __device__ __forceinline__ void locate(const TreeDev& tr, float px, float py, fl
 
 // The leaf of point q (q < Q) of a point query: its slot, and its feature row or -1 (an empty leaf).  The one place
 // where a query point is transformed, clamped and descended: svoxt_query_fwd / _bwd and svoxt_assign_leaves /
-// svoxt_snap_points all come through here, so they agree on the leaf of every point.
+// svoxt_snap_points all come through here, so they agree on the leaf of every point -- and svoxt_interp_* through
+// query_leaf, for the leaf-local coordinates and the cell (L = LeafCell); t: the point in tree space before the clamp.
+template <bool N2, class L>
+__device__ __forceinline__ void query_leaf(const TreeDev& tr, const float* __restrict__ points, int64_t q, L& lf, float& tx, float& ty,
+                                           float& tz) {
+    const float* p = points + 3 * q;
+    tx = tr.offset[0] + tr.scaling[0] * p[0];
+    ty = tr.offset[1] + tr.scaling[1] * p[1];
+    tz = tr.offset[2] + tr.scaling[2] * p[2];
+    locate<N2, false, L>(tr, tx, ty, tz, lf);
+}
+
 template <bool N2>
 __device__ __forceinline__ int32_t query_locate(const TreeDev& tr, const float* __restrict__ points, int64_t q, uint32_t& slot) {
-    const float* p = points + 3 * q;
-    const float px = tr.offset[0] + tr.scaling[0] * p[0];
-    const float py = tr.offset[1] + tr.scaling[1] * p[1];
-    const float pz = tr.offset[2] + tr.scaling[2] * p[2];
+    float px, py, pz;
     Leaf lf;
-    locate<N2>(tr, px, py, pz, lf);
+    query_leaf<N2>(tr, points, q, lf, px, py, pz);
     slot = lf.slot;
     const int32_t idx = tr.data[lf.slot];
     return (idx >= 0 && (int64_t)idx < tr.M) ? idx : -1;

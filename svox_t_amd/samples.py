@@ -71,6 +71,28 @@ class RaySamples:
             plans[M] = RowPlan(_C.row_plan(self.row.contiguous(), M))
         return plans[M]
 
+    def points(self, rays: Rays, at: str = "mid"):
+        """float32 [T, 3]: a world point per sample, origins[ray] + dirs[ray] * z with z = depth + 0.5 * length ("mid") or
+        z = depth ("entry") -- what tree.interp(samples.points(rays)) looks up in front of sample_weights / accumulate.
+        `rays` are the Rays the samples were marched from, with explicit origins and dirs; depth is measured along
+        `dirs` as given (the march's own scale).  Plain torch, differentiable in nothing.  Camera-mode and NDC rays are
+        refused: their origins and directions are formed inside the kernels."""
+        if at not in ("mid", "entry"):
+            raise RuntimeError('points: at must be "mid" or "entry"')
+        if not isinstance(rays, Rays):
+            raise RuntimeError("points: rays must be the Rays the samples were marched from (camera-mode and NDC rays are "
+                               "not served: their origins and directions are formed inside the kernels)")
+        o, d = rays.origins, rays.dirs
+        for name, x in (("origins", o), ("dirs", d)):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (self.Q, 3):
+                raise RuntimeError(f"points: rays.{name} must be float32 [Q, 3] with Q = {self.Q}, the rays the samples were marched from")
+            if x.device != self.ray.device:
+                raise RuntimeError("points: the rays must be on the device of the samples")
+        with torch.no_grad():
+            z = self.depth + 0.5 * self.length if at == "mid" else self.depth
+            idx = self.ray.long()
+            return o.detach()[idx] + d.detach()[idx] * z[:, None]
+
     def select(self, keep):
         """(RaySamples, index int64 [T']): the samples with keep[k] set, in their old order, as lists of their own -- the
         same Q rays (a ray may become empty), ray / row / depth / length copied bit for bit -- and every kept sample's

@@ -22,6 +22,7 @@ from torch import autograd, nn
 from svox_t_amd.helpers import DataFormat, LocalIndex, N3TreeView, _get_c_extension
 
 _C = _get_c_extension()
+_X = _C._extras            # (interp's wrappers are reached here, not as csrc.* names)
 
 # int(1e10) as int32: the fill value of `data` in the reference (svox.py:124).
 EMPTY_INDEX = 1410065408
@@ -138,6 +139,121 @@ class _QueryVerticalFunction(autograd.Function):
             return _C.query_vertical_backward(ctx.tree_spec, ctx.saved_tensors[0],
                                               grad_out.contiguous()), None, None
         return None, None, None
+
+
+_INTERP_FILL = ("self", "zero")
+
+
+class InterpStencil:
+    """What N3Tree.interp_stencil returns: the eight feature rows and trilinear weights of every point (include/svoxt.h,
+    "interp").
+
+    rows     int32 [Q, 8]     corner j = 4 b_x + 2 b_y + b_z; corner 0 is the point's own leaf; -1: no row
+    weights  float32 [Q, 8]   >= 0, summing to 1 within a few float32 roundings
+    Neither is meant to be edited: a row plan built before an edit of `rows` describes the old rows."""
+
+    def __init__(self, rows, weights):
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 8:
+            raise RuntimeError("rows must be int32 [Q, 8]")
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(rows.shape):
+            raise RuntimeError("weights must be float32 [Q, 8], one entry per entry of rows")
+        self.rows, self.weights = rows, weights
+
+    def __len__(self) -> int:
+        return self.rows.shape[0]
+
+    def __iter__(self):
+        return iter((self.rows, self.weights))
+
+    def row_plan(self, M: int):
+        """The RowPlan (svox_t_amd.samples) of `rows` viewed as int32 [8 Q] for a table of M rows: for every row the
+        entries e = 8 q + j that name it, in ascending e.  Built on the GPU with one host read, cached per M."""
+        from svox_t_amd.samples import RowPlan
+        M = _C._extras._check_rows_extent(M, "row_plan")
+        if not self.rows.is_cuda:
+            raise RuntimeError("row_plan: only the GPU (HIP) path exists; the stencil must be on the GPU")
+        plans = self.__dict__.setdefault("_row_plans", {})
+        if M not in plans:
+            plans[M] = RowPlan(_C.row_plan(self.rows.contiguous().reshape(-1), M))
+        return plans[M]
+
+
+class _InterpRowsFunction(autograd.Function):
+    """interp_rows: gradient flows to argument 0 (the table) only."""
+
+    @staticmethod
+    def forward(ctx, table, stencil, cols):
+        ctx.stencil, ctx.cols, ctx.shape = stencil, cols, tuple(table.shape)
+        return _X.interp_rows_fwd(table.detach().contiguous(), stencil.rows, stencil.weights, cols)
+
+    @staticmethod
+    @autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        M, K = ctx.shape
+        plan = ctx.stencil.row_plan(M)                           # built on the first backward: one host read
+        return _X.interp_rows_bwd(grad_out.contiguous(), ctx.stencil.weights, plan.arrays, ctx.cols, K), None, None
+
+
+class _InterpFunction(autograd.Function):
+    """N3Tree.interp with points that require a gradient: gradients flow to the table (argument 0) and the points (1)."""
+
+    @staticmethod
+    def forward(ctx, table, points, tree_spec, stencil, cols):
+        ctx.stencil, ctx.cols, ctx.shape, ctx.tree_spec = stencil, cols, tuple(table.shape), tree_spec
+        table = table.detach().contiguous()
+        ctx.save_for_backward(table, points)
+        return _X.interp_rows_fwd(table, stencil.rows, stencil.weights, cols)
+
+    @staticmethod
+    @autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        table, points = ctx.saved_tensors
+        g = grad_out.contiguous()
+        M, K = ctx.shape
+        gt = gp = None
+        if ctx.needs_input_grad[0]:
+            gt = _X.interp_rows_bwd(g, ctx.stencil.weights, ctx.stencil.row_plan(M).arrays, ctx.cols, K)
+        if ctx.needs_input_grad[1]:
+            gp = _X.interp_points_bwd(ctx.tree_spec, points, ctx.stencil.rows, table, g, ctx.cols)
+        return gt, gp, None, None, None
+
+
+def _interp_columns(dim, K, dev, what):
+    """`dim` (None, int, slice, list or tensor, N3Tree.tv's convention) -> int32 distinct columns on `dev`, None for all."""
+    if dim is None:
+        return None
+    if isinstance(dim, torch.Tensor):
+        dim = dim.cpu()
+    try:
+        picked = torch.arange(K)[dim].reshape(-1)
+    except (IndexError, TypeError) as e:
+        raise RuntimeError(f"{what}: dim does not select columns of a table of {K}: {e}") from None
+    if picked.numel() == 0:
+        raise RuntimeError(f"{what}: dim selects no column")
+    if picked.unique().numel() != picked.numel():
+        raise RuntimeError(f"{what}: dim selects a column twice")
+    return picked.to(device=dev, dtype=torch.int32)
+
+
+def interp_rows(stencil, table, dim=None):
+    """out float32 [Q, C]: out[q, jc] = sum over the stencil's eight corners, in ascending corner, of
+    weights[q, j] * table[rows[q, j], cols[jc]]; corners without a row (-1) are skipped.  `dim` selects the columns as
+    N3Tree.tv's does (None: all K); the column axis is kept.  The smooth counterpart of gather_rows: one stencil serves
+    any number of tables of the same height.
+
+    Differentiable in `table`, once: the gradient is a full [M, K] table, every element written, summed per entry over
+    stencil.row_plan(M) in reduce_rows' fixed order -- no [8 Q, C] tensor, no atomics, the same bits in every run.  The
+    plan is built on the first backward (one host read) and cached on the stencil.  GPU only."""
+    if not isinstance(stencil, InterpStencil):
+        raise RuntimeError("interp_rows: stencil must be an InterpStencil (N3Tree.interp_stencil)")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+        raise RuntimeError("interp_rows: table must be float32 [M, K], K >= 1")
+    if not table.is_cuda or not stencil.rows.is_cuda:
+        raise RuntimeError("interp_rows: only the GPU (HIP) path exists; the stencil and the table must be on the GPU")
+    cols = _interp_columns(dim, table.shape[1], table.device, "interp_rows")
+    return _InterpRowsFunction.apply(table, stencil, cols)
 
 
 class _WarpVerticalFunction(autograd.Function):
@@ -355,6 +471,69 @@ class N3Tree(nn.Module):
         if not self.data.is_cuda:
             raise RuntimeError("snap: only the GPU (HIP) path exists; move the tree to a GPU")
         return _C.snap_points(self._spec(self.features, world=world), indices)
+
+    # ------------------------------------------------------------ trilinear
+    def _interp_points(self, what, points, world):
+        """The point argument of interp / interp_stencil: float32 [Q, 3] on the tree's GPU, or LocalIndex of one (the
+        tree's own coordinates).  Returns (points, world)."""
+        if isinstance(points, LocalIndex):
+            points, world = points.val, False
+        if not self.data.is_cuda:
+            raise RuntimeError(f"{what}: only the GPU (HIP) path exists; move the tree to a GPU")
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError(f"{what}: points must be float32 [Q, 3]")
+        if not points.is_cuda:
+            raise RuntimeError(f"{what}: only the GPU (HIP) path exists; the points must be on the tree's GPU")
+        return points, bool(world)
+
+    def interp_stencil(self, points, world=True, fill="self", features=None):
+        """InterpStencil(rows int32 [Q, 8], weights float32 [Q, 8]) of the points (float32 [Q, 3]; world coordinates, the
+        tree's own with world=False or a LocalIndex): for every point the feature rows of the eight cells around it AT ITS
+        LEAF'S LEVEL and their trilinear weights (csrc/svoxt_interp.hip; include/svoxt.h has the definition, operation by
+        operation).  The point's position against its leaf's centre picks, per axis, the neighbouring cell on that side
+        (c + s_a) and the fraction f_a = |l_a - 0.5|; corner j = 4 b_x + 2 b_y + b_z has weight prod(b_a ? f_a :
+        1 - f_a) and the row of the leaf that forward() reports at the centre of its cell -- a coarser leaf, the same
+        size, or, where finer leaves cover the cell, the one at its centre.  Corner 0 is the point's own leaf.
+
+        fill="self": a corner without a row (outside the cube, an empty leaf) takes the point's own row -- clamp to
+        edge, the silhouette of the piecewise-constant field stays hard.  fill="zero": it takes row -1, which
+        interp_rows skips.  A point in an empty leaf gets eight rows of -1 either way.
+
+        The field built from a stencil is continuous inside leaves and across faces between leaves of equal depth; it
+        is NOT continuous across a change of level.  `features` (default: the tree's own table) only says how many rows
+        there are.  Integer descents and twelve float operations per point; not differentiable.  GPU only."""
+        if fill not in _INTERP_FILL:
+            raise RuntimeError(f"interp_stencil: fill must be one of {_INTERP_FILL}")
+        points, world = self._interp_points("interp_stencil", points, world)
+        table = self.features if features is None else features
+        with torch.no_grad():
+            rows, weights = _X.interp_stencil(self._spec(table.detach(), world=world), points.detach().contiguous(), fill)
+        return InterpStencil(rows, weights)
+
+    def interp(self, points, features=None, dim=None, world=True, fill="self"):
+        """out float32 [Q, C]: the trilinear lookup of `features` (float32 [M, K]; default: the tree's own) at `points`
+        (float32 [Q, 3]; world coordinates, the tree's own with world=False or a LocalIndex) --
+        interp_rows(self.interp_stencil(points, world, fill), features, dim), see there for the definition and for
+        `fill`.  `dim` selects columns as tv()'s does (the column axis is kept).  At the exact centre of a leaf this is
+        forward()'s row, bit for bit.
+
+        Differentiable, once, in `features` (a full [M, K] gradient over the stencil's row plan, reduce_rows' fixed
+        order, no atomics) and, where points.requires_grad, in `points`: the exact derivative of the value as defined,
+        inside a leaf -- it is 0 along an axis on which the point lies outside the cube, and it does not see the jumps
+        across a change of level.  No parity claim: the reference has no such operator.  GPU only."""
+        if fill not in _INTERP_FILL:
+            raise RuntimeError(f"interp: fill must be one of {_INTERP_FILL}")
+        points, world = self._interp_points("interp", points, world)
+        table = self.features if features is None else features
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] < 1:
+            raise RuntimeError("interp: features must be float32 [M, K], K >= 1")
+        if not table.is_cuda:
+            raise RuntimeError("interp: only the GPU (HIP) path exists; features must be on the tree's GPU")
+        stencil = self.interp_stencil(points, world=world, fill=fill, features=table)
+        if not points.requires_grad:
+            return interp_rows(stencil, table, dim)
+        cols = _interp_columns(dim, table.shape[1], table.device, "interp")
+        return _InterpFunction.apply(table, points.contiguous(), self._spec(table.detach(), world=world), stencil, cols)
 
     def leaf_boxes(self, world=True):
         """LeafBoxes(leaf_node, corners, lengths, depths, rows) of EVERY leaf slot, in `_all_leaves()` order, computed
