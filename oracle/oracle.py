@@ -144,6 +144,17 @@ def out_data_dim(opt: RenderOptions, K: int) -> int:
     return K
 
 
+def _check_lobes(format: int, basis_dim: int, extra) -> None:
+    """SG reads basis_dim rows of (sharpness, axis[3]) from `extra`, ASG basis_dim rows of 11 floats (precalc_basis in
+    svoxt_oracle.cpp): without them the C++ side would read through a null pointer or past the end."""
+    if format not in (FORMAT_SG, FORMAT_ASG):
+        return
+    cols = 4 if format == FORMAT_SG else 11
+    if extra is None or extra.ndim != 2 or extra.shape[0] < basis_dim or extra.shape[1] < cols:
+        raise ValueError(f"{'SG' if format == FORMAT_SG else 'ASG'}{basis_dim} needs lobes: extra [>= {basis_dim}, >= {cols}], "
+                         f"got {None if extra is None else tuple(extra.shape)}")
+
+
 def _rays(tree: Tree, origins, dirs, vdirs):
     o, d, v = (_c(x, tree.dtype) for x in (origins, dirs, vdirs))
     assert o.shape == d.shape == v.shape and o.shape[1] == 3
@@ -167,6 +178,7 @@ class transformation_matrices:
 
 
 def volume_render(tree: Tree, origins, dirs, vdirs, opt: RenderOptions, count=False):
+    _check_lobes(opt.format, opt.basis_dim, tree.extra)
     o, d, v = _rays(tree, origins, dirs, vdirs)
     Q = o.shape[0]
     out = np.zeros((Q, out_data_dim(opt, tree.K)), dtype=tree.dtype)
@@ -183,6 +195,7 @@ def volume_render_weights(tree: Tree, origins, dirs, vdirs, opt: RenderOptions):
     returns (out, weight_accum [n_internal, N, N, N] float64) -- per leaf slot, the sum of the
     compositing weights of the samples taken in that leaf."""
     assert tree.dtype == np.float32
+    _check_lobes(opt.format, opt.basis_dim, tree.extra)
     o, d, v = _rays(tree, origins, dirs, vdirs)
     Q = o.shape[0]
     out = np.zeros((Q, out_data_dim(opt, tree.K)), dtype=np.float32)
@@ -197,6 +210,7 @@ def volume_render_backward(tree: Tree, origins, dirs, vdirs, opt: RenderOptions,
     """Returns grad [M, K] float64 (and sum |contribution| if want_abs; want_abs="both": also the
     tighter scale that prices `accum` by the reference's own sequential addends, see
     trace_ray_backward in svoxt_oracle.cpp -- (grad, abs_sum, abs_sum_tight))."""
+    _check_lobes(opt.format, opt.basis_dim, tree.extra)
     o, d, v = _rays(tree, origins, dirs, vdirs)
     g = _c(grad_output, tree.dtype)
     Q = o.shape[0]
@@ -356,6 +370,7 @@ def basis(format: int, basis_dim: int, dirs, extra=None):
     d = _c(dirs, np.float32)
     out = np.zeros((d.shape[0], basis_dim), dtype=np.float32)
     e = None if extra is None else _c(extra, np.float32)
+    _check_lobes(format, basis_dim, e)
     lib().svoxt_oracle_basis_f32(ctypes.c_int(format), ctypes.c_int(basis_dim), _p(e),
                                  ctypes.c_int(0 if e is None else e.shape[0]),
                                  ctypes.c_int(0 if e is None else e.shape[1]),

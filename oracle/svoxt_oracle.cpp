@@ -515,6 +515,12 @@ void trace_ray_backward(const Tree<T>& tree, const RaySetup<T>& r, const RenderO
     }
     {   // PASS 2 (:439-494)
         T light_intensity = 1.f, t = r.tmin;
+        // View rotations only: pass 2 shades every sample with the basis pass 1 left behind (above), so what it takes
+        // off `accum` is NOT what pass 1 put on -- accum does not come back down, and its size (and rounding error) is
+        // that of pass 1's addends PLUS pass 2's subtrahends so far.  Without them the scale of a sigma entry could be
+        // orders of magnitude below the entry itself (tests/test_route_matrix_host.py keeps a case).  Without view
+        // rotations the subtrahends are the addends over again and both sums stay 0: the scales are unchanged.
+        double sub_scale = 0.0, sub_scale_tight = 0.0;
         while (t < r.tmax) {
             const Step<T> s = march_step<T>(tree, r, opt, t);
             if (s.sigma > 0.0) {
@@ -522,6 +528,7 @@ void trace_ray_backward(const Tree<T>& tree, const RaySetup<T>& r, const RenderO
                 const T att = exp_T<T>(-s.delta_t * s.sigma * r.delta_scale);
                 const T weight = light_intensity * (1.f - att);
                 T total_color = 0.f;
+                double color_mag = 0.0;
                 if (opt.format != FORMAT_RGBA) {
                     for (int c = 0; c < out_data_dim; ++c) {
                         const int off = c * opt.basis_dim;
@@ -529,6 +536,8 @@ void trace_ray_backward(const Tree<T>& tree, const RaySetup<T>& r, const RenderO
                         for (int i = opt.min_comp; i <= opt.max_comp; ++i)
                             tmp += basis_fn[i] * s.row[off + i];
                         total_color += 1.0 / (1.0 + exp_T<T>(-tmp)) * grad_output[c];
+                        if (tree.xform != nullptr)
+                            color_mag += std::fabs(1.0 / (1.0 + (double)exp_T<T>(-tmp)) * (double)grad_output[c]);
                     }
                 } else {
                     for (int j = 0; j < out_data_dim; ++j)
@@ -536,6 +545,10 @@ void trace_ray_backward(const Tree<T>& tree, const RaySetup<T>& r, const RenderO
                 }
                 light_intensity *= att;
                 accum -= weight * total_color;
+                if (tree.xform != nullptr) {
+                    sub_scale += std::fabs((double)weight) * color_mag;
+                    sub_scale_tight += std::fabs((double)weight * (double)total_color);
+                }
                 const T toadd = s.delta_t * r.delta_scale * (total_color * light_intensity - accum)
                               + s.delta_t * r.delta_scale * grad_output[out_data_dim] * light_intensity_ray;
                 // the sigma term is delta times a difference of O(1) quantities;
@@ -545,7 +558,7 @@ void trace_ray_backward(const Tree<T>& tree, const RaySetup<T>& r, const RenderO
                 const double dd = std::fabs((double)s.delta_t * (double)r.delta_scale);
                 const double rest = std::fabs((double)total_color * (double)light_intensity)
                                   + std::fabs((double)grad_output[out_data_dim] * (double)light_intensity_ray);
-                add(base + K - 1, toadd, dd * (rest + accum_scale), dd * (rest + accum_scale_tight));
+                add(base + K - 1, toadd, dd * (rest + accum_scale + sub_scale), dd * (rest + accum_scale_tight + sub_scale_tight));
             }
             t += s.delta_t;
         }

@@ -859,6 +859,8 @@ def _volume_render(tree, rays, opt, record):
         etab = _attach_sigma_mask(tree, ct, 0.0 if will_record else float(co.sigma_thresh), keep=not will_record,
                                   table=wide and split and not NATIVE_MATH, begin=lists)
     LAST_ROUTE["forward_terms"] = False
+    # (for the label: with BWD_LIST_SAMPLES = 0 nothing is recorded, and a specialised payload still has its own kernel)
+    special = bool(can_rec or not record or _lib.svoxt_can_record(ctypes.byref(ct), ctypes.byref(co)))
     # march and shade of a 3-channel payload as ONE launch (fwd_roles_kernel): the conditions of the library's launch_fwd_roles
     roles = bool(FWD_OVERLAP and LIST_POOL and ct.sigma_mask and ct.N == 2 and ct.xform is None and ct.weight_accum is None
                  and cr.Q > 0 and ((co.format == FORMAT_RGBA and ct.K == 4) or
@@ -868,7 +870,7 @@ def _volume_render(tree, rays, opt, record):
                               + (", native exp / rcp)" if NATIVE_MATH else ")") if wide else
                               "fwd_roles_kernel (march + shade_tile in one launch)" if roles else
                               "march_rec_kernel + shade_tile_kernel (two-kernel forward)") if split
-                             else ("render_fwd_kernel" if can_rec or not record else "render_fwd_generic_kernel (no specialised instance: accumulators in "
+                             else ("render_fwd_kernel" if special else "render_fwd_generic_kernel (no specialised instance: accumulators in "
                                    "memory as the reference keeps them)")) + (", recording sample lists" if will_record else "")
     with _on(dev):
         out = torch.empty((cr.Q, get_out_data_dim(opt, ct.K)), dtype=torch.float32, device=dev)
