@@ -1332,6 +1332,63 @@ int svoxt_samples_select_emit(const uint8_t* keep, int64_t T, const void* worksp
                               const int32_t* row, const float* depth, const float* length, int64_t T_out, int32_t* ray_out,
                               int32_t* row_out, float* depth_out, float* length_out, int64_t* index, void* stream);
 
+/* ---- new lists out of old ones: split and merge (svoxt_cut.hip; not in the reference) --------------
+ * The conventions of the select triple above: a segment is clipped to [0, T), Q and T below 2^31, float32, every operation
+ * rounded by itself, no contraction, no float atomic: the same bits in every run.  Each pair is count (one 64-bit total on
+ * the device, which the caller reads back and refuses from 2^31 on) and emit.  Entry points added under ABI v22.
+ *   svoxt_samples_split_*     every sample k cut into m_k equal pieces, in list order:
+ *                                 mf = ceilf(length / max_length)   (pieces == NULL; max_length > 0, +inf allowed), or
+ *                                 mf = (float)pieces[k]             (pieces: device int32 [T]; max_length must then be 0)
+ *                                 m = 1 where length > 0 is false (0, negative, NaN) or mf >= 1 is false,
+ *                                 m = (int)min(mf, (float)max_pieces) otherwise         (max_pieces in [1, 2^30])
+ *                                 m == 1: the sample copied bit for bit;  else step = length / (float)m and piece p < m has
+ *                                 depth + (float)p * step and length step.  Every piece keeps ray and row.
+ *       _workspace_bytes(T)   device bytes (8-byte aligned) shared by the pair; -1: T negative or 2^31 and more; 0 for T = 0
+ *       _count                pos = the number of pieces before each sample (32-bit scan over T + 1 entries),
+ *                             offsets_out int64 [Q + 1] = pos[clamped offsets[q]], total int64 [1] = the 64-bit sum of m
+ *                             (both device, 8-byte aligned; offsets_out means nothing where total >= 2^32).  T = 0: zeros.
+ *       _emit                 with the same T and workspace (unchanged since _count) and T_out = total: a lane per piece j
+ *                             finds its source k by a binary search in pos and writes ray / row / depth / length and
+ *                             index int64 [T_out] = k.  Nothing is written at or behind T_out.
+ *   svoxt_samples_merge_*     the union of two lists of the SAME Q rays (depth along the same direction vectors): per ray the
+ *                             pieces between all breakpoints of both lists that at least one list covers, with the index of
+ *                             the covering sample of each list (-1: none).  A sample is [s, e), s = depth, e = depth + length
+ *                             (one float32 add); each list has a current sample and a cursor c that starts at its s.  Until
+ *                             both lists are exhausted, the first rule that applies:
+ *                               1. a current sample with e > s false (length 0, negative, NaN; NaN depth) is emitted whole and
+ *                                  alone: (s, length, its index, -1); A's before B's.  That list advances.
+ *                               2. B exhausted or e_a <= c_b: A alone from c_a, length = A's length if c_a == s_a else
+ *                                  e_a - c_a.  A advances.
+ *                               3. A exhausted or e_b <= c_a: the same for B.
+ *                               4. c_a < c_b: A alone, (c_a, c_b - c_a); c_a = c_b.
+ *                               5. c_b < c_a: B alone, (c_b, c_a - c_b); c_b = c_a.
+ *                               6. c_a == c_b: hi = min(e_a, e_b); both indices, depth c_a, length = A's length if c_a == s_a
+ *                                  and hi == e_a, else B's length if c_b == s_b and hi == e_b, else hi - c_a;
+ *                                  c_a = c_b = hi; each list with e <= hi advances.
+ *                             A ray has at most 2 (n_a + n_b) pieces; merging with an empty list, or a list of samples with
+ *                             e > s with itself, returns the list bit for bit.  Samples outside every segment take no part.
+ *       _workspace_bytes(Q)   device bytes (8-byte aligned) of _count; -1: Q negative or 2^31 and more; 0 for Q = 0
+ *       _count                walks every ray once; offsets_out int64 [Q + 1] (offsets_out[Q] = total) and total int64 [1],
+ *                             the 64-bit number of pieces.  Arrays of a list with T = 0 may be NULL (offsets not).
+ *       _emit                 walks again and writes ray (= q), row (= -1), depth, length, index_a, index_b int64 at
+ *                             offsets_out[q] ..; never at or behind min(offsets_out[q + 1], T_out).
+ * No allocation, no synchronisation. */
+int64_t svoxt_samples_split_workspace_bytes(int64_t T);
+int svoxt_samples_split_count(const float* length, const int32_t* pieces, float max_length, int32_t max_pieces, const int64_t* offsets,
+                              int64_t Q, int64_t T, int64_t* offsets_out, int64_t* total, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+int svoxt_samples_split_emit(int64_t T, const void* workspace, int64_t workspace_bytes, const int32_t* ray, const int32_t* row,
+                             const float* depth, const float* length, int64_t T_out, int32_t* ray_out, int32_t* row_out,
+                             float* depth_out, float* length_out, int64_t* index, void* stream);
+int64_t svoxt_samples_merge_workspace_bytes(int64_t Q);
+int svoxt_samples_merge_count(const int64_t* offsets_a, const float* depth_a, const float* length_a, int64_t T_a, const int64_t* offsets_b,
+                              const float* depth_b, const float* length_b, int64_t T_b, int64_t Q, int64_t* offsets_out, int64_t* total,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_samples_merge_emit(const int64_t* offsets_a, const float* depth_a, const float* length_a, int64_t T_a, const int64_t* offsets_b,
+                             const float* depth_b, const float* length_b, int64_t T_b, int64_t Q, const int64_t* offsets_out, int64_t T_out,
+                             int32_t* ray_out, int32_t* row_out, float* depth_out, float* length_out, int64_t* index_a, int64_t* index_b,
+                             void* stream);
+
 /* ---- samples to feature rows and back (svoxt_rows.hip; not in the reference) ----------------------
  * The row side of the per-sample interface: a gather of table rows by sample, and its inverse, a reduction of
  * per-sample values by feature row over a fixed-order plan.  Gather only: no atomics on floats anywhere, every result

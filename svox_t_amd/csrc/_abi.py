@@ -212,6 +212,13 @@ EXPORTS = {
     "svoxt_samples_select_workspace_bytes": (_i64, [_i64]),
     "svoxt_samples_select_count": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_samples_select_emit": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_samples_split_workspace_bytes": (_i64, [_i64]),
+    "svoxt_samples_split_count": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_samples_split_emit": (ctypes.c_int, [_i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_samples_merge_workspace_bytes": (_i64, [_i64]),
+    "svoxt_samples_merge_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "svoxt_samples_merge_emit": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp]),
     "svoxt_row_plan_workspace_bytes": (_i64, [_i64, _i64]),
     "svoxt_row_plan_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "svoxt_row_plan_long": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -1576,6 +1576,94 @@ def samples_select(keep, offsets, ray, row, depth, length):
 
 
 # ---------------------------------------------------------------------------
+# New lists out of old ones (svoxt_cut.hip; not in the reference)
+# ---------------------------------------------------------------------------
+SPLIT_MAX_PIECES = 1 << 30                                       # the largest max_pieces svoxt_samples_split_count takes
+
+
+def _cut_total(total, what) -> int:
+    """The one host read of a count / emit pair of svoxt_cut.hip: the 64-bit total, refused from 2^31 on before anything
+    is allocated or emitted."""
+    n = int(total.item())
+    if n >= 1 << 31:
+        raise RuntimeError(f"{what}: the result would hold {n} samples; a list holds fewer than 2^31")
+    return n
+
+
+def _new_lists(Tn, dev):
+    return (torch.empty((Tn,), dtype=torch.int32, device=dev), torch.empty((Tn,), dtype=torch.int32, device=dev),
+            torch.empty((Tn,), dtype=torch.float32, device=dev), torch.empty((Tn,), dtype=torch.float32, device=dev))
+
+
+def samples_split(offsets, ray, row, depth, length, max_length=None, pieces=None, max_pieces=4096):
+    """(offsets' int64 [Q + 1], ray', row', depth', length', index int64 [T'], T') of svoxt_samples_split_count / _emit:
+    exactly one of max_length (a float > 0) and pieces (int32 [T]).  One host read (T')."""
+    if (max_length is None) == (pieces is None):
+        raise RuntimeError("split: exactly one of max_length and pieces must be given")
+    if isinstance(max_pieces, bool) or not isinstance(max_pieces, int) or not 1 <= max_pieces <= SPLIT_MAX_PIECES:
+        raise RuntimeError("split: max_pieces must be an int in [1, 2^30]")
+    if pieces is None:
+        if isinstance(max_length, (bool, torch.Tensor)) or not isinstance(max_length, (int, float)) or not max_length > 0:
+            raise RuntimeError("split: max_length must be a float > 0 (inf allowed)")
+        max_length = float(max_length)
+    if not isinstance(length, torch.Tensor) or length.dim() != 1:
+        raise RuntimeError("length must be float32 [T]")
+    T = length.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    for name, x, dt in (("ray", ray, torch.int32), ("row", row, torch.int32), ("depth", depth, torch.float32), ("length", length, torch.float32)):
+        _check_per_sample(x, name, T, dev, dtype=dt)
+    if pieces is not None:
+        _check_per_sample(pieces, "pieces", T, dev, dtype=torch.int32)
+    with _on(dev):
+        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+        total = torch.empty((1,), dtype=torch.int64, device=dev)
+        nbytes = _lib.svoxt_samples_split_workspace_bytes(T)
+        ws = _workspace(dev, nbytes, "split: T must be below 2^31")
+        _call("svoxt_samples_split_count", _ptr(length), None if pieces is None else _ptr(pieces), 0.0 if pieces is not None else max_length,
+              max_pieces, _ptr(offsets), Q, T, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
+        Tn = _cut_total(total, "split")                 # the one host read
+        ray_o, row_o, depth_o, length_o = _new_lists(Tn, dev)
+        index = torch.empty((Tn,), dtype=torch.int64, device=dev)
+        if Tn > 0:
+            _call("svoxt_samples_split_emit", T, _ptr(ws), nbytes, _ptr(ray), _ptr(row), _ptr(depth), _ptr(length), Tn,
+                  _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o), _ptr(index), _stream(dev))
+    return offsets_out, ray_o, row_o, depth_o, length_o, index, Tn
+
+
+def samples_merge(offsets_a, depth_a, length_a, offsets_b, depth_b, length_b):
+    """(offsets' int64 [Q + 1], ray', row' (-1), depth', length', index_a int64 [T'], index_b int64 [T'], T') of
+    svoxt_samples_merge_count / _emit for two lists of the same Q rays.  One host read (T')."""
+    for name, d, ln in (("a", depth_a, length_a), ("b", depth_b, length_b)):
+        if not isinstance(d, torch.Tensor) or d.dim() != 1 or not isinstance(ln, torch.Tensor):
+            raise RuntimeError(f"depth_{name} and length_{name} must be float32 [T_{name}]")
+    Ta, Tb = depth_a.shape[0], depth_b.shape[0]
+    Q = _check_csr(offsets_a, Ta)
+    if _check_csr(offsets_b, Tb) != Q:
+        raise RuntimeError(f"merge_samples: the lists are of {Q} and {offsets_b.shape[0] - 1} rays; they must be lists of the same rays")
+    dev = offsets_a.device
+    if offsets_b.device != dev:
+        raise RuntimeError("merge_samples: the two lists must be on the same device")
+    for name, x, T in (("depth_a", depth_a, Ta), ("length_a", length_a, Ta), ("depth_b", depth_b, Tb), ("length_b", length_b, Tb)):
+        _check_per_sample(x, name, T, dev)
+    with _on(dev):
+        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+        total = torch.empty((1,), dtype=torch.int64, device=dev)
+        nbytes = _lib.svoxt_samples_merge_workspace_bytes(Q)
+        ws = _workspace(dev, nbytes, "merge_samples: Q must be below 2^31")
+        lists = (_ptr(offsets_a), _ptr(depth_a), _ptr(length_a), Ta, _ptr(offsets_b), _ptr(depth_b), _ptr(length_b), Tb, Q)
+        _call("svoxt_samples_merge_count", *lists, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
+        Tn = _cut_total(total, "merge_samples")         # the one host read
+        ray_o, row_o, depth_o, length_o = _new_lists(Tn, dev)
+        index_a = torch.empty((Tn,), dtype=torch.int64, device=dev)
+        index_b = torch.empty((Tn,), dtype=torch.int64, device=dev)
+        if Tn > 0:
+            _call("svoxt_samples_merge_emit", *lists, _ptr(offsets_out), Tn, _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o),
+                  _ptr(index_a), _ptr(index_b), _stream(dev))
+    return offsets_out, ray_o, row_o, depth_o, length_o, index_a, index_b, Tn
+
+
+# ---------------------------------------------------------------------------
 # Samples to feature rows and back (svoxt_rows.hip; not in the reference; DESIGN.md 4.21)
 # ---------------------------------------------------------------------------
 ROW_CHUNK = 256                                                   # SVOXT_ROW_CHUNK (include/svoxt.h)

@@ -10,6 +10,9 @@
     trans = ray_scan(samples, att, "prod", exclusive=True)         # running sum / prod / max / min along every ray
     index, frac = ray_quantile(samples, w, [0.5])                  # where the running weight crosses q * total; quantile_depth: the depth
     sub, index = samples.select(w > 1e-3)                          # the kept samples as a RaySamples of its own; values[index] follows
+    fine, index = samples.split(max_length=0.01)                   # every crossing cut into equal pieces (or pieces=int32 [T])
+    m, ia, ib = merge_samples(sa, sb)                              # two trees a ray: the union of two lists of the SAME rays, and
+    s_a, s_b = take_samples(sig_a, ia), take_samples(sig_b, ib)    # per piece each list's sample or -1: 0 where a tree has no sample there
 
 Every per-sample loss is then a few lines of torch around HIP operators whose results, gradients included, have the same
 bits in every run: the gradient of gather_rows reaches the table through reduce_rows' fixed-order row plan (DESIGN.md
@@ -107,6 +110,89 @@ class RaySamples:
                 keep.contiguous(), self.offsets.contiguous(), self.ray.contiguous(), self.row.contiguous(), self.depth.contiguous(),
                 self.length.contiguous())
         return RaySamples(offsets, ray, row, depth, length), index
+
+    def split(self, max_length=None, *, pieces=None, max_pieces: int = 4096):
+        """(RaySamples, index int64 [T']): every sample cut into equal pieces, in list order, as lists of their own over
+        the same Q rays, and every piece's source sample: values[index] carries any per-sample tensor over.  Exactly one
+        of `max_length` (a Python float > 0, inf allowed: no piece longer than it) and `pieces` (int32 [T] on the samples'
+        device: a count per sample).  For sample k, float32, every operation rounded by itself:
+
+            mf = ceilf(length / max_length)  or  (float)pieces[k]
+            m = 1 where length > 0 is false (0, negative, NaN) or mf >= 1 is false;  else m = (int)min(mf, (float)max_pieces)
+            m == 1: the sample copied bit for bit;  else step = length / (float)m, piece p: depth + (float)p * step, length step
+
+        Every piece keeps `ray` and `row`.  split(max_length=inf) and split(pieces=ones) are these lists array for array.
+        Count, scan, emit on the GPU -- a lane per OUTPUT piece, which finds its source by a binary search in the scan --
+        with one host read (T'); a result of 2^31 samples or more is refused before anything is allocated.  Not
+        differentiable: the results are indices and distances.  The result holds no cached row plan."""
+        if (max_length is None) == (pieces is None):
+            raise RuntimeError("split: exactly one of max_length and pieces must be given")
+        if pieces is not None and (not isinstance(pieces, torch.Tensor) or pieces.dtype != torch.int32 or tuple(pieces.shape) != (len(self),)):
+            raise RuntimeError("split: pieces must be int32 [T], one entry per sample")
+        if pieces is None and (isinstance(max_length, (bool, torch.Tensor)) or not isinstance(max_length, (int, float)) or not max_length > 0):
+            raise RuntimeError("split: max_length must be a float > 0 (inf allowed)")
+        if isinstance(max_pieces, bool) or not isinstance(max_pieces, int) or not 1 <= max_pieces <= _X.SPLIT_MAX_PIECES:
+            raise RuntimeError("split: max_pieces must be an int in [1, 2^30]")
+        _require_gpu("split", self, pieces)
+        with torch.no_grad():
+            offsets, ray, row, depth, length, index, _ = _X.samples_split(
+                self.offsets.contiguous(), self.ray.contiguous(), self.row.contiguous(), self.depth.contiguous(), self.length.contiguous(),
+                max_length, None if pieces is None else pieces.contiguous(), max_pieces)
+        return RaySamples(offsets, ray, row, depth, length), index
+
+
+def merge_samples(a: RaySamples, b: RaySamples):
+    """(RaySamples m, index_a int64 [T'], index_b int64 [T']): the union of two lists along shared rays -- per ray the
+    pieces between all breakpoints of both lists that at least one of them covers, and for every piece the sample of `a`
+    and of `b` that covers it (-1: none): take_samples(values_a, index_a) carries a per-sample tensor of `a` over.
+
+    `a` and `b` must be lists of the SAME rays -- the same Q, the same origins and direction vectors, as from two
+    renderers' ray_samples(rays) -- through two trees of any centre and radius: `depth` is the parameter along `dirs` as
+    given (RaySamples.points), so the depths of both lists are comparable.  Only Q and the device are checked.  m.row is -1
+    everywhere: a merged sample names no single feature row; rows are reached through gather_rows(a, table_a) and
+    take_samples(..., index_a).  m holds no cached row plan.
+
+    The walk (include/svoxt.h states it rule by rule): a sample is [s, e) with s = depth, e = depth + length (one float32
+    add); neighbours inside one list are never compared.  A sample with e > s false (length 0, negative or NaN, NaN depth)
+    is emitted whole and alone, A's before B's, and cuts nothing.  Otherwise the pieces run from breakpoint to breakpoint;
+    a piece that is all of a source sample takes that sample's length bit for bit, any other the float32 difference of
+    its ends.  So merge_samples(a, empty) is `a` array for array with index_a = arange and index_b = -1 (mirrored for b);
+    merge_samples(a, a) is `a` with both indices arange where no sample of `a` is degenerate; a ray has at most
+    2 (n_a + n_b) pieces; the pieces with index_a == k tile [s_k, e_k).  Output depths are monotone except where an input
+    list overlaps itself: the march's own neighbours overlap by a unit in the last place now and then, and the sliver is
+    emitted as a piece.  With sigma = sigma_a + sigma_b per piece the composite of two piecewise-constant media is exact
+    in the sense of the interval form.
+
+    A lane per ray walks both segments, once to count and once to emit; one host read (T'), refused from 2^31 on before
+    anything is allocated.  Not differentiable: indices and distances.  There is no CPU path."""
+    if not isinstance(a, RaySamples) or not isinstance(b, RaySamples):
+        raise RuntimeError("merge_samples: a and b must be RaySamples")
+    if a.Q != b.Q:
+        raise RuntimeError(f"merge_samples: a holds {a.Q} rays, b {b.Q}; they must be lists of the same rays")
+    _require_gpu("merge_samples", a)
+    _require_gpu("merge_samples", b)
+    if a.offsets.device != b.offsets.device:
+        raise RuntimeError("merge_samples: a and b must be on the same device")
+    with torch.no_grad():
+        offsets, ray, row, depth, length, index_a, index_b, _ = _X.samples_merge(
+            a.offsets.contiguous(), a.depth.contiguous(), a.length.contiguous(), b.offsets.contiguous(), b.depth.contiguous(),
+            b.length.contiguous())
+    return RaySamples(offsets, ray, row, depth, length), index_a, index_b
+
+
+def take_samples(values, index, fill: float = 0.0):
+    """values[index] where index >= 0 and `fill` where it is -1 (merge_samples: the piece has no sample of that list);
+    -1 never wraps to the last element.  values: [T, ...], index: int64 [T']; the result is [T', ...].  Plain torch:
+    gradients reach `values` through the indexing."""
+    if not isinstance(values, torch.Tensor) or values.dim() < 1:
+        raise RuntimeError("take_samples: values must be a tensor [T, ...], one row per sample")
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1:
+        raise RuntimeError("take_samples: index must be int64 [T']")
+    if values.shape[0] == 0:
+        return values.new_full((index.shape[0],) + tuple(values.shape[1:]), fill)
+    hit = index >= 0
+    out = values[index.clamp_min(0)]
+    return torch.where(hit.reshape((-1,) + (1,) * (values.dim() - 1)), out, torch.full_like(out, fill))
 
 
 class RowPlan:
