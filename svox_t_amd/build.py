@@ -28,7 +28,7 @@ SOURCES = ["svoxt_kernels.hip", "svoxt_bwd.hip", "svoxt_build.hip", "svoxt_motio
            "svoxt_distort.hip", "svoxt_samples.hip", "svoxt_rows.hip", "svoxt_rowgrad.hip", "svoxt_shade.hip", "svoxt_scan.hip",
            "svoxt_interp.hip", "svoxt_cut.hip"]
 HEADERS = ["svoxt_device.h", "svoxt_host.h", "svoxt_launch.h", "svoxt_lists.h", "svoxt_fwd_kernels.h", "svoxt_bwd_kernels.h",
-           "svoxt_misc_kernels.h", "svoxt_sort.h", "svoxt_raylists.h", "svoxt_raysweep.h", "svoxt_rowwalk.h", "svoxt_tile_reduce.inc", "svoxt_wave.h", "svoxt_workspace.h", os.path.join("..", "..", "include", "svoxt.h")]
+           "svoxt_misc_kernels.h", "svoxt_sort.h", "svoxt_raylists.h", "svoxt_raysweep.h", "svoxt_rowwalk.h", "svoxt_listemit.h", "svoxt_tile_reduce.inc", "svoxt_wave.h", "svoxt_workspace.h", os.path.join("..", "..", "include", "svoxt.h")]
 
 # -ffp-contract=off is part of the numerical contract (svoxt_device.h): the
 # stepping arithmetic must not be fused into FMAs.

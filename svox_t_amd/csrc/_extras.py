@@ -1375,14 +1375,37 @@ def ray_samples(tree: TreeSpec, rays, opt: RenderOptions, min_sigma=None):
             T = int(offsets[Q].item())                  # the one host read
             if T >= 1 << 31:
                 raise RuntimeError(f"ray_samples: {T} samples; a batch's lists hold fewer than 2^31 (split the batch)")
-        row = torch.empty((T,), dtype=torch.int32, device=dev)
-        ray = torch.empty((T,), dtype=torch.int32, device=dev)
-        depth = torch.empty((T,), dtype=torch.float32, device=dev)
-        length = torch.empty((T,), dtype=torch.float32, device=dev)
+        row, ray, depth, length = _new_lists(T, dev)
         if T > 0:
             _call("svoxt_ray_samples_emit", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), ms, _ptr(offsets), _ptr(row),
                   _ptr(ray), _ptr(depth), _ptr(length), _stream(dev))
     return offsets, row, ray, depth, length, T
+
+
+def _new_lists(Tn, dev):
+    """The four per-sample arrays of a list of Tn samples: two int32 (ray and row), two float32 (depth and length)."""
+    return (torch.empty((Tn,), dtype=torch.int32, device=dev), torch.empty((Tn,), dtype=torch.int32, device=dev),
+            torch.empty((Tn,), dtype=torch.float32, device=dev), torch.empty((Tn,), dtype=torch.float32, device=dev))
+
+
+def _count_and_emit(what, extent, dev, Q, nbytes, count, emit, n_index=1):
+    """The pair of calls of a list producer that makes new lists out of old ones (select, split, merge_samples):
+    count(offsets_out, total, workspace, workspace_bytes) -- the tail of every svoxt_samples_*_count --, the one host
+    read, then emit((workspace, workspace_bytes), offsets_out, T', the pointers of ray', row', depth', length' and of
+    n_index index arrays) where T' > 0.  A total of 2^31 or more is refused before anything is allocated or emitted
+    (select's T' <= T never gets there).  `extent`: "T" or "Q", what the workspace is sized by.  Returns (offsets', ray', row', depth', length', index.., T')."""
+    with _on(dev):
+        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+        total = torch.empty((1,), dtype=torch.int64, device=dev)
+        ws = _workspace(dev, nbytes, f"{what}: {extent} must be below 2^31")
+        count(_ptr(offsets_out), _ptr(total), _ptr(ws), nbytes)
+        Tn = int(total.item())                          # the one host read
+        if Tn >= 1 << 31:
+            raise RuntimeError(f"{what}: the result would hold {Tn} samples; a list holds fewer than 2^31")
+        new = _new_lists(Tn, dev) + tuple(torch.empty((Tn,), dtype=torch.int64, device=dev) for _ in range(n_index))
+        if Tn > 0:
+            emit((_ptr(ws), nbytes), _ptr(offsets_out), Tn, tuple(_ptr(x) for x in new))
+    return (offsets_out,) + new + (Tn,)
 
 
 def _check_csr(offsets, T) -> int:
@@ -1557,42 +1580,17 @@ def samples_select(keep, offsets, ray, row, depth, length):
     _check_per_sample(keep, "keep", T, dev, dtype=torch.bool)
     for name, x, dt in (("ray", ray, torch.int32), ("row", row, torch.int32), ("depth", depth, torch.float32), ("length", length, torch.float32)):
         _check_per_sample(x, name, T, dev, dtype=dt)
-    with _on(dev):
-        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
-        total = torch.empty((1,), dtype=torch.int64, device=dev)
-        nbytes = _lib.svoxt_samples_select_workspace_bytes(T)
-        ws = _workspace(dev, nbytes, "select: T must be below 2^31")
-        _call("svoxt_samples_select_count", _ptr(keep), _ptr(offsets), Q, T, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
-        Tn = int(total.item())                          # the one host read
-        ray_o = torch.empty((Tn,), dtype=torch.int32, device=dev)
-        row_o = torch.empty((Tn,), dtype=torch.int32, device=dev)
-        depth_o = torch.empty((Tn,), dtype=torch.float32, device=dev)
-        length_o = torch.empty((Tn,), dtype=torch.float32, device=dev)
-        index = torch.empty((Tn,), dtype=torch.int64, device=dev)
-        if Tn > 0:
-            _call("svoxt_samples_select_emit", _ptr(keep), T, _ptr(ws), nbytes, _ptr(ray), _ptr(row), _ptr(depth), _ptr(length), Tn,
-                  _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o), _ptr(index), _stream(dev))
-    return offsets_out, ray_o, row_o, depth_o, length_o, index, Tn
+    old = (_ptr(ray), _ptr(row), _ptr(depth), _ptr(length))
+    return _count_and_emit(
+        "select", "T", dev, Q, _lib.svoxt_samples_select_workspace_bytes(T),
+        lambda *out: _call("svoxt_samples_select_count", _ptr(keep), _ptr(offsets), Q, T, *out, _stream(dev)),
+        lambda ws, _offsets_out, Tn, new: _call("svoxt_samples_select_emit", _ptr(keep), T, *ws, *old, Tn, *new, _stream(dev)))
 
 
 # ---------------------------------------------------------------------------
 # New lists out of old ones (svoxt_cut.hip; not in the reference)
 # ---------------------------------------------------------------------------
 SPLIT_MAX_PIECES = 1 << 30                                       # the largest max_pieces svoxt_samples_split_count takes
-
-
-def _cut_total(total, what) -> int:
-    """The one host read of a count / emit pair of svoxt_cut.hip: the 64-bit total, refused from 2^31 on before anything
-    is allocated or emitted."""
-    n = int(total.item())
-    if n >= 1 << 31:
-        raise RuntimeError(f"{what}: the result would hold {n} samples; a list holds fewer than 2^31")
-    return n
-
-
-def _new_lists(Tn, dev):
-    return (torch.empty((Tn,), dtype=torch.int32, device=dev), torch.empty((Tn,), dtype=torch.int32, device=dev),
-            torch.empty((Tn,), dtype=torch.float32, device=dev), torch.empty((Tn,), dtype=torch.float32, device=dev))
 
 
 def samples_split(offsets, ray, row, depth, length, max_length=None, pieces=None, max_pieces=4096):
@@ -1615,20 +1613,12 @@ def samples_split(offsets, ray, row, depth, length, max_length=None, pieces=None
         _check_per_sample(x, name, T, dev, dtype=dt)
     if pieces is not None:
         _check_per_sample(pieces, "pieces", T, dev, dtype=torch.int32)
-    with _on(dev):
-        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
-        total = torch.empty((1,), dtype=torch.int64, device=dev)
-        nbytes = _lib.svoxt_samples_split_workspace_bytes(T)
-        ws = _workspace(dev, nbytes, "split: T must be below 2^31")
-        _call("svoxt_samples_split_count", _ptr(length), None if pieces is None else _ptr(pieces), 0.0 if pieces is not None else max_length,
-              max_pieces, _ptr(offsets), Q, T, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
-        Tn = _cut_total(total, "split")                 # the one host read
-        ray_o, row_o, depth_o, length_o = _new_lists(Tn, dev)
-        index = torch.empty((Tn,), dtype=torch.int64, device=dev)
-        if Tn > 0:
-            _call("svoxt_samples_split_emit", T, _ptr(ws), nbytes, _ptr(ray), _ptr(row), _ptr(depth), _ptr(length), Tn,
-                  _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o), _ptr(index), _stream(dev))
-    return offsets_out, ray_o, row_o, depth_o, length_o, index, Tn
+    old = (_ptr(ray), _ptr(row), _ptr(depth), _ptr(length))
+    return _count_and_emit(
+        "split", "T", dev, Q, _lib.svoxt_samples_split_workspace_bytes(T),
+        lambda *out: _call("svoxt_samples_split_count", _ptr(length), None if pieces is None else _ptr(pieces),
+                           0.0 if pieces is not None else max_length, max_pieces, _ptr(offsets), Q, T, *out, _stream(dev)),
+        lambda ws, _offsets_out, Tn, new: _call("svoxt_samples_split_emit", T, *ws, *old, Tn, *new, _stream(dev)))
 
 
 def samples_merge(offsets_a, depth_a, length_a, offsets_b, depth_b, length_b):
@@ -1646,21 +1636,11 @@ def samples_merge(offsets_a, depth_a, length_a, offsets_b, depth_b, length_b):
         raise RuntimeError("merge_samples: the two lists must be on the same device")
     for name, x, T in (("depth_a", depth_a, Ta), ("length_a", length_a, Ta), ("depth_b", depth_b, Tb), ("length_b", length_b, Tb)):
         _check_per_sample(x, name, T, dev)
-    with _on(dev):
-        offsets_out = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
-        total = torch.empty((1,), dtype=torch.int64, device=dev)
-        nbytes = _lib.svoxt_samples_merge_workspace_bytes(Q)
-        ws = _workspace(dev, nbytes, "merge_samples: Q must be below 2^31")
-        lists = (_ptr(offsets_a), _ptr(depth_a), _ptr(length_a), Ta, _ptr(offsets_b), _ptr(depth_b), _ptr(length_b), Tb, Q)
-        _call("svoxt_samples_merge_count", *lists, _ptr(offsets_out), _ptr(total), _ptr(ws), nbytes, _stream(dev))
-        Tn = _cut_total(total, "merge_samples")         # the one host read
-        ray_o, row_o, depth_o, length_o = _new_lists(Tn, dev)
-        index_a = torch.empty((Tn,), dtype=torch.int64, device=dev)
-        index_b = torch.empty((Tn,), dtype=torch.int64, device=dev)
-        if Tn > 0:
-            _call("svoxt_samples_merge_emit", *lists, _ptr(offsets_out), Tn, _ptr(ray_o), _ptr(row_o), _ptr(depth_o), _ptr(length_o),
-                  _ptr(index_a), _ptr(index_b), _stream(dev))
-    return offsets_out, ray_o, row_o, depth_o, length_o, index_a, index_b, Tn
+    lists = (_ptr(offsets_a), _ptr(depth_a), _ptr(length_a), Ta, _ptr(offsets_b), _ptr(depth_b), _ptr(length_b), Tb, Q)
+    return _count_and_emit(
+        "merge_samples", "Q", dev, Q, _lib.svoxt_samples_merge_workspace_bytes(Q),
+        lambda *out: _call("svoxt_samples_merge_count", *lists, *out, _stream(dev)),
+        lambda _ws, offsets_out, Tn, new: _call("svoxt_samples_merge_emit", *lists, offsets_out, Tn, *new, _stream(dev)), n_index=2)
 
 
 # ---------------------------------------------------------------------------
@@ -1682,6 +1662,13 @@ class RowPlanArrays(NamedTuple):
     M: int
     n_outside: int
     longest: int
+
+
+def _plan_args(plan: RowPlanArrays, with_M: bool = True) -> tuple:
+    """A plan as the C ABI takes it: row_ptr, perm, M (svoxt_reduce_rows and svoxt_interp_rows_bwd have it there,
+    svoxt_shade_samples_bwd in front: with_M False), long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks."""
+    return ((_ptr(plan.row_ptr), _ptr(plan.perm)) + ((plan.M,) if with_M else ()) +
+            (_ptr(plan.long_rows), _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), plan.long_rows.shape[0], plan.chunk_long.shape[0]))
 
 
 def _check_rows_extent(M, what) -> int:
@@ -1769,13 +1756,11 @@ def sample_reduce_rows(values: torch.Tensor, plan: RowPlanArrays, op: str = "sum
         K = C
     elif _check_cols(cols, int(K), dev) != C:
         raise RuntimeError("values must have one column per selected column")
-    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
     with _on(dev):
         out = torch.empty((M, K), dtype=torch.float32, device=dev)
-        nbytes = _lib.svoxt_reduce_rows_workspace_bytes(n_chunks, C)
+        nbytes = _lib.svoxt_reduce_rows_workspace_bytes(plan.chunk_long.shape[0], C)
         ws = _workspace(dev, nbytes, "reduce_rows: chunks * C must be below 2^38")
-        _call("svoxt_reduce_rows", _ptr(values), T, C, _ptr(plan.row_ptr), _ptr(plan.perm), M, _ptr(plan.long_rows),
-              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(cols), 0 if cols is None else C, int(K),
+        _call("svoxt_reduce_rows", _ptr(values), T, C, *_plan_args(plan), _ptr(cols), 0 if cols is None else C, int(K),
               ROWS_OPS[op], float(empty), _ptr(out), _ptr(ws), nbytes, _stream(dev))
     return out
 
@@ -1941,14 +1926,12 @@ def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: b
             raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] on the device of the plan")
         _check_input(basis, "basis")
     co = _pack_opts(opt)
-    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
     with _on(dev):
         grad = torch.empty((M, K), dtype=torch.float32, device=dev)
-        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)
+        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], K)
         ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
         _call("svoxt_shade_samples_bwd", ctypes.byref(co), M, K, _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q, 1 if activate else 0,
-              _ptr(values), _ptr(grad_values), _ptr(grad_sigma), _ptr(plan.row_ptr), _ptr(plan.perm), _ptr(plan.long_rows),
-              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(grad), _ptr(ws), nbytes, _stream(dev))
+              _ptr(values), _ptr(grad_values), _ptr(grad_sigma), *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
     return grad
 
 
@@ -2051,14 +2034,12 @@ def interp_rows_bwd(grad_out: torch.Tensor, weights: torch.Tensor, plan: RowPlan
         K = C
     elif _check_cols(cols, int(K), dev) != C:
         raise RuntimeError("grad_out must have one column per selected column")
-    n_long, n_chunks = plan.long_rows.shape[0], plan.chunk_long.shape[0]
     with _on(dev):
         grad = torch.empty((M, int(K)), dtype=torch.float32, device=dev)
-        nbytes = _lib.svoxt_interp_rows_bwd_workspace_bytes(n_chunks, C)
+        nbytes = _lib.svoxt_interp_rows_bwd_workspace_bytes(plan.chunk_long.shape[0], C)
         ws = _workspace(dev, nbytes, "interp: chunks * C must be below 2^38")
-        _call("svoxt_interp_rows_bwd", _ptr(grad_out), _ptr(weights), Q, C, _ptr(plan.row_ptr), _ptr(plan.perm), M, _ptr(plan.long_rows),
-              _ptr(plan.long_chunk_ptr), _ptr(plan.chunk_long), n_long, n_chunks, _ptr(cols), 0 if cols is None else C, int(K), _ptr(grad),
-              _ptr(ws), nbytes, _stream(dev))
+        _call("svoxt_interp_rows_bwd", _ptr(grad_out), _ptr(weights), Q, C, *_plan_args(plan), _ptr(cols), 0 if cols is None else C, int(K),
+              _ptr(grad), _ptr(ws), nbytes, _stream(dev))
     return grad
 
 

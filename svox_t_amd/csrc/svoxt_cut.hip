@@ -2,7 +2,7 @@
 // The per-sample family's conventions (svoxt_samples.hip): ray q's segment is max(offsets[q], 0) .. min(offsets[q + 1], T),
 // float32, every operation rounded by itself, no contraction, no float atomic, no LDS: the same bits in every run.
 //
-//   split    count -> scan -> emit (svoxt_workspace.h).  A lane per sample forms its number of pieces
+//   split    count -> scan -> emit (svoxt_listemit.h, the per-sample shape).  A lane per sample forms its number of pieces
 //                m = 1                                    where length > 0 is false, or mf >= 1 is false
 //                m = (int)min(mf, (float)max_pieces)      otherwise;  mf = ceilf(length / max_length) or (float)pieces[k]
 //            and each wavefront adds its lanes' counts to one 64-bit total; pos = exclusive scan of m over T + 1 entries,
@@ -11,7 +11,7 @@
 //            lane over the 64 entries behind that --, p = j - pos[k]:
 //                m == 1:  depth and length copied bit for bit
 //                else:    step = length / (float)m;  depth' = depth + (float)p * step;  length' = step
-//   merge    count -> scan -> emit, a lane per ray.  Both kernels compile the same walk (merge_walk below) over the ray's two
+//   merge    count -> scan -> emit (the per-ray shape), a lane per ray.  Both kernels compile the same walk (merge_walk below) over the ray's two
 //            segments, once to count the pieces and once to write them at offsets'[q] ..; the count kernel adds each
 //            wavefront's pieces to one 64-bit total.
 // C ABI: svoxt_samples_split_* / svoxt_samples_merge_* (include/svoxt.h).
@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
+#include "svoxt_listemit.h"
 #include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
@@ -28,24 +28,8 @@
 namespace svoxt {
 
 // -------------------------------------------------------------------------------------------------------------- split
-// workspace of svoxt_samples_split_count, read again by _emit: [total u64] [m u32[T + 1]] [pos u32[T + 1]] [chunk sums];
-// the total is cleared
-struct SplitSpace {
-    unsigned long long* total;
-    uint32_t *m, *pos, *chunks;
-    size_t clear_bytes, bytes;
-};
-static SplitSpace split_carve(void* workspace, int64_t T) {
-    SplitSpace sp;
-    Carver w(workspace);
-    sp.total = w.take<unsigned long long>(1);
-    sp.clear_bytes = w.bytes();
-    sp.m = w.take<uint32_t>((size_t)T + 1);
-    sp.pos = w.take<uint32_t>((size_t)T + 1);
-    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)T + 1));
-    sp.bytes = w.bytes();
-    return sp;
-}
+// workspace of svoxt_samples_split_count, read again by _emit: the per-sample ListSpace (svoxt_listemit.h) with a total,
+// counts = m, starts = pos
 
 // The entries k <= T, strided over at most kSplitCountBlocks workgroups; entry T is the scan's end and holds 0.  A lane adds
 // its counts up and a wavefront sends one atomic: with a lane per sample and an atomic per 64 of them, the 92 000
@@ -66,16 +50,7 @@ split_count_kernel(const float* __restrict__ length, const int32_t* __restrict__
         m_out[k] = m;
         sum += m;
     }
-    sum = wave_all_sum(sum);
-    if ((threadIdx.x & 63) == 0 && sum != 0ull) atomicAdd(total, sum);
-}
-
-__global__ void __launch_bounds__(kLaunchBlock)
-split_offsets_kernel(const uint32_t* __restrict__ pos, const unsigned long long* __restrict__ sum, const int64_t* __restrict__ offsets,
-                     int64_t Q, int64_t T, int64_t* __restrict__ offsets_out, int64_t* __restrict__ total) {
-    const int64_t i = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    if (i <= Q) offsets_out[i] = (int64_t)pos[min(max(offsets[i], (int64_t)0), T)];
-    if (i == 0) total[0] = (int64_t)sum[0];                      // (64 bits: pos wraps at 2^32, the caller refuses from 2^31)
+    wave_add_to_total(sum, total);
 }
 
 // a lane per output piece
@@ -120,23 +95,7 @@ split_emit_kernel(const uint32_t* __restrict__ pos, int64_t T, int64_t T_out, co
 }
 
 // -------------------------------------------------------------------------------------------------------------- merge
-// workspace of svoxt_samples_merge_count: [total u64] [counts u32[Q]] [starts u32[Q]] [chunk sums]; the total is cleared
-struct MergeSpace {
-    unsigned long long* total;
-    uint32_t *counts, *starts, *chunks;
-    size_t clear_bytes, bytes;
-};
-static MergeSpace merge_carve(void* workspace, int64_t Q) {
-    MergeSpace sp;
-    Carver w(workspace);
-    sp.total = w.take<unsigned long long>(1);
-    sp.clear_bytes = w.bytes();
-    sp.counts = w.take<uint32_t>((size_t)Q);
-    sp.starts = w.take<uint32_t>((size_t)Q);
-    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)Q));
-    sp.bytes = w.bytes();
-    return sp;
-}
+// workspace of svoxt_samples_merge_count: the per-ray ListSpace (svoxt_listemit.h) with a total
 
 // One list of a ray under the walk: the current sample [s, e) with its length as stored, and the cursor c inside it.
 struct CutList {
@@ -212,16 +171,7 @@ merge_count_kernel(CutLists L, int64_t Q, uint32_t* __restrict__ counts, unsigne
         merge_walk(L, q, [&](float, float, int64_t, int64_t) { ++n; });
         counts[q] = (uint32_t)n;
     }
-    const unsigned long long sum = wave_all_sum(n);
-    if ((threadIdx.x & 63) == 0 && sum != 0ull) atomicAdd(total, sum);
-}
-
-__global__ void __launch_bounds__(kLaunchBlock)
-merge_offsets_kernel(const uint32_t* __restrict__ starts, const unsigned long long* __restrict__ sum, int64_t Q,
-                     int64_t* __restrict__ offsets_out, int64_t* __restrict__ total) {
-    const int64_t i = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    if (i < Q) offsets_out[i] = (int64_t)starts[i];
-    else if (i == Q) offsets_out[Q] = total[0] = (int64_t)sum[0];
+    wave_add_to_total(n, total);
 }
 
 __global__ void __launch_bounds__(kLaunchBlock)
@@ -247,23 +197,6 @@ merge_emit_kernel(CutLists L, int64_t Q, const int64_t* __restrict__ offsets_out
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-static bool overlap(const void* a, const void* b, double bytes) {
-    if (a == nullptr || b == nullptr) return false;
-    const double x = (double)(uintptr_t)a, y = (double)(uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-static int extent_check(int64_t v, const char* name, const char* fn) {
-    if (v < 0 || v > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: %s must be in [0, 2^31)", fn, name);
-    return SVOXT_OK;
-}
-static int clear_counts(int64_t* offsets_out, int64_t Q, int64_t* total, hipStream_t st, const char* fn) {
-    hipError_t e = hipMemsetAsync(offsets_out, 0, (size_t)(Q + 1) * sizeof(int64_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(total, 0, sizeof(int64_t), st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    return SVOXT_OK;
-}
-
 // one side of a merge: its arrays may be NULL only where it has no sample
 static int merge_side_check(const int64_t* offsets, const float* depth, const float* length, int64_t T, const char* fn) {
     if (offsets == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets_a / offsets_b is NULL", fn);
@@ -280,9 +213,7 @@ using namespace svoxt;
 extern "C" {
 
 int64_t svoxt_samples_split_workspace_bytes(int64_t T) {
-    if (T < 0 || T > 0x7fffffffLL) return -1;
-    if (T == 0) return 0;
-    return (int64_t)split_carve(nullptr, T).bytes;
+    return list_space_bytes(T, 1, true);
 }
 
 int svoxt_samples_split_count(const float* length, const int32_t* pieces, float max_length, int32_t max_pieces, const int64_t* offsets,
@@ -290,12 +221,11 @@ int svoxt_samples_split_count(const float* length, const int32_t* pieces, float 
                               void* stream) {
     const char* fn = "svoxt_samples_split_count";
     int rc;
-    if ((rc = extent_check(Q, "Q", fn)) || (rc = extent_check(T, "T", fn))) return rc;
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T, "T"))) return rc;
     if (max_pieces < 1 || max_pieces > (1 << 30)) return fail(SVOXT_ERR_INVALID, "%s: max_pieces must be in [1, 2^30]", fn);
-    if (offsets_out == nullptr || total == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is NULL", fn);
-    if (misaligned(offsets_out, 8) || misaligned(total, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is not 8-byte aligned", fn);
+    if ((rc = counts_out_check(fn, offsets_out, total))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (T == 0) return clear_counts(offsets_out, Q, total, st, fn);          // nothing to cut: empty lists, nothing else is read
+    if (T == 0) return clear_counts(fn, offsets_out, Q, total, st);          // nothing to cut: empty lists, nothing else is read
     if (pieces == nullptr && max_length == 0.f) return fail(SVOXT_ERR_INVALID, "%s: neither max_length nor pieces is given", fn);
     if (pieces != nullptr && max_length != 0.f) return fail(SVOXT_ERR_INVALID, "%s: both max_length and pieces are given (max_length must be 0 with pieces)", fn);
     if (pieces == nullptr && !(max_length > 0.f)) return fail(SVOXT_ERR_INVALID, "%s: max_length must be > 0", fn);
@@ -303,18 +233,13 @@ int svoxt_samples_split_count(const float* length, const int32_t* pieces, float 
     if (misaligned(offsets, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets is not 8-byte aligned", fn);
     if (misaligned(length, 4) || misaligned(pieces, 4)) return fail(SVOXT_ERR_INVALID, "%s: length / pieces is not 4-byte aligned", fn);
     if (overlap(offsets, offsets_out, 8.0 * (double)(Q + 1))) return fail(SVOXT_ERR_INVALID, "%s: offsets_out overlaps offsets", fn);
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_samples_split_workspace_bytes(T), "svoxt_samples_split_workspace_bytes(T)")))
+    ListSpace sp;
+    if ((rc = list_space_check(fn, workspace, workspace_bytes, (size_t)T + 1, true, "svoxt_samples_split_workspace_bytes(T)", &sp)) ||
+        (rc = memset_async(workspace, sp.clear_bytes, st, fn)))
         return rc;
-    const SplitSpace sp = split_carve(workspace, T);
-    const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
     hipLaunchKernelGGL(split_count_kernel, dim3(min(launch_blocks(T + 1), (unsigned)kSplitCountBlocks)), dim3(kLaunchBlock), 0, st, length, pieces, max_length,
-                       (float)max_pieces, T, sp.m, sp.total);
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.m, (size_t)T + 1, sp.chunks, sp.pos, st, fn))) return rc;
-    hipLaunchKernelGGL(split_offsets_kernel, dim3(launch_blocks(Q + 1)), dim3(kLaunchBlock), 0, st, sp.pos, sp.total, offsets, Q, T,
-                       offsets_out, total);
-    return check_launch(fn);
+                       (float)max_pieces, T, sp.counts, sp.total);
+    return list_pos_offsets<true>(fn, sp, offsets, Q, T, offsets_out, total, st);
 }
 
 int svoxt_samples_split_emit(int64_t T, const void* workspace, int64_t workspace_bytes, const int32_t* ray, const int32_t* row,
@@ -322,29 +247,20 @@ int svoxt_samples_split_emit(int64_t T, const void* workspace, int64_t workspace
                              float* depth_out, float* length_out, int64_t* index, void* stream) {
     const char* fn = "svoxt_samples_split_emit";
     int rc;
-    if ((rc = extent_check(T, "T", fn))) return rc;
-    if (T_out < 0 || T_out > 0x7fffffffLL || (T_out > 0 && T == 0)) return fail(SVOXT_ERR_INVALID, "%s: T_out must be in [0, 2^31), 0 for T = 0", fn);
+    if ((rc = extent31_check(fn, T, "T"))) return rc;
+    if (!in31(T_out) || (T_out > 0 && T == 0)) return fail(SVOXT_ERR_INVALID, "%s: T_out must be in [0, 2^31), 0 for T = 0", fn);
     if (T_out == 0) return SVOXT_OK;
-    if (ray == nullptr || row == nullptr || depth == nullptr || length == nullptr)
-        return fail(SVOXT_ERR_INVALID, "%s: ray / row / depth / length is NULL", fn);
-    if (ray_out == nullptr || row_out == nullptr || depth_out == nullptr || length_out == nullptr || index == nullptr)
-        return fail(SVOXT_ERR_INVALID, "%s: an output is NULL", fn);
-    if (misaligned(ray, 4) || misaligned(row, 4) || misaligned(depth, 4) || misaligned(length, 4) || misaligned(ray_out, 4) ||
-        misaligned(row_out, 4) || misaligned(depth_out, 4) || misaligned(length_out, 4) || misaligned(index, 8))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (index: 8 bytes, the other arrays: 4)", fn);
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_samples_split_workspace_bytes(T), "svoxt_samples_split_workspace_bytes(T)")))
+    ListSpace sp;
+    if ((rc = emit_arrays_check(fn, ray, row, depth, length, ray_out, row_out, depth_out, length_out, index)) ||
+        (rc = list_space_check(fn, workspace, workspace_bytes, (size_t)T + 1, true, "svoxt_samples_split_workspace_bytes(T)", &sp)))
         return rc;
-    const SplitSpace sp = split_carve(const_cast<void*>(workspace), T);
-    hipLaunchKernelGGL(split_emit_kernel, dim3(launch_blocks(T_out)), dim3(kLaunchBlock), 0, (hipStream_t)stream, sp.pos, T, T_out, ray,
+    hipLaunchKernelGGL(split_emit_kernel, dim3(launch_blocks(T_out)), dim3(kLaunchBlock), 0, (hipStream_t)stream, sp.starts, T, T_out, ray,
                        row, depth, length, ray_out, row_out, depth_out, length_out, index);
     return check_launch(fn);
 }
 
 int64_t svoxt_samples_merge_workspace_bytes(int64_t Q) {
-    if (Q < 0 || Q > 0x7fffffffLL) return -1;
-    if (Q == 0) return 0;
-    return (int64_t)merge_carve(nullptr, Q).bytes;
+    return list_space_bytes(Q, 0, true);
 }
 
 int svoxt_samples_merge_count(const int64_t* offsets_a, const float* depth_a, const float* length_a, int64_t T_a, const int64_t* offsets_b,
@@ -352,25 +268,21 @@ int svoxt_samples_merge_count(const int64_t* offsets_a, const float* depth_a, co
                               void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "svoxt_samples_merge_count";
     int rc;
-    if ((rc = extent_check(Q, "Q", fn)) || (rc = extent_check(T_a, "T_a", fn)) || (rc = extent_check(T_b, "T_b", fn))) return rc;
-    if (offsets_out == nullptr || total == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is NULL", fn);
-    if (misaligned(offsets_out, 8) || misaligned(total, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is not 8-byte aligned", fn);
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T_a, "T_a")) || (rc = extent31_check(fn, T_b, "T_b")) ||
+        (rc = counts_out_check(fn, offsets_out, total)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (Q == 0 || (T_a == 0 && T_b == 0)) return clear_counts(offsets_out, Q, total, st, fn);        // nothing to merge: empty lists
+    if (Q == 0 || (T_a == 0 && T_b == 0)) return clear_counts(fn, offsets_out, Q, total, st);        // nothing to merge: empty lists
     if ((rc = merge_side_check(offsets_a, depth_a, length_a, T_a, fn)) || (rc = merge_side_check(offsets_b, depth_b, length_b, T_b, fn))) return rc;
     if (overlap(offsets_a, offsets_out, 8.0 * (double)(Q + 1)) || overlap(offsets_b, offsets_out, 8.0 * (double)(Q + 1)))
         return fail(SVOXT_ERR_INVALID, "%s: offsets_out overlaps offsets_a / offsets_b", fn);
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_samples_merge_workspace_bytes(Q), "svoxt_samples_merge_workspace_bytes(Q)")))
+    ListSpace sp;
+    if ((rc = list_space_check(fn, workspace, workspace_bytes, (size_t)Q, true, "svoxt_samples_merge_workspace_bytes(Q)", &sp)) ||
+        (rc = memset_async(workspace, sp.clear_bytes, st, fn)))
         return rc;
-    const MergeSpace sp = merge_carve(workspace, Q);
-    const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
     const CutLists L{offsets_a, offsets_b, depth_a, length_a, depth_b, length_b, T_a, T_b};
     hipLaunchKernelGGL(merge_count_kernel, dim3(launch_blocks(Q)), dim3(kLaunchBlock), 0, st, L, Q, sp.counts, sp.total);
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.counts, (size_t)Q, sp.chunks, sp.starts, st, fn))) return rc;
-    hipLaunchKernelGGL(merge_offsets_kernel, dim3(launch_blocks(Q + 1)), dim3(kLaunchBlock), 0, st, sp.starts, sp.total, Q, offsets_out, total);
-    return check_launch(fn);
+    return list_ray_offsets<true>(fn, sp, Q, offsets_out, total, st);
 }
 
 int svoxt_samples_merge_emit(const int64_t* offsets_a, const float* depth_a, const float* length_a, int64_t T_a, const int64_t* offsets_b,
@@ -379,8 +291,9 @@ int svoxt_samples_merge_emit(const int64_t* offsets_a, const float* depth_a, con
                              void* stream) {
     const char* fn = "svoxt_samples_merge_emit";
     int rc;
-    if ((rc = extent_check(Q, "Q", fn)) || (rc = extent_check(T_a, "T_a", fn)) || (rc = extent_check(T_b, "T_b", fn))) return rc;
-    if (T_out < 0 || T_out > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T_out must be in [0, 2^31)", fn);
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T_a, "T_a")) || (rc = extent31_check(fn, T_b, "T_b")) ||
+        (rc = extent31_check(fn, T_out, "T_out")))
+        return rc;
     if (T_out == 0 || Q == 0) return SVOXT_OK;
     if ((rc = merge_side_check(offsets_a, depth_a, length_a, T_a, fn)) || (rc = merge_side_check(offsets_b, depth_b, length_b, T_b, fn))) return rc;
     if (offsets_out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets_out is NULL", fn);

@@ -26,6 +26,11 @@
 
 namespace svoxt {
 
+// One wavefront per workgroup: the finest scheduling granularity for kernels whose
+// wavefronts differ 10x in cost (measured: 64 -> 492, 128 -> 485, 256 -> 477,
+// 512 -> 466 Mrays/s on the headline workload).
+constexpr int kBlock = 64;
+
 struct TreeDev {
     const float* __restrict__ features;
     int64_t M;

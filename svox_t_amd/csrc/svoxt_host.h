@@ -1,5 +1,6 @@
 // svoxt_host.h -- host-side helpers shared by the translation units of
-// libsvoxt_hip.so (not part of the public C ABI).
+// libsvoxt_hip.so (not part of the public C ABI): compile-time dispatch, the error text, the checks of the C structs,
+// the argument predicates of the per-sample units, the exclusive scan.
 #pragma once
 
 #include <type_traits>
@@ -44,8 +45,34 @@ inline bool xf_roles_basis(int basis_dim) { return XfRolesBases::has(basis_dim);
 // Records the text svoxt_last_error() returns on this thread and hands back `code`.
 int set_error(int code, const char* fmt, const char* a = "", const char* b = "");
 
+inline int fail(int code, const char* fmt, const char* a = "", const char* b = "") { return set_error(code, fmt, a, b); }
+
 // hipGetLastError() -> SVOXT_OK / SVOXT_ERR_HIP (+ error text)
 int check_launch(const char* what);
+
+// The argument predicates of the per-sample units, each once.  A NULL pointer is aligned and overlaps
+// nothing: whether it may be NULL is the entry point's own check.
+inline unsigned nblocks(int64_t Q) { return (unsigned)((Q + kBlock - 1) / kBlock); }
+inline bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+inline bool overlap(const void* a, const void* b, double bytes) {
+    if (a == nullptr || b == nullptr) return false;
+    const double x = (double)(uintptr_t)a, y = (double)(uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+// an extent that int32 indices reach: a number of rays, samples, rows or chunks
+inline bool in31(int64_t v) { return v >= 0 && v <= 0x7fffffffLL; }
+inline int extent31_check(const char* fn, int64_t v, const char* name) {
+    return in31(v) ? SVOXT_OK : fail(SVOXT_ERR_INVALID, "%s: %s must be in [0, 2^31)", fn, name);
+}
+// the elements of an [a, b] array that a launch of a lane per element covers: below 2^38
+constexpr double kMaxElems = 274877906944.0;
+inline bool elems_fit(double a, double b) { return a * b < kMaxElems; }
+// zeros into `bytes` bytes at p on `st`
+inline int memset_async(void* p, size_t bytes, hipStream_t st, const char* fn) {
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
+    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+    return SVOXT_OK;
+}
 
 // Argument validation shared by every entry point (the TORCH_CHECKs of
 // data_spec.hpp:57-64, 85-110 for raw pointers); `fn` names the caller in the error text.

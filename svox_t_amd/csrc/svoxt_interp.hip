@@ -23,7 +23,6 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
 #include "svoxt_rowwalk.h"
 #include "svoxt_workspace.h"
 
@@ -272,22 +271,19 @@ interp_points_bwd_kernel(TreeDev tr, const float* __restrict__ points, int64_t Q
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-
 constexpr int64_t kInterpMaxQ = 0x0fffffffLL;                     // 8 Q < 2^31: the entries e = 8 q + j are int32 in the plan
 
 static int interp_extents_check(int64_t Q, int64_t M, const char* fn) {
     if (Q < 0 || Q > kInterpMaxQ) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^28) (8 Q < 2^31)", fn);
-    if (M < 0 || M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be in [0, 2^31)", fn);
-    return SVOXT_OK;
+    return extent31_check(fn, M, "M");
 }
 
 static int interp_cols_check(const int32_t* cols, int32_t n_cols, int32_t K, const char* fn) {
     if (K < 1) return fail(SVOXT_ERR_INVALID, "%s: K must be >= 1", fn);
-    if ((cols == nullptr) != (n_cols == 0) || n_cols < 0 || n_cols > K)
-        return fail(SVOXT_ERR_INVALID, "%s: cols / n_cols must be NULL / 0 (all columns) or n_cols in [1, K] distinct columns", fn);
-    return SVOXT_OK;
+    return cols_check(fn, cols, n_cols, K);
 }
+// Q points by C columns, M rows by K
+static bool interp_elems_fit(int64_t Q, int C, int64_t M, int K) { return elems_fit((double)Q, C) && elems_fit((double)M, K); }
 
 }  // namespace svoxt
 
@@ -324,7 +320,7 @@ int svoxt_interp_rows_fwd(const float* table, int64_t M, int32_t K, const int32_
     int rc;
     if ((rc = interp_extents_check(Q, M, fn)) || (rc = interp_cols_check(cols, n_cols, K, fn))) return rc;
     const int C = cols != nullptr ? n_cols : K;
-    if ((double)Q * C >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!interp_elems_fit(Q, C, M, K))
         return fail(SVOXT_ERR_INVALID, "%s: Q * columns and M * K must be below 2^38", fn);
     if (Q == 0) return SVOXT_OK;
     if (rows == nullptr || weights == nullptr || out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: rows / weights / out is NULL", fn);
@@ -347,7 +343,7 @@ int svoxt_interp_rows_fwd(const float* table, int64_t M, int32_t K, const int32_
 }
 
 int64_t svoxt_interp_rows_bwd_workspace_bytes(int64_t n_chunks, int32_t C) {
-    if (n_chunks < 0 || n_chunks > 0x7fffffffLL || C < 1 || (double)n_chunks * C >= 274877906944.0) return -1;
+    if (!in31(n_chunks) || C < 1 || !elems_fit((double)n_chunks, C)) return -1;
     if (n_chunks == 0) return 0;
     return (int64_t)align256(sizeof(float) * (size_t)n_chunks * (size_t)C);
 }
@@ -361,32 +357,25 @@ int svoxt_interp_rows_bwd(const float* grad_out, const float* weights, int64_t Q
     if ((rc = interp_extents_check(Q, M, fn)) || (rc = interp_cols_check(cols, n_cols, K, fn))) return rc;
     if (C != (cols != nullptr ? n_cols : K))
         return fail(SVOXT_ERR_INVALID, "%s: grad_out must have one column per selected column (C = n_cols, or C = K without cols)", fn);
-    if ((double)Q * C >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!interp_elems_fit(Q, C, M, K))
         return fail(SVOXT_ERR_INVALID, "%s: Q * C and M * K must be below 2^38", fn);
     const int64_t T = 8 * Q;
-    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
-        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, 8 Q / (SVOXT_ROW_CHUNK + 1))]", fn);
-    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
-        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, 8 Q / SVOXT_ROW_CHUNK + n_long]", fn);
+    const RowPlanRef plan{row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};
+    if ((rc = row_plan_check(fn, plan, "8 Q"))) return rc;
     if (M == 0) return SVOXT_OK;
     if (grad == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad / row_ptr is NULL", fn);
     if (Q > 0 && (grad_out == nullptr || weights == nullptr || perm == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: grad_out / weights / perm is NULL", fn);
-    if (n_long > 0 && (long_rows == nullptr || long_chunk_ptr == nullptr || chunk_long == nullptr))
-        return fail(SVOXT_ERR_INVALID, "%s: long_rows / long_chunk_ptr / chunk_long is NULL", fn);
-    if (misaligned(grad_out, 4) || misaligned(weights, 4) || misaligned(row_ptr, 4) || misaligned(perm, 4) || misaligned(long_rows, 4) ||
-        misaligned(long_chunk_ptr, 4) || misaligned(chunk_long, 4) || misaligned(cols, 4) || misaligned(grad, 4) || misaligned(workspace, 4))
+    if ((rc = row_plan_long_check(fn, plan))) return rc;
+    if (misaligned(grad_out, 4) || misaligned(weights, 4) || row_plan_misaligned(plan) || misaligned(cols, 4) || misaligned(grad, 4) ||
+        misaligned(workspace, 4))
         return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
     if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_interp_rows_bwd_workspace_bytes(n_chunks, C),
                                             "svoxt_interp_rows_bwd_workspace_bytes(n_chunks, C)")))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (cols != nullptr) {                                       // every element written
-        const hipError_t e = hipMemsetAsync(grad, 0, sizeof(float) * (size_t)M * (size_t)K, st);
-        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    }
+    if (cols != nullptr && (rc = memset_async(grad, sizeof(float) * (size_t)M * (size_t)K, st, fn))) return rc;     // every element written
     const InterpValues src{weights, grad_out, T, (int)C};
-    rows_launch<ROWS_SUM, ROWS_SUM>(src, T, (int)C, row_ptr, perm, M, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks, cols, (int)K, 0.f,
-                                    grad, static_cast<float*>(workspace), st);
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, (int)C, plan, cols, (int)K, 0.f, grad, static_cast<float*>(workspace), st);
     return check_launch(fn);
 }
 
@@ -399,7 +388,7 @@ int svoxt_interp_points_bwd(const svoxt_tree* tree, const float* points, int64_t
     if (tree->N > 16) return fail(SVOXT_ERR_INVALID, "%s: branching factor N must be in [2, 16]", fn);
     if ((rc = interp_extents_check(Q, M, fn)) || (rc = interp_cols_check(cols, n_cols, K, fn))) return rc;
     const int C = cols != nullptr ? n_cols : K;
-    if ((double)Q * C >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!interp_elems_fit(Q, C, M, K))
         return fail(SVOXT_ERR_INVALID, "%s: Q * columns and M * K must be below 2^38", fn);
     if (Q == 0) return SVOXT_OK;
     if (points == nullptr || rows == nullptr || grad_out == nullptr || grad_points == nullptr)

@@ -13,9 +13,7 @@
 
 namespace svoxt {
 
-inline int fail(int code, const char* fmt, const char* a = "", const char* b = "") { return set_error(code, fmt, a, b); }
-
-inline unsigned nblocks(int64_t Q) { return (unsigned)((Q + kBlock - 1) / kBlock); }
+// (fail() and nblocks() are svoxt_host.h's)
 
 // sample lists: rec[tile][block of 8][lane][8], 8 bytes per record (rec_index)
 inline int64_t rec_rays(int64_t Q) { return (Q + 63) / 64 * 64; }

@@ -15,10 +15,7 @@
 
 namespace svoxt {
 
-// One wavefront per workgroup: the finest scheduling granularity for kernels whose
-// wavefronts differ 10x in cost (measured: 64 -> 492, 128 -> 485, 256 -> 477,
-// 512 -> 466 Mrays/s on the headline workload).
-constexpr int kBlock = 64;
+// (kBlock, one wavefront per workgroup, is svoxt_device.h's: the per-sample units march with it too)
 
 // ---------------------------------------------------------------------------
 // Forward: trace_ray (rt_kernel.cu:222-328) + render_ray_kernel (:655-671)

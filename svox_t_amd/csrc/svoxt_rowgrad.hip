@@ -28,7 +28,6 @@
 
 #include "svoxt_device.h"
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
 #include "svoxt_rowwalk.h"
 #include "svoxt_workspace.h"
 
@@ -253,8 +252,6 @@ struct GradValues {
 };
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-
 // the basis values a ray keeps: none for RGBA rows and for the opacity backward
 static int basis_floats(const svoxt_options* opt, int C) { return (opt->format != SVOXT_FORMAT_RGBA && C > 0) ? opt->basis_dim : 0; }
 
@@ -267,12 +264,12 @@ static int rowgrad_check(const svoxt_tree* tree, const svoxt_rays* rays, const s
     if (tree->xform != nullptr) return fail(SVOXT_ERR_INVALID, "%s: transformation_matrices (tree.xform) are not served by the deterministic backward", fn);
     if (rays->Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: too many rays (ray indices are int32)", fn);
     if (tree->M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be below 2^31", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
+    if ((rc = extent31_check(fn, T, "T"))) return rc;
     const int C = grad_cols - 1;
     if (C < 0) return fail(SVOXT_ERR_INVALID, "%s: grad_cols must be >= 1", fn);
     if (C > 0 && svoxt_out_data_dim(opt, tree->K) != grad_cols)
         return fail(SVOXT_ERR_INVALID, "%s: grad_out columns do not match get_out_data_dim (C + 1)", fn);
-    if ((double)T * (C + 1) >= 274877906944.0 || (double)tree->M * tree->K >= 274877906944.0)
+    if (!elems_fit((double)T, C + 1) || !elems_fit((double)tree->M, tree->K))
         return fail(SVOXT_ERR_INVALID, "%s: T * (C + 1) and M * K must be below 2^38", fn);
     if (rays->Q > 0 && (offsets == nullptr || grad_out == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: offsets / grad_out is NULL", fn);
     if (misaligned(offsets, 8) || misaligned(grad_out, 4)) return fail(SVOXT_ERR_INVALID, "%s: offsets (8 bytes) / grad_out (4 bytes) is misaligned", fn);
@@ -292,9 +289,9 @@ using namespace svoxt;
 extern "C" {
 
 int64_t svoxt_render_grad_rows_workspace_bytes(int64_t Q, int64_t T, int64_t M, int32_t K, int32_t C, int32_t basis_dim) {
-    if (Q < 0 || Q > 0x7fffffffLL || T < 0 || T > 0x7fffffffLL || M < 0 || M > 0x7fffffffLL) return -1;
+    if (!in31(Q) || !in31(T) || !in31(M)) return -1;
     if (K < 1 || C < 0 || C >= K || basis_dim < 0 || basis_dim > 25) return -1;
-    if ((double)T * (C + 1) >= 274877906944.0 || (double)M * K >= 274877906944.0) return -1;
+    if (!elems_fit((double)T, C + 1) || !elems_fit((double)M, K)) return -1;
     if (T == 0) return 0;
     return (int64_t)rowgrad_carve(nullptr, Q, T, M, K, C, basis_dim).bytes;
 }
@@ -337,11 +334,7 @@ int svoxt_render_grad_rows_plan(const svoxt_tree* tree, const svoxt_rays* rays, 
     int rc;
     if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, T > 0, fn))) return rc;
     if (info == nullptr || misaligned(info, 8)) return fail(SVOXT_ERR_INVALID, "%s: info is NULL or not 8-byte aligned", fn);
-    if (T == 0) {
-        const hipError_t e = hipMemsetAsync(info, 0, sizeof(int64_t) * 4, (hipStream_t)stream);
-        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-        return SVOXT_OK;
-    }
+    if (T == 0) return memset_async(info, sizeof(int64_t) * 4, (hipStream_t)stream, fn);
     const int C = grad_cols - 1;
     const RowGradSpace sp = rowgrad_carve(workspace, rays->Q, T, tree->M, tree->K, C, basis_floats(opt, C));
     return svoxt_row_plan_build(sp.row, T, tree->M, sp.row_ptr, sp.perm, info, sp.plan, sp.plan_bytes, stream);
@@ -382,11 +375,8 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
     const int K = tree->K;
     const int gs = grad_stride > 0 ? grad_stride : K;
     if (gs < K) return fail(SVOXT_ERR_INVALID, "%s: grad_stride smaller than data_dim", fn);
-    if ((double)M * gs >= 274877906944.0) return fail(SVOXT_ERR_INVALID, "%s: M * grad_stride must be below 2^38", fn);
-    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
-        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
-    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
-        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    if (!elems_fit((double)M, gs)) return fail(SVOXT_ERR_INVALID, "%s: M * grad_stride must be below 2^38", fn);
+    if ((rc = row_plan_check(fn, RowPlanRef{nullptr, nullptr, nullptr, nullptr, nullptr, T, M, n_long, n_chunks}))) return rc;   // (its counts)
     if (M == 0) return SVOXT_OK;
     if (grad == nullptr || misaligned(grad, 4)) return fail(SVOXT_ERR_INVALID, "%s: grad is NULL or not 4-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
@@ -403,8 +393,8 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
     const GradValues src{sp.ray, sp.wgt, sp.sigc, sp.chan, sp.basis, grad_out, T, rays->Q, K, C, bd, opt->min_comp, opt->max_comp,
                          opt->format == SVOXT_FORMAT_RGBA};
     // a lane per (row, column) over all K columns; the row stride stands where reduce_rows has its table's width
-    rows_launch<ROWS_SUM, ROWS_SUM>(src, T, K, sp.row_ptr, sp.perm, M, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long, n_long, n_chunks,
-                                    nullptr, gs, 0.f, grad, sp.partials, st);
+    const RowPlanRef plan{sp.row_ptr, sp.perm, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long, T, M, n_long, n_chunks};
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, K, plan, nullptr, gs, 0.f, grad, sp.partials, st);
     return check_launch(fn);
 }
 

@@ -22,7 +22,6 @@
 #include <stdint.h>
 
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
 #include "svoxt_rowwalk.h"
 #include "svoxt_sort.h"
 #include "svoxt_wave.h"
@@ -162,18 +161,9 @@ gather_rows4_kernel(const float4* __restrict__ table, int64_t M, int K4, const i
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-
 static int rows_extents_check(int64_t T, int64_t M, const char* fn) {
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    if (M < 0 || M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be in [0, 2^31)", fn);
-    return SVOXT_OK;
-}
-
-static int memset_async(void* p, size_t bytes, hipStream_t st, const char* fn) {
-    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-    return SVOXT_OK;
+    const int rc = extent31_check(fn, T, "T");
+    return rc ? rc : extent31_check(fn, M, "M");
 }
 
 }  // namespace svoxt
@@ -183,7 +173,7 @@ using namespace svoxt;
 extern "C" {
 
 int64_t svoxt_row_plan_workspace_bytes(int64_t T, int64_t M) {
-    if (T < 0 || T > 0x7fffffffLL || M < 0 || M > 0x7fffffffLL) return -1;
+    if (!in31(T) || !in31(M)) return -1;
     if (T == 0) return 0;
     return (int64_t)row_plan_carve(nullptr, T, M).bytes;
 }
@@ -236,15 +226,12 @@ int svoxt_row_plan_long(const int32_t* row_ptr, int64_t T, int64_t M, int64_t n_
                         int64_t workspace_bytes, int32_t* long_rows, int32_t* long_chunk_ptr, int32_t* chunk_long, void* stream) {
     const char* fn = "svoxt_row_plan_long";
     int rc;
-    if ((rc = rows_extents_check(T, M, fn))) return rc;
-    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
-        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
-    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
-        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    const RowPlanRef plan{row_ptr, nullptr, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};   // (the arrays to write)
+    if ((rc = rows_extents_check(T, M, fn)) || (rc = row_plan_check(fn, plan))) return rc;
     if (long_chunk_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: long_chunk_ptr is NULL", fn);
     if (n_long > 0 && (row_ptr == nullptr || long_rows == nullptr || chunk_long == nullptr))
         return fail(SVOXT_ERR_INVALID, "%s: row_ptr / long_rows / chunk_long is NULL", fn);
-    if (misaligned(row_ptr, 4) || misaligned(long_rows, 4) || misaligned(long_chunk_ptr, 4) || misaligned(chunk_long, 4))
+    if (row_plan_misaligned(plan))
         return fail(SVOXT_ERR_INVALID, "%s: row_ptr / long_rows / long_chunk_ptr / chunk_long is not 4-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     if (n_long == 0) return memset_async(long_chunk_ptr, sizeof(int32_t), st, fn);
@@ -266,10 +253,9 @@ int svoxt_gather_rows(const float* table, int64_t M, int32_t K, const int32_t* r
     int rc;
     if ((rc = rows_extents_check(T, M, fn))) return rc;
     if (K < 1) return fail(SVOXT_ERR_INVALID, "%s: K must be >= 1", fn);
-    if ((cols == nullptr) != (n_cols == 0) || n_cols < 0 || n_cols > K)
-        return fail(SVOXT_ERR_INVALID, "%s: cols / n_cols must be NULL / 0 (all columns) or n_cols in [1, K] distinct columns", fn);
+    if ((rc = cols_check(fn, cols, n_cols, K))) return rc;
     const int Kc = cols != nullptr ? n_cols : K;
-    if ((double)T * Kc >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!elems_fit((double)T, Kc) || !elems_fit((double)M, K))
         return fail(SVOXT_ERR_INVALID, "%s: T * columns and M * K must be below 2^38", fn);
     if (T == 0) return SVOXT_OK;
     if (row == nullptr || out == nullptr) return fail(SVOXT_ERR_INVALID, "%s: row / out is NULL", fn);
@@ -288,7 +274,7 @@ int svoxt_gather_rows(const float* table, int64_t M, int32_t K, const int32_t* r
 }
 
 int64_t svoxt_reduce_rows_workspace_bytes(int64_t n_chunks, int32_t C) {
-    if (n_chunks < 0 || n_chunks > 0x7fffffffLL || C < 1 || (double)n_chunks * C >= 274877906944.0) return -1;
+    if (!in31(n_chunks) || C < 1 || !elems_fit((double)n_chunks, C)) return -1;
     if (n_chunks == 0) return 0;
     return (int64_t)align256(sizeof(float) * (size_t)n_chunks * (size_t)C);
 }
@@ -299,27 +285,22 @@ int svoxt_reduce_rows(const float* values, int64_t T, int32_t C, const int32_t* 
                       int64_t workspace_bytes, void* stream) {
     const char* fn = "svoxt_reduce_rows";
     int rc;
+    const RowPlanRef plan{row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};
     if ((rc = rows_extents_check(T, M, fn))) return rc;
     if (C < 1 || K < 1) return fail(SVOXT_ERR_INVALID, "%s: C and K must be >= 1", fn);
-    if ((cols == nullptr) != (n_cols == 0) || n_cols < 0 || n_cols > K)
-        return fail(SVOXT_ERR_INVALID, "%s: cols / n_cols must be NULL / 0 (all columns) or n_cols in [1, K] distinct columns", fn);
+    if ((rc = cols_check(fn, cols, n_cols, K))) return rc;
     if (C != (cols != nullptr ? n_cols : K))
         return fail(SVOXT_ERR_INVALID, "%s: values must have one column per selected column (C = n_cols, or C = K without cols)", fn);
     if (op != ROWS_SUM && op != ROWS_MEAN && op != ROWS_MAX && op != ROWS_MIN)
         return fail(SVOXT_ERR_INVALID, "%s: op must be one of SVOXT_ROWS_SUM / MEAN / MAX / MIN", fn);
-    if ((double)T * C >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!elems_fit((double)T, C) || !elems_fit((double)M, K))
         return fail(SVOXT_ERR_INVALID, "%s: T * C and M * K must be below 2^38", fn);
-    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
-        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
-    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
-        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    if ((rc = row_plan_check(fn, plan))) return rc;
     if (M == 0) return SVOXT_OK;
     if (out == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: out / row_ptr is NULL", fn);
     if (T > 0 && (values == nullptr || perm == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: values / perm is NULL", fn);
-    if (n_long > 0 && (long_rows == nullptr || long_chunk_ptr == nullptr || chunk_long == nullptr))
-        return fail(SVOXT_ERR_INVALID, "%s: long_rows / long_chunk_ptr / chunk_long is NULL", fn);
-    if (misaligned(values, 4) || misaligned(row_ptr, 4) || misaligned(perm, 4) || misaligned(long_rows, 4) || misaligned(long_chunk_ptr, 4) ||
-        misaligned(chunk_long, 4) || misaligned(cols, 4) || misaligned(out, 4) || misaligned(workspace, 4))
+    if ((rc = row_plan_long_check(fn, plan))) return rc;
+    if (misaligned(values, 4) || row_plan_misaligned(plan) || misaligned(cols, 4) || misaligned(out, 4) || misaligned(workspace, 4))
         return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
     if (n_long > 0 &&
         (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_reduce_rows_workspace_bytes(n_chunks, C), "svoxt_reduce_rows_workspace_bytes(n_chunks, C)")))
@@ -330,8 +311,7 @@ int svoxt_reduce_rows(const float* values, int64_t T, int32_t C, const int32_t* 
     const bool ok = with_int(IntSet<ROWS_SUM, ROWS_MEAN, ROWS_MAX, ROWS_MIN>{}, op, [&](auto OP) {
         // the partials of a mean are the sum's; the division is the join's (and the short rows')
         constexpr int PART = OP.value == ROWS_MEAN ? (int)ROWS_SUM : OP.value;
-        rows_launch<OP.value, PART>(TableValues{values, T, (int)C}, T, (int)C, row_ptr, perm, M, long_rows, long_chunk_ptr, chunk_long, n_long,
-                                    n_chunks, cols, (int)K, empty, out, partials, st);
+        rows_launch<OP.value, PART>(TableValues{values, T, (int)C}, (int)C, plan, cols, (int)K, empty, out, partials, st);
         return true;
     });
     if (!ok) return fail(SVOXT_ERR_INVALID, "%s: op must be one of SVOXT_ROWS_SUM / MEAN / MAX / MIN", fn);

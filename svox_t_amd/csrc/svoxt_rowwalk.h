@@ -9,6 +9,8 @@
 //                       SVOXT_ROW_CHUNK samples, and writes `empty` for rows without one;
 //   rows_chunk_kernel   a lane per (chunk, column) of the long rows leaves the chunk's partial in the workspace;
 //   rows_join_kernel    a lane per (long row, column) joins the partials in chunk order.
+// On the host: RowPlanRef, a caller's plan as one value, the checks every entry point over a plan makes
+// of it (row_plan_check, row_plan_long_check, row_plan_misaligned, cols_check), and rows_launch.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -135,19 +137,50 @@ rows_join_kernel(const float* __restrict__ partials, int C, const int32_t* __res
     out[r * K + c] = acc;
 }
 
+// A caller's row plan as one host-side value: what svoxt_row_plan_build / _long wrote for T samples (or entries) and M
+// rows.  The entry points build it from their arguments; the kernels take its pointers one by one (rows_launch), as
+// __restrict__ parameters.
+struct RowPlanRef {
+    const int32_t *row_ptr, *perm, *long_rows, *long_chunk_ptr, *chunk_long;
+    int64_t T, M, n_long, n_chunks;
+};
+// The counts of the long rows against T and M; `t_name` is what the caller's text calls T ("8 Q" for a stencil's entries).
+inline int row_plan_check(const char* fn, const RowPlanRef& p, const char* t_name = "T") {
+    if (p.n_long < 0 || p.n_long > p.M || p.n_long > p.T / (kRowChunk + 1))
+        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, %s / (SVOXT_ROW_CHUNK + 1))]", fn, t_name);
+    if (p.n_chunks < 2 * p.n_long || p.n_chunks > p.T / kRowChunk + p.n_long)
+        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, %s / SVOXT_ROW_CHUNK + n_long]", fn, t_name);
+    return SVOXT_OK;
+}
+// the long rows' arrays of a plan that is read: there where there are long rows
+inline int row_plan_long_check(const char* fn, const RowPlanRef& p) {
+    if (p.n_long > 0 && (p.long_rows == nullptr || p.long_chunk_ptr == nullptr || p.chunk_long == nullptr))
+        return fail(SVOXT_ERR_INVALID, "%s: long_rows / long_chunk_ptr / chunk_long is NULL", fn);
+    return SVOXT_OK;
+}
+inline bool row_plan_misaligned(const RowPlanRef& p) {
+    return misaligned(p.row_ptr, 4) || misaligned(p.perm, 4) || misaligned(p.long_rows, 4) || misaligned(p.long_chunk_ptr, 4) ||
+           misaligned(p.chunk_long, 4);
+}
+// a column selection over a table of K columns: none (NULL / 0), or n_cols of them
+inline int cols_check(const char* fn, const int32_t* cols, int32_t n_cols, int32_t K) {
+    if ((cols == nullptr) != (n_cols == 0) || n_cols < 0 || n_cols > K)
+        return fail(SVOXT_ERR_INVALID, "%s: cols / n_cols must be NULL / 0 (all columns) or n_cols in [1, K] distinct columns", fn);
+    return SVOXT_OK;
+}
+
 // The three launches over a plan on `st`: the short rows, and with long rows their chunks and the join.  PART is the
 // op of the chunk partials (a mean's are the sum's; the division is the join's and the short rows').
 template <int OP, int PART, class V>
-inline void rows_launch(const V& src, int64_t T, int C, const int32_t* row_ptr, const int32_t* perm, int64_t M, const int32_t* long_rows,
-                        const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks, const int32_t* cols,
-                        int K, float empty, float* out, float* partials, hipStream_t st) {
-    hipLaunchKernelGGL((rows_short_kernel<OP, V>), dim3(launch_blocks(M * C)), dim3(kLaunchBlock), 0, st, src, T, C, row_ptr, perm, M, cols, K,
-                       empty, out);
-    if (n_long > 0) {
-        hipLaunchKernelGGL((rows_chunk_kernel<PART, V>), dim3(launch_blocks(n_chunks * C)), dim3(kLaunchBlock), 0, st, src, T, C, row_ptr, perm,
-                           M, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks, partials);
-        hipLaunchKernelGGL((rows_join_kernel<OP>), dim3(launch_blocks(n_long * C)), dim3(kLaunchBlock), 0, st, partials, C, row_ptr, M,
-                           long_rows, long_chunk_ptr, n_long, n_chunks, cols, K, out);
+inline void rows_launch(const V& src, int C, const RowPlanRef& p, const int32_t* cols, int K, float empty, float* out, float* partials,
+                        hipStream_t st) {
+    hipLaunchKernelGGL((rows_short_kernel<OP, V>), dim3(launch_blocks(p.M * C)), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr, p.perm, p.M,
+                       cols, K, empty, out);
+    if (p.n_long > 0) {
+        hipLaunchKernelGGL((rows_chunk_kernel<PART, V>), dim3(launch_blocks(p.n_chunks * C)), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr,
+                           p.perm, p.M, p.long_rows, p.long_chunk_ptr, p.chunk_long, p.n_long, p.n_chunks, partials);
+        hipLaunchKernelGGL((rows_join_kernel<OP>), dim3(launch_blocks(p.n_long * C)), dim3(kLaunchBlock), 0, st, partials, C, p.row_ptr, p.M,
+                           p.long_rows, p.long_chunk_ptr, p.n_long, p.n_chunks, cols, K, out);
     }
 }
 

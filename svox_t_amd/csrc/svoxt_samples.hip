@@ -4,8 +4,8 @@
 //   ray_samples      count -> scan -> emit.  Both kernels take the shared walk (setup_ray, then walk_samples / walk_crossings
 //                    of svoxt_device.h), one lane per ray by ray_of_thread, through one adapter (ray_samples below).  The count
 //                    kernel writes counts[q] at the ray's own index and adds each wavefront's count to one 64-bit total;
-//                    exclusive_scan (svoxt_host.h) turns the counts into starts, widened to int64 offsets[Q + 1] with the
-//                    64-bit total at offsets[Q].  The emit kernel marches again and writes (row, ray, depth, length) at
+//                    the per-ray tail of svoxt_listemit.h scans the counts into starts and widens them to int64
+//                    offsets[Q + 1] with the 64-bit total at offsets[Q].  The emit kernel marches again and writes (row, ray, depth, length) at
 //                    offsets[q] + k, never at or behind offsets[q + 1]: the lists are in ray-index order whatever the lane
 //                    assignment was.  No float sum anywhere: bit-identical from run to run.
 //                        depth = delta_scale * t         (the `entry` z of the depth moments, this operand order)
@@ -24,31 +24,13 @@
 
 #include "svoxt_device.h"
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
+#include "svoxt_listemit.h"
 #include "svoxt_wave.h"
 #include "svoxt_workspace.h"
 
 #pragma clang fp contract(off)
 
 namespace svoxt {
-
-// workspace of svoxt_ray_samples_count: [total u64] [counts u32[Q]] [starts u32[Q]] [chunk sums]; the total is cleared
-struct SamplesSpace {
-    unsigned long long* total;
-    uint32_t *counts, *starts, *chunks;
-    size_t clear_bytes, bytes;
-};
-static SamplesSpace samples_carve(void* workspace, int64_t Q) {
-    SamplesSpace sp;
-    Carver w(workspace);
-    sp.total = w.take<unsigned long long>(1);
-    sp.clear_bytes = w.bytes();
-    sp.counts = w.take<uint32_t>((size_t)Q);
-    sp.starts = w.take<uint32_t>((size_t)Q);
-    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)Q));
-    sp.bytes = w.bytes();
-    return sp;
-}
 
 // The samples of ray q in march order: f(row, depth, length) per sample of the shared walk (svoxt_device.h); without
 // FILTER per crossing whose data word names a feature row -- the crossing layer: sigma is not read.
@@ -72,16 +54,7 @@ samples_count_kernel(TreeDev tr, RaysDev rays, Opts opt, float min_sigma, uint32
         ray_samples<N2, FILTER>(tr, rays, opt, min_sigma, q, [&](int32_t, float, float) { ++n; });
         counts[q] = n;
     }
-    const uint32_t sum = wave_all_sum(n);                        // (a wavefront's 64 counts: far below 2^32)
-    if ((threadIdx.x & 63) == 0 && sum != 0u) atomicAdd(total, (unsigned long long)sum);
-}
-
-__global__ void __launch_bounds__(kLaunchBlock)
-samples_offsets_kernel(const uint32_t* __restrict__ starts, const unsigned long long* __restrict__ total, int64_t Q,
-                       int64_t* __restrict__ offsets) {
-    const int64_t i = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    if (i < Q) offsets[i] = (int64_t)starts[i];
-    else if (i == Q) offsets[Q] = (int64_t)total[0];
+    wave_add_to_total(n, total);                                 // (a wavefront's 64 counts: far below 2^32)
 }
 
 template <bool N2, bool FILTER>
@@ -204,8 +177,6 @@ sample_accumulate_bwd_kernel(const int32_t* __restrict__ ray, int64_t Q, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-
 static int ray_samples_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
                              const int64_t* offsets, const char* fn) {
     int rc;
@@ -219,9 +190,8 @@ static int ray_samples_check(const svoxt_tree* tree, const svoxt_rays* rays, con
 
 // the CSR arguments of the four per-sample entry points: Q rays, T samples, both below 2^31
 static int csr_check(int64_t Q, int64_t T, const char* fn) {
-    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    return SVOXT_OK;
+    const int rc = extent31_check(fn, Q, "Q");
+    return rc ? rc : extent31_check(fn, T, "T");
 }
 
 }  // namespace svoxt
@@ -231,9 +201,7 @@ using namespace svoxt;
 extern "C" {
 
 int64_t svoxt_ray_samples_workspace_bytes(int64_t Q) {
-    if (Q < 0 || Q > 0x7fffffffLL) return -1;
-    if (Q == 0) return 0;
-    return (int64_t)samples_carve(nullptr, Q).bytes;
+    return list_space_bytes(Q, 0, true);
 }
 
 int svoxt_ray_samples_count(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
@@ -243,17 +211,14 @@ int svoxt_ray_samples_count(const svoxt_tree* tree, const svoxt_rays* rays, cons
     if ((rc = ray_samples_check(tree, rays, opt, min_sigma, offsets, fn))) return rc;
     const int64_t Q = rays->Q;
     if (Q == 0) return SVOXT_OK;
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_ray_samples_workspace_bytes(Q), "svoxt_ray_samples_workspace_bytes(Q)")))
-        return rc;
-    const SamplesSpace sp = samples_carve(workspace, Q);
+    ListSpace sp;
+    if ((rc = list_space_check(fn, workspace, workspace_bytes, (size_t)Q, true, "svoxt_ray_samples_workspace_bytes(Q)", &sp))) return rc;
     const TreeDev tr = to_dev(tree);
     const RaysDev rd = to_dev(rays, tree);
     const Opts od = to_dev(opt);
     const float ms = min_sigma != nullptr ? *min_sigma : 0.f;
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(workspace, 0, sp.clear_bytes, st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+    if ((rc = memset_async(workspace, sp.clear_bytes, st, fn))) return rc;
     with_bool(tree->N == 2, [&](auto N2) {
         return with_bool(min_sigma != nullptr, [&](auto FILTER) {
             hipLaunchKernelGGL((samples_count_kernel<N2.value, FILTER.value>), dim3(nblocks(Q)), dim3(kBlock), 0, st, tr, rd, od, ms,
@@ -261,9 +226,7 @@ int svoxt_ray_samples_count(const svoxt_tree* tree, const svoxt_rays* rays, cons
             return true;
         });
     });
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.counts, (size_t)Q, sp.chunks, sp.starts, st, fn))) return rc;
-    hipLaunchKernelGGL(samples_offsets_kernel, dim3(launch_blocks(Q + 1)), dim3(kLaunchBlock), 0, st, sp.starts, sp.total, Q, offsets);
-    return check_launch(fn);
+    return list_ray_offsets<false>(fn, sp, Q, offsets, nullptr, st);     // (the caller reads the total at offsets[Q])
 }
 
 int svoxt_ray_samples_emit(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
@@ -328,7 +291,7 @@ int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, co
     const char* fn = "svoxt_sample_accumulate_fwd";
     int rc;
     if ((rc = csr_check(Q, T, fn))) return rc;
-    if (C < 1 || (double)Q * C >= 274877906944.0 || (double)T * C >= 274877906944.0)
+    if (C < 1 || !elems_fit((double)Q, C) || !elems_fit((double)T, C))
         return fail(SVOXT_ERR_INVALID, "%s: C must be >= 1 with Q * C and T * C below 2^38", fn);
     if (values == nullptr && C != 1 && T > 0) return fail(SVOXT_ERR_INVALID, "%s: values is NULL: C must be 1 (the plain sum of w)", fn);
     if (Q == 0) return SVOXT_OK;
@@ -346,7 +309,7 @@ int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const 
     const char* fn = "svoxt_sample_accumulate_bwd";
     int rc;
     if ((rc = csr_check(Q, T, fn))) return rc;
-    if (C < 1 || (double)Q * C >= 274877906944.0 || (double)T * C >= 274877906944.0)
+    if (C < 1 || !elems_fit((double)Q, C) || !elems_fit((double)T, C))
         return fail(SVOXT_ERR_INVALID, "%s: C must be >= 1 with Q * C and T * C below 2^38", fn);
     if (values == nullptr && T > 0 && (C != 1 || grad_values != nullptr))
         return fail(SVOXT_ERR_INVALID, "%s: values is NULL: C must be 1 and grad_values NULL", fn);

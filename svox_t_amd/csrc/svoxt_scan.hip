@@ -17,14 +17,14 @@
 //                                that wrote the identity sends its g nowhere)
 //   ray_quantile   a lane per (ray, quantile): c += w over the samples with w > 0; the first of them with c >= target,
 //                  and where inside it the target lies
-//   select         flag -> scan -> emit (svoxt_workspace.h): pos = exclusive scan of keep over T + 1 entries;
+//   select         flag -> scan -> emit (svoxt_listemit.h, the per-sample shape without a 64-bit total): pos = exclusive scan of keep over T + 1 entries;
 //                  offsets'[q] = pos[clamped offsets[q]], T' = pos[T]; a lane per sample copies the kept samples to pos[k]
 // C ABI: svoxt_ray_scan_* / svoxt_ray_quantile / svoxt_samples_select_* (include/svoxt.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
+#include "svoxt_listemit.h"
 #include "svoxt_workspace.h"
 
 #pragma clang fp contract(off)
@@ -166,33 +166,13 @@ ray_quantile_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, c
 }
 
 // ------------------------------------------------------------------------------------------------------------- select
-// workspace of svoxt_samples_select_count, read again by _emit: [flag u32[T + 1]] [pos u32[T + 1]] [chunk sums]
-struct SelectSpace {
-    uint32_t *flag, *pos, *chunks;
-    size_t bytes;
-};
-static SelectSpace select_carve(void* workspace, int64_t T) {
-    SelectSpace sp;
-    Carver w(workspace);
-    sp.flag = w.take<uint32_t>((size_t)T + 1);
-    sp.pos = w.take<uint32_t>((size_t)T + 1);
-    sp.chunks = w.take<uint32_t>(exclusive_scan_chunks((size_t)T + 1));
-    sp.bytes = w.bytes();
-    return sp;
-}
+// workspace of svoxt_samples_select_count, read again by _emit: the per-sample ListSpace (svoxt_listemit.h) without a
+// total (T' <= T), counts = flag, starts = pos
 
 __global__ void __launch_bounds__(kLaunchBlock)
 select_flag_kernel(const uint8_t* __restrict__ keep, int64_t T, uint32_t* __restrict__ flag) {
     const int64_t k = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
     if (k <= T) flag[k] = (k < T && keep[k] != 0) ? 1u : 0u;
-}
-
-__global__ void __launch_bounds__(kLaunchBlock)
-select_offsets_kernel(const uint32_t* __restrict__ pos, const int64_t* __restrict__ offsets, int64_t Q, int64_t T,
-                      int64_t* __restrict__ offsets_out, int64_t* __restrict__ total) {
-    const int64_t i = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
-    if (i <= Q) offsets_out[i] = (int64_t)pos[min(max(offsets[i], (int64_t)0), T)];
-    if (i == 0) total[0] = (int64_t)pos[T];
 }
 
 __global__ void __launch_bounds__(kLaunchBlock)
@@ -212,17 +192,10 @@ select_emit_kernel(const uint8_t* __restrict__ keep, const uint32_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-static bool overlap(const void* a, const void* b, double bytes) {
-    if (a == nullptr || b == nullptr) return false;
-    const double x = (double)(uintptr_t)a, y = (double)(uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
 static int scan_check(int64_t Q, int64_t T, int32_t C, int32_t op, int32_t flags, const char* fn) {
-    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    if (C < 1 || (double)Q * C >= 274877906944.0 || (double)T * C >= 274877906944.0)
+    int rc;
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T, "T"))) return rc;
+    if (C < 1 || !elems_fit((double)Q, C) || !elems_fit((double)T, C))
         return fail(SVOXT_ERR_INVALID, "%s: C must be >= 1 with Q * C and T * C below 2^38", fn);
     if (op < SVOXT_SCAN_SUM || op > SVOXT_SCAN_MIN) return fail(SVOXT_ERR_INVALID, "%s: op must be SVOXT_SCAN_SUM / PROD / MAX / MIN (0 .. 3)", fn);
     if ((flags & ~(SVOXT_SCAN_EXCLUSIVE | SVOXT_SCAN_REVERSE)) != 0)
@@ -280,8 +253,7 @@ int svoxt_ray_scan_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float
     const bool ex = (flags & SVOXT_SCAN_EXCLUSIVE) != 0, rev = (flags & SVOXT_SCAN_REVERSE) != 0;
     hipStream_t st = (hipStream_t)stream;
     // one entry per sample: samples outside every segment get 0
-    const hipError_t e = hipMemsetAsync(grad_values, 0, (size_t)T * (size_t)C * sizeof(float), st);
-    if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+    if ((rc = memset_async(grad_values, (size_t)T * (size_t)C * sizeof(float), st, fn))) return rc;
     if (Q == 0) return SVOXT_OK;
     const dim3 grid(launch_blocks(Q * C)), block(kLaunchBlock);
     if (op == SVOXT_SCAN_SUM) launch_scan_fwd<SVOXT_SCAN_SUM>(offsets, Q, T, grad_out, (int)C, ex, !rev, grad_values, st);
@@ -297,9 +269,9 @@ int svoxt_ray_scan_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float
 int svoxt_ray_quantile(const int64_t* offsets, int64_t Q, int64_t T, const float* w, const float* q, int32_t nq, int32_t normalize,
                        int64_t* index, float* frac, void* stream) {
     const char* fn = "svoxt_ray_quantile";
-    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    if (nq < 1 || (double)Q * nq >= 274877906944.0) return fail(SVOXT_ERR_INVALID, "%s: nq must be >= 1 with Q * nq below 2^38", fn);
+    int rc;
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T, "T"))) return rc;
+    if (nq < 1 || !elems_fit((double)Q, nq)) return fail(SVOXT_ERR_INVALID, "%s: nq must be >= 1 with Q * nq below 2^38", fn);
     if (Q == 0) return SVOXT_OK;
     if (offsets == nullptr || q == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets / q is NULL", fn);
     if (index == nullptr || frac == nullptr) return fail(SVOXT_ERR_INVALID, "%s: index / frac is NULL", fn);
@@ -312,37 +284,23 @@ int svoxt_ray_quantile(const int64_t* offsets, int64_t Q, int64_t T, const float
 }
 
 int64_t svoxt_samples_select_workspace_bytes(int64_t T) {
-    if (T < 0 || T > 0x7fffffffLL) return -1;
-    if (T == 0) return 0;
-    return (int64_t)select_carve(nullptr, T).bytes;
+    return list_space_bytes(T, 1, false);
 }
 
 int svoxt_samples_select_count(const uint8_t* keep, const int64_t* offsets, int64_t Q, int64_t T, int64_t* offsets_out, int64_t* total,
                                void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "svoxt_samples_select_count";
     int rc;
-    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    if (offsets_out == nullptr || total == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is NULL", fn);
-    if (misaligned(offsets_out, 8) || misaligned(total, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets_out / total is not 8-byte aligned", fn);
+    if ((rc = extent31_check(fn, Q, "Q")) || (rc = extent31_check(fn, T, "T")) || (rc = counts_out_check(fn, offsets_out, total))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (T == 0) {                                                // nothing to keep: empty lists
-        hipError_t e = hipMemsetAsync(offsets_out, 0, (size_t)(Q + 1) * sizeof(int64_t), st);
-        if (e == hipSuccess) e = hipMemsetAsync(total, 0, sizeof(int64_t), st);
-        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-        return SVOXT_OK;
-    }
+    if (T == 0) return clear_counts(fn, offsets_out, Q, total, st);          // nothing to keep: empty lists
     if (keep == nullptr || offsets == nullptr) return fail(SVOXT_ERR_INVALID, "%s: keep / offsets is NULL", fn);
     if (misaligned(offsets, 8)) return fail(SVOXT_ERR_INVALID, "%s: offsets is not 8-byte aligned", fn);
     if (overlap(offsets, offsets_out, 8.0 * (double)(Q + 1))) return fail(SVOXT_ERR_INVALID, "%s: offsets_out overlaps offsets", fn);
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_samples_select_workspace_bytes(T), "svoxt_samples_select_workspace_bytes(T)")))
-        return rc;
-    const SelectSpace sp = select_carve(workspace, T);
-    hipLaunchKernelGGL(select_flag_kernel, dim3(launch_blocks(T + 1)), dim3(kLaunchBlock), 0, st, keep, T, sp.flag);
-    if ((rc = check_launch(fn)) || (rc = exclusive_scan(sp.flag, (size_t)T + 1, sp.chunks, sp.pos, st, fn))) return rc;
-    hipLaunchKernelGGL(select_offsets_kernel, dim3(launch_blocks(Q + 1)), dim3(kLaunchBlock), 0, st, sp.pos, offsets, Q, T, offsets_out, total);
-    return check_launch(fn);
+    ListSpace sp;
+    if ((rc = list_space_check(fn, workspace, workspace_bytes, (size_t)T + 1, false, "svoxt_samples_select_workspace_bytes(T)", &sp))) return rc;
+    hipLaunchKernelGGL(select_flag_kernel, dim3(launch_blocks(T + 1)), dim3(kLaunchBlock), 0, st, keep, T, sp.counts);
+    return list_pos_offsets<false>(fn, sp, offsets, Q, T, offsets_out, total, st);    // (T' = pos[T])
 }
 
 int svoxt_samples_select_emit(const uint8_t* keep, int64_t T, const void* workspace, int64_t workspace_bytes, const int32_t* ray,
@@ -350,22 +308,15 @@ int svoxt_samples_select_emit(const uint8_t* keep, int64_t T, const void* worksp
                               int32_t* row_out, float* depth_out, float* length_out, int64_t* index, void* stream) {
     const char* fn = "svoxt_samples_select_emit";
     int rc;
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
+    if ((rc = extent31_check(fn, T, "T"))) return rc;
     if (T_out < 0 || T_out > T) return fail(SVOXT_ERR_INVALID, "%s: T_out must be in [0, T]", fn);
     if (T_out == 0) return SVOXT_OK;
     if (keep == nullptr) return fail(SVOXT_ERR_INVALID, "%s: keep is NULL", fn);
-    if (ray == nullptr || row == nullptr || depth == nullptr || length == nullptr)
-        return fail(SVOXT_ERR_INVALID, "%s: ray / row / depth / length is NULL", fn);
-    if (ray_out == nullptr || row_out == nullptr || depth_out == nullptr || length_out == nullptr || index == nullptr)
-        return fail(SVOXT_ERR_INVALID, "%s: an output is NULL", fn);
-    if (misaligned(ray, 4) || misaligned(row, 4) || misaligned(depth, 4) || misaligned(length, 4) || misaligned(ray_out, 4) ||
-        misaligned(row_out, 4) || misaligned(depth_out, 4) || misaligned(length_out, 4) || misaligned(index, 8))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (index: 8 bytes, the other arrays: 4)", fn);
-    if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
-    if ((rc = workspace_check(fn, workspace, workspace_bytes, svoxt_samples_select_workspace_bytes(T), "svoxt_samples_select_workspace_bytes(T)")))
+    ListSpace sp;
+    if ((rc = emit_arrays_check(fn, ray, row, depth, length, ray_out, row_out, depth_out, length_out, index)) ||
+        (rc = list_space_check(fn, workspace, workspace_bytes, (size_t)T + 1, false, "svoxt_samples_select_workspace_bytes(T)", &sp)))
         return rc;
-    const SelectSpace sp = select_carve(const_cast<void*>(workspace), T);
-    hipLaunchKernelGGL(select_emit_kernel, dim3(launch_blocks(T)), dim3(kLaunchBlock), 0, (hipStream_t)stream, keep, sp.pos, T, T_out, ray,
+    hipLaunchKernelGGL(select_emit_kernel, dim3(launch_blocks(T)), dim3(kLaunchBlock), 0, (hipStream_t)stream, keep, sp.starts, T, T_out, ray,
                        row, depth, length, ray_out, row_out, depth_out, length_out, index);
     return check_launch(fn);
 }

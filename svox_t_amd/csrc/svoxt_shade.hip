@@ -17,7 +17,6 @@
 
 #include "svoxt_device.h"
 #include "svoxt_host.h"
-#include "svoxt_launch.h"
 #include "svoxt_rowwalk.h"
 #include "svoxt_workspace.h"
 
@@ -154,16 +153,13 @@ struct ShadeValues {
 };
 
 // ------------------------------------------------------------------------------------------------------------- checks
-static bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-
 // C and the basis values a ray has (0 for RGBA) for a table of K columns; what both directions check first
 static int shade_dims(const svoxt_options* opt, int64_t M, int32_t K, int64_t T, int64_t Q, int* C, int* bd, const char* fn) {
     if (opt == nullptr) return fail(SVOXT_ERR_INVALID, "%s: options is NULL", fn);
     if (opt->format < SVOXT_FORMAT_RGBA || opt->format > SVOXT_FORMAT_ASG) return fail(SVOXT_ERR_INVALID, "%s: unknown data format", fn);
     if (K < 1) return fail(SVOXT_ERR_INVALID, "%s: K must be >= 1", fn);
-    if (T < 0 || T > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: T must be in [0, 2^31)", fn);
-    if (M < 0 || M > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: M must be in [0, 2^31)", fn);
-    if (Q < 0 || Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: Q must be in [0, 2^31)", fn);
+    int rc;
+    if ((rc = extent31_check(fn, T, "T")) || (rc = extent31_check(fn, M, "M")) || (rc = extent31_check(fn, Q, "Q"))) return rc;
     if (opt->format == SVOXT_FORMAT_RGBA) {
         *bd = 0;
         *C = K - 1;
@@ -174,7 +170,7 @@ static int shade_dims(const svoxt_options* opt, int64_t M, int32_t K, int64_t T,
         *bd = opt->basis_dim;
         *C = (K - 1) / opt->basis_dim;
     }
-    if ((double)T * (*C + 1) >= 274877906944.0 || (double)M * K >= 274877906944.0)
+    if (!elems_fit((double)T, *C + 1) || !elems_fit((double)M, K))
         return fail(SVOXT_ERR_INVALID, "%s: T * (C + 1) and M * K must be below 2^38", fn);
     return SVOXT_OK;
 }
@@ -226,7 +222,7 @@ int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const s
 }
 
 int64_t svoxt_shade_samples_bwd_workspace_bytes(int64_t n_chunks, int32_t K) {
-    if (n_chunks < 0 || n_chunks > 0x7fffffffLL || K < 1 || (double)n_chunks * K >= 274877906944.0) return -1;
+    if (!in31(n_chunks) || K < 1 || !elems_fit((double)n_chunks, K)) return -1;
     if (n_chunks == 0) return 0;
     Carver w(nullptr);
     w.take<float>((size_t)n_chunks * (size_t)K);
@@ -240,11 +236,8 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
                             float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* fn = "svoxt_shade_samples_bwd";
     int rc, C, bd;
-    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn))) return rc;
-    if (n_long < 0 || n_long > M || n_long > T / (kRowChunk + 1))
-        return fail(SVOXT_ERR_INVALID, "%s: n_long must be in [0, min(M, T / (SVOXT_ROW_CHUNK + 1))]", fn);
-    if (n_chunks < 2 * n_long || n_chunks > T / kRowChunk + n_long)
-        return fail(SVOXT_ERR_INVALID, "%s: n_chunks must be in [2 n_long, T / SVOXT_ROW_CHUNK + n_long]", fn);
+    const RowPlanRef plan{row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};
+    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn)) || (rc = row_plan_check(fn, plan))) return rc;
     if (M == 0) return SVOXT_OK;
     if (grad == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad / row_ptr is NULL", fn);
     if (C == 0) grad_values = nullptr;                           // (no colour column: nothing of it is read)
@@ -252,11 +245,9 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
     const bool reads_basis = grad_values != nullptr && bd > 0;
     if (T > 0 && (perm == nullptr || (reads_values && values == nullptr) || (reads_basis && (ray == nullptr || (Q > 0 && basis == nullptr)))))
         return fail(SVOXT_ERR_INVALID, "%s: perm / values / ray / basis is NULL", fn);
-    if (n_long > 0 && (long_rows == nullptr || long_chunk_ptr == nullptr || chunk_long == nullptr))
-        return fail(SVOXT_ERR_INVALID, "%s: long_rows / long_chunk_ptr / chunk_long is NULL", fn);
+    if ((rc = row_plan_long_check(fn, plan))) return rc;
     if (misaligned(ray, 4) || misaligned(basis, 4) || misaligned(values, 4) || misaligned(grad_values, 4) || misaligned(grad_sigma, 4) ||
-        misaligned(row_ptr, 4) || misaligned(perm, 4) || misaligned(long_rows, 4) || misaligned(long_chunk_ptr, 4) ||
-        misaligned(chunk_long, 4) || misaligned(grad, 4) || misaligned(workspace, 4))
+        row_plan_misaligned(plan) || misaligned(grad, 4) || misaligned(workspace, 4))
         return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
     if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K),
                                             "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)")))
@@ -265,8 +256,7 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
     float* partials = w.take<float>((size_t)n_chunks * (size_t)K);
     const ShadeValues src{ray, values, basis, grad_values, grad_sigma, T, Q, (int)K, C, bd, (int)opt->min_comp, (int)opt->max_comp, activate != 0};
     // a lane per (row, column) over all K columns: every element of grad is written
-    rows_launch<ROWS_SUM, ROWS_SUM>(src, T, (int)K, row_ptr, perm, M, long_rows, long_chunk_ptr, chunk_long, n_long, n_chunks, nullptr, (int)K,
-                                    0.f, grad, partials, (hipStream_t)stream);
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, (int)K, plan, nullptr, (int)K, 0.f, grad, partials, (hipStream_t)stream);
     return check_launch(fn);
 }
 

@@ -35,6 +35,14 @@ __device__ __forceinline__ V wave_group_sum(V v) {
     return v;
 }
 
+// The tail of a count kernel (svoxt_listemit.h), called by every lane of the wavefront: its lanes' counts summed, and
+// one atomic from lane 0 onto the 64-bit total where the sum is not zero (integers: the same total in every run).
+template <typename V>
+__device__ __forceinline__ void wave_add_to_total(V n, unsigned long long* __restrict__ total) {
+    const V sum = wave_all_sum(n);
+    if ((threadIdx.x & 63) == 0 && sum != (V)0) atomicAdd(total, (unsigned long long)sum);
+}
+
 // ---- reductions, result in LANE 0 only (__shfl_down, 32 down to 1; the other lanes end with partial results)
 template <typename V, typename Op>
 __device__ __forceinline__ V wave_to0(V v, Op op) {

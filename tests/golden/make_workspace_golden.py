@@ -1,5 +1,5 @@
-"""Regenerate tests/golden/workspace_bytes.json: what the *_workspace_bytes queries of the tree operators answer, recorded
-from the library that is loaded (SVOXT_LIB names another build than the in-tree one):
+"""Regenerate tests/golden/workspace_bytes.json: what the *_workspace_bytes queries of the tree operators and of the
+per-sample family answer, recorded from the library that is loaded (SVOXT_LIB names another build than the in-tree one):
 
     SVOXT_LIB=/path/to/libsvoxt_hip.so python tests/golden/make_workspace_golden.py
 
@@ -19,6 +19,11 @@ OUT = os.path.join(HERE, "workspace_bytes.json")
 NM = [(1, 0), (100, 500), (123841, 668912)]            # (n_internal, M)
 LEAVES = [0, 500, 866888]
 POINTS = [0, 100, 200000]
+# (rays, samples, feature rows, K, colour channels, basis values a ray); the last is the headline workload (640 000 rays,
+# 5.9 M samples, synth.shell_tree(8)'s rows of 28 floats: SH, 3 channels of 9).  CHUNKS: chunks of long rows, at most
+# T / 256 + T / 257 of them.
+SAMPLES = [(1, 1, 1, 1, 0, 0), (100, 500, 100, 4, 3, 0), (640000, 5900000, 668912, 28, 3, 9)]
+CHUNKS = [1, 2, 5900000 // 256 + 5900000 // 257]
 
 
 def cases():
@@ -40,6 +45,13 @@ def cases():
     for P, n_voxels, radius in [(0, 2, 0.0), (100, 16, 0.25), (200000, 128, 0.05)]:
         out.append(("svoxt_p2v_workspace_bytes", [P, n_voxels, [-1.0, -1.0, -1.0], [2.0, 2.0, 2.0], radius]))
     out += [("svoxt_build_workspace_bytes", [depth]) for depth in (1, 4, 8)]
+    # the per-sample family: the smallest legal extents, small ones, the headline workload's
+    for (Q, T, M, K, C, bd), chunks in zip(SAMPLES, CHUNKS):
+        out += [("svoxt_ray_samples_workspace_bytes", [Q]), ("svoxt_samples_select_workspace_bytes", [T]),
+                ("svoxt_samples_split_workspace_bytes", [T]), ("svoxt_samples_merge_workspace_bytes", [Q]),
+                ("svoxt_row_plan_workspace_bytes", [T, M]), ("svoxt_reduce_rows_workspace_bytes", [chunks, K]),
+                ("svoxt_shade_samples_bwd_workspace_bytes", [chunks, K]), ("svoxt_interp_rows_bwd_workspace_bytes", [chunks, K]),
+                ("svoxt_render_grad_rows_workspace_bytes", [Q, T, M, K, C, bd])]
     return out
 
 

@@ -19,7 +19,11 @@ def test_the_golden_file_covers_the_generators_cases():
         "svoxt_prune_workspace_bytes", "svoxt_merge_workspace_bytes", "svoxt_subdivide_workspace_bytes",
         "svoxt_frontier_workspace_bytes", "svoxt_neighbors_workspace_bytes", "svoxt_tv_plan_workspace_bytes",
         "svoxt_tv_workspace_bytes", "svoxt_assign_workspace_bytes", "svoxt_quantize_workspace_bytes",
-        "svoxt_p2v_workspace_bytes", "svoxt_build_workspace_bytes"}
+        "svoxt_p2v_workspace_bytes", "svoxt_build_workspace_bytes",
+        "svoxt_ray_samples_workspace_bytes", "svoxt_samples_select_workspace_bytes", "svoxt_samples_split_workspace_bytes",
+        "svoxt_samples_merge_workspace_bytes", "svoxt_row_plan_workspace_bytes", "svoxt_reduce_rows_workspace_bytes",
+        "svoxt_shade_samples_bwd_workspace_bytes", "svoxt_interp_rows_bwd_workspace_bytes",
+        "svoxt_render_grad_rows_workspace_bytes"}
 
 
 @pytest.mark.parametrize("g", GOLDEN, ids=lambda g: g["query"][6:-16] + "-" + "-".join(str(a) for a in g["args"] if not isinstance(a, list)))
@@ -38,3 +42,17 @@ def test_four_queries_written_out():
         assert _C._lib.svoxt_merge_workspace_bytes(n, M) == want["svoxt_merge_workspace_bytes"][i]
         assert _C._lib.svoxt_subdivide_workspace_bytes(n, 2, M) == want["svoxt_subdivide_workspace_bytes"][i]
         assert _C._lib.svoxt_frontier_workspace_bytes(n) == want["svoxt_frontier_workspace_bytes"][i]
+
+
+def test_list_producer_queries_written_out():
+    """The four list producers (svoxt_listemit.h: one carve for all of them) at the headline workload's 640 000 rays and
+    5.9 M samples, in the test itself.  Per ray: a 64-bit total, Q counts, Q starts, the scan's chunk sums; per sample:
+    T + 1 of each, select without the total (256 bytes less than split)."""
+    Q, T = 640000, 5900000
+    assert _C._lib.svoxt_ray_samples_workspace_bytes(Q) == 5121024
+    assert _C._lib.svoxt_samples_merge_workspace_bytes(Q) == 5121024
+    assert _C._lib.svoxt_samples_select_workspace_bytes(T) == 47206144
+    assert _C._lib.svoxt_samples_split_workspace_bytes(T) == 47206400
+    for query in ("svoxt_ray_samples_workspace_bytes", "svoxt_samples_merge_workspace_bytes", "svoxt_samples_select_workspace_bytes",
+                  "svoxt_samples_split_workspace_bytes"):
+        assert getattr(_C._lib, query)(0) == 0 and getattr(_C._lib, query)(-1) == -1 and getattr(_C._lib, query)(1 << 31) == -1
