@@ -1276,6 +1276,50 @@ int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, co
 int svoxt_sample_accumulate_bwd(const int32_t* ray, int64_t Q, int64_t T, const float* w, const float* values, int32_t C,
                                 const float* grad_out, float* grad_w, float* grad_values, void* stream);
 
+/* ---- sample faces and the gradient in the rays (svoxt_samples.hip; not in the reference) -----------
+ * The geometric half of a gradient in the rays: how every sample's depth and length move with the ray's origin and
+ * direction.  Both ends of a crossing lie on axis-aligned planes -- faces of a leaf, or of the cube for a ray's first
+ * crossing --, z = (P_a - o_a) / d_a in the parameter along rays.dirs AS GIVEN (what depth is), so dz/do_a = -1 / d_a and
+ * dz/dd_a = -z / d_a, nothing on the other axes.  Only the march knows the axes.  Entry points added under ABI v22.
+ *   svoxt_ray_samples_emit_faces   svoxt_ray_samples_emit with a fifth array, face uint8 [T] = entry | exit << 2 (any
+ *                             alignment); row / ray / depth / length are svoxt_ray_samples_emit's bit for bit, after the same
+ *                             svoxt_ray_samples_count.  In the march's own float32 values:
+ *                                 exit    m_a = fmaxf(-l_a * i_a, -l_a * i_a + i_a) on the leaf-local point l and the ray's
+ *                                         inverse direction i (the three values whose minimum is the step across the
+ *                                         leaf); the first axis in x, y, z (0, 1, 2) that holds min(m_x, m_y, m_z), found
+ *                                         by a strict-less update (a NaN never takes over)
+ *                                 entry   the exit of the crossing marched immediately before on the same ray, whether that
+ *                                         crossing was a sample or not (empty leaves and leaves at or under min_sigma
+ *                                         advance it); for the ray's first crossing, with n_a = fminf(t1, t2) of the cube's
+ *                                         slab test: tmin > 0: the first axis in x, y, z with n_a == tmin (3 if none);
+ *                                         otherwise 3, "no plane" -- the origin lies inside or on the cube and depth does
+ *                                         not depend on the ray
+ *   svoxt_sample_geometry_bwd      grad_origins / grad_dirs float32 [Q, 3] for grad_depth / grad_length float32 [T] (either may
+ *                             be NULL: zeros) and dirs float32 [Q, 3], the direction vectors the lists were marched from.  A
+ *                             lane per ray, its segment in list order, float32 without contraction, six accumulators
+ *                             go[3] and gd[3] that start at 0; THIS SEQUENCE IS THE DEFINITION.  Per sample k with
+ *                             gz_in = grad_depth[k] - grad_length[k] and gz_out = grad_length[k]:
+ *                                 a = face & 3;         if a < 3 and d[a] != 0:  u = gz_in / d[a];   go[a] -= u;  gd[a] -= u * depth[k]
+ *                                 b = (face >> 2) & 3;  if b < 3 and d[b] != 0:  v = gz_out / d[b];  go[b] -= v;  gd[b] -= v * (depth[k] + length[k])
+ *                             the entry term first; depth + length is one float32 add.  Every ray's three and three values
+ *                             are written, zeros for a ray without samples.  No atomics: the same bits in every run.
+ *                             It is the gradient of the two PLANES.  Two terms of the order of step_size are left out by
+ *                             definition: depth of a crossing after a ray's first is its plane's z plus one
+ *                             step_size * delta_scale (the previous crossing's overshoot), length holds one more, and
+ *                             delta_scale = 1 / |scaling * d| depends on dirs.
+ *   svoxt_sample_weights_bwd_length   svoxt_sample_weights_bwd's pass with a second output from the same bracket:
+ *                                 grad_length_k = sigma_k ((grad_w_k T_after - total) + grad_alpha T_end),  0 where sigma <= 0
+ *                             grad_sigma has svoxt_sample_weights_bwd's bits.  Both outputs are required.
+ * Q = 0 is a valid no-op (and T = 0 for svoxt_sample_weights_bwd_length).  No allocation, no synchronisation. */
+int svoxt_ray_samples_emit_faces(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* min_sigma,
+                                 const int64_t* offsets, int32_t* row, int32_t* ray, float* depth, float* length, uint8_t* face,
+                                 void* stream);
+int svoxt_sample_geometry_bwd(const int64_t* offsets, int64_t Q, int64_t T, const uint8_t* face, const float* depth, const float* length,
+                              const float* dirs, const float* grad_depth, const float* grad_length, float* grad_origins,
+                              float* grad_dirs, void* stream);
+int svoxt_sample_weights_bwd_length(const int64_t* offsets, int64_t Q, int64_t T, const float* length, const float* sigma,
+                                    const float* grad_w, const float* grad_alpha, float* grad_sigma, float* grad_length, void* stream);
+
 /* ---- scans, quantiles and subsets of the lists (svoxt_scan.hip; not in the reference) -------------
  * The conventions of the per-sample primitives above: ray q's segment is max(offsets[q], 0) .. min(offsets[q + 1], T),
  * Q and T below 2^31, float32, sequential in list order without contraction, no float atomic: the same bits in every run.

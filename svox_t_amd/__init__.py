@@ -18,7 +18,7 @@ from svox_t_amd.gridw import GridWeights, grid_weights  # noqa: F401
 from svox_t_amd.quant import quantize_median_cut  # noqa: F401
 from svox_t_amd.optim import FeatureAdam, FeatureRMSprop, FeatureSGD  # noqa: F401
 from svox_t_amd.samples import (RaySamples, RowPlan, accumulate, composite, gather_rows, merge_samples,  # noqa: F401
-                                quantile_depth, ray_quantile, ray_scan, reduce_rows, sample_weights, shade_samples,
+                                quantile_depth, ray_quantile, ray_scan, reduce_rows, sample_geometry, sample_weights, shade_samples,
                                 take_samples)
 
 __version__ = "0.1.0"
@@ -27,4 +27,4 @@ __all__ = ["N3Tree", "N3TreeView", "VolumeRenderer", "Rays", "NDCConfig",
            "blend_transformation_matrix", "voxelize", "grid_weights", "GridWeights", "quantize_median_cut",
            "FeatureSGD", "FeatureRMSprop", "FeatureAdam", "RaySamples", "sample_weights", "accumulate", "composite",
            "RowPlan", "gather_rows", "reduce_rows", "shade_samples", "ray_scan", "ray_quantile", "quantile_depth",
-           "InterpStencil", "interp_rows", "merge_samples", "take_samples"]
+           "InterpStencil", "interp_rows", "merge_samples", "take_samples", "sample_geometry"]

@@ -204,6 +204,10 @@ EXPORTS = {
     "svoxt_ray_samples_emit": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _P(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_sample_weights_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_sample_weights_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_ray_samples_emit_faces": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _P(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp]),
+    "svoxt_sample_geometry_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoxt_sample_weights_bwd_length": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoxt_sample_accumulate_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp]),
     "svoxt_sample_accumulate_bwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "svoxt_ray_scan_fwd": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),

@@ -1348,11 +1348,12 @@ def distortion_backward(tree: TreeSpec, rays, opt: RenderOptions, grad_output: t
 # ---------------------------------------------------------------------------
 # Per-sample interface (svoxt_samples.hip; not in the reference)
 # ---------------------------------------------------------------------------
-def ray_samples(tree: TreeSpec, rays, opt: RenderOptions, min_sigma=None):
+def ray_samples(tree: TreeSpec, rays, opt: RenderOptions, min_sigma=None, faces=False):
     """The leaf crossings of a ray batch as CSR lists (include/svoxt.h, svoxt_ray_samples_count / _emit): returns
     (offsets int64 [Q + 1], row int32 [T], ray int32 [T], depth float32 [T], length float32 [T], T).  `rays`: a RaysSpec
     or a CameraSpec, walked as depth_moments walks them; the lists are in ray-index order.  min_sigma None: every crossing
-    with a feature row; a number: only those with features[row, -1] > min_sigma.  One host read (T); T >= 2^31 raises."""
+    with a feature row; a number: only those with features[row, -1] > min_sigma.  One host read (T); T >= 2^31 raises.
+    faces=True: svoxt_ray_samples_emit_faces in place of the emit, and a seventh result, face uint8 [T]."""
     import svox_t_amd.csrc as csrc
     ms = None
     if min_sigma is not None:
@@ -1376,10 +1377,14 @@ def ray_samples(tree: TreeSpec, rays, opt: RenderOptions, min_sigma=None):
             if T >= 1 << 31:
                 raise RuntimeError(f"ray_samples: {T} samples; a batch's lists hold fewer than 2^31 (split the batch)")
         row, ray, depth, length = _new_lists(T, dev)
-        if T > 0:
+        face = torch.empty((T,), dtype=torch.uint8, device=dev) if faces else None
+        if T > 0 and faces:
+            _call("svoxt_ray_samples_emit_faces", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), ms, _ptr(offsets), _ptr(row),
+                  _ptr(ray), _ptr(depth), _ptr(length), _ptr(face), _stream(dev))
+        elif T > 0:
             _call("svoxt_ray_samples_emit", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), ms, _ptr(offsets), _ptr(row),
                   _ptr(ray), _ptr(depth), _ptr(length), _stream(dev))
-    return offsets, row, ray, depth, length, T
+    return (offsets, row, ray, depth, length, T, face) if faces else (offsets, row, ray, depth, length, T)
 
 
 def _new_lists(Tn, dev):
@@ -1463,6 +1468,59 @@ def sample_weights_backward(offsets, length, sigma, grad_w, grad_alpha):
         _call("svoxt_sample_weights_bwd", _ptr(offsets), Q, T, _ptr(length), _ptr(sigma), _ptr(grad_w), _ptr(grad_alpha), _ptr(gs),
               _stream(dev))
     return gs
+
+
+def _check_per_ray(x, name, Q, dev, cols=None):
+    shape = (Q,) if cols is None else (Q, cols)
+    _check_input(x, name)
+    if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != dev:
+        raise RuntimeError(f"{name} must be float32 {'[Q]' if cols is None else f'[Q, {cols}]'} with Q = {Q} rays, on the device of offsets")
+
+
+def sample_weights_backward_length(offsets, length, sigma, grad_w, grad_alpha):
+    """(grad_sigma, grad_length), both float32 [T], of svoxt_sample_weights_bwd_length: one pass, grad_sigma with
+    sample_weights_backward's bits; grad_w [T] / grad_alpha [Q] may be None (zeros)."""
+    T = sigma.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(length, "length", T, dev)
+    _check_per_sample(sigma, "sigma", T, dev)
+    if grad_w is not None:
+        _check_per_sample(grad_w, "grad_w", T, dev)
+    if grad_alpha is not None:
+        _check_per_ray(grad_alpha, "grad_alpha", Q, dev)
+    with _on(dev):
+        gs = torch.empty((T,), dtype=torch.float32, device=dev)
+        gl = torch.empty((T,), dtype=torch.float32, device=dev)
+        _call("svoxt_sample_weights_bwd_length", _ptr(offsets), Q, T, _ptr(length), _ptr(sigma), _ptr(grad_w), _ptr(grad_alpha), _ptr(gs),
+              _ptr(gl), _stream(dev))
+    return gs, gl
+
+
+def sample_geometry_backward(offsets, face, depth, length, dirs, grad_depth, grad_length):
+    """(grad_origins, grad_dirs), both float32 [Q, 3], of svoxt_sample_geometry_bwd for face uint8 [T], depth / length
+    float32 [T] and dirs float32 [Q, 3]; grad_depth / grad_length [T] may be None (zeros).  Every ray is written."""
+    if not isinstance(face, torch.Tensor) or face.dtype != torch.uint8 or face.dim() != 1:
+        raise RuntimeError("face must be uint8 [T]")
+    T = face.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(face, "face", T, dev, dtype=torch.uint8)
+    _check_per_sample(depth, "depth", T, dev)
+    _check_per_sample(length, "length", T, dev)
+    if not isinstance(dirs, torch.Tensor):
+        raise RuntimeError("dirs must be float32 [Q, 3]")
+    _check_per_ray(dirs, "dirs", Q, dev, 3)
+    if grad_depth is not None:
+        _check_per_sample(grad_depth, "grad_depth", T, dev)
+    if grad_length is not None:
+        _check_per_sample(grad_length, "grad_length", T, dev)
+    with _on(dev):
+        go = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        gd = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_sample_geometry_bwd", _ptr(offsets), Q, T, _ptr(face), _ptr(depth), _ptr(length), _ptr(dirs), _ptr(grad_depth),
+              _ptr(grad_length), _ptr(go), _ptr(gd), _stream(dev))
+    return go, gd
 
 
 def sample_accumulate(offsets, w, values=None):

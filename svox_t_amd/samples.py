@@ -13,6 +13,9 @@
     fine, index = samples.split(max_length=0.01)                   # every crossing cut into equal pieces (or pieces=int32 [T])
     m, ia, ib = merge_samples(sa, sb)                              # two trees a ray: the union of two lists of the SAME rays, and
     s_a, s_b = take_samples(sig_a, ia), take_samples(sig_b, ib)    # per piece each list's sample or -1: 0 where a tree has no sample there
+    samples = renderer.ray_samples(rays, faces=True)               # + samples.face: the planes every crossing begins and ends on, and
+    depth, length = sample_geometry(samples, rays)                 # the two list arrays, differentiable in rays.origins / rays.dirs
+    w, alpha = sample_weights(samples, sigma, length=length)       # (a camera pose refined against a fixed tree)
 
 Every per-sample loss is then a few lines of torch around HIP operators whose results, gradients included, have the same
 bits in every run: the gradient of gather_rows reaches the table through reduce_rows' fixed-order row plan (DESIGN.md
@@ -38,10 +41,13 @@ class RaySamples:
     row     int32 [T]       the feature row of the leaf crossed
     depth   float32 [T]     distance at which the ray enters the leaf (the "entry" z of render_depth_moments)
     length  float32 [T]     length of the crossing (+ step_size), in the same units
+    face    uint8 [T]       optional (ray_samples(faces=True), else None): entry | exit << 2, the axis (0, 1, 2) of the plane
+                            the crossing begins on -- 3: none, the ray starts inside the cube -- and of the one it ends on
+                            (include/svoxt.h, svoxt_ray_samples_emit_faces); what sample_geometry needs
     """
 
-    def __init__(self, offsets, ray, row, depth, length):
-        self.offsets, self.ray, self.row, self.depth, self.length = offsets, ray, row, depth, length
+    def __init__(self, offsets, ray, row, depth, length, face=None):
+        self.offsets, self.ray, self.row, self.depth, self.length, self.face = offsets, ray, row, depth, length, face
         if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1:
             raise RuntimeError("offsets must be int64 [Q + 1]")
         T = ray.shape[0] if isinstance(ray, torch.Tensor) and ray.dim() == 1 else -1
@@ -49,6 +55,11 @@ class RaySamples:
                             ("length", length, torch.float32)):
             if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (T,):
                 raise RuntimeError(f"{name} must be {str(dt).split('.')[-1]} [T], one entry per sample")
+        if face is not None:
+            if not isinstance(face, torch.Tensor) or face.dtype != torch.uint8 or tuple(face.shape) != (T,):
+                raise RuntimeError("face must be uint8 [T], one entry per sample")
+            if face.device != ray.device:
+                raise RuntimeError("face must be on the device of the samples")
 
     @property
     def Q(self) -> int:
@@ -74,12 +85,15 @@ class RaySamples:
             plans[M] = RowPlan(_C.row_plan(self.row.contiguous(), M))
         return plans[M]
 
-    def points(self, rays: Rays, at: str = "mid"):
+    def points(self, rays: Rays, at: str = "mid", *, geometry=None):
         """float32 [T, 3]: a world point per sample, origins[ray] + dirs[ray] * z with z = depth + 0.5 * length ("mid") or
         z = depth ("entry") -- what tree.interp(samples.points(rays)) looks up in front of sample_weights / accumulate.
         `rays` are the Rays the samples were marched from, with explicit origins and dirs; depth is measured along
         `dirs` as given (the march's own scale).  Plain torch, differentiable in nothing.  Camera-mode and NDC rays are
-        refused: their origins and directions are formed inside the kernels."""
+        refused: their origins and directions are formed inside the kernels.
+
+        :param geometry: (depth, length), two float32 [T] tensors -- sample_geometry(samples, rays)'s -- used in place of
+            the lists' own: the same formula without no_grad, differentiable in rays.origins, rays.dirs and both tensors."""
         if at not in ("mid", "entry"):
             raise RuntimeError('points: at must be "mid" or "entry"')
         if not isinstance(rays, Rays):
@@ -91,6 +105,16 @@ class RaySamples:
                 raise RuntimeError(f"points: rays.{name} must be float32 [Q, 3] with Q = {self.Q}, the rays the samples were marched from")
             if x.device != self.ray.device:
                 raise RuntimeError("points: the rays must be on the device of the samples")
+        if geometry is not None:
+            if not isinstance(geometry, (tuple, list)) or len(geometry) != 2:
+                raise RuntimeError("points: geometry must be (depth, length), as sample_geometry returns them")
+            for name, x in zip(("depth", "length"), geometry):
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (len(self),) or x.device != self.ray.device:
+                    raise RuntimeError(f"points: geometry's {name} must be float32 [T] on the device of the samples")
+            depth, length = geometry
+            z = depth + 0.5 * length if at == "mid" else depth
+            idx = self.ray.long()
+            return o[idx] + d[idx] * z[:, None]
         with torch.no_grad():
             z = self.depth + 0.5 * self.length if at == "mid" else self.depth
             idx = self.ray.long()
@@ -100,7 +124,7 @@ class RaySamples:
         """(RaySamples, index int64 [T']): the samples with keep[k] set, in their old order, as lists of their own -- the
         same Q rays (a ray may become empty), ray / row / depth / length copied bit for bit -- and every kept sample's
         position in the old lists: values[index] carries any per-sample tensor over, gradients flow through torch's
-        indexing.  `keep` is torch.bool [T] on the samples' device.  Flag, scan, emit on the GPU with one host read (T');
+        indexing.  `face` is carried where the lists have it.  `keep` is torch.bool [T] on the samples' device.  Flag, scan, emit on the GPU with one host read (T');
         the result holds no cached row plan."""
         if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != (len(self),):
             raise RuntimeError("select: keep must be torch.bool [T], one entry per sample")
@@ -109,7 +133,8 @@ class RaySamples:
             offsets, ray, row, depth, length, index, _ = _X.samples_select(
                 keep.contiguous(), self.offsets.contiguous(), self.ray.contiguous(), self.row.contiguous(), self.depth.contiguous(),
                 self.length.contiguous())
-        return RaySamples(offsets, ray, row, depth, length), index
+            face = None if self.face is None else self.face[index]
+        return RaySamples(offsets, ray, row, depth, length, face), index
 
     def split(self, max_length=None, *, pieces=None, max_pieces: int = 4096):
         """(RaySamples, index int64 [T']): every sample cut into equal pieces, in list order, as lists of their own over
@@ -124,7 +149,8 @@ class RaySamples:
         Every piece keeps `ray` and `row`.  split(max_length=inf) and split(pieces=ones) are these lists array for array.
         Count, scan, emit on the GPU -- a lane per OUTPUT piece, which finds its source by a binary search in the scan --
         with one host read (T'); a result of 2^31 samples or more is refused before anything is allocated.  Not
-        differentiable: the results are indices and distances.  The result holds no cached row plan."""
+        differentiable: the results are indices and distances.  The result holds no cached row plan and no `face`: a piece's
+        ends are not leaf faces (sample_geometry refuses it; carry depth[index], length[index] over in torch instead)."""
         if (max_length is None) == (pieces is None):
             raise RuntimeError("split: exactly one of max_length and pieces must be given")
         if pieces is not None and (not isinstance(pieces, torch.Tensor) or pieces.dtype != torch.int32 or tuple(pieces.shape) != (len(self),)):
@@ -164,7 +190,7 @@ def merge_samples(a: RaySamples, b: RaySamples):
     in the sense of the interval form.
 
     A lane per ray walks both segments, once to count and once to emit; one host read (T'), refused from 2^31 on before
-    anything is allocated.  Not differentiable: indices and distances.  There is no CPU path."""
+    anything is allocated.  Not differentiable: indices and distances; m.face is None (see split).  There is no CPU path."""
     if not isinstance(a, RaySamples) or not isinstance(b, RaySamples):
         raise RuntimeError("merge_samples: a and b must be RaySamples")
     if a.Q != b.Q:
@@ -216,13 +242,16 @@ class RowPlan:
         return self.row_ptr[1:] - self.row_ptr[:-1]
 
 
-def _ray_samples(self, rays: Rays, *, features=None, min_sigma=None, image_shape=None, sort_rays=None) -> RaySamples:
+def _ray_samples(self, rays: Rays, *, features=None, min_sigma=None, image_shape=None, sort_rays=None, faces=False) -> RaySamples:
     """The leaf crossings of a ray batch as RaySamples: every crossing of the shared march whose leaf holds a feature
     row, or with `min_sigma` only those whose sigma exceeds it (0.0: the set the backwards walk, sigma > 0).
 
     :param features: the feature table sigma is read from (default: the tree's own); read only with min_sigma
     :param image_shape, sort_rays: see forward -- they change how the rays are walked, never the lists
-    Nothing here is differentiable: the lists are indices and distances of the march.  One host read (the total)."""
+    :param faces: also fill RaySamples.face, a byte per sample (entry | exit << 2: the axes of the planes the crossing
+        begins and ends on); the other five arrays are those of faces=False bit for bit.  The emit kernel is another one.
+    Nothing here is differentiable: the lists are indices and distances of the march; sample_geometry(samples, rays) of a
+    faces=True list is the route from depth and length back to rays.origins and rays.dirs.  One host read (the total)."""
     self._require_gpu(True, "ray_samples")
     if features is None:
         features = self.tree.features
@@ -230,8 +259,11 @@ def _ray_samples(self, rays: Rays, *, features=None, min_sigma=None, image_shape
         spec = self.tree._spec(features.detach())
         rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
         rspec.need_grad = False
-        offsets, row, ray, depth, length, _ = _C.ray_samples(spec, rspec, self._get_options(), min_sigma)
-    return RaySamples(offsets, ray, row, depth, length)
+        if not faces:
+            offsets, row, ray, depth, length, _ = _C.ray_samples(spec, rspec, self._get_options(), min_sigma)
+            return RaySamples(offsets, ray, row, depth, length)
+        offsets, row, ray, depth, length, _, face = _C.ray_samples(spec, rspec, self._get_options(), min_sigma, True)
+    return RaySamples(offsets, ray, row, depth, length, face)
 
 
 VolumeRenderer.ray_samples = _ray_samples
@@ -339,22 +371,49 @@ def _require_gpu(what, samples, *tensors):
 
 class _SampleWeightsFunction(autograd.Function):
     @staticmethod
-    def forward(ctx, sigma, samples):
+    def forward(ctx, sigma, samples, length=None):
         sigma = sigma.contiguous()
-        w, alpha = _C.sample_weights(samples.offsets, samples.length, sigma)
+        ctx.has_length = length is not None
+        length = samples.length if length is None else length.contiguous()
+        w, alpha = _C.sample_weights(samples.offsets, length, sigma)
         ctx.samples = samples
-        ctx.save_for_backward(sigma)
+        ctx.save_for_backward(*((sigma, length) if ctx.has_length else (sigma,)))
         return w, alpha
 
     @staticmethod
     def backward(ctx, grad_w, grad_alpha):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        (sigma,) = ctx.saved_tensors
+        need_length = ctx.has_length and ctx.needs_input_grad[2]
+        if not (ctx.needs_input_grad[0] or need_length):
+            return None, None, None
+        sigma = ctx.saved_tensors[0]
         s = ctx.samples
+        length = ctx.saved_tensors[1] if ctx.has_length else s.length
         gw = None if grad_w is None else grad_w.contiguous()
         ga = None if grad_alpha is None else grad_alpha.contiguous()
-        return _C.sample_weights_backward(s.offsets, s.length, sigma, gw, ga), None
+        if not need_length:
+            return _C.sample_weights_backward(s.offsets, length, sigma, gw, ga), None, None
+        gs, gl = _X.sample_weights_backward_length(s.offsets, length, sigma, gw, ga)    # (both from one pass)
+        return (gs if ctx.needs_input_grad[0] else None), None, gl
+
+
+class _SampleGeometryFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, origins, dirs, samples):
+        ctx.samples = samples
+        ctx.set_materialize_grads(False)                         # (a None upstream gradient stays None: the kernel's null pointer)
+        ctx.save_for_backward(dirs)
+        return samples.depth.clone(), samples.length.clone()     # (copies: autograd wants outputs of its own; no kernel of ours)
+
+    @staticmethod
+    def backward(ctx, grad_depth, grad_length):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        (dirs,) = ctx.saved_tensors
+        s = ctx.samples
+        gd = None if grad_depth is None else grad_depth.contiguous()
+        gl = None if grad_length is None else grad_length.contiguous()
+        go, gdir = _X.sample_geometry_backward(s.offsets, s.face, s.depth, s.length, dirs.detach().contiguous(), gd, gl)
+        return (go if ctx.needs_input_grad[0] else None), (gdir if ctx.needs_input_grad[1] else None), None
 
 
 class _AccumulateFunction(autograd.Function):
@@ -380,19 +439,67 @@ class _AccumulateFunction(autograd.Function):
         return gw, gv, None
 
 
-def sample_weights(samples: RaySamples, sigma):
+def sample_geometry(samples: RaySamples, rays: Rays):
+    """(depth, length), float32 [T]: the two list arrays of `samples`, same bits, as tensors that are differentiable in
+    rays.origins and rays.dirs -- the geometric half of a gradient in the rays.  The forward launches no
+    kernel.  `samples` must carry `face` (ray_samples(faces=True), or a select of such lists); `rays` are the Rays the
+    samples were marched from, with explicit origins and dirs, float32 [Q, 3] on the samples' device.  Camera-mode and NDC
+    rays are refused as points refuses them: pinhole_rays is torch and differentiable in c2w already.
+
+    Both ends of a crossing lie on axis-aligned planes, z = (P_a - o_a) / d_a in the parameter along `dirs` as given, so
+    dz/do_a = -1 / d_a and dz/dd_a = -z / d_a.  Backward, a lane per ray over its segment in list order, float32, no
+    contraction, six accumulators from 0 (include/svoxt.h, svoxt_sample_geometry_bwd, is the definition), per sample with
+    gz_in = g_depth - g_length and gz_out = g_length:
+
+        a = entry;  if a < 3 and d[a] != 0:  u = gz_in  / d[a];  go[a] -= u;  gd[a] -= u * depth
+        b = exit;   if          d[b] != 0:   v = gz_out / d[b];  go[b] -= v;  gd[b] -= v * (depth + length)
+
+    Every ray's gradient is written (zeros without samples); no atomics, the same bits in every run.  It is the gradient
+    of the two PLANES: two terms of the order of step_size are left out by definition -- depth of a later crossing is its
+    plane's z plus one step_size * delta_scale, length holds another, and delta_scale depends on dirs.  The crossing set
+    itself is piecewise constant in the rays.  The view-dependent half (view_basis in viewdirs, shade_samples in basis)
+    is not here: reach it through gather_rows and a basis written in torch."""
+    if not isinstance(samples, RaySamples):
+        raise RuntimeError("sample_geometry: samples must be a RaySamples")
+    if samples.face is None:
+        raise RuntimeError("sample_geometry: the samples carry no `face`: march them with ray_samples(faces=True) (select keeps "
+                           "face; the lists of split and merge_samples have none: their pieces' ends are not leaf faces -- "
+                           "carry depth[index] and length[index] over in torch instead)")
+    if not isinstance(rays, Rays):
+        raise RuntimeError("sample_geometry: rays must be the Rays the samples were marched from (camera-mode and NDC rays are "
+                           "not served: pinhole_rays is differentiable in c2w already)")
+    o, d = rays.origins, rays.dirs
+    for name, x in (("origins", o), ("dirs", d)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (samples.Q, 3):
+            raise RuntimeError(f"sample_geometry: rays.{name} must be float32 [Q, 3] with Q = {samples.Q}, the rays the samples were marched from")
+        if x.device != samples.ray.device:
+            raise RuntimeError("sample_geometry: the rays must be on the device of the samples")
+    _require_gpu("sample_geometry", samples, o, d)
+    return _SampleGeometryFunction.apply(o, d, samples)
+
+
+def sample_weights(samples: RaySamples, sigma, length=None):
     """(w float32 [T], alpha float32 [Q]) from a density per sample, differentiable in `sigma`:
 
         per ray, in list order:  att = exp(-(length * sigma));  w = T * (1 - att);  T *= att;      alpha = 1 - T_end
 
     A sample with sigma <= 0 gets w = 0, leaves T unchanged and receives no gradient, as the march skips it.  No
     thresholds and no early stop (the convention of the package's backwards).  With sigma = features[samples.row, -1]
-    alpha has the bits of opacity_render and of render_depth_moments' third column."""
+    alpha has the bits of opacity_render and of render_depth_moments' third column.
+
+    :param length: float32 [T] used in place of samples.length by the same operation sequence (length = samples.length:
+        today's bits) -- sample_geometry's --, which makes the operator differentiable in it: grad_length[k] =
+        sigma[k] * the bracket grad_sigma[k] multiplies by length[k], 0 where sigma <= 0; both from one pass."""
     if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or sigma.dim() != 1 or \
             not isinstance(samples, RaySamples) or sigma.shape[0] != len(samples):
         raise RuntimeError("sigma must be float32 [T], one entry per sample")
-    _require_gpu("sample_weights", samples, sigma)
-    return _SampleWeightsFunction.apply(sigma, samples)
+    if length is None:
+        _require_gpu("sample_weights", samples, sigma)
+        return _SampleWeightsFunction.apply(sigma, samples)
+    if not isinstance(length, torch.Tensor) or length.dtype != torch.float32 or tuple(length.shape) != (len(samples),):
+        raise RuntimeError("length must be float32 [T], one entry per sample")
+    _require_gpu("sample_weights", samples, sigma, length)
+    return _SampleWeightsFunction.apply(sigma, samples, length)
 
 
 def accumulate(samples: RaySamples, w, values=None):
