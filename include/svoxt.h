@@ -1632,8 +1632,89 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
  *                             row_ptr not NULL; with T > 0 perm and what the given gradients make it read (values, ray,
  *                             basis) not NULL; with n_long > 0 long_rows, long_chunk_ptr, chunk_long not NULL; alignment
  *                             (4 bytes); with n_long > 0 the workspace not NULL and at least the query's size.
+ *
+ * The gradient in the view direction: the view-dependent half of a gradient in the rays, beside
+ * svoxt_sample_geometry_bwd.  Two gathers, float32 without contraction, no float atomic, no [T, K] array, no workspace:
+ * every result is bit-identical from run to run.  Entry points added under ABI v22.
+ *
+ *   svoxt_view_basis_bwd      grad_vdirs float32 [Q, 3] for grad_basis float32 [Q, basis_dim] and basis, the forward's own
+ *                             [Q, basis_dim] (read for SG only; may be NULL otherwise).  A lane per ray, every ray written.
+ *                             With (x, y, z) = rays.vdirs[q] AS GIVEN -- the forward does not normalise the direction, so
+ *                             the derivative is not projected on the sphere -- and g_i = grad_basis[q, i]: three
+ *                             accumulators gx, gy, gz from 0.f, and for i ascending
+ *                                 gx += g_i * X_i;  gy += g_i * Y_i;  gz += g_i * Z_i        (product rounded, then the add)
+ *                             with (X_i, Y_i, Z_i) the analytic derivative of the expression svoxt_view_basis evaluates
+ *                             for component i; a partial written `.` below is identically zero and is NOT added.  THIS
+ *                             SEQUENCE IS THE DEFINITION.  SH, with the constants C1, C2[5], C3[7], C4[9] of the forward
+ *                             and xx = x * x, yy, zz, xy = x * y, yz = y * z, xz = x * z, every product and difference
+ *                             one float32 operation in the order written (left to right):
+ *                                 i     X_i                          Y_i                           Z_i
+ *                                 0     .                            .                             .
+ *                                 1     .                            -C1                           .
+ *                                 2     .                            .                             C1
+ *                                 3     -C1                          .                             .
+ *                                 4     C2[0] * y                    C2[0] * x                     .
+ *                                 5     .                            C2[1] * z                     C2[1] * y
+ *                                 6     C2[2] * (-2 * x)             C2[2] * (-2 * y)              C2[2] * (4 * z)
+ *                                 7     C2[3] * z                    .                             C2[3] * x
+ *                                 8     C2[4] * (2 * x)              C2[4] * (-2 * y)              .
+ *                                 9     C3[0] * (6 * xy)             C3[0] * a                     .
+ *                                 10    C3[1] * yz                   C3[1] * xz                    C3[1] * xy
+ *                                 11    C3[2] * (-2 * xy)            C3[2] * (4 * zz - xx - 3 * yy)   C3[2] * (8 * yz)
+ *                                 12    C3[3] * (-6 * xz)            C3[3] * (-6 * yz)             C3[3] * (6 * zz - 3 * xx - 3 * yy)
+ *                                 13    C3[4] * (4 * zz - 3 * xx - yy)   C3[4] * (-2 * xy)         C3[4] * (8 * xz)
+ *                                 14    C3[5] * (2 * xz)             C3[5] * (-2 * yz)             C3[5] * (xx - yy)
+ *                                 15    C3[6] * a                    C3[6] * (-6 * xy)             .
+ *                                 16    C4[0] * (y * p)              C4[0] * (x * m)               .
+ *                                 17    C4[1] * ((6 * xy) * z)       C4[1] * (z * a)               C4[1] * (y * p)
+ *                                 18    C4[2] * (y * s1)             C4[2] * (x * s1)              C4[2] * ((14 * xy) * z)
+ *                                 19    .                            C4[3] * (z * s3)              C4[3] * (y * t3)
+ *                                 20    .                            .                             C4[4] * (z * (140 * zz - 60))
+ *                                 21    C4[5] * (z * s3)             .                             C4[5] * (x * t3)
+ *                                 22    C4[6] * ((2 * x) * s1)       C4[6] * ((-2 * y) * s1)       C4[6] * ((xx - yy) * (14 * z))
+ *                                 23    C4[7] * (z * a)              C4[7] * ((-6 * xy) * z)       C4[7] * (x * m)
+ *                                 24    C4[8] * (x * (4 * xx - 12 * yy))   C4[8] * (y * (4 * yy - 12 * xx))   .
+ *                             a = 3 * xx - 3 * yy, p = 3 * xx - yy, m = xx - 3 * yy, s1 = 7 * zz - 1, s3 = 7 * zz - 3,
+ *                             t3 = 21 * zz - 3.  (Component 6 is formed through double in the forward; its derivative is
+ *                             the float32 line above.)  Only the components basis_dim holds (1 / 4 / 9 / 16 / 25).
+ *                             SG, lobe i = extra_data[i, :]:    s = basis[q, i] * lobe[0];  (X, Y, Z) = s * lobe[1 .. 3]
+ *                                 -- the forward's own output, no exponential is computed.
+ *                             ASG:  S, dot_x, dot_y and E = expf(-lobe[0] * dot_x * dot_x - lobe[1] * dot_y * dot_y) by the
+ *                                 forward's sequence (E is recomputed, never out_i / S: S may be 0);  SE = S * E;
+ *                                 cx = (-2 * lobe[0]) * dot_x;  cy = (-2 * lobe[1]) * dot_y;  for the axis a = 0, 1, 2:
+ *                                 (lobe[8 + a] * E + SE * (cx * lobe[2 + a] + cy * lobe[5 + a])) / (float)basis_dim
+ *                             The gradient in the lobe parameters (extra_data) is not formed.  Checked: as
+ *                             svoxt_view_basis; rays.c2w NULL (camera mode has no viewdirs tensor to receive a gradient);
+ *                             tree.xform NULL; grad_basis, grad_vdirs (SG: basis) not NULL; alignment (4 bytes).  RGBA and
+ *                             Q = 0: a no-op.
+ *
+ *   svoxt_shade_samples_bwd_basis   grad_basis float32 [Q, basis_dim], the gradient with respect to svoxt_shade_samples_fwd's
+ *                             basis for grad_values [T, C] over the lists (offsets int64 [Q + 1], row, ray).  Every
+ *                             element is written.  THIS SEQUENCE IS THE DEFINITION, for every ray q and component i in
+ *                             [min_comp, max_comp]:
+ *                                 acc = 0.f
+ *                                 for k = max(offsets[q], 0) .. min(offsets[q + 1], T) - 1, in list order:
+ *                                     if ray[k] == q and 0 <= row[k] < M:
+ *                                         for c = 0 .. C - 1:
+ *                                             acc += (grad_values[k, c] * d[k, c]) * features[row[k], c * basis_dim + i]
+ *                                 grad_basis[q, i] = acc
+ *                             d[k, c] = (float)((double)sig * (1.0 - (double)sig)), sig = values[k, c], the forward's own
+ *                             output: the factor of svoxt_shade_samples_bwd, so the two gradients of one forward agree
+ *                             term for term.  With activate == 0 the bracket is grad_values[k, c] alone and values is not
+ *                             read.  For i outside [min_comp, max_comp] grad_basis[q, i] = 0.f and nothing is read; a ray
+ *                             without samples gets zeros.  A sample standing in ray q's segment whose ray[k] is another
+ *                             ray contributes nothing (svoxt_ray_samples_emit never writes one).  basis_dim lanes a ray walk
+ *                             its segment together; a workgroup holds whole rays.  grad_values NULL, C = 0 or T = 0: zeros,
+ *                             nothing is read.  RGBA and Q = 0: a no-op.  Checked: as svoxt_shade_samples_fwd; offsets
+ *                             (8-byte aligned), grad_basis not NULL; with a gradient to read: row, ray, values (activate
+ *                             != 0), features (M > 0) not NULL; alignment (4 bytes).
  * No allocation, no synchronisation. */
 int svoxt_view_basis(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, float* basis, void* stream);
+int svoxt_view_basis_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* basis,
+                         const float* grad_basis, float* grad_vdirs, void* stream);
+int svoxt_shade_samples_bwd_basis(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const int64_t* offsets,
+                                  const int32_t* row, const int32_t* ray, int64_t T, int64_t Q, int32_t activate,
+                                  const float* values, const float* grad_values, float* grad_basis, void* stream);
 int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const int32_t* row,
                             const int32_t* ray, int64_t T, const float* basis, int64_t Q, int32_t activate, float* values,
                             float* sigma, void* stream);

@@ -1924,7 +1924,7 @@ def _shade_dims(opt: RenderOptions, K: int):
     return C, (0 if int(opt.format) == 0 else int(opt.basis_dim))
 
 
-def _check_shade(features, row, ray, basis, Q, opt):
+def _check_shade(features, row, ray, basis, Q, opt, with_basis=True):
     """The checks the two directions of shade_samples share; returns (M, K, T, C, basis_dim, device)."""
     if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
         raise RuntimeError("features must be float32 [M, K], K >= 1")
@@ -1937,7 +1937,7 @@ def _check_shade(features, row, ray, basis, Q, opt):
     _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
     (M, K) = features.shape
     C, bd = _shade_dims(opt, K)
-    if bd > 0:
+    if bd > 0 and with_basis:
         if not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (Q, bd):
             raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] (view_basis of the samples' rays)")
         _check_input(basis, "basis")
@@ -1991,6 +1991,50 @@ def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: b
         _call("svoxt_shade_samples_bwd", ctypes.byref(co), M, K, _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q, 1 if activate else 0,
               _ptr(values), _ptr(grad_values), _ptr(grad_sigma), *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
     return grad
+
+
+def view_basis_backward(tree: TreeSpec, rays, opt: RenderOptions, basis, grad_basis) -> torch.Tensor:
+    """grad_viewdirs float32 [Q, 3] of svoxt_view_basis_bwd for grad_basis float32 [Q, basis_dim] and `basis`, view_basis'
+    own output for these rays (read for SG).  `rays`: a RaysSpec with explicit viewdirs; RGBA: zeros."""
+    if _numel(tree.transformation_matrices):
+        raise RuntimeError("view_basis: transformation_matrices are not served by shade_samples (the per-leaf rotation of "
+                           "the view direction); use forward")
+    ct, cr, co = _pack_tree(tree), _pack_rays(rays), _pack_opts(opt)
+    dev = tree.features.device
+    Q = int(cr.Q)
+    bd = 0 if int(opt.format) == 0 else int(opt.basis_dim)
+    if bd == 0:
+        return torch.zeros((Q, 3), dtype=torch.float32, device=dev)
+    for name, x in (("basis", basis), ("grad_basis", grad_basis)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (Q, bd) or x.device != dev:
+            raise RuntimeError(f"{name} must be float32 [Q, basis_dim] = [{Q}, {bd}] on the device of the tree")
+        _check_input(x, name)
+    with _on(dev):
+        gv = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_view_basis_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(basis), _ptr(grad_basis), _ptr(gv),
+              _stream(dev))
+    return gv
+
+
+def shade_samples_bwd_basis(features, offsets, row, ray, Q: int, opt: RenderOptions, activate: bool, values, grad_values) -> torch.Tensor:
+    """grad_basis float32 [Q, basis_dim] of svoxt_shade_samples_bwd_basis for features float32 [M, K] over the lists (offsets
+    int64 [Q + 1], row / ray int32 [T]); values is the forward's output, grad_values [T, C] may be None (zeros).  RGBA: an
+    empty [Q, 0] tensor, no kernel."""
+    M, K, T, C, bd, dev = _check_shade(features, row, ray, None, Q, opt, with_basis=False)
+    if _check_csr(offsets, T) != Q:
+        raise RuntimeError(f"offsets must be int64 [Q + 1] with Q = {Q}")
+    if offsets.device != dev:
+        raise RuntimeError("offsets must be on the device of the features")
+    _check_per_sample(values, "values", T, dev, C)
+    if grad_values is not None:
+        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    co = _pack_opts(opt)
+    with _on(dev):
+        gb = torch.empty((Q, bd), dtype=torch.float32, device=dev)
+        if bd > 0:
+            _call("svoxt_shade_samples_bwd_basis", _ptr(features), M, K, ctypes.byref(co), _ptr(offsets), _ptr(row), _ptr(ray), T, Q,
+                  1 if activate else 0, _ptr(values), _ptr(grad_values), _ptr(gb), _stream(dev))
+    return gb
 
 
 # ---------------------------------------------------------------------------

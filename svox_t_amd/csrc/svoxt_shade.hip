@@ -10,8 +10,13 @@
 //   backward     the row kernels of svoxt_rowwalk.h, a lane per (row, column) over all K columns, the value of sample k
 //                at column j formed on the fly (ShadeValues): a colour column (g_values[k, c] * d[k, c]) *
 //                basis[ray[k], i], the sigma column g_sigma[k], every other column 0.f.  sig is the forward's own output.
-// Per sample 4 * (C + 1) bytes out of the forward; the backward keeps values, basis and ray.  C ABI: svoxt_view_basis,
-// svoxt_shade_samples_* (include/svoxt.h).
+//   view gradient
+//                view_basis_bwd_kernel    a lane per ray: the analytic derivative of precalc_basis' expression, summed over
+//                                         the components in ascending order into grad_viewdirs[q, 0:3]
+//                shade_bwd_basis_kernel   basis_dim lanes a ray over its segment in list order: grad_basis[q, i], the sum of
+//                                         (g_values[k, c] * d[k, c]) * features[row[k], c * bd + i]; whole rays a workgroup
+// Per sample 4 * (C + 1) bytes out of the forward; the backward keeps values, basis and ray (and the table's pointer where
+// the basis requires grad).  C ABI: svoxt_view_basis, svoxt_view_basis_bwd, svoxt_shade_samples_* (include/svoxt.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +39,88 @@ view_basis_kernel(TreeDev tr, RaysDev rays, int format, int bd, float* __restric
     load_vdir(rays, q, vd);
     precalc_basis<0>(format, bd, tr, vd[0], vd[1], vd[2], basis + q * bd);
 }
+
+// lane q: grad_vdirs[q, :] = sum over i ascending of grad_basis[q, i] * d out_i / d (x, y, z), the analytic derivative of
+// the expression precalc_basis evaluates, in the three components as given (include/svoxt.h states the sequence).  A
+// partial that is identically zero is not added.  grad_basis[q, i] is read at compile-time indices guarded by bd, the
+// lobes of SG / ASG one at a time from memory: no private array, nothing in scratch.
+#define SVOXT_VB_ADD(g, dx, dy, dz) do { gx += (g) * (dx); gy += (g) * (dy); gz += (g) * (dz); } while (0)
+__global__ void __launch_bounds__(kLaunchBlock)
+view_basis_bwd_kernel(TreeDev tr, RaysDev rays, int format, int bd, const float* __restrict__ basis,
+                      const float* __restrict__ grad_basis, float* __restrict__ grad_vdirs) {
+    const int64_t q = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    if (q >= rays.Q) return;
+    float vd[3];
+    load_vdir(rays, q, vd);
+    const float x = vd[0], y = vd[1], z = vd[2];
+    const float* __restrict__ gb = grad_basis + q * bd;
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (format == FMT_SH) {
+        const float xx = x * x, yy = y * y, zz = z * z;
+        const float xy = x * y, yz = y * z, xz = x * z;
+        if (bd == 25 || bd == 16 || bd == 9 || bd == 4) {
+            gy += gb[1] * -kC1;
+            gz += gb[2] * kC1;
+            gx += gb[3] * -kC1;
+        }
+        if (bd == 25 || bd == 16 || bd == 9) {
+            { const float g = gb[4]; gx += g * (kC2[0] * y); gy += g * (kC2[0] * x); }
+            { const float g = gb[5]; gy += g * (kC2[1] * z); gz += g * (kC2[1] * y); }
+            SVOXT_VB_ADD(gb[6], kC2[2] * (-2.f * x), kC2[2] * (-2.f * y), kC2[2] * (4.f * z));
+            { const float g = gb[7]; gx += g * (kC2[3] * z); gz += g * (kC2[3] * x); }
+            { const float g = gb[8]; gx += g * (kC2[4] * (2.f * x)); gy += g * (kC2[4] * (-2.f * y)); }
+        }
+        if (bd == 25 || bd == 16) {
+            const float a = 3.f * xx - 3.f * yy;
+            { const float g = gb[9]; gx += g * (kC3[0] * (6.f * xy)); gy += g * (kC3[0] * a); }
+            SVOXT_VB_ADD(gb[10], kC3[1] * yz, kC3[1] * xz, kC3[1] * xy);
+            SVOXT_VB_ADD(gb[11], kC3[2] * (-2.f * xy), kC3[2] * (4.f * zz - xx - 3.f * yy), kC3[2] * (8.f * yz));
+            SVOXT_VB_ADD(gb[12], kC3[3] * (-6.f * xz), kC3[3] * (-6.f * yz), kC3[3] * (6.f * zz - 3.f * xx - 3.f * yy));
+            SVOXT_VB_ADD(gb[13], kC3[4] * (4.f * zz - 3.f * xx - yy), kC3[4] * (-2.f * xy), kC3[4] * (8.f * xz));
+            SVOXT_VB_ADD(gb[14], kC3[5] * (2.f * xz), kC3[5] * (-2.f * yz), kC3[5] * (xx - yy));
+            { const float g = gb[15]; gx += g * (kC3[6] * a); gy += g * (kC3[6] * (-6.f * xy)); }
+        }
+        if (bd == 25) {
+            const float a = 3.f * xx - 3.f * yy;                 // (as above)
+            const float p = 3.f * xx - yy, m = xx - 3.f * yy;
+            const float s1 = 7.f * zz - 1.f, s3 = 7.f * zz - 3.f, t3 = 21.f * zz - 3.f;
+            { const float g = gb[16]; gx += g * (kC4[0] * (y * p)); gy += g * (kC4[0] * (x * m)); }
+            SVOXT_VB_ADD(gb[17], kC4[1] * ((6.f * xy) * z), kC4[1] * (z * a), kC4[1] * (y * p));
+            SVOXT_VB_ADD(gb[18], kC4[2] * (y * s1), kC4[2] * (x * s1), kC4[2] * ((14.f * xy) * z));
+            { const float g = gb[19]; gy += g * (kC4[3] * (z * s3)); gz += g * (kC4[3] * (y * t3)); }
+            gz += gb[20] * (kC4[4] * (z * (140.f * zz - 60.f)));
+            { const float g = gb[21]; gx += g * (kC4[5] * (z * s3)); gz += g * (kC4[5] * (x * t3)); }
+            SVOXT_VB_ADD(gb[22], kC4[6] * ((2.f * x) * s1), kC4[6] * ((-2.f * y) * s1), kC4[6] * ((xx - yy) * (14.f * z)));
+            SVOXT_VB_ADD(gb[23], kC4[7] * (z * a), kC4[7] * ((-6.f * xy) * z), kC4[7] * (x * m));
+            { const float g = gb[24]; gx += g * (kC4[8] * (x * (4.f * xx - 12.f * yy))); gy += g * (kC4[8] * (y * (4.f * yy - 12.f * xx))); }
+        }
+    } else if (format == FMT_SG) {
+        const float* __restrict__ b = basis + q * bd;
+        for (int i = 0; i < bd; ++i) {
+            const float* lobe = tr.extra + (int64_t)i * tr.extra_cols;
+            const float g = gb[i], s = b[i] * lobe[0];           // (the forward's own output: no exponential here)
+            SVOXT_VB_ADD(g, s * lobe[1], s * lobe[2], s * lobe[3]);
+        }
+    } else if (format == FMT_ASG) {
+        const float dir[3] = {x, y, z};
+        for (int i = 0; i < bd; ++i) {
+            const float* lobe = tr.extra + (int64_t)i * tr.extra_cols;
+            const float S = dot3(dir, lobe + 8);
+            const float dot_x = dot3(dir, lobe + 2);
+            const float dot_y = dot3(dir, lobe + 5);
+            const float E = pexpf(-lobe[0] * dot_x * dot_x - lobe[1] * dot_y * dot_y);     // (the forward's sequence)
+            const float SE = S * E;
+            const float cx = (-2.f * lobe[0]) * dot_x, cy = (-2.f * lobe[1]) * dot_y;
+            const float g = gb[i], n = (float)bd;
+            SVOXT_VB_ADD(g, (lobe[8] * E + SE * (cx * lobe[2] + cy * lobe[5])) / n,
+                         (lobe[9] * E + SE * (cx * lobe[3] + cy * lobe[6])) / n,
+                         (lobe[10] * E + SE * (cx * lobe[4] + cy * lobe[7])) / n);
+        }
+    }
+    float* __restrict__ o = grad_vdirs + 3 * q;
+    o[0] = gx; o[1] = gy; o[2] = gz;
+}
+#undef SVOXT_VB_ADD
 
 // ------------------------------------------------------------------------------------------------------------ forward
 // one channel's value from tmp: the backward's pass-1 sig, or tmp itself
@@ -152,6 +239,47 @@ struct ShadeValues {
     }
 };
 
+// ----------------------------------------------------------------------------------------------------- backward, basis
+// grad_basis[q, i] = the sum over ray q's segment in list order, and per sample over c ascending, of
+// (grad_values[k, c] * d[k, c]) * features[row[k], c * bd + i] -- ShadeValues::Col::at's factor times the coefficient the
+// forward multiplied basis[q, i] by.  bd lanes a ray walk the segment together: lane i reads frow[c * bd + i], so a
+// ray's lanes read neighbouring floats of one row and the same grad_values / values words.  A block holds
+// kLaunchBlock / bd whole rays (its last kLaunchBlock % bd lanes idle): no ray's lanes straddle two blocks.  One
+// accumulator a lane; CS: C at compile time (0: the run-time loop).
+template <int CS>
+__global__ void __launch_bounds__(kLaunchBlock)
+shade_bwd_basis_kernel(const float* __restrict__ features, int64_t M, int K, int C_rt, int bd, int min_comp, int max_comp,
+                       bool activate, int64_t Q, int64_t T, const int64_t* __restrict__ offsets, const int32_t* __restrict__ row,
+                       const int32_t* __restrict__ ray, const float* __restrict__ values, const float* __restrict__ gv,
+                       float* __restrict__ grad_basis) {
+    const int C = CS > 0 ? CS : C_rt;
+    const int rays_per_block = kLaunchBlock / bd;
+    const int r = (int)threadIdx.x / bd, i = (int)threadIdx.x - r * bd;
+    const int64_t q = (int64_t)blockIdx.x * rays_per_block + r;
+    if (r >= rays_per_block || q >= Q) return;
+    float acc = 0.f;
+    if (gv != nullptr && i >= min_comp && i <= max_comp) {
+        const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+        for (int64_t k = b; k < e; ++k) {
+            const int64_t idx = row[k];
+            if (ray[k] != q || idx < 0 || idx >= M) continue;
+            const float* __restrict__ f = features + idx * K + i;
+            const float* __restrict__ g = gv + k * C;
+            const float* __restrict__ v = values + k * C;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                float t = g[c];
+                if (activate) {
+                    const float sig = v[c];
+                    t = t * (float)((double)sig * (1.0 - (double)sig));
+                }
+                acc += t * f[c * bd];
+            }
+        }
+    }
+    grad_basis[q * bd + i] = acc;
+}
+
 // ------------------------------------------------------------------------------------------------------------- checks
 // C and the basis values a ray has (0 for RGBA) for a table of K columns; what both directions check first
 static int shade_dims(const svoxt_options* opt, int64_t M, int32_t K, int64_t T, int64_t Q, int* C, int* bd, const char* fn) {
@@ -193,6 +321,52 @@ int svoxt_view_basis(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt
     const RaysDev rd = to_dev(rays, tree);
     hipLaunchKernelGGL(view_basis_kernel, dim3(launch_blocks(rays->Q)), dim3(kLaunchBlock), 0, (hipStream_t)stream, tr, rd, (int)opt->format,
                        (int)opt->basis_dim, basis);
+    return check_launch(fn);
+}
+
+int svoxt_view_basis_bwd(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const float* basis,
+                         const float* grad_basis, float* grad_vdirs, void* stream) {
+    const char* fn = "svoxt_view_basis_bwd";
+    int rc;
+    if ((rc = check_tree(tree, fn)) || (rc = check_rays(rays, fn)) || (rc = check_opts(opt, tree, fn, true))) return rc;
+    if (rays->c2w != nullptr) return fail(SVOXT_ERR_INVALID, "%s: camera mode has no viewdirs tensor to receive a gradient (rays.c2w must be NULL)", fn);
+    if (tree->xform != nullptr) return fail(SVOXT_ERR_INVALID, "%s: transformation_matrices (tree.xform) are not served by shade_samples", fn);
+    if (rays->Q > 0x7fffffffLL) return fail(SVOXT_ERR_INVALID, "%s: too many rays (ray indices are int32)", fn);
+    if (opt->format == SVOXT_FORMAT_RGBA || rays->Q == 0) return SVOXT_OK;     // [Q, 0]: no basis, no gradient
+    if (grad_basis == nullptr || grad_vdirs == nullptr || (opt->format == SVOXT_FORMAT_SG && basis == nullptr))
+        return fail(SVOXT_ERR_INVALID, "%s: grad_basis / grad_vdirs / basis (SG) is NULL", fn);
+    if (misaligned(basis, 4) || misaligned(grad_basis, 4) || misaligned(grad_vdirs, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    const TreeDev tr = to_dev(tree);
+    const RaysDev rd = to_dev(rays, tree);
+    hipLaunchKernelGGL(view_basis_bwd_kernel, dim3(launch_blocks(rays->Q)), dim3(kLaunchBlock), 0, (hipStream_t)stream, tr, rd,
+                       (int)opt->format, (int)opt->basis_dim, basis, grad_basis, grad_vdirs);
+    return check_launch(fn);
+}
+
+int svoxt_shade_samples_bwd_basis(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const int64_t* offsets,
+                                  const int32_t* row, const int32_t* ray, int64_t T, int64_t Q, int32_t activate,
+                                  const float* values, const float* grad_values, float* grad_basis, void* stream) {
+    const char* fn = "svoxt_shade_samples_bwd_basis";
+    int rc, C, bd;
+    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn))) return rc;
+    if (bd == 0 || Q == 0) return SVOXT_OK;                      // RGBA: no basis, no gradient
+    if (offsets == nullptr || grad_basis == nullptr) return fail(SVOXT_ERR_INVALID, "%s: offsets / grad_basis is NULL", fn);
+    if (C == 0 || T == 0) grad_values = nullptr;                 // (zeros: nothing is read)
+    if (grad_values != nullptr &&
+        (row == nullptr || ray == nullptr || (activate != 0 && values == nullptr) || (M > 0 && features == nullptr)))
+        return fail(SVOXT_ERR_INVALID, "%s: row / ray / values / features is NULL", fn);
+    if (misaligned(offsets, 8) || misaligned(features, 4) || misaligned(row, 4) || misaligned(ray, 4) || misaligned(values, 4) ||
+        misaligned(grad_values, 4) || misaligned(grad_basis, 4))
+        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets: 8 bytes, the others: 4)", fn);
+    const int rays_per_block = kLaunchBlock / bd;
+    const dim3 grid((unsigned)((Q + rays_per_block - 1) / rays_per_block));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kLaunchBlock), 0, (hipStream_t)stream, features, M, (int)K, C, bd, (int)opt->min_comp,
+                           (int)opt->max_comp, activate != 0, Q, T, offsets, row, ray, values, grad_values, grad_basis);
+    };
+    if (C == 3) launch(shade_bwd_basis_kernel<3>);
+    else launch(shade_bwd_basis_kernel<0>);
     return check_launch(fn);
 }
 

@@ -7,6 +7,7 @@
     out, alpha, w = composite(samples, f[:, -1], values)           # the two chained
     wmax = reduce_rows(samples, w.detach(), M, "max")              # [M]: a per-row statistic of per-sample values
     rgb, sigma = renderer.shade_samples(samples, features, rays)   # [T, C], [T]: the samples' colours and densities, no [T, K]
+                                                                   # (differentiable in features, and in rays.viewdirs / basis: DESIGN.md 4.30)
     trans = ray_scan(samples, att, "prod", exclusive=True)         # running sum / prod / max / min along every ray
     index, frac = ray_quantile(samples, w, [0.5])                  # where the running weight crosses q * total; quantile_depth: the depth
     sub, index = samples.select(w > 1e-3)                          # the kept samples as a RaySamples of its own; values[index] follows
@@ -275,14 +276,45 @@ def _refuse_transformation_matrices(what):
                        "direction is out of scope here (forward takes them; see INTEGRATION.md)")
 
 
+class _ViewBasisFunction(autograd.Function):
+    @staticmethod
+    def forward(ctx, viewdirs, renderer, rays, image_shape):
+        basis = _C.view_basis(renderer.tree._spec(renderer.tree.features.detach()), _rays_spec_from_rays(rays, image_shape),
+                              renderer._get_options())
+        ctx.renderer, ctx.rays = renderer, rays
+        ctx.save_for_backward(basis)
+        return basis
+
+    @staticmethod
+    @autograd.function.once_differentiable
+    def backward(ctx, grad_basis):
+        (basis,) = ctx.saved_tensors
+        r, rays = ctx.renderer, ctx.rays
+        with torch.no_grad():
+            spec = _rays_spec_from_rays(Rays(rays.origins.detach(), rays.dirs.detach(), rays.viewdirs.detach()))
+            spec.need_grad = False
+            gv = _X.view_basis_backward(r.tree._spec(r.tree.features.detach()), spec, r._get_options(), basis, grad_basis.contiguous())
+        return gv, None, None, None
+
+
 def _view_basis(self, rays: Rays, *, image_shape=None, transformation_matrices=None):
     """basis float32 [Q, basis_dim]: every ray's basis values exactly as the render kernels form them from its view
     direction -- SH 1 / 4 / 9 / 16 / 25, SG / ASG from tree.extra_data -- every component, whatever [min_comp, max_comp]
-    says.  RGBA: an empty [Q, 0] tensor.  A lane per ray, no march; not differentiable.  `image_shape` is accepted as the
-    neighbours take it and changes nothing."""
+    says.  RGBA: an empty [Q, 0] tensor.  A lane per ray, no march.  `image_shape` is accepted as the neighbours take it
+    and changes nothing.
+
+    Differentiable in rays.viewdirs when `rays` is an explicit Rays whose viewdirs require grad (the same forward, the
+    same bits): the backward is one kernel, a lane per ray, the analytic derivative of the expression the forward
+    evaluates summed over the components in ascending order (include/svoxt.h, svoxt_view_basis_bwd, is the definition;
+    DESIGN.md 4.30).  The derivative is taken in the three components as given -- the forward does not normalise, so
+    nothing is projected on the sphere; pinhole_rays' own normalisation is torch and supplies the rest of the chain.  Once
+    differentiable; not in the SG / ASG lobe parameters.  Every other call runs under no_grad as before."""
     if transformation_matrices is not None:
         _refuse_transformation_matrices("view_basis")
     self._require_gpu(True, "view_basis")
+    if isinstance(rays, Rays) and isinstance(rays.viewdirs, torch.Tensor) and rays.viewdirs.requires_grad and torch.is_grad_enabled() \
+            and int(self._get_options().format) != 0:
+        return _ViewBasisFunction.apply(rays.viewdirs, self, rays, image_shape)
     with torch.no_grad():
         return _C.view_basis(self.tree._spec(self.tree.features.detach()), _rays_spec_from_rays(rays, image_shape), self._get_options())
 
@@ -290,25 +322,38 @@ def _view_basis(self, rays: Rays, *, image_shape=None, transformation_matrices=N
 class _ShadeSamplesFunction(autograd.Function):
     @staticmethod
     def forward(ctx, features, samples, basis, opt, activate):
-        values, sigma = _C.shade_samples_fwd(features.contiguous(), samples.row, samples.ray, basis, samples.Q, opt, activate)
+        features = features.contiguous()
+        basis_grad = basis is not None and basis.requires_grad
+        if basis is not None:
+            basis = basis.detach().contiguous()
+        values, sigma = _C.shade_samples_fwd(features, samples.row, samples.ray, basis, samples.Q, opt, activate)
         ctx.samples, ctx.opt, ctx.activate, ctx.shape = samples, opt, activate, tuple(features.shape)
-        ctx.has_basis = basis is not None
+        ctx.has_basis, ctx.basis_grad = basis is not None, basis_grad
         ctx.set_materialize_grads(False)                         # (a None upstream gradient stays None: the kernel's null pointer)
-        ctx.save_for_backward(*((values,) if basis is None else (values, basis)))  # (sig: the forward's own output)
+        saved = (values,) if basis is None else (values, basis)  # (sig: the forward's own output)
+        ctx.save_for_backward(*(saved + (features,) if basis_grad else saved))      # (the table: only for grad_basis)
         return values, sigma
 
     @staticmethod
     def backward(ctx, grad_values, grad_sigma):
-        if not ctx.needs_input_grad[0]:
+        need_basis = ctx.basis_grad and ctx.needs_input_grad[2]
+        if need_basis and torch.is_grad_enabled():
+            raise RuntimeError("shade_samples: the gradient in `basis` is once differentiable (no double backward)")
+        if not (ctx.needs_input_grad[0] or need_basis):
             return None, None, None, None, None
         values = ctx.saved_tensors[0]
         basis = ctx.saved_tensors[1] if ctx.has_basis else None
         s = ctx.samples
         gv = None if grad_values is None else grad_values.contiguous()
         gs = None if grad_sigma is None else grad_sigma.contiguous()
-        plan = s.row_plan(ctx.shape[0])
-        grad = _C.shade_samples_bwd(ctx.shape, s.ray, basis, s.Q, ctx.opt, ctx.activate, values, gv, gs, plan.arrays)
-        return grad, None, None, None, None
+        grad = grad_basis = None
+        if ctx.needs_input_grad[0]:
+            plan = s.row_plan(ctx.shape[0])
+            grad = _C.shade_samples_bwd(ctx.shape, s.ray, basis, s.Q, ctx.opt, ctx.activate, values, gv, gs, plan.arrays)
+        if need_basis:
+            grad_basis = _X.shade_samples_bwd_basis(ctx.saved_tensors[2], s.offsets.contiguous(), s.row, s.ray, s.Q, ctx.opt, ctx.activate,
+                                                    values, gv)
+        return grad, None, grad_basis, None, None
 
 
 def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True,
@@ -323,7 +368,15 @@ def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, 
     :param rays: the Rays the samples were marched from (view_basis is called), or
     :param basis: what view_basis returned for them, float32 [Q, basis_dim]; RGBA needs neither
     Differentiable in `features`: the gradient is a full [M, K] table, every element written, summed per entry over
-    samples.row_plan(M) in reduce_rows' fixed order -- no [T, K] tensor, no atomics, the same bits in every run."""
+    samples.row_plan(M) in reduce_rows' fixed order -- no [T, K] tensor, no atomics, the same bits in every run.
+
+    Differentiable in `basis` too where it requires grad (and through `rays=` in rays.viewdirs: view_basis is then the
+    differentiable call): grad_basis[q, i] = the sum over ray q's samples in list order, and over c ascending inside a
+    sample, of (grad_values[k, c] * d[k, c]) * features[row[k], c * basis_dim + i], d the factor the table's gradient uses
+    (include/svoxt.h, svoxt_shade_samples_bwd_basis, is the definition).  basis_dim lanes a ray walk its
+    segment together; exact zeros outside [min_comp, max_comp] and for a ray without samples; no atomics, no [T, K]
+    tensor.  Each gradient is computed only when asked for; `features` is kept for the backward only when the basis
+    requires grad.  Once differentiable; transformation_matrices stay refused."""
     if transformation_matrices is not None:
         _refuse_transformation_matrices("shade_samples")
     if not isinstance(samples, RaySamples):
@@ -344,7 +397,10 @@ def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, 
     self._require_gpu(True, "shade_samples")
     _require_gpu("shade_samples", samples, features, basis)
     if int(opt.format) != 0:
-        basis = self.view_basis(rays) if basis is None else basis.detach().contiguous()
+        if basis is None:
+            basis = self.view_basis(rays)                        # (differentiable where rays.viewdirs requires grad)
+        elif not (basis.requires_grad and torch.is_grad_enabled()):
+            basis = basis.detach().contiguous()
         if basis.shape[0] != samples.Q:
             raise RuntimeError(f"shade_samples: `rays` holds {basis.shape[0]} rays, the samples were marched from {samples.Q}")
     return _ShadeSamplesFunction.apply(features, samples, basis, opt, bool(activate))
@@ -457,8 +513,8 @@ def sample_geometry(samples: RaySamples, rays: Rays):
     Every ray's gradient is written (zeros without samples); no atomics, the same bits in every run.  It is the gradient
     of the two PLANES: two terms of the order of step_size are left out by definition -- depth of a later crossing is its
     plane's z plus one step_size * delta_scale, length holds another, and delta_scale depends on dirs.  The crossing set
-    itself is piecewise constant in the rays.  The view-dependent half (view_basis in viewdirs, shade_samples in basis)
-    is not here: reach it through gather_rows and a basis written in torch."""
+    itself is piecewise constant in the rays.  The view-dependent half is view_basis in viewdirs and shade_samples in
+    basis: with both, a rendered colour is differentiable in a camera pose."""
     if not isinstance(samples, RaySamples):
         raise RuntimeError("sample_geometry: samples must be a RaySamples")
     if samples.face is None:
