@@ -1725,6 +1725,84 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
                             const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks,
                             float* grad, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- shade_samples with per-row rotations of the view direction (svoxt_viewrot.hip) ----
+ * What the render kernels do with tree.xform, for the per-sample interface: the basis of sample k is evaluated at its ray's
+ * view direction rotated by its FEATURE ROW's matrix, and the colour is differentiable in the table, in the matrices and in
+ * the directions.  The reference has no gradient in the matrices.  Explicit pointers, no svoxt_tree: features float32
+ * [M, K]; rotations float32 [M, rot_dim, rot_dim], rot_dim 3 or 4, of which the upper-left 3 x 3 is read; viewdirs float32
+ * [Q, 3]; extra float32 [extra_rows, extra_cols], the lobes of SG / ASG (tree.extra_data; not read for SH).  Float32
+ * without contraction, no float atomic, no [T, basis_dim] and no [T, K] array: every result is bit-identical from run to
+ * run.  Entry points added under ABI v22.  A format with a basis only: RGBA is refused (svoxt_shade_samples_* serve it).
+ *
+ * THE DEFINITION.  For sample k with row r = row[k] and ray q = ray[k], d = rot_dim, m = rotations + r * d * d and
+ * (v0, v1, v2) = viewdirs[q] as given -- nothing is normalised:
+ *     u0 = m[0] * v0 + m[1] * v1 + m[2] * v2;   u1 = m[d] * v0 + m[d + 1] * v1 + m[d + 2] * v2;
+ *     u2 = m[2 d] * v0 + m[2 d + 1] * v1 + m[2 d + 2] * v2                       (left to right, every operation rounded)
+ *     B[0 .. basis_dim) = the basis values svoxt_view_basis forms at the direction (u0, u1, u2)
+ *     tmp = 0.f;  for i = min_comp .. max_comp: tmp += B[i] * features[r, c * basis_dim + i]
+ *     values[k, c] = activate ? (float)(1.0 / (1.0 + (double)expf(-tmp))) : tmp;      sigma[k] = features[r, K - 1]
+ * A sample whose row is outside [0, M) gets values = 0 and sigma = 0, one whose ray is outside [0, Q) values = 0; neither
+ * takes part in any gradient.
+ *
+ *   svoxt_shade_rot_fwd       values float32 [T, C], sigma float32 [T].  A lane per (sample, channel) and one per sample for
+ *                             sigma; the SH sizes at compile time, the basis in registers; SG / ASG one lobe at a time.
+ *                             T = 0: a no-op.
+ *   svoxt_shade_rot_bwd       grad float32 [M, K] for grad_values [T, C] / grad_sigma [T] (either may be NULL: zeros).
+ *                             Every element is written.  Colour column (c, i), i in the component range: the sum over the
+ *                             row's samples of (grad_values[k, c] * d[k, c]) * B_i(k) -- activate == 0: grad_values[k, c] *
+ *                             B_i(k) --, d[k, c] = (float)((double)sig * (1.0 - (double)sig)), sig = values[k, c], B_i(k)
+ *                             recomputed from m and v by the forward's sequence; the sigma column: the sum of
+ *                             grad_sigma[k]; every other column 0.f.  The order is svoxt_reduce_rows' over the plan of
+ *                             `row` and M (samples ascending, chunks of SVOXT_ROW_CHUNK from 0.f, the partials in chunk
+ *                             order).  A lane per (row, column) loads the row's matrix once.  workspace:
+ *                             svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K).  M = 0: a no-op.
+ *   svoxt_shade_rot_bwd_dir   gu float32 [T, 3], the gradient in (u0, u1, u2) of every sample -- the one per-sample array
+ *                             the next two entry points read, 12 bytes a sample.  With t[k, c] = grad_values[k, c] *
+ *                             d[k, c] (activate == 0: grad_values[k, c]):
+ *                                 gB_i = 0.f;  for c = 0 .. C - 1: gB_i += t[k, c] * features[r, c * basis_dim + i]
+ *                                                                            (0.f for i outside [min_comp, max_comp])
+ *                                 gu[k, :] = svoxt_view_basis_bwd's sequence at the direction (u0, u1, u2) with grad_basis =
+ *                                            gB: the same table of partials, the same ascending order; SG multiplies by
+ *                                            B_i(k) recomputed by the forward's sequence where that operator reads its
+ *                                            saved output; ASG as there.
+ *                             Zeros for a sample outside its ranges and for grad_values NULL (or C = 0).  A lane per
+ *                             sample, C = 3 with t in registers.  T = 0: a no-op.
+ *   svoxt_shade_rot_bwd_rotations   grad_rotations float32 [M, rot_dim, rot_dim], every element written, zeros outside the
+ *                             3 x 3 block: grad[r, a, b] = the sum over the row's samples, in svoxt_reduce_rows' order over
+ *                             the same plan, of gu[k, a] * viewdirs[ray[k], b] (0.f for a ray outside [0, Q)).  A lane per
+ *                             (row, a, b).  workspace: svoxt_shade_samples_bwd_workspace_bytes(n_chunks, rot_dim *
+ *                             rot_dim).  M = 0: a no-op.
+ *   svoxt_shade_rot_bwd_viewdirs    grad_vdirs float32 [Q, 3], every ray written, zeros without samples.  A lane per ray,
+ *                             three accumulators from 0.f, over k = max(offsets[q], 0) .. min(offsets[q + 1], T) - 1 in
+ *                             list order; a sample with ray[k] != q or a row outside [0, M) is passed over; else
+ *                                 for a = 0, 1, 2:  for b = 0, 1, 2:  acc[b] += m[a * d + b] * gu[k, a]
+ *                             Q = 0: a no-op.
+ * Checked, before any launch: options not NULL, a format with a basis, basis_dim in [1, 25] (SH: 1, 4, 9, 16 or 25),
+ * min_comp / max_comp inside [0, basis_dim), SG / ASG: extra not NULL with at least basis_dim rows and 4 / 11 columns;
+ * rot_dim 3 or 4; K >= 1; T, M, Q in [0, 2^31); T * (C + 1) and M * K below 2^38; n_long / n_chunks as svoxt_row_plan_long;
+ * what is read or written not NULL; alignment (4 bytes; offsets 8); no output overlapping an input (or the other output);
+ * with n_long > 0 the workspace not NULL and at least the query's size.  No allocation, no synchronisation. */
+int svoxt_shade_rot_fwd(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const float* extra,
+                        int32_t extra_rows, int32_t extra_cols, const float* rotations, int32_t rot_dim, const float* viewdirs,
+                        int64_t Q, const int32_t* row, const int32_t* ray, int64_t T, int32_t activate, float* values,
+                        float* sigma, void* stream);
+int svoxt_shade_rot_bwd(const svoxt_options* opt, int64_t M, int32_t K, const float* extra, int32_t extra_rows,
+                        int32_t extra_cols, const float* rotations, int32_t rot_dim, const float* viewdirs, int64_t Q,
+                        const int32_t* row, const int32_t* ray, int64_t T, int32_t activate, const float* values,
+                        const float* grad_values, const float* grad_sigma, const int32_t* row_ptr, const int32_t* perm,
+                        const int32_t* long_rows, const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long,
+                        int64_t n_chunks, float* grad, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_shade_rot_bwd_dir(const float* features, int64_t M, int32_t K, const svoxt_options* opt, const float* extra,
+                            int32_t extra_rows, int32_t extra_cols, const float* rotations, int32_t rot_dim,
+                            const float* viewdirs, int64_t Q, const int32_t* row, const int32_t* ray, int64_t T,
+                            int32_t activate, const float* values, const float* grad_values, float* gu, void* stream);
+int svoxt_shade_rot_bwd_rotations(const float* gu, const float* viewdirs, int64_t Q, const int32_t* ray, int64_t T, int64_t M,
+                                  int32_t rot_dim, const int32_t* row_ptr, const int32_t* perm, const int32_t* long_rows,
+                                  const int32_t* long_chunk_ptr, const int32_t* chunk_long, int64_t n_long, int64_t n_chunks,
+                                  float* grad_rotations, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_shade_rot_bwd_viewdirs(const float* gu, const float* rotations, int32_t rot_dim, int64_t M, const int64_t* offsets,
+                                 const int32_t* row, const int32_t* ray, int64_t T, int64_t Q, float* grad_vdirs, void* stream);
+
 /* ---- interp: a trilinear lookup over the leaves around a point (svoxt_interp.hip; not in the reference)
  * A lookup that is continuous in position where svoxt_query_fwd is piecewise constant, with the gradients with respect
  * to the table and to the point.  Gather only, a fixed float32 order, no float atomic: every result is bit-identical

@@ -26,9 +26,9 @@ SOURCES = ["svoxt_kernels.hip", "svoxt_bwd.hip", "svoxt_build.hip", "svoxt_motio
            "svoxt_p2v.hip", "svoxt_prune.hip", "svoxt_gridw.hip", "svoxt_quant.hip", "svoxt_merge.hip", "svoxt_assign.hip",
            "svoxt_optim.hip", "svoxt_subdivide.hip", "svoxt_neighbors.hip", "svoxt_depthmom.hip",
            "svoxt_distort.hip", "svoxt_samples.hip", "svoxt_rows.hip", "svoxt_rowgrad.hip", "svoxt_shade.hip", "svoxt_scan.hip",
-           "svoxt_interp.hip", "svoxt_cut.hip"]
+           "svoxt_interp.hip", "svoxt_cut.hip", "svoxt_viewrot.hip"]
 HEADERS = ["svoxt_device.h", "svoxt_host.h", "svoxt_launch.h", "svoxt_lists.h", "svoxt_fwd_kernels.h", "svoxt_bwd_kernels.h",
-           "svoxt_misc_kernels.h", "svoxt_sort.h", "svoxt_raylists.h", "svoxt_raysweep.h", "svoxt_rowwalk.h", "svoxt_listemit.h", "svoxt_tile_reduce.inc", "svoxt_wave.h", "svoxt_workspace.h", os.path.join("..", "..", "include", "svoxt.h")]
+           "svoxt_misc_kernels.h", "svoxt_sort.h", "svoxt_raylists.h", "svoxt_raysweep.h", "svoxt_rowwalk.h", "svoxt_shade.h", "svoxt_listemit.h", "svoxt_tile_reduce.inc", "svoxt_wave.h", "svoxt_workspace.h", os.path.join("..", "..", "include", "svoxt.h")]
 
 # -ffp-contract=off is part of the numerical contract (svoxt_device.h): the
 # stepping arithmetic must not be fused into FMAs.

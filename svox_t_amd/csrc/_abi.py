@@ -244,6 +244,15 @@ EXPORTS = {
                                                _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "svoxt_view_basis_bwd": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp, _vp, _vp]),
     "svoxt_shade_samples_bwd_basis": (ctypes.c_int, [_vp, _i64, _i32, _P(_COptions), _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "svoxt_shade_rot_fwd": (ctypes.c_int, [_vp, _i64, _i32, _P(_COptions), _vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32,
+                                           _vp, _vp, _vp]),
+    "svoxt_shade_rot_bwd": (ctypes.c_int, [_P(_COptions), _i64, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "svoxt_shade_rot_bwd_dir": (ctypes.c_int, [_vp, _i64, _i32, _P(_COptions), _vp, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64,
+                                               _i32, _vp, _vp, _vp, _vp]),
+    "svoxt_shade_rot_bwd_rotations": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp,
+                                                     _vp, _i64, _vp]),
+    "svoxt_shade_rot_bwd_viewdirs": (ctypes.c_int, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "svoxt_interp_stencil": (ctypes.c_int, [_P(_CTree), _vp, _i64, _i32, _vp, _vp, _vp]),
     "svoxt_interp_rows_fwd": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
     "svoxt_interp_rows_bwd_workspace_bytes": (_i64, [_i64, _i32]),

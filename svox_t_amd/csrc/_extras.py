@@ -2038,6 +2038,146 @@ def shade_samples_bwd_basis(features, offsets, row, ray, Q: int, opt: RenderOpti
 
 
 # ---------------------------------------------------------------------------
+# shade_samples with per-row rotations of the view direction (svoxt_viewrot.hip)
+# ---------------------------------------------------------------------------
+def _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt):
+    """The checks the rotated call's directions share; returns (M, K, T, C, basis_dim, device, the C ABI's view-side arguments:
+    extra, extra_rows, extra_cols, rotations, rot_dim, viewdirs, Q)."""
+    if int(opt.format) == 0:
+        raise RuntimeError("rotations: RGBA has no basis to rotate (shade_samples_fwd serves it)")
+    if isinstance(features, tuple):                              # (M, K) of a table whose values are not read
+        M, K = (int(v) for v in features)
+        if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
+            raise RuntimeError("row must be int32 [T]")
+        T, dev = row.shape[0], row.device
+        _check_per_sample(row, "row", T, dev, dtype=torch.int32)
+        _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+        C, bd = _shade_dims(opt, K)
+        if M >= 1 << 31 or T >= 1 << 31 or Q >= 1 << 31:
+            raise RuntimeError("M, T and Q must be below 2^31")
+    else:
+        M, K, T, C, bd, dev = _check_shade(features, row, ray, None, Q, opt, with_basis=False)
+    if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
+            or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)) or rotations.shape[0] != M:
+        raise RuntimeError(f"rotations must be float32 [M, 3, 3] or [M, 4, 4] with M = {M}, one matrix per feature row")
+    if not isinstance(viewdirs, torch.Tensor) or viewdirs.dtype != torch.float32 or tuple(viewdirs.shape) != (Q, 3):
+        raise RuntimeError(f"viewdirs must be float32 [Q, 3] with Q = {Q}")
+    for name, x in (("rotations", rotations), ("viewdirs", viewdirs)):
+        _check_input(x, name)
+        if x.device != dev:
+            raise RuntimeError(f"{name} must be on the device of the features")
+    rows = cols = 0
+    if int(opt.format) in (2, 3):
+        if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.dim() != 2 or extra.device != dev:
+            raise RuntimeError("SG / ASG need the lobes: extra float32 [basis_dim, >= 4 / 11] on the device of the features")
+        _check_input(extra, "extra")
+        rows, cols = extra.shape
+    else:
+        extra = None
+    return M, K, T, C, bd, dev, (_ptr(extra), rows, cols, _ptr(rotations), rotations.shape[1], _ptr(viewdirs), Q)
+
+
+def shade_rot_fwd(features, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool = True):
+    """(values float32 [T, C], sigma float32 [T]) of svoxt_shade_rot_fwd: shade_samples_fwd with the basis of rotations[row] *
+    viewdirs[ray].  rotations float32 [M, 3, 3] or [M, 4, 4], viewdirs float32 [Q, 3], extra: the lobes of SG / ASG."""
+    M, K, T, C, bd, dev, view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
+    co = _pack_opts(opt)
+    with _on(dev):
+        values = torch.empty((T, C), dtype=torch.float32, device=dev)
+        sigma = torch.empty((T,), dtype=torch.float32, device=dev)
+        _call("svoxt_shade_rot_fwd", _ptr(features), M, K, ctypes.byref(co), *view, _ptr(row), _ptr(ray), T, 1 if activate else 0,
+              _ptr(values), _ptr(sigma), _stream(dev))
+    return values, sigma
+
+
+def shade_rot_bwd(shape, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool, values, grad_values,
+                  grad_sigma, plan: RowPlanArrays) -> torch.Tensor:
+    """grad float32 [M, K] of svoxt_shade_rot_bwd for a table of `shape` = (M, K) over the samples' row plan (the table's
+    values are not read); values is the forward's output, grad_values [T, C] / grad_sigma [T] may be None (zeros)."""
+    if not isinstance(plan, RowPlanArrays):
+        raise RuntimeError("plan must be a row plan")
+    M, K, T, C, bd, dev, view = _check_rot(tuple(shape), row, ray, rotations, viewdirs, extra, Q, opt)
+    if plan.M != M or plan.T != T:
+        raise RuntimeError("the plan must be built for the table's M rows and the T samples")
+    _check_per_sample(values, "values", T, dev, C)
+    if grad_values is not None:
+        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    if grad_sigma is not None:
+        _check_per_sample(grad_sigma, "grad_sigma", T, dev)
+    co = _pack_opts(opt)
+    with _on(dev):
+        grad = torch.empty((M, K), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], K)
+        ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
+        _call("svoxt_shade_rot_bwd", ctypes.byref(co), M, K, *view, _ptr(row), _ptr(ray), T, 1 if activate else 0, _ptr(values),
+              _ptr(grad_values), _ptr(grad_sigma), *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
+    return grad
+
+
+def shade_rot_bwd_dir(features, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool, values,
+                      grad_values) -> torch.Tensor:
+    """gu float32 [T, 3] of svoxt_shade_rot_bwd_dir: the gradient in every sample's rotated direction, the one scratch the
+    gradients in the rotations and in the view directions read; grad_values [T, C] may be None (zeros)."""
+    M, K, T, C, bd, dev, view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
+    _check_per_sample(values, "values", T, dev, C)
+    if grad_values is not None:
+        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    co = _pack_opts(opt)
+    with _on(dev):
+        gu = torch.empty((T, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_shade_rot_bwd_dir", _ptr(features), M, K, ctypes.byref(co), *view, _ptr(row), _ptr(ray), T, 1 if activate else 0,
+              _ptr(values), _ptr(grad_values), _ptr(gu), _stream(dev))
+    return gu
+
+
+def shade_rot_bwd_rotations(gu, viewdirs, ray, shape, plan: RowPlanArrays) -> torch.Tensor:
+    """grad_rotations float32 of `shape` = (M, d, d) of svoxt_shade_rot_bwd_rotations: grad[m, a, b] = the sum of gu[k, a] *
+    viewdirs[ray[k], b] over the row plan; zeros outside the 3 x 3 block of a 4 x 4."""
+    if not isinstance(plan, RowPlanArrays):
+        raise RuntimeError("plan must be a row plan")
+    M, d, d2 = (int(v) for v in shape)
+    T = plan.T
+    if plan.M != M or d != d2 or d not in (3, 4):
+        raise RuntimeError("the plan must be built for the M matrices of [M, 3, 3] or [M, 4, 4]")
+    dev = plan.row_ptr.device
+    _check_per_sample(gu, "gu", T, dev, 3)
+    _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+    if not isinstance(viewdirs, torch.Tensor) or viewdirs.dtype != torch.float32 or viewdirs.dim() != 2 or viewdirs.shape[1] != 3 \
+            or viewdirs.device != dev:
+        raise RuntimeError("viewdirs must be float32 [Q, 3] on the device of the plan")
+    _check_input(viewdirs, "viewdirs")
+    with _on(dev):
+        grad = torch.empty((M, d, d), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], d * d)
+        ws = _workspace(dev, nbytes, "shade_samples: chunks must be below 2^31")
+        _call("svoxt_shade_rot_bwd_rotations", _ptr(gu), _ptr(viewdirs), viewdirs.shape[0], _ptr(ray), T, M, d,
+              *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
+    return grad
+
+
+def shade_rot_bwd_viewdirs(gu, rotations, offsets, row, ray) -> torch.Tensor:
+    """grad_viewdirs float32 [Q, 3] of svoxt_shade_rot_bwd_viewdirs: per ray, over its segment in list order,
+    acc[b] += rotations[row[k], a, b] * gu[k, a]; zeros for a ray without samples."""
+    if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
+        raise RuntimeError("row must be int32 [T]")
+    T = row.shape[0]
+    Q = _check_csr(offsets, T)
+    dev = offsets.device
+    _check_per_sample(row, "row", T, dev, dtype=torch.int32)
+    _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
+    _check_per_sample(gu, "gu", T, dev, 3)
+    if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
+            or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)) or rotations.device != dev:
+        raise RuntimeError("rotations must be float32 [M, 3, 3] or [M, 4, 4] on the device of offsets")
+    _check_input(rotations, "rotations")
+    with _on(dev):
+        gv = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        _call("svoxt_shade_rot_bwd_viewdirs", _ptr(gu), _ptr(rotations), rotations.shape[1], rotations.shape[0], _ptr(offsets), _ptr(row),
+              _ptr(ray), T, Q, _ptr(gv), _stream(dev))
+    return gv
+
+
+# ---------------------------------------------------------------------------
 # interp: a trilinear lookup over the leaves around a point (svoxt_interp.hip; not in the reference; DESIGN.md 4.26)
 # ---------------------------------------------------------------------------
 INTERP_FILLS = {"self": 0, "zero": 1}                             # SVOXT_INTERP_FILL_* (include/svoxt.h)

@@ -8,6 +8,8 @@
     wmax = reduce_rows(samples, w.detach(), M, "max")              # [M]: a per-row statistic of per-sample values
     rgb, sigma = renderer.shade_samples(samples, features, rays)   # [T, C], [T]: the samples' colours and densities, no [T, K]
                                                                    # (differentiable in features, and in rays.viewdirs / basis: DESIGN.md 4.30)
+    rgb, sigma = renderer.shade_samples(samples, features, rays, rotations=mats)   # the basis at mats[row] @ viewdirs[ray], what forward's
+                                                                   # transformation_matrices do; differentiable in mats too
     trans = ray_scan(samples, att, "prod", exclusive=True)         # running sum / prod / max / min along every ray
     index, frac = ray_quantile(samples, w, [0.5])                  # where the running weight crosses q * total; quantile_depth: the depth
     sub, index = samples.select(w > 1e-3)                          # the kept samples as a RaySamples of its own; values[index] follows
@@ -273,7 +275,8 @@ VolumeRenderer.ray_samples = _ray_samples
 # ------------------------------------------------------------------------------------------------ shading the samples
 def _refuse_transformation_matrices(what):
     raise RuntimeError(f"VolumeRenderer.{what}: transformation_matrices are not served: the per-leaf rotation of the view "
-                       "direction is out of scope here (forward takes them; see INTEGRATION.md)")
+                       "direction is out of scope here (forward takes them; shade_samples takes them as `rotations=`, with "
+                       "`rays=`; see INTEGRATION.md)")
 
 
 class _ViewBasisFunction(autograd.Function):
@@ -356,8 +359,67 @@ class _ShadeSamplesFunction(autograd.Function):
         return grad, None, grad_basis, None, None
 
 
+class _ShadeRotatedFunction(autograd.Function):
+    """shade_samples(rotations=): the rotated call's own Function; the plain call keeps _ShadeSamplesFunction."""
+
+    @staticmethod
+    def forward(ctx, features, rotations, viewdirs, samples, extra, opt, activate):
+        features, rotations, viewdirs = features.contiguous(), rotations.contiguous(), viewdirs.contiguous()
+        values, sigma = _X.shade_rot_fwd(features, samples.row, samples.ray, rotations, viewdirs, extra, samples.Q, opt, activate)
+        ctx.samples, ctx.extra, ctx.opt, ctx.activate = samples, extra, opt, activate
+        ctx.view_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        ctx.set_materialize_grads(False)                         # (a None upstream gradient stays None: the kernel's null pointer)
+        ctx.shape = tuple(features.shape)
+        saved = (values, viewdirs, rotations)                    # (sig: the forward's own output)
+        ctx.save_for_backward(*(saved + (features,) if ctx.view_grad else saved))      # (the table: only for gu)
+        return values, sigma
+
+    @staticmethod
+    def backward(ctx, grad_values, grad_sigma):
+        need_f, need_r, need_v = ctx.needs_input_grad[:3]
+        if not (need_f or need_r or need_v):
+            return (None,) * 7
+        if torch.is_grad_enabled():
+            raise RuntimeError("shade_samples: the gradients of the rotated call are once differentiable (no double backward)")
+        values, viewdirs, rotations = ctx.saved_tensors[:3]
+        s, M = ctx.samples, ctx.shape[0]
+        gv = None if grad_values is None else grad_values.contiguous()
+        gs = None if grad_sigma is None else grad_sigma.contiguous()
+        grad = grad_rot = grad_view = None
+        if need_f:
+            grad = _X.shade_rot_bwd(ctx.shape, s.row, s.ray, rotations, viewdirs, ctx.extra, s.Q, ctx.opt, ctx.activate, values, gv, gs,
+                                    s.row_plan(M).arrays)
+        if need_r or need_v:
+            gu = _X.shade_rot_bwd_dir(ctx.saved_tensors[3], s.row, s.ray, rotations, viewdirs, ctx.extra, s.Q, ctx.opt, ctx.activate,
+                                      values, gv)
+            if need_r:
+                grad_rot = _X.shade_rot_bwd_rotations(gu, viewdirs, s.ray, tuple(rotations.shape), s.row_plan(M).arrays)
+            if need_v:
+                grad_view = _X.shade_rot_bwd_viewdirs(gu, rotations, s.offsets.contiguous(), s.row, s.ray)
+        return grad, grad_rot, grad_view, None, None, None, None
+
+
+def _shade_rotated(self, samples, features, rays, rotations, opt, activate):
+    """shade_samples(rotations=) for a format with a basis: the checks of the view side, then the rotated Function."""
+    if not isinstance(rays, Rays):
+        raise RuntimeError("shade_samples: `rotations` needs `rays`, the Rays the samples were marched from, with explicit viewdirs "
+                           "(camera-mode and NDC rays are not served: their directions are formed inside the kernels)")
+    v = rays.viewdirs
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (samples.Q, 3):
+        raise RuntimeError(f"shade_samples: rays.viewdirs must be float32 [Q, 3] with Q = {samples.Q}, the rays the samples were marched from")
+    if v.device != features.device:
+        raise RuntimeError("shade_samples: the rays must be on the device of the features")
+    self._require_gpu(True, "shade_samples")
+    _require_gpu("shade_samples", samples, features, rotations, v)
+    extra = None
+    if int(opt.format) in (2, 3):                                # SG / ASG: the lobes
+        extra = self.tree.extra_data
+        extra = None if extra is None else extra.detach().contiguous()
+    return _ShadeRotatedFunction.apply(features, rotations, v, samples, extra, opt, activate)
+
+
 def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True,
-                   transformation_matrices=None):
+                   transformation_matrices=None, rotations=None):
     """(values float32 [T, C], sigma float32 [T]): the colour of every sample -- the basis of its ray's view direction
     dotted into its feature row's coefficients over [min_comp, max_comp], then the sigmoid (activate=False: the dot
     product itself) -- and its density features[row, -1].  C = out_data_dim - 1: K - 1 for RGBA, (K - 1) // basis_dim
@@ -376,7 +438,20 @@ def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, 
     (include/svoxt.h, svoxt_shade_samples_bwd_basis, is the definition).  basis_dim lanes a ray walk its
     segment together; exact zeros outside [min_comp, max_comp] and for a ray without samples; no atomics, no [T, K]
     tensor.  Each gradient is computed only when asked for; `features` is kept for the backward only when the basis
-    requires grad.  Once differentiable; transformation_matrices stay refused."""
+    requires grad.  Once differentiable.
+
+    :param rotations: float32 [M, 3, 3] or [M, 4, 4] (the upper-left 3 x 3 is read), one matrix per FEATURE ROW, indexed as
+        forward(transformation_matrices=) indexes it -- what warp_vertices(...)[1] or blend_transformation_matrix
+        returns: the basis is evaluated at u = rotations[row[k]] @ viewdirs[ray[k]] for every sample, nothing normalised
+        (include/svoxt.h, svoxt_shade_rot_fwd, is the definition; DESIGN.md 4.31).  Needs `rays`, an explicit Rays;
+        excludes `basis`.  RGBA ignores it, as forward does.  A Function of its own, differentiable once in `features`
+        (the same full [M, K] table over the row plan, the basis values recomputed from the matrix and the direction),
+        in `rotations` (grad[m, a, b] = the sum over the row plan, in reduce_rows' order, of gu[k, a] * viewdirs[ray[k], b])
+        and in rays.viewdirs (per ray in list order, acc[b] += rotations[row[k], a, b] * gu[k, a]); gu float32 [T, 3], 12
+        bytes a sample, is view_basis' backward at u with grad_basis[i] = sum_c (grad_values[k, c] * d[k, c]) *
+        features[row[k], c * basis_dim + i].  No atomics, the same bits in every run; each gradient only when asked for;
+        `features` is kept for the backward only when rotations or viewdirs require grad.  Without `rotations` nothing
+        changes.  The keyword `transformation_matrices` stays refused here and on view_basis (a per-ray basis has no row)."""
     if transformation_matrices is not None:
         _refuse_transformation_matrices("shade_samples")
     if not isinstance(samples, RaySamples):
@@ -386,8 +461,21 @@ def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, 
     if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
         raise RuntimeError("shade_samples: features must be float32 [M, K], K >= 1")
     opt = self._get_options()
+    if rotations is not None:
+        if basis is not None:
+            raise RuntimeError("shade_samples: `rotations` and `basis` exclude each other: a per-ray basis has no row to rotate by "
+                               "(pass `rays`)")
+        if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
+                or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)):
+            raise RuntimeError("shade_samples: rotations must be float32 [M, 3, 3] or [M, 4, 4], one matrix per feature row")
+        if rotations.shape[0] != features.shape[0]:
+            raise RuntimeError(f"shade_samples: rotations holds {rotations.shape[0]} matrices, the feature table {features.shape[0]} rows")
+        if rotations.device != features.device:
+            raise RuntimeError("shade_samples: rotations must be on the device of the features")
+        if int(opt.format) != 0:
+            return _shade_rotated(self, samples, features, rays, rotations, opt, bool(activate))
     if int(opt.format) == 0:
-        basis = None
+        basis = None                                             # (RGBA: no basis, and rotations rotate nothing -- uses_xform)
     elif basis is None:
         if rays is None:
             raise RuntimeError("shade_samples: a format with a basis needs `rays` or a `basis` from view_basis")
@@ -410,11 +498,13 @@ VolumeRenderer.view_basis = _view_basis
 VolumeRenderer.shade_samples = _shade_samples
 
 
-def shade_samples(renderer: VolumeRenderer, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True):
-    """renderer.shade_samples(samples, features, rays, basis=basis, activate=activate) as a function, beside gather_rows."""
+def shade_samples(renderer: VolumeRenderer, samples: RaySamples, features=None, rays: Rays = None, *, basis=None, activate=True,
+                  rotations=None):
+    """renderer.shade_samples(samples, features, rays, basis=basis, activate=activate, rotations=rotations) as a function,
+    beside gather_rows."""
     if not isinstance(renderer, VolumeRenderer):
         raise RuntimeError("shade_samples: the first argument must be the VolumeRenderer whose format shades the samples")
-    return renderer.shade_samples(samples, features, rays, basis=basis, activate=activate)
+    return renderer.shade_samples(samples, features, rays, basis=basis, activate=activate, rotations=rotations)
 
 
 def _require_gpu(what, samples, *tensors):
