@@ -37,6 +37,7 @@
 namespace svoxt {
 
 constexpr int kAssignBlock = kLaunchBlock;
+static_assert(kAssignBlock == kLaunchBlock, "assign_copy_kernel and assign_reduce_kernel index by launch_lane()");
 constexpr int kMaxWalk = 128;            // levels a corner walk follows before it gives up (NaN): a malformed table
 enum { AS_LAST = SVOXT_ASSIGN_LAST, AS_SUM = SVOXT_ASSIGN_SUM, AS_MEAN = SVOXT_ASSIGN_MEAN, AS_MAX = SVOXT_ASSIGN_MAX,
        AS_MIN = SVOXT_ASSIGN_MIN };
@@ -95,7 +96,7 @@ template <typename V>
 __global__ void __launch_bounds__(kAssignBlock)
 assign_copy_kernel(const int32_t* __restrict__ row, const int32_t* __restrict__ winner, int64_t Q, int lpr,
                    const V* __restrict__ values, V* __restrict__ table) {
-    const int64_t t = (int64_t)blockIdx.x * kAssignBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t q = t / lpr;
     const int j = (int)(t - q * lpr);
     if (q >= Q) return;
@@ -140,7 +141,7 @@ __global__ void __launch_bounds__(kAssignBlock)
 assign_reduce_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ heads,
                      const uint32_t* __restrict__ rank, int64_t Q, uint32_t M, int lpr, int op, const V* __restrict__ values,
                      V* __restrict__ table) {
-    const int64_t t = (int64_t)blockIdx.x * kAssignBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t g = t / lpr;
     const int j = (int)(t - g * lpr);
     if (g >= (int64_t)rank[Q]) return;
@@ -266,7 +267,7 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
         hipLaunchKernelGGL((n2 ? assign_locate_kernel<true, false> : assign_locate_kernel<false, false>), dim3(launch_blocks(Q)),
                            dim3(kAssignBlock), 0, st, tr, points, Q, sp.row, sp.winner, (uint32_t*)nullptr, row_count);
         if ((rc = check_launch(fn))) return rc;
-        const dim3 grid(launch_blocks(Q * lpr));
+        const dim3 grid = launch_grid(Q * lpr);
         if (vec)
             hipLaunchKernelGGL(assign_copy_kernel<float4a>, grid, dim3(kAssignBlock), 0, st, sp.row, sp.winner, Q, lpr,
                                reinterpret_cast<const float4a*>(values), reinterpret_cast<float4a*>(table));
@@ -295,7 +296,7 @@ int svoxt_assign_leaves(const svoxt_tree* tree, const float* points, int64_t Q, 
     hipLaunchKernelGGL(scatter_ranked_kernel<uint32_t>, dim3(launch_blocks(Q)), dim3(kLaunchBlock), 0, st, flag, rank, Q, Q, sp.heads);
     if ((rc = check_launch(fn))) return rc;
     const int64_t groups = Q < M ? Q : M;                          // an upper bound: the kernel reads the number itself
-    const dim3 grid(launch_blocks(groups * lpr));
+    const dim3 grid = launch_grid(groups * lpr);
     if (vec)
         hipLaunchKernelGGL(assign_reduce_kernel<float4a>, grid, dim3(kAssignBlock), 0, st, sp.keys[cur], sp.vals[cur], sp.heads, rank, Q,
                            (uint32_t)M, lpr, (int)reduce, reinterpret_cast<const float4a*>(values), reinterpret_cast<float4a*>(table));

@@ -160,7 +160,7 @@ template <typename V>
 __global__ void __launch_bounds__(kLaunchBlock)
 interp_rows_fwd_kernel(const V* __restrict__ table, int64_t M, int KU, const int32_t* __restrict__ rows, const float* __restrict__ weights,
                        int64_t Q, const int32_t* __restrict__ cols, int CU, int lg, V* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t q = t >> lg;
     if (q >= Q) return;
     const int s = (int)(t & ((1 << lg) - 1));
@@ -332,12 +332,12 @@ int svoxt_interp_rows_fwd(const float* table, int64_t M, int32_t K, const int32_
     const int units = vec ? K / 4 : C;
     int lg = 0;                                                  // lanes per point: the power of two from the units up, 64 at most
     while ((1 << lg) < units && lg < 6) ++lg;
-    const unsigned blocks = launch_blocks(Q << lg);
+    const dim3 blocks = launch_grid(Q << lg);
     if (vec)
-        hipLaunchKernelGGL(interp_rows_fwd_kernel<float4i>, dim3(blocks), dim3(kLaunchBlock), 0, st, reinterpret_cast<const float4i*>(table), M,
+        hipLaunchKernelGGL(interp_rows_fwd_kernel<float4i>, blocks, dim3(kLaunchBlock), 0, st, reinterpret_cast<const float4i*>(table), M,
                            units, rows, weights, Q, (const int32_t*)nullptr, units, lg, reinterpret_cast<float4i*>(out));
     else
-        hipLaunchKernelGGL(interp_rows_fwd_kernel<float>, dim3(blocks), dim3(kLaunchBlock), 0, st, table, M, (int)K, rows, weights, Q, cols, C,
+        hipLaunchKernelGGL(interp_rows_fwd_kernel<float>, blocks, dim3(kLaunchBlock), 0, st, table, M, (int)K, rows, weights, Q, cols, C,
                            lg, out);
     return check_launch(fn);
 }

@@ -218,7 +218,9 @@ __global__ void __launch_bounds__(kTvBlock)
 tv_rows_kernel(const float* __restrict__ f, int64_t M, int K, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ other,
                const uint8_t* __restrict__ meta, const int32_t* __restrict__ cols, int Kc, const float* __restrict__ wtab, float divisor,
                float scale, float* __restrict__ partials, float* G) {
-    const int64_t t = (int64_t)blockIdx.x * kTvBlock + threadIdx.x;
+    const int64_t blk = launch_block();
+    if (blk * kTvBlock >= M * Kc) return;                        // (a workgroup the grid's fold added: it has no partial)
+    const int64_t t = blk * kTvBlock + threadIdx.x;
     const int64_t r = t / Kc;
     float l = 0.f;
     if (r < M) {
@@ -263,7 +265,7 @@ tv_rows_kernel(const float* __restrict__ f, int64_t M, int K, const int32_t* __r
             if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
             __syncthreads();
         }
-        if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+        if (threadIdx.x == 0) partials[blk] = red[0];
     }
 }
 
@@ -284,10 +286,10 @@ tv_loss_kernel(const float* __restrict__ partials, int64_t B, float divisor, flo
 }
 
 template <int P, int MODE>
-static void tv_launch(unsigned blocks, hipStream_t st, const float* f, int64_t M, int K, const int32_t* row_ptr, const int32_t* other,
+static void tv_launch(dim3 blocks, hipStream_t st, const float* f, int64_t M, int K, const int32_t* row_ptr, const int32_t* other,
                       const uint8_t* meta, const int32_t* cols, int Kc, const float* wtab, float divisor, float scale, float* partials,
                       float* G) {
-    hipLaunchKernelGGL((tv_rows_kernel<P, MODE>), dim3(blocks), dim3(kTvBlock), 0, st, f, M, K, row_ptr, other, meta, cols, Kc, wtab,
+    hipLaunchKernelGGL((tv_rows_kernel<P, MODE>), blocks, dim3(kTvBlock), 0, st, f, M, K, row_ptr, other, meta, cols, Kc, wtab,
                        divisor, scale, partials, G);
 }
 
@@ -454,7 +456,7 @@ int svoxt_tv_rows(const float* features, int64_t M, int32_t K, const int32_t* ro
     }
     const int64_t B = (M * Kc + kTvBlock - 1) / kTvBlock;
     float* partials = static_cast<float*>(workspace);
-    const unsigned blocks = (unsigned)B;
+    const dim3 blocks = launch_grid(M * Kc, kTvBlock);           // B workgroups (and what the fold adds: they leave at once)
 #define SVOXT_TV_GO(P, MODE) tv_launch<P, MODE>(blocks, st, features, M, K, row_ptr, other, meta, cols, Kc, depth_weights, divisor, scale, partials, table)
     if (p == 2) {
         if (mode == TV_LOSS) SVOXT_TV_GO(2, TV_LOSS); else if (mode == TV_LOSS_GRAD) SVOXT_TV_GO(2, TV_LOSS_GRAD); else SVOXT_TV_GO(2, TV_ACCUMULATE);

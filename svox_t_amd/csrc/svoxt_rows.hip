@@ -139,7 +139,7 @@ row_chunk_long_kernel(const int32_t* __restrict__ long_chunk_ptr, int64_t n_long
 __global__ void __launch_bounds__(kLaunchBlock)
 gather_rows_kernel(const float* __restrict__ table, int64_t M, int K, const int32_t* __restrict__ row, int64_t T,
                    const int32_t* __restrict__ cols, int Kc, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t k = t / Kc;
     if (k >= T) return;
     const int j = (int)(t - k * Kc);
@@ -152,7 +152,7 @@ gather_rows_kernel(const float* __restrict__ table, int64_t M, int K, const int3
 __global__ void __launch_bounds__(kLaunchBlock)
 gather_rows4_kernel(const float4* __restrict__ table, int64_t M, int K4, const int32_t* __restrict__ row, int64_t T,
                     float4* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t k = t / K4;
     if (k >= T) return;
     const int j = (int)(t - k * K4);
@@ -265,10 +265,10 @@ int svoxt_gather_rows(const float* table, int64_t M, int32_t K, const int32_t* r
     hipStream_t st = (hipStream_t)stream;
     if (cols == nullptr && K % 4 == 0 && !misaligned(table, 16) && !misaligned(out, 16)) {
         const int K4 = K / 4;
-        hipLaunchKernelGGL(gather_rows4_kernel, dim3(launch_blocks(T * K4)), dim3(kLaunchBlock), 0, st, reinterpret_cast<const float4*>(table),
+        hipLaunchKernelGGL(gather_rows4_kernel, launch_grid(T * K4), dim3(kLaunchBlock), 0, st, reinterpret_cast<const float4*>(table),
                            M, K4, row, T, reinterpret_cast<float4*>(out));
     } else {
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(launch_blocks(T * Kc)), dim3(kLaunchBlock), 0, st, table, M, (int)K, row, T, cols, Kc, out);
+        hipLaunchKernelGGL(gather_rows_kernel, launch_grid(T * Kc), dim3(kLaunchBlock), 0, st, table, M, (int)K, row, T, cols, Kc, out);
     }
     return check_launch(fn);
 }

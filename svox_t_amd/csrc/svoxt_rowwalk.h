@@ -68,7 +68,7 @@ template <int OP, class V>
 __global__ void __launch_bounds__(kLaunchBlock)
 rows_short_kernel(V src, int64_t T, int C, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ perm, int64_t M,
                   const int32_t* __restrict__ cols, int K, float empty, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t r = t / C;
     if (r >= M) return;
     const int j = (int)(t - r * C);
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(kLaunchBlock)
 rows_chunk_kernel(V src, int64_t T, int C, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ perm, int64_t M,
                   const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr,
                   const int32_t* __restrict__ chunk_long, int64_t n_long, int64_t n_chunks, float* __restrict__ partials) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t ch = t / C;
     if (ch >= n_chunks) return;
     const int j = (int)(t - ch * C);
@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(kLaunchBlock)
 rows_join_kernel(const float* __restrict__ partials, int C, const int32_t* __restrict__ row_ptr, int64_t M,
                  const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr, int64_t n_long, int64_t n_chunks,
                  const int32_t* __restrict__ cols, int K, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t li = t / C;
     if (li >= n_long) return;
     const int j = (int)(t - li * C);
@@ -174,12 +174,12 @@ inline int cols_check(const char* fn, const int32_t* cols, int32_t n_cols, int32
 template <int OP, int PART, class V>
 inline void rows_launch(const V& src, int C, const RowPlanRef& p, const int32_t* cols, int K, float empty, float* out, float* partials,
                         hipStream_t st) {
-    hipLaunchKernelGGL((rows_short_kernel<OP, V>), dim3(launch_blocks(p.M * C)), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr, p.perm, p.M,
+    hipLaunchKernelGGL((rows_short_kernel<OP, V>), launch_grid(p.M * C), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr, p.perm, p.M,
                        cols, K, empty, out);
     if (p.n_long > 0) {
-        hipLaunchKernelGGL((rows_chunk_kernel<PART, V>), dim3(launch_blocks(p.n_chunks * C)), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr,
+        hipLaunchKernelGGL((rows_chunk_kernel<PART, V>), launch_grid(p.n_chunks * C), dim3(kLaunchBlock), 0, st, src, p.T, C, p.row_ptr,
                            p.perm, p.M, p.long_rows, p.long_chunk_ptr, p.chunk_long, p.n_long, p.n_chunks, partials);
-        hipLaunchKernelGGL((rows_join_kernel<OP>), dim3(launch_blocks(p.n_long * C)), dim3(kLaunchBlock), 0, st, partials, C, p.row_ptr, p.M,
+        hipLaunchKernelGGL((rows_join_kernel<OP>), launch_grid(p.n_long * C), dim3(kLaunchBlock), 0, st, partials, C, p.row_ptr, p.M,
                            p.long_rows, p.long_chunk_ptr, p.n_long, p.n_chunks, cols, K, out);
     }
 }

@@ -267,7 +267,7 @@ sample_weights_bwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_
 __global__ void __launch_bounds__(kLaunchBlock)
 sample_accumulate_fwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ w,
                              const float* __restrict__ values, int C, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t q = t / C;
     if (q >= Q) return;
     const int c = (int)(t - q * C);
@@ -487,7 +487,7 @@ int svoxt_sample_accumulate_fwd(const int64_t* offsets, int64_t Q, int64_t T, co
     if (T > 0 && w == nullptr) return fail(SVOXT_ERR_INVALID, "%s: w is NULL", fn);
     if (misaligned(offsets, 8) || misaligned(w, 4) || misaligned(values, 4) || misaligned(out, 4))
         return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets: 8 bytes, the float arrays: 4)", fn);
-    hipLaunchKernelGGL(sample_accumulate_fwd_kernel, dim3(launch_blocks(Q * C)), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T,
+    hipLaunchKernelGGL(sample_accumulate_fwd_kernel, launch_grid(Q * C), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T,
                        w, values, (int)C, out);
     return check_launch(fn);
 }

@@ -53,7 +53,7 @@ struct ScanWalk {
     int64_t n, at, step;
 };
 __device__ __forceinline__ bool scan_walk(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, int C, bool reverse, ScanWalk& w) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t q = t / C;
     if (q >= Q) return false;
     const int64_t c = t - q * C;
@@ -133,7 +133,7 @@ ray_scan_arg_bwd_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t 
 __global__ void __launch_bounds__(kLaunchBlock)
 ray_quantile_kernel(const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ w,
                     const float* __restrict__ qs, int nq, bool normalize, int64_t* __restrict__ index, float* __restrict__ frac) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t q = t / nq;
     if (q >= Q) return;
     const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
@@ -206,7 +206,7 @@ static int scan_check(int64_t Q, int64_t T, int32_t C, int32_t op, int32_t flags
 template <int OP>
 static void launch_scan_fwd(const int64_t* offsets, int64_t Q, int64_t T, const float* values, int C, bool exclusive, bool reverse,
                             float* out, hipStream_t st) {
-    hipLaunchKernelGGL(ray_scan_fwd_kernel<OP>, dim3(launch_blocks(Q * C)), dim3(kLaunchBlock), 0, st, offsets, Q, T, values, C,
+    hipLaunchKernelGGL(ray_scan_fwd_kernel<OP>, launch_grid(Q * C), dim3(kLaunchBlock), 0, st, offsets, Q, T, values, C,
                        exclusive, reverse, out);
 }
 
@@ -255,7 +255,7 @@ int svoxt_ray_scan_bwd(const int64_t* offsets, int64_t Q, int64_t T, const float
     // one entry per sample: samples outside every segment get 0
     if ((rc = memset_async(grad_values, (size_t)T * (size_t)C * sizeof(float), st, fn))) return rc;
     if (Q == 0) return SVOXT_OK;
-    const dim3 grid(launch_blocks(Q * C)), block(kLaunchBlock);
+    const dim3 grid = launch_grid(Q * C), block(kLaunchBlock);
     if (op == SVOXT_SCAN_SUM) launch_scan_fwd<SVOXT_SCAN_SUM>(offsets, Q, T, grad_out, (int)C, ex, !rev, grad_values, st);
     else if (op == SVOXT_SCAN_PROD)
         hipLaunchKernelGGL(ray_scan_prod_bwd_kernel, grid, block, 0, st, offsets, Q, T, values, (int)C, ex, rev, grad_out, grad_values);
@@ -278,7 +278,7 @@ int svoxt_ray_quantile(const int64_t* offsets, int64_t Q, int64_t T, const float
     if (T > 0 && w == nullptr) return fail(SVOXT_ERR_INVALID, "%s: w is NULL", fn);
     if (misaligned(offsets, 8) || misaligned(index, 8) || misaligned(w, 4) || misaligned(q, 4) || misaligned(frac, 4))
         return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (offsets, index: 8 bytes, the float arrays: 4)", fn);
-    hipLaunchKernelGGL(ray_quantile_kernel, dim3(launch_blocks(Q * nq)), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T, w, q,
+    hipLaunchKernelGGL(ray_quantile_kernel, launch_grid(Q * nq), dim3(kLaunchBlock), 0, (hipStream_t)stream, offsets, Q, T, w, q,
                        (int)nq, normalize != 0, index, frac);
     return check_launch(fn);
 }

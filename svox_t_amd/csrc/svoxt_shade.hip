@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(kLaunchBlock)
 shade_fwd_kernel(const float* __restrict__ features, int64_t M, int K, int C, int bd, int min_comp, int max_comp, bool activate,
                  int64_t Q, int64_t T, const int32_t* __restrict__ row, const int32_t* __restrict__ ray,
                  const float* __restrict__ basis, float* __restrict__ values, float* __restrict__ sigma) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t k = t / (C + 1);
     if (k >= T) return;
     const int c = (int)(t - k * (C + 1));
@@ -100,7 +100,7 @@ shade_fwd_kernel(const float* __restrict__ features, int64_t M, int K, int C, in
 __global__ void __launch_bounds__(kLaunchBlock)
 shade_fwd_rgba4_kernel(const float4* __restrict__ features, int64_t M, int K4, bool activate, int64_t T,
                        const int32_t* __restrict__ row, float* __restrict__ values, float* __restrict__ sigma) {
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t k = t / K4;
     if (k >= T) return;
     const int j = (int)(t - k * K4);
@@ -296,10 +296,10 @@ int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const s
     hipStream_t st = (hipStream_t)stream;
     if (bd == 0 && K % 4 == 0 && !misaligned(features, 16)) {
         const int K4 = K / 4;
-        hipLaunchKernelGGL(shade_fwd_rgba4_kernel, dim3(launch_blocks(T * K4)), dim3(kLaunchBlock), 0, st,
+        hipLaunchKernelGGL(shade_fwd_rgba4_kernel, launch_grid(T * K4), dim3(kLaunchBlock), 0, st,
                            reinterpret_cast<const float4*>(features), M, K4, activate != 0, T, row, values, sigma);
     } else {
-        hipLaunchKernelGGL(shade_fwd_kernel, dim3(launch_blocks(T * (C + 1))), dim3(kLaunchBlock), 0, st, features, M, (int)K, C, bd,
+        hipLaunchKernelGGL(shade_fwd_kernel, launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, st, features, M, (int)K, C, bd,
                            (int)opt->min_comp, (int)opt->max_comp, activate != 0, Q, T, row, ray, basis, values, sigma);
     }
     return check_launch(fn);

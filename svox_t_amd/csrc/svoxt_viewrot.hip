@@ -84,7 +84,7 @@ shade_rot_fwd_kernel(const float* __restrict__ features, int K, int C, int bd_rt
                      int64_t T, const int32_t* __restrict__ row, const int32_t* __restrict__ ray, float* __restrict__ values,
                      float* __restrict__ sigma) {
     const int bd = BD > 0 ? BD : bd_rt;
-    const int64_t t = (int64_t)blockIdx.x * kLaunchBlock + threadIdx.x;
+    const int64_t t = launch_lane();
     const int64_t k = t / (C + 1);
     if (k >= T) return;
     const int c = (int)(t - k * (C + 1));
@@ -372,7 +372,7 @@ int svoxt_shade_rot_fwd(const float* features, int64_t M, int32_t K, const svoxt
         return fail(SVOXT_ERR_INVALID, "%s: values / sigma overlaps an input or the other output", fn);
     const RotDev R = rot_dev(opt, a, M, Q);
     with_basis(opt, [&](auto BD) {
-        hipLaunchKernelGGL((shade_rot_fwd_kernel<decltype(BD)::value>), dim3(launch_blocks(T * (C + 1))), dim3(kLaunchBlock), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((shade_rot_fwd_kernel<decltype(BD)::value>), launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, (hipStream_t)stream,
                            features, (int)K, C, bd, (int)opt->min_comp, (int)opt->max_comp, activate != 0, R, T, row, ray, values, sigma);
     });
     return check_launch(fn);

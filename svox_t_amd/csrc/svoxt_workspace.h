@@ -26,6 +26,22 @@ constexpr int kStrideBlocksMax = 2048;       // workgroups of a striding pass, a
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline unsigned launch_blocks(int64_t n) { return (unsigned)((n + kLaunchBlock - 1) / kLaunchBlock); }
+// A launch of a lane per ELEMENT of an array that may hold 2^32 elements or more (the "below 2^38" entry points).  HIP
+// launches fewer than 2^32 work-items along a grid dimension, so from kGridFoldBlocks workgroups on the workgroups fold
+// over grid.y; the kernel's lane index is launch_lane(), its workgroup's launch_block().  Below that the grid is the
+// one-dimensional grid of launch_blocks(n) and blockIdx.y is 0.  The fold may add up to kGridFoldBlocks - 1 workgroups
+// behind the last element: every such kernel leaves on its extent check, as its last workgroup's tail lanes do.
+constexpr int64_t kGridFoldBlocks = (int64_t)1 << 22;            // 2^30 lanes along x
+inline dim3 launch_grid(int64_t n, int block = kLaunchBlock) {
+    const int64_t b = (n + block - 1) / block;
+    if (b <= kGridFoldBlocks) return dim3((unsigned)b);
+    return dim3((unsigned)kGridFoldBlocks, (unsigned)((b + kGridFoldBlocks - 1) / kGridFoldBlocks));
+}
+__device__ __forceinline__ int64_t launch_block() { return (int64_t)blockIdx.y * gridDim.x + blockIdx.x; }
+// (launch_lane() is for kernels of kLaunchBlock threads a workgroup; one launched with another `block` forms its lane from
+// launch_block() itself, as tv_rows_kernel does)
+__device__ __forceinline__ int64_t launch_lane() { return launch_block() * kLaunchBlock + threadIdx.x; }
+
 inline unsigned stride_blocks(int64_t n) {
     const unsigned need = launch_blocks(n);
     return need < (unsigned)kStrideBlocksMax ? need : (unsigned)kStrideBlocksMax;
