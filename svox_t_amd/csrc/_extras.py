@@ -1924,41 +1924,79 @@ def _shade_dims(opt: RenderOptions, K: int):
     return C, (0 if int(opt.format) == 0 else int(opt.basis_dim))
 
 
+def _check_basis(x, name, Q, bd, dev, where, device_refusal=None):
+    """x must be float32 [Q, basis_dim] on `dev`; `where` ends the refusal, `device_refusal` is a text of its own for the device."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (Q, bd) \
+            or (device_refusal is None and x.device != dev):
+        raise RuntimeError(f"{name} must be float32 [Q, basis_dim] = [{Q}, {bd}] {where}")
+    _check_input(x, name)
+    if x.device != dev:
+        raise RuntimeError(device_refusal)
+
+
+def _check_grads(values, grad_values, grad_sigma, T, dev, C):
+    """The forward's values [T, C] and the upstream gradients grad_values [T, C] / grad_sigma [T], either None for zeros."""
+    _check_per_sample(values, "values", T, dev, C)
+    if grad_values is not None:
+        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    if grad_sigma is not None:
+        _check_per_sample(grad_sigma, "grad_sigma", T, dev)
+
+
 def _check_shade(features, row, ray, basis, Q, opt, with_basis=True):
-    """The checks the two directions of shade_samples share; returns (M, K, T, C, basis_dim, device)."""
-    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
-        raise RuntimeError("features must be float32 [M, K], K >= 1")
-    _check_input(features, "features")
-    dev = features.device
+    """The sample side every direction of shade_samples checks: features float32 [M, K], or the (M, K) of a table whose values
+    are not read; row / ray int32 [T]; the plain forward's basis; the 2^31 limits.  Returns (M, K, T, C, basis_dim, device)."""
+    dev = None
+    if not isinstance(features, tuple):
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+            raise RuntimeError("features must be float32 [M, K], K >= 1")
+        _check_input(features, "features")
+        dev = features.device
+        features = features.shape
+    M, K = (int(v) for v in features)
     if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
         raise RuntimeError("row must be int32 [T]")
-    T = row.shape[0]
+    T, dev = row.shape[0], (row.device if dev is None else dev)
     _check_per_sample(row, "row", T, dev, dtype=torch.int32)
     _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
-    (M, K) = features.shape
     C, bd = _shade_dims(opt, K)
     if bd > 0 and with_basis:
-        if not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (Q, bd):
-            raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] (view_basis of the samples' rays)")
-        _check_input(basis, "basis")
-        if basis.device != dev:
-            raise RuntimeError("basis must be on the device of the features")
+        _check_basis(basis, "basis", Q, bd, dev, "(view_basis of the samples' rays)", "basis must be on the device of the features")
     if M >= 1 << 31 or T >= 1 << 31 or Q >= 1 << 31:
         raise RuntimeError("M, T and Q must be below 2^31")
     return M, K, T, C, bd, dev
 
 
-def shade_samples_fwd(features, row, ray, basis, Q: int, opt: RenderOptions, activate: bool = True):
-    """(values float32 [T, C], sigma float32 [T]) of svoxt_shade_samples_fwd for features float32 [M, K], row / ray int32 [T]
-    and basis float32 [Q, basis_dim] (RGBA: not read, may be None)."""
-    M, K, T, C, bd, dev = _check_shade(features, row, ray, basis, Q, opt)
+def _shade_fwd(entry, features, dims, view, opt, activate):
+    """(values, sigma) of the forward `entry`, plain or rotated: `view` is what the entry point takes between the options and
+    `activate` (the lists and the view side)."""
+    M, K, T, C, _, dev = dims
     co = _pack_opts(opt)
     with _on(dev):
         values = torch.empty((T, C), dtype=torch.float32, device=dev)
         sigma = torch.empty((T,), dtype=torch.float32, device=dev)
-        _call("svoxt_shade_samples_fwd", _ptr(features), M, K, ctypes.byref(co), _ptr(row), _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q,
-              1 if activate else 0, _ptr(values), _ptr(sigma), _stream(dev))
+        _call(entry, _ptr(features), M, K, ctypes.byref(co), *view, 1 if activate else 0, _ptr(values), _ptr(sigma), _stream(dev))
     return values, sigma
+
+
+def _shade_bwd(entry, M, K, dev, view, opt, activate, values, grad_values, grad_sigma, plan):
+    """grad float32 [M, K] of the table backward `entry`, plain or rotated: `view` as in _shade_fwd."""
+    co = _pack_opts(opt)
+    with _on(dev):
+        grad = torch.empty((M, K), dtype=torch.float32, device=dev)
+        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], K)
+        ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
+        _call(entry, ctypes.byref(co), M, K, *view, 1 if activate else 0, _ptr(values), _ptr(grad_values), _ptr(grad_sigma),
+              *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
+    return grad
+
+
+def shade_samples_fwd(features, row, ray, basis, Q: int, opt: RenderOptions, activate: bool = True):
+    """(values float32 [T, C], sigma float32 [T]) of svoxt_shade_samples_fwd for features float32 [M, K], row / ray int32 [T]
+    and basis float32 [Q, basis_dim] (RGBA: not read, may be None)."""
+    dims = _check_shade(features, row, ray, basis, Q, opt)
+    view = (_ptr(row), _ptr(ray), dims[2], _ptr(basis) if dims[4] > 0 else None, Q)
+    return _shade_fwd("svoxt_shade_samples_fwd", features, dims, view, opt, activate)
 
 
 def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: bool, values, grad_values, grad_sigma,
@@ -1974,23 +2012,11 @@ def shade_samples_bwd(shape, ray, basis, Q: int, opt: RenderOptions, activate: b
     C, bd = _shade_dims(opt, K)
     dev = plan.row_ptr.device
     _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
-    _check_per_sample(values, "values", T, dev, C)
-    if grad_values is not None:
-        _check_per_sample(grad_values, "grad_values", T, dev, C)
-    if grad_sigma is not None:
-        _check_per_sample(grad_sigma, "grad_sigma", T, dev)
+    _check_grads(values, grad_values, grad_sigma, T, dev, C)
     if bd > 0:
-        if not isinstance(basis, torch.Tensor) or basis.dtype != torch.float32 or tuple(basis.shape) != (Q, bd) or basis.device != dev:
-            raise RuntimeError(f"basis must be float32 [Q, basis_dim] = [{Q}, {bd}] on the device of the plan")
-        _check_input(basis, "basis")
-    co = _pack_opts(opt)
-    with _on(dev):
-        grad = torch.empty((M, K), dtype=torch.float32, device=dev)
-        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], K)
-        ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
-        _call("svoxt_shade_samples_bwd", ctypes.byref(co), M, K, _ptr(ray), T, _ptr(basis) if bd > 0 else None, Q, 1 if activate else 0,
-              _ptr(values), _ptr(grad_values), _ptr(grad_sigma), *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
-    return grad
+        _check_basis(basis, "basis", Q, bd, dev, "on the device of the plan")
+    view = (_ptr(ray), T, _ptr(basis) if bd > 0 else None, Q)
+    return _shade_bwd("svoxt_shade_samples_bwd", M, K, dev, view, opt, activate, values, grad_values, grad_sigma, plan)
 
 
 def view_basis_backward(tree: TreeSpec, rays, opt: RenderOptions, basis, grad_basis) -> torch.Tensor:
@@ -2005,10 +2031,8 @@ def view_basis_backward(tree: TreeSpec, rays, opt: RenderOptions, basis, grad_ba
     bd = 0 if int(opt.format) == 0 else int(opt.basis_dim)
     if bd == 0:
         return torch.zeros((Q, 3), dtype=torch.float32, device=dev)
-    for name, x in (("basis", basis), ("grad_basis", grad_basis)):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (Q, bd) or x.device != dev:
-            raise RuntimeError(f"{name} must be float32 [Q, basis_dim] = [{Q}, {bd}] on the device of the tree")
-        _check_input(x, name)
+    _check_basis(basis, "basis", Q, bd, dev, "on the device of the tree")
+    _check_basis(grad_basis, "grad_basis", Q, bd, dev, "on the device of the tree")
     with _on(dev):
         gv = torch.empty((Q, 3), dtype=torch.float32, device=dev)
         _call("svoxt_view_basis_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(basis), _ptr(grad_basis), _ptr(gv),
@@ -2025,9 +2049,7 @@ def shade_samples_bwd_basis(features, offsets, row, ray, Q: int, opt: RenderOpti
         raise RuntimeError(f"offsets must be int64 [Q + 1] with Q = {Q}")
     if offsets.device != dev:
         raise RuntimeError("offsets must be on the device of the features")
-    _check_per_sample(values, "values", T, dev, C)
-    if grad_values is not None:
-        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    _check_grads(values, grad_values, None, T, dev, C)
     co = _pack_opts(opt)
     with _on(dev):
         gb = torch.empty((Q, bd), dtype=torch.float32, device=dev)
@@ -2040,25 +2062,19 @@ def shade_samples_bwd_basis(features, offsets, row, ray, Q: int, opt: RenderOpti
 # ---------------------------------------------------------------------------
 # shade_samples with per-row rotations of the view direction (svoxt_viewrot.hip)
 # ---------------------------------------------------------------------------
+def _is_rotations(x) -> bool:
+    """float32 [M, 3, 3] or [M, 4, 4]: one matrix per feature row"""
+    return isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 3 and tuple(x.shape[1:]) in ((3, 3), (4, 4))
+
+
 def _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt):
-    """The checks the rotated call's directions share; returns (M, K, T, C, basis_dim, device, the C ABI's view-side arguments:
-    extra, extra_rows, extra_cols, rotations, rot_dim, viewdirs, Q)."""
+    """The checks the rotated call's directions share; `features`: a table or its (M, K), as _check_shade takes it.  Returns
+    ((M, K, T, C, basis_dim, device), view), view what the C ABI takes of the view side and the lists: extra, extra_rows,
+    extra_cols, rotations, rot_dim, viewdirs, Q, row, ray, T."""
     if int(opt.format) == 0:
         raise RuntimeError("rotations: RGBA has no basis to rotate (shade_samples_fwd serves it)")
-    if isinstance(features, tuple):                              # (M, K) of a table whose values are not read
-        M, K = (int(v) for v in features)
-        if not isinstance(row, torch.Tensor) or row.dtype != torch.int32 or row.dim() != 1:
-            raise RuntimeError("row must be int32 [T]")
-        T, dev = row.shape[0], row.device
-        _check_per_sample(row, "row", T, dev, dtype=torch.int32)
-        _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
-        C, bd = _shade_dims(opt, K)
-        if M >= 1 << 31 or T >= 1 << 31 or Q >= 1 << 31:
-            raise RuntimeError("M, T and Q must be below 2^31")
-    else:
-        M, K, T, C, bd, dev = _check_shade(features, row, ray, None, Q, opt, with_basis=False)
-    if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
-            or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)) or rotations.shape[0] != M:
+    M, K, T, C, bd, dev = dims = _check_shade(features, row, ray, None, Q, opt, with_basis=False)
+    if not _is_rotations(rotations) or rotations.shape[0] != M:
         raise RuntimeError(f"rotations must be float32 [M, 3, 3] or [M, 4, 4] with M = {M}, one matrix per feature row")
     if not isinstance(viewdirs, torch.Tensor) or viewdirs.dtype != torch.float32 or tuple(viewdirs.shape) != (Q, 3):
         raise RuntimeError(f"viewdirs must be float32 [Q, 3] with Q = {Q}")
@@ -2074,20 +2090,14 @@ def _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt):
         rows, cols = extra.shape
     else:
         extra = None
-    return M, K, T, C, bd, dev, (_ptr(extra), rows, cols, _ptr(rotations), rotations.shape[1], _ptr(viewdirs), Q)
+    return dims, (_ptr(extra), rows, cols, _ptr(rotations), rotations.shape[1], _ptr(viewdirs), Q, _ptr(row), _ptr(ray), T)
 
 
 def shade_rot_fwd(features, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool = True):
     """(values float32 [T, C], sigma float32 [T]) of svoxt_shade_rot_fwd: shade_samples_fwd with the basis of rotations[row] *
     viewdirs[ray].  rotations float32 [M, 3, 3] or [M, 4, 4], viewdirs float32 [Q, 3], extra: the lobes of SG / ASG."""
-    M, K, T, C, bd, dev, view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
-    co = _pack_opts(opt)
-    with _on(dev):
-        values = torch.empty((T, C), dtype=torch.float32, device=dev)
-        sigma = torch.empty((T,), dtype=torch.float32, device=dev)
-        _call("svoxt_shade_rot_fwd", _ptr(features), M, K, ctypes.byref(co), *view, _ptr(row), _ptr(ray), T, 1 if activate else 0,
-              _ptr(values), _ptr(sigma), _stream(dev))
-    return values, sigma
+    dims, view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
+    return _shade_fwd("svoxt_shade_rot_fwd", features, dims, view, opt, activate)
 
 
 def shade_rot_bwd(shape, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool, values, grad_values,
@@ -2096,37 +2106,24 @@ def shade_rot_bwd(shape, row, ray, rotations, viewdirs, extra, Q: int, opt: Rend
     values are not read); values is the forward's output, grad_values [T, C] / grad_sigma [T] may be None (zeros)."""
     if not isinstance(plan, RowPlanArrays):
         raise RuntimeError("plan must be a row plan")
-    M, K, T, C, bd, dev, view = _check_rot(tuple(shape), row, ray, rotations, viewdirs, extra, Q, opt)
+    (M, K, T, C, _, dev), view = _check_rot(tuple(shape), row, ray, rotations, viewdirs, extra, Q, opt)
     if plan.M != M or plan.T != T:
         raise RuntimeError("the plan must be built for the table's M rows and the T samples")
-    _check_per_sample(values, "values", T, dev, C)
-    if grad_values is not None:
-        _check_per_sample(grad_values, "grad_values", T, dev, C)
-    if grad_sigma is not None:
-        _check_per_sample(grad_sigma, "grad_sigma", T, dev)
-    co = _pack_opts(opt)
-    with _on(dev):
-        grad = torch.empty((M, K), dtype=torch.float32, device=dev)
-        nbytes = _lib.svoxt_shade_samples_bwd_workspace_bytes(plan.chunk_long.shape[0], K)
-        ws = _workspace(dev, nbytes, "shade_samples: chunks * K must be below 2^38")
-        _call("svoxt_shade_rot_bwd", ctypes.byref(co), M, K, *view, _ptr(row), _ptr(ray), T, 1 if activate else 0, _ptr(values),
-              _ptr(grad_values), _ptr(grad_sigma), *_plan_args(plan, with_M=False), _ptr(grad), _ptr(ws), nbytes, _stream(dev))
-    return grad
+    _check_grads(values, grad_values, grad_sigma, T, dev, C)
+    return _shade_bwd("svoxt_shade_rot_bwd", M, K, dev, view, opt, activate, values, grad_values, grad_sigma, plan)
 
 
 def shade_rot_bwd_dir(features, row, ray, rotations, viewdirs, extra, Q: int, opt: RenderOptions, activate: bool, values,
                       grad_values) -> torch.Tensor:
     """gu float32 [T, 3] of svoxt_shade_rot_bwd_dir: the gradient in every sample's rotated direction, the one scratch the
     gradients in the rotations and in the view directions read; grad_values [T, C] may be None (zeros)."""
-    M, K, T, C, bd, dev, view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
-    _check_per_sample(values, "values", T, dev, C)
-    if grad_values is not None:
-        _check_per_sample(grad_values, "grad_values", T, dev, C)
+    (M, K, T, C, _, dev), view = _check_rot(features, row, ray, rotations, viewdirs, extra, Q, opt)
+    _check_grads(values, grad_values, None, T, dev, C)
     co = _pack_opts(opt)
     with _on(dev):
         gu = torch.empty((T, 3), dtype=torch.float32, device=dev)
-        _call("svoxt_shade_rot_bwd_dir", _ptr(features), M, K, ctypes.byref(co), *view, _ptr(row), _ptr(ray), T, 1 if activate else 0,
-              _ptr(values), _ptr(grad_values), _ptr(gu), _stream(dev))
+        _call("svoxt_shade_rot_bwd_dir", _ptr(features), M, K, ctypes.byref(co), *view, 1 if activate else 0, _ptr(values), _ptr(grad_values),
+              _ptr(gu), _stream(dev))
     return gu
 
 
@@ -2166,8 +2163,7 @@ def shade_rot_bwd_viewdirs(gu, rotations, offsets, row, ray) -> torch.Tensor:
     _check_per_sample(row, "row", T, dev, dtype=torch.int32)
     _check_per_sample(ray, "ray", T, dev, dtype=torch.int32)
     _check_per_sample(gu, "gu", T, dev, 3)
-    if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
-            or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)) or rotations.device != dev:
+    if not _is_rotations(rotations) or rotations.device != dev:
         raise RuntimeError("rotations must be float32 [M, 3, 3] or [M, 4, 4] on the device of offsets")
     _check_input(rotations, "rotations")
     with _on(dev):

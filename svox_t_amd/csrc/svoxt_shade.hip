@@ -3,12 +3,13 @@
 // table entry over the row plan in svoxt_reduce_rows' order -- no [T, K] array and no float atomic anywhere.
 //
 //   view_basis   view_basis_kernel        a lane per ray, no march: precalc_basis<0> of load_vdir into basis[q, :]
-//   forward      shade_fwd_kernel         a lane per (sample, channel) and one per sample behind them for sigma
-//                                         (rowgrad_shade_kernel's cut: a sample's lanes read the same feature row)
+// The shading core is svoxt_shade.h's, shared with svoxt_viewrot.hip; here it runs over the basis source TableBasis, the
+// per-ray table basis[ray[k], i] (bd at run time, 0 for RGBA).
+//   forward      shade_fwd_kernel<TableBasis>  a lane per (sample, channel) and one per sample behind them for sigma
 //                shade_fwd_rgba4_kernel   RGBA rows of K = 4 K4 floats in a 16-byte aligned table: a lane per (sample,
 //                                         four columns), one 16-byte load each (gather_rows4_kernel's cut)
 //   backward     the row kernels of svoxt_rowwalk.h, a lane per (row, column) over all K columns, the value of sample k
-//                at column j formed on the fly (ShadeValues): a colour column (g_values[k, c] * d[k, c]) *
+//                at column j formed on the fly (ShadeValues<TableBasis>): a colour column (g_values[k, c] * d[k, c]) *
 //                basis[ray[k], i], the sigma column g_sigma[k], every other column 0.f.  sig is the forward's own output.
 //   view gradient
 //                view_basis_bwd_kernel    a lane per ray: the analytic derivative of precalc_basis' expression, summed over
@@ -61,40 +62,6 @@ view_basis_bwd_kernel(TreeDev tr, RaysDev rays, int format, int bd, const float*
 }
 
 // ------------------------------------------------------------------------------------------------------------ forward
-// lane t = k * (C + 1) + c.  c < C: values[k, c]; c == C: sigma[k]
-__global__ void __launch_bounds__(kLaunchBlock)
-shade_fwd_kernel(const float* __restrict__ features, int64_t M, int K, int C, int bd, int min_comp, int max_comp, bool activate,
-                 int64_t Q, int64_t T, const int32_t* __restrict__ row, const int32_t* __restrict__ ray,
-                 const float* __restrict__ basis, float* __restrict__ values, float* __restrict__ sigma) {
-    const int64_t t = launch_lane();
-    const int64_t k = t / (C + 1);
-    if (k >= T) return;
-    const int c = (int)(t - k * (C + 1));
-    const int64_t idx = row[k];
-    const bool inside = idx >= 0 && idx < M;
-    const float* __restrict__ frow = features + (inside ? idx : 0) * K;
-    if (c == C) {
-        sigma[k] = inside ? frow[K - 1] : 0.f;
-        return;
-    }
-    float v = 0.f;
-    if (inside) {
-        if (bd > 0) {
-            const int64_t q = ray[k];
-            if (q >= 0 && q < Q) {                               // (a ray outside [0, Q): zeros, as a row outside [0, M))
-                const float* __restrict__ b = basis + q * bd;
-                const int off = c * bd;
-                float tmp = 0.f;
-                for (int i = min_comp; i <= max_comp; ++i) tmp += b[i] * frow[off + i];
-                v = shade_value(tmp, activate);
-            }
-        } else {
-            v = shade_value(frow[c], activate);
-        }
-    }
-    values[k * C + c] = v;
-}
-
 // lane t = k * K4 + j: columns 4 j .. 4 j + 3 of sample k's RGBA row (K = 4 K4, C = K - 1, the table 16-byte aligned);
 // the last column of the last lane is sigma
 __global__ void __launch_bounds__(kLaunchBlock)
@@ -116,65 +83,9 @@ shade_fwd_rgba4_kernel(const float4* __restrict__ features, int64_t M, int K4, b
     else o[3] = inside ? shade_value(x.w, activate) : 0.f;
 }
 
-// ------------------------------------------------------------------------------------------------------------- values
-// The contribution of sample k to column j of its row, for the row kernels of svoxt_rowwalk.h.  A NULL upstream gradient
-// is zeros: its columns are ZERO columns, nothing is read.
-struct ShadeValues {
-    const int32_t* __restrict__ ray;
-    const float* __restrict__ values;
-    const float* __restrict__ basis;
-    const float* __restrict__ gv;
-    const float* __restrict__ gs;
-    int64_t T, Q;
-    int K, C, bd, min_comp, max_comp;
-    bool activate;
-    enum { ZERO, SIGMA, BASIS, BASIS_LINEAR, RGBA, RGBA_LINEAR };
-    struct Col {
-        const int32_t* __restrict__ ray;
-        const float* __restrict__ v;       // BASIS / RGBA: values + c
-        const float* __restrict__ b;       // BASIS, BASIS_LINEAR: basis + i
-        const float* __restrict__ g;       // SIGMA: g_sigma;  the colour modes: g_values + c
-        int64_t T, Q;
-        int mode, C, bd;
-        __device__ __forceinline__ float at(int64_t k) const {
-            if (mode == ZERO || k < 0 || k >= T) return 0.f;
-            if (mode == SIGMA) return g[k];
-            const float gc = g[k * C];
-            if (mode == RGBA_LINEAR) return gc;
-            if (mode == RGBA) {
-                const float sig = v[k * C];
-                return gc * (sig * (1.f - sig));
-            }
-            const int64_t q = ray[k];
-            if (q < 0 || q >= Q) return 0.f;                     // (the forward gave this sample zeros)
-            if (mode == BASIS_LINEAR) return gc * b[q * bd];
-            const float sig = v[k * C];
-            const float d = (float)((double)sig * (1.0 - (double)sig));
-            return (gc * d) * b[q * bd];
-        }
-    };
-    __device__ __forceinline__ Col col(int j) const {
-        Col o{ray, values, basis, gs, T, Q, ZERO, C, bd};
-        if (j == K - 1) {
-            if (gs != nullptr) o.mode = SIGMA;
-        } else if (gv == nullptr) {
-            // (zeros upstream: every colour column is 0.f)
-        } else if (bd == 0) {
-            if (j < C) { o.mode = activate ? RGBA : RGBA_LINEAR; o.v = values + j; o.g = gv + j; }
-        } else if (j < C * bd) {
-            const int c = j / bd, i = j - c * bd;
-            if (i >= min_comp && i <= max_comp) {
-                o.mode = activate ? BASIS : BASIS_LINEAR;
-                o.v = values + c; o.b = basis + i; o.g = gv + c;
-            }
-        }
-        return o;
-    }
-};
-
 // ----------------------------------------------------------------------------------------------------- backward, basis
 // grad_basis[q, i] = the sum over ray q's segment in list order, and per sample over c ascending, of
-// (grad_values[k, c] * d[k, c]) * features[row[k], c * bd + i] -- ShadeValues::Col::at's factor times the coefficient the
+// (grad_values[k, c] * d[k, c]) * features[row[k], c * bd + i] -- the table backward's factor (shade_bracket) times the coefficient the
 // forward multiplied basis[q, i] by.  bd lanes a ray walk the segment together: lane i reads frow[c * bd + i], so a
 // ray's lanes read neighbouring floats of one row and the same grad_values / values words.  A block holds
 // kLaunchBlock / bd whole rays (its last kLaunchBlock % bd lanes idle): no ray's lanes straddle two blocks.  One
@@ -200,14 +111,7 @@ shade_bwd_basis_kernel(const float* __restrict__ features, int64_t M, int K, int
             const float* __restrict__ g = gv + k * C;
             const float* __restrict__ v = values + k * C;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                float t = g[c];
-                if (activate) {
-                    const float sig = v[c];
-                    t = t * (float)((double)sig * (1.0 - (double)sig));
-                }
-                acc += t * f[c * bd];
-            }
+            for (int c = 0; c < C; ++c) acc += shade_bracket(g[c], v + c, activate) * f[c * bd];
         }
     }
     grad_basis[q * bd + i] = acc;
@@ -285,22 +189,15 @@ int svoxt_shade_samples_fwd(const float* features, int64_t M, int32_t K, const s
                             float* sigma, void* stream) {
     const char* fn = "svoxt_shade_samples_fwd";
     int rc, C, bd;
-    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn))) return rc;
-    if (T == 0) return SVOXT_OK;
-    if (row == nullptr || sigma == nullptr || (C > 0 && values == nullptr)) return fail(SVOXT_ERR_INVALID, "%s: row / values / sigma is NULL", fn);
-    if (M > 0 && features == nullptr) return fail(SVOXT_ERR_INVALID, "%s: features is NULL", fn);
-    if (bd > 0 && C > 0 && (ray == nullptr || (Q > 0 && basis == nullptr))) return fail(SVOXT_ERR_INVALID, "%s: ray / basis is NULL", fn);
-    if (misaligned(features, 4) || misaligned(row, 4) || misaligned(ray, 4) || misaligned(basis, 4) || misaligned(values, 4) ||
-        misaligned(sigma, 4))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    if ((rc = shade_fwd_check(fn, opt, nullptr, features, M, K, row, ray, T, basis, Q, values, sigma, &C, &bd)) || T == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (bd == 0 && K % 4 == 0 && !misaligned(features, 16)) {
         const int K4 = K / 4;
         hipLaunchKernelGGL(shade_fwd_rgba4_kernel, launch_grid(T * K4), dim3(kLaunchBlock), 0, st,
                            reinterpret_cast<const float4*>(features), M, K4, activate != 0, T, row, values, sigma);
     } else {
-        hipLaunchKernelGGL(shade_fwd_kernel, launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, st, features, M, (int)K, C, bd,
-                           (int)opt->min_comp, (int)opt->max_comp, activate != 0, Q, T, row, ray, basis, values, sigma);
+        hipLaunchKernelGGL(shade_fwd_kernel<TableBasis>, launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, st, features, M, (int)K, C,
+                           (int)opt->min_comp, (int)opt->max_comp, activate != 0, TableBasis{basis, Q, bd}, T, row, ray, values, sigma);
     }
     return check_launch(fn);
 }
@@ -321,24 +218,14 @@ int svoxt_shade_samples_bwd(const svoxt_options* opt, int64_t M, int32_t K, cons
     const char* fn = "svoxt_shade_samples_bwd";
     int rc, C, bd;
     const RowPlanRef plan{row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};
-    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn)) || (rc = row_plan_check(fn, plan))) return rc;
-    if (M == 0) return SVOXT_OK;
-    if (grad == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad / row_ptr is NULL", fn);
-    if (C == 0) grad_values = nullptr;                           // (no colour column: nothing of it is read)
-    const bool reads_values = grad_values != nullptr && activate != 0;
-    const bool reads_basis = grad_values != nullptr && bd > 0;
-    if (T > 0 && (perm == nullptr || (reads_values && values == nullptr) || (reads_basis && (ray == nullptr || (Q > 0 && basis == nullptr)))))
-        return fail(SVOXT_ERR_INVALID, "%s: perm / values / ray / basis is NULL", fn);
-    if ((rc = row_plan_long_check(fn, plan))) return rc;
-    if (misaligned(ray, 4) || misaligned(basis, 4) || misaligned(values, 4) || misaligned(grad_values, 4) || misaligned(grad_sigma, 4) ||
-        row_plan_misaligned(plan) || misaligned(grad, 4) || misaligned(workspace, 4))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
-    if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K),
-                                            "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)")))
+    float* partials;
+    if ((rc = shade_bwd_check(fn, opt, nullptr, plan, K, nullptr, ray, basis, Q, activate, values, &grad_values, grad_sigma, grad, workspace,
+                              &C, &bd)) || M == 0)
         return rc;
-    Carver w(workspace);
-    float* partials = w.take<float>((size_t)n_chunks * (size_t)K);
-    const ShadeValues src{ray, values, basis, grad_values, grad_sigma, T, Q, (int)K, C, bd, (int)opt->min_comp, (int)opt->max_comp, activate != 0};
+    if ((rc = shade_partials(fn, plan, K, workspace, workspace_bytes, "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)", &partials)))
+        return rc;
+    const ShadeValues<TableBasis> src{ray, values, grad_values, grad_sigma, TableBasis{basis, Q, bd}, T, (int)K, C, (int)opt->min_comp,
+                                      (int)opt->max_comp, activate != 0};
     // a lane per (row, column) over all K columns: every element of grad is written
     rows_launch<ROWS_SUM, ROWS_SUM>(src, (int)K, plan, nullptr, (int)K, 0.f, grad, partials, (hipStream_t)stream);
     return check_launch(fn);

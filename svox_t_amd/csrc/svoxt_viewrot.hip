@@ -4,12 +4,12 @@
 // in the feature table, in the rotations and in the view directions.  No [T, basis_dim] and no [T, K] array, no float
 // atomic anywhere; every result has the same bits in every run.
 //
-//   forward      shade_rot_fwd_kernel<BD>      a lane per (sample, channel) and one per sample behind them for sigma, as
-//                                              shade_fwd_kernel; the lane rotates its ray's direction by its row's matrix
-//                                              and forms the basis (SH: BD at compile time, in registers; SG / ASG: one
-//                                              lobe at a time)
-//   features     the row kernels of svoxt_rowwalk.h over ShadeRotValues<BD>: a lane per (row, column) holds the row's matrix
-//                (loaded once, at its first sample) and forms (g_values[k, c] * d[k, c]) * B_i(k) on the fly
+// The shading core is svoxt_shade.h's, over the basis source RotBasis<BD> (SH: BD at compile time, in registers; SG / ASG:
+// one lobe at a time); this file holds what only the rotated call has, and the entry points.
+//   forward      shade_fwd_kernel<RotBasis<BD>>  the plain call's kernel; the lane rotates its ray's direction by its row's
+//                                              matrix and forms the basis
+//   features     the row kernels of svoxt_rowwalk.h over ShadeValues<RotBasis<BD>>: a lane per (row, column) holds the row's
+//                matrix (loaded once, at its first sample) and forms (g_values[k, c] * d[k, c]) * B_i(k) on the fly
 //   gu           shade_rot_dir_kernel<BD, CS>  a lane per sample: gB_i = sum_c t[k, c] * features[row, c * bd + i], then
 //                                              view_basis_grad (svoxt_shade.h) at u(k) into gu[k, 0:3], 12 bytes a sample
 //   rotations    the row kernels over RotGradValues: a lane per (row, a, b) sums gu[k, a] * viewdirs[ray[k], b]
@@ -28,163 +28,7 @@
 
 namespace svoxt {
 
-// the lobes of SG / ASG as the basis functions take them: a TreeDev of which nothing else is read
-__host__ __device__ __forceinline__ TreeDev lobes_only(const float* extra, int extra_rows, int extra_cols) {
-    TreeDev tr{};
-    tr.extra = extra;
-    tr.extra_rows = extra_rows;
-    tr.extra_cols = extra_cols;
-    return tr;
-}
-
-// the rotated call's view side: rotations float32 [M, d, d] (the upper-left 3 x 3 is read), viewdirs float32 [Q, 3]
-struct RotDev {
-    const float* __restrict__ rot;
-    const float* __restrict__ vdirs;
-    const float* __restrict__ extra;
-    int64_t M, Q;
-    int d, extra_rows, extra_cols, format;
-};
-
-// the upper-left 3 x 3 of row idx's matrix, in registers
-struct Mat3 {
-    float m00, m01, m02, m10, m11, m12, m20, m21, m22;
-    __device__ __forceinline__ void load(const float* __restrict__ rot, int64_t idx, int d) {
-        const float* __restrict__ m = rot + idx * (d * d);
-        m00 = m[0]; m01 = m[1]; m02 = m[2];
-        m10 = m[d]; m11 = m[d + 1]; m12 = m[d + 2];
-        m20 = m[2 * d]; m21 = m[2 * d + 1]; m22 = m[2 * d + 2];
-    }
-    // u = m * v, rotated_dir's sequence
-    __device__ __forceinline__ void apply(const float* __restrict__ v, float& u0, float& u1, float& u2) const {
-        const float v0 = v[0], v1 = v[1], v2 = v[2];
-        u0 = m00 * v0 + m01 * v1 + m02 * v2;
-        u1 = m10 * v0 + m11 * v1 + m12 * v2;
-        u2 = m20 * v0 + m21 * v1 + m22 * v2;
-    }
-};
-
-// component i of the SH basis of BD values at (x, y, z): precalc_basis<BD> into registers, selected without an index
-template <int BD>
-__device__ __forceinline__ float sh_component(const TreeDev& tr, float x, float y, float z, int i) {
-    float B[BD];
-    precalc_basis<BD>(FMT_SH, BD, tr, x, y, z, B);
-    float b = 0.f;
-#pragma unroll
-    for (int I = 0; I < BD; ++I)
-        if (i == I) b = B[I];
-    return b;
-}
-
-// ------------------------------------------------------------------------------------------------------------ forward
-// lane t = k * (C + 1) + c.  c < C: values[k, c]; c == C: sigma[k].  BD: the SH basis' size (0: SG / ASG, bd lobes)
-template <int BD>
-__global__ void __launch_bounds__(kLaunchBlock)
-shade_rot_fwd_kernel(const float* __restrict__ features, int K, int C, int bd_rt, int min_comp, int max_comp, bool activate, RotDev R,
-                     int64_t T, const int32_t* __restrict__ row, const int32_t* __restrict__ ray, float* __restrict__ values,
-                     float* __restrict__ sigma) {
-    const int bd = BD > 0 ? BD : bd_rt;
-    const int64_t t = launch_lane();
-    const int64_t k = t / (C + 1);
-    if (k >= T) return;
-    const int c = (int)(t - k * (C + 1));
-    const int64_t idx = row[k];
-    const bool inside = idx >= 0 && idx < R.M;
-    const float* __restrict__ frow = features + (inside ? idx : 0) * K;
-    if (c == C) {
-        sigma[k] = inside ? frow[K - 1] : 0.f;
-        return;
-    }
-    float v = 0.f;
-    const int64_t q = ray[k];
-    if (inside && q >= 0 && q < R.Q) {                           // (a ray outside [0, Q): zeros, as a row outside [0, M))
-        const TreeDev tr = lobes_only(R.extra, R.extra_rows, R.extra_cols);
-        Mat3 m;
-        m.load(R.rot, idx, R.d);
-        float u0, u1, u2;
-        m.apply(R.vdirs + 3 * q, u0, u1, u2);
-        const float* __restrict__ f = frow + c * bd;
-        float tmp = 0.f;
-        if constexpr (BD > 0) {
-            float B[BD];
-            precalc_basis<BD>(FMT_SH, BD, tr, u0, u1, u2, B);
-#pragma unroll
-            for (int i = 0; i < BD; ++i)
-                if (i >= min_comp && i <= max_comp) tmp += B[i] * f[i];
-        } else {
-            for (int i = min_comp; i <= max_comp; ++i) tmp += lobe_value(R.format, tr, u0, u1, u2, i, bd) * f[i];
-        }
-        v = shade_value(tmp, activate);
-    }
-    values[k * C + c] = v;
-}
-
 // ------------------------------------------------------------------------------------------------------------- values
-// The contribution of sample k to column j of its row, for the row kernels of svoxt_rowwalk.h, beside ShadeValues: the
-// basis value is recomputed from the row's matrix and the ray's direction by the forward's sequence.  All samples a lane
-// walks name one row: the lane loads that row's matrix at its first sample and keeps it.  A NULL upstream gradient is
-// zeros: its columns are ZERO columns, nothing is read.
-template <int BD>
-struct ShadeRotValues {
-    const int32_t* __restrict__ row;
-    const int32_t* __restrict__ ray;
-    const float* __restrict__ values;
-    const float* __restrict__ gv;
-    const float* __restrict__ gs;
-    RotDev R;
-    int64_t T;
-    int K, C, bd, min_comp, max_comp;
-    bool activate;
-    enum { ZERO, SIGMA, BASIS, BASIS_LINEAR };
-    struct Col {
-        const int32_t* __restrict__ row;
-        const int32_t* __restrict__ ray;
-        const float* __restrict__ v;       // BASIS: values + c
-        const float* __restrict__ g;       // SIGMA: g_sigma;  the colour modes: g_values + c
-        RotDev R;
-        int64_t T;
-        int mode, C, bd, i;
-        mutable Mat3 m;
-        mutable bool have;
-        __device__ __forceinline__ float at(int64_t k) const {
-            if (mode == ZERO || k < 0 || k >= T) return 0.f;
-            if (mode == SIGMA) return g[k];
-            const float gc = g[k * C];
-            const int64_t q = ray[k];
-            if (q < 0 || q >= R.Q) return 0.f;                   // (the forward gave this sample zeros)
-            if (!have) {
-                const int64_t idx = row[k];
-                if (idx < 0 || idx >= R.M) return 0.f;           // (a plan names no such sample)
-                m.load(R.rot, idx, R.d);
-                have = true;
-            }
-            float u0, u1, u2;
-            m.apply(R.vdirs + 3 * q, u0, u1, u2);
-            const TreeDev tr = lobes_only(R.extra, R.extra_rows, R.extra_cols);
-            float b;
-            if constexpr (BD > 0) b = sh_component<BD>(tr, u0, u1, u2, i);
-            else b = lobe_value(R.format, tr, u0, u1, u2, i, bd);
-            if (mode == BASIS_LINEAR) return gc * b;
-            const float sig = v[k * C];
-            const float d = (float)((double)sig * (1.0 - (double)sig));
-            return (gc * d) * b;
-        }
-    };
-    __device__ __forceinline__ Col col(int j) const {
-        Col o{row, ray, values, gs, R, T, ZERO, C, bd, 0, Mat3{}, false};
-        if (j == K - 1) {
-            if (gs != nullptr) o.mode = SIGMA;
-        } else if (gv != nullptr && j < C * bd) {
-            const int c = j / bd, i = j - c * bd;
-            if (i >= min_comp && i <= max_comp) {
-                o.mode = activate ? BASIS : BASIS_LINEAR;
-                o.v = values + c; o.g = gv + c; o.i = i;
-            }
-        }
-        return o;
-    }
-};
-
 // gu[k, a] * viewdirs[ray[k], b] at column j = a * d + b of the row's matrix; the columns outside the 3 x 3 block are ZERO
 struct RotGradValues {
     const int32_t* __restrict__ ray;
@@ -237,14 +81,7 @@ shade_rot_dir_kernel(const float* __restrict__ features, int K, int C_rt, int bd
         const float* __restrict__ frow = features + idx * K;
         const float* __restrict__ g = gv + k * C;
         const float* __restrict__ v = values + k * C;
-        auto bracket = [&](int c) {
-            float t = g[c];
-            if (activate) {
-                const float sig = v[c];
-                t = t * (float)((double)sig * (1.0 - (double)sig));
-            }
-            return t;
-        };
+        auto bracket = [&](int c) { return shade_bracket(g[c], v + c, activate); };
         [[maybe_unused]] float ts[CS > 0 ? CS : 1];
         if constexpr (CS > 0) {
 #pragma unroll
@@ -305,31 +142,6 @@ inline bool ranges_overlap(const void* a, double a_bytes, const void* b, double 
     return x < y + b_bytes && y < x + a_bytes;
 }
 
-// what the rotated call is given, as the entry points check it: a format with a basis, its lobes, the matrices, the directions
-struct RotArgs {
-    const float *extra, *rotations, *viewdirs;
-    int32_t extra_rows, extra_cols, rot_dim;
-};
-static int rot_check(const char* fn, const svoxt_options* opt, const RotArgs& a, int64_t M, int64_t Q) {
-    if (opt->format == SVOXT_FORMAT_RGBA)
-        return fail(SVOXT_ERR_INVALID, "%s: RGBA has no basis to rotate (svoxt_shade_samples_* serve it)", fn);
-    if (opt->format == SVOXT_FORMAT_SH && !special_basis(opt->basis_dim))
-        return fail(SVOXT_ERR_INVALID, "%s: SH basis_dim must be 1, 4, 9, 16 or 25", fn);
-    if (opt->format == SVOXT_FORMAT_SG || opt->format == SVOXT_FORMAT_ASG) {
-        const int need = opt->format == SVOXT_FORMAT_SG ? 4 : 11;
-        if (a.extra == nullptr || a.extra_rows < opt->basis_dim || a.extra_cols < need)
-            return fail(SVOXT_ERR_INVALID, "%s: SG/ASG formats need extra [basis_dim, >=4/11]", fn);
-    }
-    if (a.rot_dim != 3 && a.rot_dim != 4) return fail(SVOXT_ERR_INVALID, "%s: rot_dim must be 3 or 4", fn);
-    if ((M > 0 && a.rotations == nullptr) || (Q > 0 && a.viewdirs == nullptr))
-        return fail(SVOXT_ERR_INVALID, "%s: rotations / viewdirs is NULL", fn);
-    if (misaligned(a.extra, 4) || misaligned(a.rotations, 4) || misaligned(a.viewdirs, 4))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
-    return SVOXT_OK;
-}
-static RotDev rot_dev(const svoxt_options* opt, const RotArgs& a, int64_t M, int64_t Q) {
-    return RotDev{a.rotations, a.viewdirs, a.extra, M, Q, (int)a.rot_dim, (int)a.extra_rows, (int)a.extra_cols, (int)opt->format};
-}
 // `out` of out_bytes against the inputs of a rotated call
 static bool rot_out_overlaps(const void* out, double out_bytes, const float* features, int64_t M, int32_t K, const RotArgs& a, int64_t Q,
                              const int32_t* row, const int32_t* ray, int64_t T) {
@@ -359,21 +171,16 @@ int svoxt_shade_rot_fwd(const float* features, int64_t M, int32_t K, const svoxt
     const char* fn = "svoxt_shade_rot_fwd";
     int rc, C, bd;
     const RotArgs a{extra, rotations, viewdirs, extra_rows, extra_cols, rot_dim};
-    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn)) || (rc = rot_check(fn, opt, a, M, Q))) return rc;
-    if (T == 0) return SVOXT_OK;
-    if (row == nullptr || sigma == nullptr || (C > 0 && (values == nullptr || ray == nullptr)))
-        return fail(SVOXT_ERR_INVALID, "%s: row / ray / values / sigma is NULL", fn);
-    if (M > 0 && features == nullptr) return fail(SVOXT_ERR_INVALID, "%s: features is NULL", fn);
-    if (misaligned(features, 4) || misaligned(row, 4) || misaligned(ray, 4) || misaligned(values, 4) || misaligned(sigma, 4))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    if ((rc = shade_fwd_check(fn, opt, &a, features, M, K, row, ray, T, nullptr, Q, values, sigma, &C, &bd)) || T == 0) return rc;
     const double vb = 4.0 * (double)T * C, sb = 4.0 * (double)T;
     if (rot_out_overlaps(values, vb, features, M, K, a, Q, row, ray, T) || rot_out_overlaps(sigma, sb, features, M, K, a, Q, row, ray, T) ||
         ranges_overlap(values, vb, sigma, sb))
         return fail(SVOXT_ERR_INVALID, "%s: values / sigma overlaps an input or the other output", fn);
     const RotDev R = rot_dev(opt, a, M, Q);
     with_basis(opt, [&](auto BD) {
-        hipLaunchKernelGGL((shade_rot_fwd_kernel<decltype(BD)::value>), launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, (hipStream_t)stream,
-                           features, (int)K, C, bd, (int)opt->min_comp, (int)opt->max_comp, activate != 0, R, T, row, ray, values, sigma);
+        using S = RotBasis<decltype(BD)::value>;
+        hipLaunchKernelGGL(shade_fwd_kernel<S>, launch_grid(T * (C + 1)), dim3(kLaunchBlock), 0, (hipStream_t)stream, features, M, (int)K, C,
+                           (int)opt->min_comp, (int)opt->max_comp, activate != 0, S{R, row, bd}, T, row, ray, values, sigma);
     });
     return check_launch(fn);
 }
@@ -388,30 +195,22 @@ int svoxt_shade_rot_bwd(const svoxt_options* opt, int64_t M, int32_t K, const fl
     int rc, C, bd;
     const RotArgs a{extra, rotations, viewdirs, extra_rows, extra_cols, rot_dim};
     const RowPlanRef plan{row_ptr, perm, long_rows, long_chunk_ptr, chunk_long, T, M, n_long, n_chunks};
-    if ((rc = shade_dims(opt, M, K, T, Q, &C, &bd, fn)) || (rc = rot_check(fn, opt, a, M, Q)) || (rc = row_plan_check(fn, plan))) return rc;
-    if (M == 0) return SVOXT_OK;
-    if (grad == nullptr || row_ptr == nullptr) return fail(SVOXT_ERR_INVALID, "%s: grad / row_ptr is NULL", fn);
-    if (C == 0) grad_values = nullptr;                           // (no colour column: nothing of it is read)
-    if (T > 0 && (perm == nullptr || (grad_values != nullptr && (row == nullptr || ray == nullptr || (activate != 0 && values == nullptr)))))
-        return fail(SVOXT_ERR_INVALID, "%s: perm / row / ray / values is NULL", fn);
-    if ((rc = row_plan_long_check(fn, plan))) return rc;
-    if (misaligned(row, 4) || misaligned(ray, 4) || misaligned(values, 4) || misaligned(grad_values, 4) || misaligned(grad_sigma, 4) ||
-        row_plan_misaligned(plan) || misaligned(grad, 4) || misaligned(workspace, 4))
-        return fail(SVOXT_ERR_INVALID, "%s: a misaligned argument (4 bytes)", fn);
+    float* partials;
+    if ((rc = shade_bwd_check(fn, opt, &a, plan, K, row, ray, nullptr, Q, activate, values, &grad_values, grad_sigma, grad, workspace, &C,
+                              &bd)) || M == 0)
+        return rc;
     const double gb = 4.0 * (double)M * K, tc = 4.0 * (double)T * C;
     if (rot_out_overlaps(grad, gb, nullptr, M, K, a, Q, row, ray, T) || ranges_overlap(grad, gb, values, tc) ||
         ranges_overlap(grad, gb, grad_values, tc) || ranges_overlap(grad, gb, grad_sigma, 4.0 * (double)T))
         return fail(SVOXT_ERR_INVALID, "%s: grad overlaps an input", fn);
-    if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K),
-                                            "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)")))
+    if ((rc = shade_partials(fn, plan, K, workspace, workspace_bytes, "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, K)", &partials)))
         return rc;
-    Carver w(workspace);
-    float* partials = w.take<float>((size_t)n_chunks * (size_t)K);
     const RotDev R = rot_dev(opt, a, M, Q);
     // a lane per (row, column) over all K columns: every element of grad is written
     with_basis(opt, [&](auto BD) {
-        const ShadeRotValues<decltype(BD)::value> src{row, ray, values, grad_values, grad_sigma, R, T, (int)K, C, bd, (int)opt->min_comp,
-                                                      (int)opt->max_comp, activate != 0};
+        using S = RotBasis<decltype(BD)::value>;
+        const ShadeValues<S> src{ray, values, grad_values, grad_sigma, S{R, row, bd}, T, (int)K, C, (int)opt->min_comp, (int)opt->max_comp,
+                                 activate != 0};
         rows_launch<ROWS_SUM, ROWS_SUM>(src, (int)K, plan, nullptr, (int)K, 0.f, grad, partials, (hipStream_t)stream);
     });
     return check_launch(fn);
@@ -471,11 +270,10 @@ int svoxt_shade_rot_bwd_rotations(const float* gu, const float* viewdirs, int64_
     if (ranges_overlap(grad_rotations, gb, gu, 12.0 * (double)T) || ranges_overlap(grad_rotations, gb, viewdirs, 12.0 * (double)Q) ||
         ranges_overlap(grad_rotations, gb, ray, 4.0 * (double)T))
         return fail(SVOXT_ERR_INVALID, "%s: grad_rotations overlaps an input", fn);
-    if (n_long > 0 && (rc = workspace_check(fn, workspace, workspace_bytes, svoxt_shade_samples_bwd_workspace_bytes(n_chunks, dd),
-                                            "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, rot_dim * rot_dim)")))
+    float* partials;
+    if ((rc = shade_partials(fn, plan, dd, workspace, workspace_bytes, "svoxt_shade_samples_bwd_workspace_bytes(n_chunks, rot_dim * rot_dim)",
+                             &partials)))
         return rc;
-    Carver w(workspace);
-    float* partials = w.take<float>((size_t)n_chunks * (size_t)dd);
     const RotGradValues src{ray, gu, viewdirs, T, Q, (int)rot_dim};
     // a lane per (row, a, b) over all rot_dim^2 columns: every element of grad_rotations is written
     rows_launch<ROWS_SUM, ROWS_SUM>(src, dd, plan, nullptr, dd, 0.f, grad_rotations, partials, (hipStream_t)stream);

@@ -322,6 +322,11 @@ def _view_basis(self, rays: Rays, *, image_shape=None, transformation_matrices=N
         return _C.view_basis(self.tree._spec(self.tree.features.detach()), _rays_spec_from_rays(rays, image_shape), self._get_options())
 
 
+def _upstream(g):
+    """An upstream gradient as the kernels take it: contiguous, or None (zeros: the kernel's null pointer)."""
+    return None if g is None else g.contiguous()
+
+
 class _ShadeSamplesFunction(autograd.Function):
     @staticmethod
     def forward(ctx, features, samples, basis, opt, activate):
@@ -347,8 +352,7 @@ class _ShadeSamplesFunction(autograd.Function):
         values = ctx.saved_tensors[0]
         basis = ctx.saved_tensors[1] if ctx.has_basis else None
         s = ctx.samples
-        gv = None if grad_values is None else grad_values.contiguous()
-        gs = None if grad_sigma is None else grad_sigma.contiguous()
+        gv, gs = _upstream(grad_values), _upstream(grad_sigma)
         grad = grad_basis = None
         if ctx.needs_input_grad[0]:
             plan = s.row_plan(ctx.shape[0])
@@ -383,8 +387,7 @@ class _ShadeRotatedFunction(autograd.Function):
             raise RuntimeError("shade_samples: the gradients of the rotated call are once differentiable (no double backward)")
         values, viewdirs, rotations = ctx.saved_tensors[:3]
         s, M = ctx.samples, ctx.shape[0]
-        gv = None if grad_values is None else grad_values.contiguous()
-        gs = None if grad_sigma is None else grad_sigma.contiguous()
+        gv, gs = _upstream(grad_values), _upstream(grad_sigma)
         grad = grad_rot = grad_view = None
         if need_f:
             grad = _X.shade_rot_bwd(ctx.shape, s.row, s.ray, rotations, viewdirs, ctx.extra, s.Q, ctx.opt, ctx.activate, values, gv, gs,
@@ -465,8 +468,7 @@ def _shade_samples(self, samples: RaySamples, features=None, rays: Rays = None, 
         if basis is not None:
             raise RuntimeError("shade_samples: `rotations` and `basis` exclude each other: a per-ray basis has no row to rotate by "
                                "(pass `rays`)")
-        if not isinstance(rotations, torch.Tensor) or rotations.dtype != torch.float32 or rotations.dim() != 3 \
-                or tuple(rotations.shape[1:]) not in ((3, 3), (4, 4)):
+        if not _X._is_rotations(rotations):
             raise RuntimeError("shade_samples: rotations must be float32 [M, 3, 3] or [M, 4, 4], one matrix per feature row")
         if rotations.shape[0] != features.shape[0]:
             raise RuntimeError(f"shade_samples: rotations holds {rotations.shape[0]} matrices, the feature table {features.shape[0]} rows")
