@@ -30,6 +30,7 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
+import typing
 
 import torch
 
@@ -336,6 +337,10 @@ class SampleLists:
         ev = torch.cuda.Event()
         ev.record()
         ent[1] = (ev, host, self.pool_blocks)
+
+    def facts(self):
+        """What the backward's route reads of these lists (_bwd_route)."""
+        return _ListFacts(self.consumed, self.terms is not None, self.terms_state, self.flags, self.exp_table is not None)
 
     def c_struct(self):
         return _CLists(self.rec.data_ptr(), self.aux.data_ptr(), self.S,
@@ -644,6 +649,17 @@ def _take_plan(kind, tree, rays, opt):
     return p
 
 
+def _replayed(kind, tree, rays, opt, grad_output):
+    """A plain backward call of operator `kind`: (the plan its forward left, grad_output in the order that forward rendered
+    in, the rays spec it rendered) -- or None: AUTO_PLAN is off or no plan applies, and the backward marches."""
+    p = _take_plan(kind, tree, rays, opt) if AUTO_PLAN else None
+    if p is None:
+        return None
+    _check_input(grad_output, "grad_output")
+    g = grad_output if p.perm is None else _permute_rows(grad_output, p.perm, scatter=False)
+    return p, g, (p.rays if p.rays is not None else rays)
+
+
 # ---------------------------------------------------------------------------
 # Payloads one step away from a specialised one (r05; VERDICT r04 item 8).  The list kernels and the per-tile backward exist
 # for three channels (x 1 / 4 / 9 / 16 / 25 basis functions or lobes) and for RGBA-style rows of 4 / 8 / 16 / 32 floats;
@@ -665,10 +681,15 @@ def _take_plan(kind, tree, rays, opt):
 PAD_PAYLOADS = True
 
 
+def _gpu_table(switch, f) -> bool:
+    """The switch is on and `f` is a float32 2-D table on the GPU (anything else: the packers will say what is wrong)."""
+    return bool(switch) and isinstance(f, torch.Tensor) and f.dim() == 2 and f.dtype == torch.float32 and f.is_cuda
+
+
 def _pad_layout(tree: TreeSpec, opt: RenderOptions):
     """None, or (K', columns of real channels, dummy columns): the specialised payload this one is rendered as."""
     f = tree.features
-    if not PAD_PAYLOADS or not isinstance(f, torch.Tensor) or f.dim() != 2 or f.dtype != torch.float32 or not f.is_cuda:
+    if not _gpu_table(PAD_PAYLOADS, f):
         return None
     K, fmt, bd = f.shape[1], int(opt.format), int(opt.basis_dim)
     if fmt == FORMAT_RGBA:
@@ -746,7 +767,7 @@ GROUP_PAYLOADS = True
 def _group_layout(tree: TreeSpec, opt: RenderOptions):
     """None, or (coefficients per channel, channels, channels per group)."""
     f = tree.features
-    if not GROUP_PAYLOADS or not isinstance(f, torch.Tensor) or f.dim() != 2 or f.dtype != torch.float32 or not f.is_cuda:
+    if not _gpu_table(GROUP_PAYLOADS, f):
         return None
     if _numel(tree._weight_accum) or _numel(getattr(tree, "transformation_matrices", None)):
         return None
@@ -812,108 +833,180 @@ def volume_render(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions, record: bo
 LAST_ROUTE = {"forward": None, "backward": None, "forward_terms": False}
 
 
-def _volume_render(tree, rays, opt, record):
-    # (r05) A forward whose march is wavefronts of its own -- every recording forward, and the two-kernel forward of rows of
-    # 8 / 16 / 32 floats -- waits for the grid cell and nothing else: for them the grid in 4 x 4 x 4 bricks and a level finer
-    # (fwd_roles_kernel at 800 x 800 / depth 8: 0.248 -> 0.234 ms; march_rec_kernel + shade_chan_kernel at 1024 x 1024 /
-    # depth 9: 0.837 -> 0.801); the one-kernel forward, short of issue slots, keeps the row-major grid (include/svoxt.h,
-    # SVOXT_ACCEL_BRICKS).
-    bricks = _numel(tree._weight_accum) == 0 and (bool(record) or (int(opt.format) == FORMAT_RGBA and tree.features.shape[1] in (8, 16, 32)
-                                                                    and FWD_SPLIT != "0"))
-    ct, cr, co = _pack_tree_accel(tree, bricks, vec_rows=True), _pack_rays(rays), _pack_opts(opt)
-    dev = tree.features.device
-    lists = None
-    wide = co.format == FORMAT_RGBA and ct.K in (8, 16, 32)
+# ---------------------------------------------------------------------------
+# The route of a render step ("One route record for the render step").  Which kernels a forward or a backward
+# takes is decided ONCE per call, by a pure function of the packed structs and the switches (_fwd_route, _bwd_route: no
+# tensor, no launch, no cache), and comes back as a record; _volume_render / _volume_render_backward allocate, attach and
+# call as the record says and name the route by its label.  What the forward must know about the backward that will follow
+# (SG / ASG lists are recorded only for the backward that reads them; the hand-over is left only for the backward that wants
+# it) it asks the predicates the backward itself decides by -- below, each written once, each reading the switches when it is
+# called (tests assign them mid-process).
+# ---------------------------------------------------------------------------
+def _tiled(cr) -> bool:
+    """A declared image of whole 8 x 8 pixel tiles: the kernels walk it tile by tile."""
+    return cr.image_width > 0 and cr.image_width % 8 == 0 and cr.image_height % 8 == 0
+
+
+def _coherent(cr, rays) -> bool:
+    """64 consecutive rays revisit the same leaves: an image walked in tiles, or a batch in svoxt_ray_order's order."""
+    return _tiled(cr) or bool(getattr(rays, "coherent", False))
+
+
+def _per_tile(coherent: bool) -> bool:
+    """BWD_GATHER: does a batch go to the per-tile backwards (where the payload has one)?  They pay off when a wavefront's
+    64 rays revisit the same leaves (0.94 -> 0.54 ms on the headline workload); on shuffled rays they lose (2.4 vs 1.65 ms)."""
+    return BWD_GATHER == 2 or (BWD_GATHER == 1 and coherent)
+
+
+def _exact_tiles() -> bool:
+    """The exact per-tile backward as ONE kernel over the forward's hand-over (lists.terms) is switched on."""
+    return bool(BWD_EXACT and BWD_TERMS and BWD_FUSED)
+
+
+def _chan_rows(fmt: int, K: int) -> bool:
+    """RGBA-style rows of 8 / 16 / 32 floats: the payloads of the channel-lane kernels."""
+    return fmt == FORMAT_RGBA and K in (8, 16, 32)
+
+
+def _xf_one_launch(ct, co) -> bool:
+    """SH 1 / 4 / 9, three channels, per-leaf view rotations, N = 2: the payloads whose rotated forward is one launch
+    (fwd_roles_kernel<XF>) and whose per-tile backward is one kernel (grad_fused_kernel<EXACT, XF>)."""
+    return bool(ct.xform) and ct.N == 2 and co.format == FORMAT_SH and co.basis_dim in (1, 4, 9) and ct.K == 3 * co.basis_dim + 1
+
+
+def _fwd_bricks(tree, opt, record) -> bool:
+    """(r05) A forward whose march is wavefronts of its own -- every recording forward, and the two-kernel forward of rows
+    of 8 / 16 / 32 floats -- waits for the grid cell and nothing else: for them the grid in 4 x 4 x 4 bricks and a level finer
+    (fwd_roles_kernel at 800 x 800 / depth 8: 0.248 -> 0.234 ms; march_rec_kernel + shade_chan_kernel at 1024 x 1024 /
+    depth 9: 0.837 -> 0.801); the one-kernel forward, short of issue slots, keeps the row-major grid (include/svoxt.h,
+    SVOXT_ACCEL_BRICKS).  Asked before the structs exist: the packer takes the answer."""
+    return _numel(tree._weight_accum) == 0 and (bool(record) or (_chan_rows(int(opt.format), tree.features.shape[1])
+                                                                   and FWD_SPLIT != "0"))
+
+
+class _ListFacts(typing.NamedTuple):
+    """What a backward's route reads of the sample lists it is given."""
+    consumed: bool          # a two-kernel backward rewrote `rec`
+    has_terms: bool         # lists.terms is allocated
+    terms_state: int        # 2 / 3: the forward left the hand-over (lane-major / position-major); 0: scratch
+    flags: int              # svoxt_sample_lists.flags
+    has_table: bool         # the forward's exponentials table is on the lists
+
+
+class _FwdRoute(typing.NamedTuple):
+    record: bool            # sample lists are recorded for the backward
+    flags: int              # svoxt_sample_lists.flags of the lists / the scratch (the image walk is added to recorded ones)
+    fills: int              # terms_state the forward leaves: 2 / 3 (lists.terms is then allocated), 0: no hand-over
+    mask: bool              # the sigma bitmask is attached, with ...
+    mask_thresh: float      # ... this threshold,
+    mask_keep: bool         # ... cached on a static feature tensor,
+    mask_table: bool        # ... and the exponentials table of rows of 8 / 16 / 32 floats built in the same pass
+    entry: str              # the library entry that is called: one of the four _FWD_* names
+    label: str              # LAST_ROUTE["forward"]
+
+    @property
+    def forward_terms(self) -> bool:
+        return self.record and self.fills in (2, 3)
+
+    def list_facts(self):
+        """The lists this forward hands to the backward, as its route will see them (None: none)."""
+        return _ListFacts(False, bool(self.fills), self.fills, self.flags, self.mask and self.mask_table) if self.record else None
+
+
+_FWD_RECORD, _FWD_SCRATCH = "svoxt_volume_render_fwd_record", "svoxt_volume_render_fwd_scratch"
+_FWD_WS, _FWD = "svoxt_volume_render_fwd_ws", "svoxt_volume_render_fwd"
+_ROLES, _TILE2 = "fwd_roles_kernel (march + shade_tile in one launch)", "march_rec_kernel + shade_tile_kernel (two-kernel forward)"
+
+
+def _fwd_route(ct, cr, co, record, coherent: bool, accel: bool, masks: bool) -> _FwdRoute:
+    """accel: an acceleration grid is attached to ct; masks: a sigma bitmask that is asked for will be attached
+    (_attach_sigma_mask: SIGMA_MASK and ct.M > 0) -- the two facts that are known only once resources are taken."""
+    wide = _chan_rows(co.format, ct.K)
     # (per-leaf weight accumulation: the library's one-kernel forward alone adds the weights -- fwd_split_payload -- so no
     # scratch, mask or table is made for a forward that would not touch them; r05: its untouched scratch was read as the
     # pool's use, the r04 mistake of the 3-channel payloads over again)
     split = ((FWD_SPLIT != "0") if FWD_SPLIT != "" else wide) and ct.weight_accum is None
     can_rec = _lib.svoxt_can_record(ctypes.byref(ct), ctypes.byref(co)) if (record and BWD_LIST_SAMPLES > 0 and cr.Q > 0) else 0
-    will_record = bool(can_rec)
-    if can_rec == 2:
-        # SG / ASG: lists serve the exact per-tile backward alone -- recorded when that is the backward that will run
-        # (the conditions of _volume_render_backward), else the backward marches by itself as before
-        tiled = cr.image_width > 0 and cr.image_width % 8 == 0 and cr.image_height % 8 == 0
-        coherent = tiled or bool(getattr(rays, "coherent", False))
-        will_record = bool(BWD_EXACT and BWD_TERMS and BWD_FUSED and (BWD_GATHER == 2 or (BWD_GATHER == 1 and coherent)))
-    lflags = _list_flags(native=NATIVE_MATH and wide)
+    # SG / ASG (2): lists serve the exact per-tile backward alone -- recorded when that is the backward that will run,
+    # else the backward marches by itself as before
+    rec = bool(_exact_tiles() and _per_tile(coherent)) if can_rec == 2 else bool(can_rec)
+    flags = _list_flags(native=NATIVE_MATH and wide)
     # per-leaf view rotations, SH 1 / 4 / 9: march and shade in one launch too (no hand-over: their backward recomputes)
-    xf_roles = bool(will_record and ct.xform and FWD_SPLIT == "" and FWD_OVERLAP and LIST_POOL and BWD_XF_FUSED and ct.N == 2
-                    and ct.weight_accum is None and co.format == FORMAT_SH and co.basis_dim in (1, 4, 9)
-                    and ct.K == 3 * co.basis_dim + 1)
+    xf_roles = bool(rec and FWD_SPLIT == "" and FWD_OVERLAP and LIST_POOL and BWD_XF_FUSED and ct.weight_accum is None
+                    and _xf_one_launch(ct, co))
     if xf_roles:
-        lflags |= LISTS_FWD_TWO_KERNELS
-    fills = _lib.svoxt_fwd_fills_terms(ctypes.byref(ct), ctypes.byref(co), lflags) \
-        if (will_record and BWD_EXACT and BWD_TERMS and BWD_FUSED and BWD_GATHER) else 0
-    # the march of the two-kernel forward reads a bit per row instead of gathering sigma -- where that
-    # forward is what runs and the stop rule (which needs sigma itself) does not apply
-    etab = None
-    lists = None
-    if will_record:
-        with _on(dev):
-            lists = SampleLists(cr.Q, _list_cap(ct, BWD_LIST_SAMPLES), dev)
-    if ((split or fills == 3 or xf_roles) and FWD_SPLIT != "0") if will_record else (split and (co.stop_thresh == 0.0 or wide)):
-        # rows of 8 / 16 / 32 floats in exact mode: the same pass leaves the rows' exponentials for the shade kernel
-        # (and, on the lists, for the per-tile backward of this feature content)
-        # (lists for a backward hold every sample with sigma > 0 whatever the forward's threshold: the mask of threshold 0)
-        etab = _attach_sigma_mask(tree, ct, 0.0 if will_record else float(co.sigma_thresh), keep=not will_record,
-                                  table=wide and split and not NATIVE_MATH, begin=lists)
-    LAST_ROUTE["forward_terms"] = False
-    # (for the label: with BWD_LIST_SAMPLES = 0 nothing is recorded, and a specialised payload still has its own kernel)
-    special = bool(can_rec or not record or _lib.svoxt_can_record(ctypes.byref(ct), ctypes.byref(co)))
+        flags |= LISTS_FWD_TWO_KERNELS
+    # the exact per-tile backward will want (att, e0, e1, e2) of every sample: does this forward have them?
+    fills = _lib.svoxt_fwd_fills_terms(ctypes.byref(ct), ctypes.byref(co), flags) if (rec and _exact_tiles() and BWD_GATHER) else 0
+    # the march of the two-kernel forward reads a bit per row instead of gathering sigma -- where that forward is what
+    # runs and the stop rule (which needs sigma itself) does not apply.  Lists for a backward hold every sample with
+    # sigma > 0 whatever the forward's threshold: the mask of threshold 0.  Rows of 8 / 16 / 32 floats in exact mode: the
+    # same pass leaves the rows' exponentials for the shade kernel (and, on the lists, for the per-tile backward)
+    mask = bool(masks and (((split or fills == 3 or xf_roles) and FWD_SPLIT != "0") if rec else
+                           (split and (co.stop_thresh == 0.0 or wide))))
     # march and shade of a 3-channel payload as ONE launch (fwd_roles_kernel): the conditions of the library's launch_fwd_roles
-    roles = bool(FWD_OVERLAP and LIST_POOL and ct.sigma_mask and ct.N == 2 and ct.xform is None and ct.weight_accum is None
+    roles = bool(FWD_OVERLAP and LIST_POOL and mask and ct.N == 2 and ct.xform is None and ct.weight_accum is None
                  and cr.Q > 0 and ((co.format == FORMAT_RGBA and ct.K == 4) or
                                    (co.format in (FORMAT_SH, FORMAT_SG, FORMAT_ASG) and co.basis_dim in (1, 4, 9, 16)
-                                    and ct.K == 3 * co.basis_dim + 1 and (co.format == FORMAT_SH or ct.accel))))
-    LAST_ROUTE["forward"] = (("march_rec_kernel + shade_chan_kernel (two-kernel forward, channels on lanes"
-                              + (", native exp / rcp)" if NATIVE_MATH else ")") if wide else
-                              "fwd_roles_kernel (march + shade_tile in one launch)" if roles else
-                              "march_rec_kernel + shade_tile_kernel (two-kernel forward)") if split
-                             else ("render_fwd_kernel" if special else "render_fwd_generic_kernel (no specialised instance: accumulators in "
-                                   "memory as the reference keeps them)")) + (", recording sample lists" if will_record else "")
+                                    and ct.K == 3 * co.basis_dim + 1 and (co.format == FORMAT_SH or accel))))
+    if xf_roles:
+        label = "fwd_roles_kernel<XF> (march + shade_tile in one launch, a basis per record)"
+    elif rec and fills == 3 and FWD_SPLIT == "":
+        label = _ROLES if roles else _TILE2
+    elif split:
+        label = ("march_rec_kernel + shade_chan_kernel (two-kernel forward, channels on lanes"
+                 + (", native exp / rcp)" if NATIVE_MATH else ")")) if wide else _ROLES if roles else _TILE2
+    # (with BWD_LIST_SAMPLES = 0 nothing is recorded, and a specialised payload still has its own kernel)
+    elif can_rec or not record or _lib.svoxt_can_record(ctypes.byref(ct), ctypes.byref(co)):
+        label = "render_fwd_kernel"
+    else:
+        label = "render_fwd_generic_kernel (no specialised instance: accumulators in memory as the reference keeps them)"
+    # scratch lists for the two-kernel forward of a call that records none (march, then shade per tile; the library falls
+    # back to the one-kernel forward for payloads it does not cover).  (r04: only where that forward is what runs -- the
+    # one-kernel forward never touched its scratch, and what note_usage then read as the pool's use was uninitialised
+    # memory: a garbage size hint, looked at again after every forward)
+    entry = _FWD_RECORD if rec else (_FWD_SCRATCH if LIST_POOL else _FWD_WS) if (split and FWD_LIST_SAMPLES > 0 and cr.Q > 0) else _FWD
+    return _FwdRoute(rec, flags, fills, mask, 0.0 if rec else float(co.sigma_thresh), not rec,
+                     bool(wide and split and not NATIVE_MATH and EXP_TABLE), entry, label + (", recording sample lists" if rec else ""))
+
+
+def _volume_render(tree, rays, opt, record):
+    ct, cr, co = _pack_tree_accel(tree, _fwd_bricks(tree, opt, record), vec_rows=True), _pack_rays(rays), _pack_opts(opt)
+    dev = tree.features.device
+    r = _fwd_route(ct, cr, co, record, _coherent(cr, rays), bool(ct.accel), bool(SIGMA_MASK and ct.M > 0))
+    lists = etab = None
+    if r.record:
+        with _on(dev):
+            lists = SampleLists(cr.Q, _list_cap(ct, BWD_LIST_SAMPLES), dev)
+    if r.mask:
+        etab = _attach_sigma_mask(tree, ct, r.mask_thresh, keep=r.mask_keep, table=r.mask_table, begin=lists)
     with _on(dev):
         out = torch.empty((cr.Q, get_out_data_dim(opt, ct.K)), dtype=torch.float32, device=dev)
-        if will_record:
+        if r.record:
             # (the walk of an image's tiles goes on the lists: the backward replays them the way they were recorded,
             # whatever svoxt_set_super_tile_rows says by then)
-            lists.flags = lflags | max(0, _lib.svoxt_image_walk(ctypes.byref(ct), ctypes.byref(cr)))
+            lists.flags = r.flags | max(0, _lib.svoxt_image_walk(ctypes.byref(ct), ctypes.byref(cr)))
             lists.bricks = bool(ct.accel and (ct.accel_log2 & 0x100))
             lists.exp_table = etab
-            if fills:
-                # the exact per-tile backward will want (att, e0, e1, e2) of every sample: this forward has them
+            if r.fills:
                 lists.terms = torch.empty((lists.pool_blocks * 512 * 4,), dtype=torch.float32, device=dev)
-                lists.terms_state = fills
+                lists.terms_state = r.fills
             cl = lists.c_struct()
-            _call("svoxt_volume_render_fwd_record", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
-                  _ptr(out), ctypes.byref(cl), _stream(dev))
+            _call(_FWD_RECORD, ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), ctypes.byref(cl), _stream(dev))
             lists.note_usage()
-            LAST_ROUTE["forward_terms"] = lists.terms_state in (2, 3)
-            if lists.terms_state == 3 and FWD_SPLIT == "":
-                LAST_ROUTE["forward"] = ("fwd_roles_kernel (march + shade_tile in one launch)" if roles else
-                                         "march_rec_kernel + shade_tile_kernel (two-kernel forward)") + ", recording sample lists"
-            if xf_roles:
-                LAST_ROUTE["forward"] = "fwd_roles_kernel<XF> (march + shade_tile in one launch, a basis per record), recording sample lists"
-        elif split and FWD_LIST_SAMPLES > 0 and cr.Q > 0:
-            # scratch for the two-kernel forward (march, then shade per tile; the library falls
-            # back to the one-kernel forward for payloads it does not cover).  (r04: only where that forward is what
-            # runs -- the one-kernel forward never touched its scratch, and what note_usage then read as the pool's
-            # use was uninitialised memory: a garbage size hint, looked at again after every forward)
-            if LIST_POOL:
-                scratch = SampleLists(cr.Q, _list_cap(ct, FWD_LIST_SAMPLES), dev, kind="scratch")
-                scratch.flags = lflags
-                cl = scratch.c_struct()
-                _call("svoxt_volume_render_fwd_scratch", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
-                      _ptr(out), ctypes.byref(cl), 0, _stream(dev))
-                scratch.note_usage()
-            else:
-                nbytes = _lib.svoxt_fwd_workspace_bytes(cr.Q, FWD_LIST_SAMPLES)
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-                _call("svoxt_volume_render_fwd_ws", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
-                      _ptr(out), _ptr(ws), nbytes, lflags, _stream(dev))
+        elif r.entry == _FWD_SCRATCH:
+            scratch = SampleLists(cr.Q, _list_cap(ct, FWD_LIST_SAMPLES), dev, kind="scratch")
+            scratch.flags = r.flags
+            cl = scratch.c_struct()
+            _call(_FWD_SCRATCH, ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), ctypes.byref(cl), 0, _stream(dev))
+            scratch.note_usage()
+        elif r.entry == _FWD_WS:
+            nbytes = _lib.svoxt_fwd_workspace_bytes(cr.Q, FWD_LIST_SAMPLES)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            _call(_FWD_WS, ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), _ptr(ws), nbytes, r.flags, _stream(dev))
         else:
-            _call("svoxt_volume_render_fwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
-                  _ptr(out), _stream(dev))
+            _call(_FWD, ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(out), _stream(dev))
+    LAST_ROUTE["forward"], LAST_ROUTE["forward_terms"] = r.label, r.forward_terms
     return (out, lists) if record else out
 
 
@@ -965,16 +1058,69 @@ def volume_render_backward(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions,
                 grad[:, -1] += gg[:, -1]
         rays._svoxt_groups = None
         return grad
-    if lists is None and fwd_output is None and AUTO_PLAN:
-        p = _take_plan("volume", tree, rays, opt)
-        if p is not None:
-            _check_input(grad_output, "grad_output")
-            g = grad_output if p.perm is None else _permute_rows(grad_output, p.perm, scatter=False)
-            fo = p.out if (p.lists is not None and p.out._version == p.over) else None
-            if fo is not None and fo.dim() == 3:
-                fo = fo.view(-1, fo.shape[2])
-            return _volume_render_backward(tree, p.rays if p.rays is not None else rays, opt, g, p.lists, fo)
+    got = _replayed("volume", tree, rays, opt, grad_output) if (lists is None and fwd_output is None) else None
+    if got is not None:
+        p, g, rr = got
+        fo = p.out if (p.lists is not None and p.out._version == p.over) else None
+        if fo is not None and fo.dim() == 3:
+            fo = fo.view(-1, fo.shape[2])
+        return _volume_render_backward(tree, rr, opt, g, p.lists, fo)
     return _volume_render_backward(tree, rays, opt, grad_output, lists, fwd_output)
+
+
+class _BwdRoute(typing.NamedTuple):
+    replay: bool            # the lists are replayed (False: they do not serve this backward, or there are none: it marches)
+    kind: str               # "march" / "replay" / "onepass" / "wide" / "merge" / "fused": the kernels, as the label names them
+    use_fo: bool            # the forward's output goes in: the single-march tolerance mode
+    terms_per_slot: int     # floats of lists.terms a list slot needs as scratch between the sweeps (0: lists.terms stays as it is)
+    coef_planes: int        # planes of lists.coef the two-kernel form writes (it rewrites rec: the lists are consumed); 0: none
+    one_kernel: bool        # list walk and merge as one kernel: coef_bytes = -1, no buffer, rec stays as recorded
+    table: bool             # the forward's exponentials table is handed over (svoxt_tree.exp_table)
+    label: str              # LAST_ROUTE["backward"]
+
+
+_BWD_MARCH = _BwdRoute(False, "march", False, 0, 0, False, False, "render_bwd_kernel (marches, one atomic row per sample)")
+
+
+def _bwd_route(ct, co, cols: int, coherent: bool, lists, has_fo: bool) -> _BwdRoute:
+    """cols: columns of grad_output; lists: the _ListFacts of the lists given, or None; has_fo: a fwd_output was given."""
+    if lists is None or lists.consumed:       # (a second backward over the same forward: the lists were rewritten)
+        return _BWD_MARCH
+    K, lobes = ct.K, co.format in (FORMAT_SG, FORMAT_ASG)
+    tile = ct.N == 2 and _per_tile(coherent)
+    # rows wider than 32 floats (SH16: 49, SH25: 76): per tile only as ONE kernel over the hand-over the recording
+    # forward left (lists.terms_state 2 / 3), exact arithmetic, no view rotations
+    wide_sh = K > 32 and (co.format == FORMAT_SH or lobes) and co.basis_dim in (16, 25) and K == 3 * co.basis_dim + 1 and \
+        lists.has_terms and lists.terms_state in (2, 3) and _exact_tiles() and ct.xform is None
+    gather = (K <= 32 or wide_sh) and cols == 4 and tile
+    if lobes and not (gather and BWD_FUSED and BWD_EXACT and ct.xform is None and lists.has_terms and lists.terms_state == 3):
+        return _BWD_MARCH                     # SG / ASG lists serve the exact per-tile backward only: march instead
+    # (the single-march tolerance mode differentiates the forward's own sum: only without thresholds)
+    use_fo = bool(has_fo and not BWD_EXACT and co.sigma_thresh == 0.0 and co.stop_thresh == 0.0)
+    if gather:
+        # (the fused kernel's exact form is the only one view rotations take: SH up to 9 basis functions)
+        if BWD_FUSED and (ct.xform is None or (not use_fo and BWD_EXACT and BWD_XF_FUSED and _xf_one_launch(ct, co))):
+            return _BwdRoute(True, "fused", use_fo, 0, 0, True, False,
+                             "grad_fused_kernel<EXACT, XF> (two sweeps over the lists, a basis per record + per-tile merge)"
+                             if ct.xform is not None else
+                             "grad_fused_kernel<EXACT> (two sweeps over the lists + per-tile merge)" if not use_fo else
+                             "grad_fused_kernel (one sweep over the lists + per-tile merge; accum from the forward's output)")
+        # with view rotations a second plane holds each sample's rotated direction
+        return _BwdRoute(True, "merge", use_fo, 0, 2 if ct.xform is not None else 1, False, False,
+                         "render_bwd_kernel<GATHER> + grad_merge_kernel (list walk, then per-tile merge)")
+    # rows of 8 / 16 / 32 floats: one sigmoid pass instead of two -- the first sweep leaves a float per list slot for the
+    # second: (attenuation, total_color) per tile (grad_wide_kernel: coherent batches on N = 2 trees), total_color alone
+    # per ray (render_bwd_kernel<ONEPASS>)
+    if _chan_rows(co.format, K) and cols == K and not use_fo and BWD_TERMS:
+        if BWD_FUSED and tile and ct.xform is None:
+            native = bool(lists.flags & LISTS_NATIVE_MATH)
+            return _BwdRoute(True, "wide", use_fo, 2, 0, True, lists.has_table and not native,
+                             "grad_wide_kernel (two sweeps over the lists, sigmoids per record once + once per distinct row; "
+                             "per-tile merge" + (", native exp / rcp)" if native else
+                                                 ", exponentials from the forward's table)" if lists.has_table else ")"))
+        return _BwdRoute(True, "onepass", use_fo, 1, 0, False, False,
+                         "render_bwd_kernel<ONEPASS> (two list walks, sigmoids formed once; one atomic row + one sigma atomic per sample)")
+    return _BwdRoute(True, "replay", use_fo, 0, 0, False, False, "render_bwd_kernel<REPLAY> (list walk, one atomic row per sample)")
 
 
 def _volume_render_backward(tree, rays, opt, grad_output, lists, fwd_output):
@@ -988,83 +1134,44 @@ def _volume_render_backward(tree, rays, opt, grad_output, lists, fwd_output):
     # Accumulate into rows that start on 64-byte boundaries (fewer memory-side
     # atomic requests per row), then hand back the dense [M, K] the caller expects.
     stride = K if (K <= 8 or K % 16 == 0) else (K + 15) // 16 * 16
-    if lists is not None and lists.consumed:
-        lists = None              # a second backward over the same forward: the lists were rewritten
-    # the two-kernel backward pays off when a wavefront's 64 rays revisit the same leaves,
-    # i.e. for image batches walked in 8x8 tiles (0.94 -> 0.54 ms on the headline workload);
-    # on shuffled rays it loses to the one-kernel backward (2.4 vs 1.65 ms)
-    tiled = cr.image_width > 0 and cr.image_width % 8 == 0 and cr.image_height % 8 == 0
-    coherent = tiled or bool(getattr(rays, "coherent", False))      # or sorted by svoxt_ray_order
-    # rows wider than 32 floats (SH16: 49, SH25: 76): per tile only as ONE kernel over the hand-over the recording
-    # forward left (lists.terms_state 2 / 3), exact arithmetic, no view rotations
-    wide_sh = K > 32 and lists is not None and co.format in (FORMAT_SH, FORMAT_SG, FORMAT_ASG) and co.basis_dim in (16, 25) and \
-        K == 3 * co.basis_dim + 1 and lists.terms is not None and lists.terms_state in (2, 3) and \
-        BWD_EXACT and BWD_FUSED and BWD_TERMS and ct.xform is None
-    gather = lists is not None and (K <= 32 or wide_sh) and grad_output.shape[1] == 4 and ct.N == 2 and \
-        (BWD_GATHER == 2 or (BWD_GATHER == 1 and coherent))
-    if lists is not None and co.format in (FORMAT_SG, FORMAT_ASG) and not (
-            gather and BWD_FUSED and BWD_EXACT and ct.xform is None and lists.terms is not None and lists.terms_state == 3):
-        lists = None              # SG / ASG lists serve the exact per-tile backward only: march instead
-        gather = False
+    r = _bwd_route(ct, co, grad_output.shape[1], _coherent(cr, rays), None if lists is None else lists.facts(),
+                   fwd_output is not None)
     with _on(dev):
-        kept = _grad_scratch(dev, M, stride) if (GRAD_SCRATCH and lists is not None and stride != K and M > 0) else None
+        kept = _grad_scratch(dev, M, stride) if (GRAD_SCRATCH and r.replay and stride != K and M > 0) else None
         buf = kept[0] if kept is not None else torch.empty((M, stride), dtype=torch.float32, device=dev)
-        if lists is not None:
+        if r.replay:
             if lists.aux.shape[0] != cr.Q or lists.aux.device != dev:
                 raise RuntimeError("sample lists do not belong to this ray batch")
             fo = None
-            # (the single-march tolerance mode differentiates the forward's own sum: only without thresholds)
-            if fwd_output is not None and not BWD_EXACT and co.sigma_thresh == 0.0 and co.stop_thresh == 0.0:
+            if r.use_fo:
                 _check_input(fwd_output, "fwd_output")
                 if fwd_output.shape != grad_output.shape or fwd_output.dtype != torch.float32:
                     raise RuntimeError("fwd_output must match grad_output")
                 fo = fwd_output
-            # (fo None: the fused kernel's exact form -- the only one view rotations take: SH up to 9 basis functions)
-            fused = gather and BWD_FUSED and (ct.xform is None or (fo is None and BWD_EXACT and BWD_XF_FUSED and co.format == FORMAT_SH
-                                                                   and co.basis_dim in (1, 4, 9)))
-            wide = co.format == FORMAT_RGBA and grad_output.shape[1] in (8, 16, 32) and K == grad_output.shape[1]
-            # ... per tile (grad_wide_kernel) for coherent batches on N = 2 trees, else per ray (render_bwd_kernel<ONEPASS>)
-            wide_tile = wide and fo is None and BWD_TERMS and BWD_FUSED and ct.N == 2 and ct.xform is None and \
-                (BWD_GATHER == 2 or (BWD_GATHER == 1 and coherent))
-            if wide and fo is None and BWD_TERMS and not gather:
-                # one sigmoid pass instead of two: the first sweep leaves a float per list slot for the second
-                need = lists.pool_blocks * 512 * (2 if wide_tile else 1)       # (attenuation, total_color) / total_color alone
+            if r.terms_per_slot:
+                need = lists.pool_blocks * 512 * r.terms_per_slot
                 if lists.terms is None or lists.terms.numel() < need:
                     lists.terms = torch.empty((need,), dtype=torch.float32, device=dev)
                 lists.terms_state = 0
-            if gather and not fused:
-                # with view rotations a second plane holds each sample's rotated direction
-                planes = 2 if ct.xform is not None else 1
-                lists.coef = torch.empty((planes * lists.S, cr.Q, 4), dtype=torch.float32, device=dev)
-                lists.consumed = True         # the two-kernel form rewrites rec
+            if r.coef_planes:
+                lists.coef = torch.empty((r.coef_planes * lists.S, cr.Q, 4), dtype=torch.float32, device=dev)
+                lists.consumed = True
             cl = lists.c_struct()
-            if wide_tile and lists.exp_table is not None and not (lists.flags & LISTS_NATIVE_MATH):
+            if r.table:
                 ct.exp_table = lists.exp_table.data_ptr()      # (the table of the feature content the lists were recorded with)
-            LAST_ROUTE["backward"] = (
-                ("grad_fused_kernel<EXACT, XF> (two sweeps over the lists, a basis per record + per-tile merge)" if ct.xform is not None else
-                 "grad_fused_kernel<EXACT> (two sweeps over the lists + per-tile merge)" if fo is None else
-                 "grad_fused_kernel (one sweep over the lists + per-tile merge; accum from the forward's output)") if fused else
-                "render_bwd_kernel<GATHER> + grad_merge_kernel (list walk, then per-tile merge)" if gather else
-                ("grad_wide_kernel (two sweeps over the lists, sigmoids per record once + once per distinct row; per-tile merge"
-                 + (", native exp / rcp)" if lists.flags & LISTS_NATIVE_MATH else
-                    ", exponentials from the forward's table)" if lists.exp_table is not None else ")"))
-                if wide_tile else
-                "render_bwd_kernel<ONEPASS> (two list walks, sigmoids formed once; one atomic row + one sigma atomic per sample)"
-                if (wide and fo is None and BWD_TERMS) else
-                "render_bwd_kernel<REPLAY> (list walk, one atomic row per sample)")
-            if fused or wide_tile:
-                cl.coef_bytes = -1            # list walk and merge as one kernel: no buffer, rec stays as recorded
+            if r.one_kernel:
+                cl.coef_bytes = -1
             if kept is not None:
                 cl.flags |= LISTS_GRAD_ZEROED
             _call("svoxt_volume_render_bwd_replay", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
                   _ptr(grad_output), grad_output.shape[1], _ptr(buf), stride, ctypes.byref(cl), _ptr(fo),
                   _stream(dev))
         else:
-            LAST_ROUTE["backward"] = "render_bwd_kernel (marches, one atomic row per sample)"
             ws_bytes = _lib.svoxt_bwd_workspace_bytes(cr.Q, BWD_LIST_SAMPLES)
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
             _call("svoxt_volume_render_bwd", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co),
                   _ptr(grad_output), grad_output.shape[1], _ptr(buf), stride, _ptr(ws), ws_bytes, _stream(dev))
+        LAST_ROUTE["backward"] = r.label
         if stride == K:
             grad = buf
         else:
@@ -1142,12 +1249,10 @@ def opacity_render_backward(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions,
     """rt_kernel.cu:1593-1616.  `lists` (optional, not in the reference): what
     opacity_render(..., record=True) returned for the same tree / rays / options; not given:
     what the forward of the same spec objects left behind (see _Plan)."""
-    if lists is None and AUTO_PLAN:
-        p = _take_plan("opacity", tree, rays, opt)
-        if p is not None:
-            _check_input(grad_output, "grad_output")
-            g = grad_output if p.perm is None else _permute_rows(grad_output, p.perm, scatter=False)
-            return _opacity_render_backward(tree, p.rays if p.rays is not None else rays, opt, g, p.lists)
+    got = _replayed("opacity", tree, rays, opt, grad_output) if lists is None else None
+    if got is not None:
+        p, g, rr = got
+        return _opacity_render_backward(tree, rr, opt, g, p.lists)
     return _opacity_render_backward(tree, rays, opt, grad_output, lists)
 
 
