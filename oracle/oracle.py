@@ -88,6 +88,12 @@ def use_libm_exp(on: bool) -> None:
     lib().svoxt_oracle_use_libm_exp(int(bool(on)))
 
 
+def double_as_reference(on: bool) -> None:
+    """Make the float64 entry points call expf / sqrtf on float-rounded arguments, as the reference's double
+    instantiation does (default off: full double precision, the yardstick of the finite-difference checks)."""
+    lib().svoxt_oracle_double_as_reference(int(bool(on)))
+
+
 def expf(x):
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.empty_like(x)
@@ -163,18 +169,20 @@ def _rays(tree: Tree, origins, dirs, vdirs):
 
 class transformation_matrices:
     """`with transformation_matrices(x):` -- per-leaf [M, 3, 3] view rotations
-    (TreeSpec.transformation_matrices) for the f32 render / backward calls inside."""
+    (TreeSpec.transformation_matrices) for the render / backward calls of `dtype` inside."""
 
-    def __init__(self, xform):
-        self.x = _c(xform, np.float32)
+    def __init__(self, xform, dtype=np.float32):
+        self.x = _c(xform, dtype)
+        self.set = lib().svoxt_oracle_set_transformation_matrices if dtype == np.float32 \
+            else lib().svoxt_oracle_set_transformation_matrices_f64
         assert self.x.ndim == 3 and self.x.shape[1:] in ((3, 3), (4, 4))
 
     def __enter__(self):
-        lib().svoxt_oracle_set_transformation_matrices(_p(self.x), int(self.x.shape[1]))
+        self.set(_p(self.x), int(self.x.shape[1]))
         return self
 
     def __exit__(self, *exc):
-        lib().svoxt_oracle_set_transformation_matrices(None, 3)
+        self.set(None, 3)
 
 
 def volume_render(tree: Tree, origins, dirs, vdirs, opt: RenderOptions, count=False):
@@ -234,15 +242,20 @@ def volume_render_backward(tree: Tree, origins, dirs, vdirs, opt: RenderOptions,
 def opacity_render(tree: Tree, origins, dirs, vdirs, opt: RenderOptions):
     o, d, v = _rays(tree, origins, dirs, vdirs)
     Q = o.shape[0]
-    out = np.zeros((Q, 1), dtype=np.float32)
-    lib().svoxt_oracle_opacity_render_f32(*tree._args(False), _p(o), _p(d), _p(v),
-                                          ctypes.c_int64(Q), ctypes.byref(opt), _p(out))
+    out = np.zeros((Q, 1), dtype=tree.dtype)
+    fn = lib().svoxt_oracle_opacity_render_f32 if tree.dtype == np.float32 else lib().svoxt_oracle_opacity_render_f64
+    fn(*tree._args(False), _p(o), _p(d), _p(v), ctypes.c_int64(Q), ctypes.byref(opt), _p(out))
     return out
 
 
 def render_depth(tree: Tree, origins, dirs, vdirs, opt: RenderOptions, count=False):
     o, d, v = _rays(tree, origins, dirs, vdirs)
     Q = o.shape[0]
+    if tree.dtype == np.float64:
+        assert not count
+        out = np.zeros((Q, 1), dtype=np.float64)
+        lib().svoxt_oracle_render_depth_f64(*tree._args(False), _p(o), _p(d), _p(v), ctypes.c_int64(Q), ctypes.byref(opt), _p(out))
+        return out
     out = np.zeros((Q, 1), dtype=np.float32)
     cnt = np.zeros(5, dtype=np.int64)
     lib().svoxt_oracle_render_depth_f32(*tree._args(False), _p(o), _p(d), _p(v),
@@ -264,17 +277,18 @@ def ray_steps(tree: Tree, origins, dirs, vdirs, opt: RenderOptions):
 
 
 def motion_render(tree: Tree, origins, dirs, vdirs, opt: RenderOptions):
-    """motion_render (rt_kernel.cu:698-778, 1480-1504), float32 only.  Returns
+    """motion_render (rt_kernel.cu:698-778, 1480-1504).  Returns
     (joint distances [Q, J], depth [Q, 1], hit_point [Q, 3], data_idx [Q, 1] int64);
     tree.extra = joint positions [J, >=3]."""
-    assert tree.dtype == np.float32 and tree.extra is not None and tree.extra.shape[1] >= 3
+    assert tree.extra is not None and tree.extra.shape[1] >= 3
     o, d, v = _rays(tree, origins, dirs, vdirs)
     Q, J = o.shape[0], tree.extra.shape[0]
-    out = np.zeros((Q, J), np.float32)
-    depth = np.zeros((Q, 1), np.float32)
-    hit = np.zeros((Q, 3), np.float32)
+    out = np.zeros((Q, J), tree.dtype)
+    depth = np.zeros((Q, 1), tree.dtype)
+    hit = np.zeros((Q, 3), tree.dtype)
     idx = np.zeros((Q, 1), np.int64)
-    lib().svoxt_oracle_motion_render_f32(*tree._args(), _p(o), _p(d), _p(v), ctypes.c_int64(Q),
+    fn = lib().svoxt_oracle_motion_render_f32 if tree.dtype == np.float32 else lib().svoxt_oracle_motion_render_f64
+    fn(*tree._args(), _p(o), _p(d), _p(v), ctypes.c_int64(Q),
                                          ctypes.byref(opt), _p(out), _p(depth), _p(hit), _p(idx))
     return out, depth, hit, idx
 
@@ -330,12 +344,13 @@ def motion_feature_render_backward(tree: Tree, motion: Motion, origins, dirs, vd
 
 
 def query(tree: Tree, points):
-    p = _c(points, np.float32)
+    p = _c(points, tree.dtype)
     Q = p.shape[0]
-    values = np.zeros((Q, tree.K), dtype=np.float32)
+    values = np.zeros((Q, tree.K), dtype=tree.dtype)
     node_ids = np.zeros(Q, dtype=np.int64)
     data_ids = np.zeros(Q, dtype=np.int64)
-    lib().svoxt_oracle_query_f32(*tree._args(False), _p(p), ctypes.c_int64(Q),
+    fn = lib().svoxt_oracle_query_f32 if tree.dtype == np.float32 else lib().svoxt_oracle_query_f64
+    fn(*tree._args(False), _p(p), ctypes.c_int64(Q),
                                  _p(values), _p(node_ids), _p(data_ids))
     return values, node_ids, data_ids
 
@@ -351,18 +366,20 @@ def query_backward(tree: Tree, points, grad_output):
     return grad
 
 
-def camera_rays(c2w, fx, fy, width, height, ndc=None):
-    """(origins, dirs, vdirs) float32 [H*W, 3] of a pinhole camera, row-major:
+def camera_rays(c2w, fx, fy, width, height, ndc=None, dtype=np.float32):
+    """(origins, dirs, vdirs) [H*W, 3] of a pinhole camera, row-major:
     cam2world_ray + maybe_world2ndc (rt_kernel.cu:1153-1190).  c2w: [3,4] or [4,4];
-    ndc: None or (ndc_width, ndc_height, ndc_focal)."""
-    c = np.ascontiguousarray(np.asarray(c2w, dtype=np.float32)[:3, :4])
+    ndc: None or (ndc_width, ndc_height, ndc_focal).  dtype float32, or float64: the
+    reference's double instantiation to the letter (its sqrtf and float NDC factors included)."""
+    c = np.ascontiguousarray(np.asarray(c2w, dtype=dtype)[:3, :4])
     n = int(width) * int(height)
-    o = np.empty((n, 3), np.float32)
-    d = np.empty((n, 3), np.float32)
-    v = np.empty((n, 3), np.float32)
+    o = np.empty((n, 3), dtype)
+    d = np.empty((n, 3), dtype)
+    v = np.empty((n, 3), dtype)
     nw, nh, nf = (-1, -1, 0.0) if ndc is None else ndc
-    lib().svoxt_oracle_camera_rays(_p(c), ctypes.c_float(fx), ctypes.c_float(fy), int(width), int(height),
-                                   int(nw), int(nh), ctypes.c_float(nf), _p(o), _p(d), _p(v))
+    fn = lib().svoxt_oracle_camera_rays if dtype == np.float32 else lib().svoxt_oracle_camera_rays_f64
+    fn(_p(c), ctypes.c_float(fx), ctypes.c_float(fy), int(width), int(height),
+       int(nw), int(nh), ctypes.c_float(nf), _p(o), _p(d), _p(v))
     return o, d, v
 
 

@@ -19,8 +19,8 @@ INF = f32(np.inf)
 def _dda_unit(c, inv):
     """_dda_unit (rt_kernel.cu:202-218) for points c [n, 3] and inverse directions inv [n, 3] -> (tmin, tmax);
     fminf / fmaxf return the operand that is not a NaN."""
-    tmin = np.zeros(len(c), f32)
-    tmax = np.full(len(c), 1e9, f32)
+    tmin = np.zeros(len(c), c.dtype)
+    tmax = np.full(len(c), 1e9, c.dtype)
     for a in range(3):
         t1 = -c[:, a] * inv[:, a]
         t2 = t1 + inv[:, a]
@@ -29,35 +29,43 @@ def _dda_unit(c, inv):
     return tmin, tmax
 
 
-def march(sigma, origins, dirs, offset, scaling, step_size=1e-3, sigma_thresh=0.0, advance_guard=True, max_steps=None):
+def march(sigma, origins, dirs, offset, scaling, step_size=1e-3, sigma_thresh=0.0, advance_guard=True, max_steps=None,
+          dtype=np.float32):
     """sigma [R, R, R] (or [R, R, R, 1]); world-space origins / dirs [Q, 3] (after any NDC warp); offset, scaling [3].
 
     Returns weight (float32, shape of sigma), hits (int64, that shape) and, per ray / for the cross-checks with the
     oracle: hit_cube [Q], steps [Q], active [Q], T [Q] (final transmittance), and weight_sum (float64 per cell: the sum
     of the weights, what N3Tree.accumulate_weights means).  advance_guard: t moves through march_advance (a step that
-    does not move t ends the march); without it the restatement is the reference's bare `t += delta_t`."""
-    sig = np.ascontiguousarray(np.asarray(sigma, f32))
+    does not move t ends the march); without it the restatement is the reference's bare `t += delta_t`.
+
+    dtype=np.float64 restates the reference's double instantiation: the same operations in double, except the calls the
+    reference makes in float there too -- sqrtf in the norm, expf, and the fmaxf of its atomicMax, which rounds every
+    weight to float before it is compared and stored."""
+    ft = dtype
+    sig = np.ascontiguousarray(np.asarray(sigma, ft))
     shape = sig.shape
     R = shape[0]
     assert shape[:3] == (R, R, R) and sig.size == R ** 3
     sig = sig.reshape(-1)
-    Rf = f32(R)
-    o = np.asarray(origins, f32).reshape(-1, 3)
-    d = np.asarray(dirs, f32).reshape(-1, 3)
-    off, sc = np.asarray(offset, f32).reshape(3), np.asarray(scaling, f32).reshape(3)
-    step, thr = f32(step_size), f32(sigma_thresh)
+    Rf = ft(R)
+    o = np.asarray(origins, ft).reshape(-1, 3)
+    d = np.asarray(dirs, ft).reshape(-1, 3)
+    off, sc = np.asarray(offset, ft).reshape(3), np.asarray(scaling, ft).reshape(3)
+    step, thr = f32(step_size), f32(sigma_thresh)                        # (RenderOptions holds floats)
+    clamp_hi = CLAMP_HI if ft == f32 else np.float64(1.0) - 1e-6
+    inf = ft(np.inf)
     Q = len(o)
     with np.errstate(all="ignore"):
         o = off + sc * o                                                 # transform_coord
         d = d * sc                                                       # _get_delta_scale
-        nrm = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-        ds = f32(1.0) / nrm
+        nrm = np.sqrt(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(f32)).astype(ft)     # sqrtf
+        ds = ft(1.0) / nrm
         d = d * ds[:, None]
-        inv = (1.0 / (d.astype(np.float64) + 1e-9)).astype(f32)          # invdir, in double
+        inv = (1.0 / (d.astype(np.float64) + 1e-9)).astype(ft)           # invdir, in double
         tmin, tmax = _dda_unit(o, inv)
         hit_cube = ~((tmax < 0) | (tmin > tmax))
         t = tmin.copy()
-        T = np.ones(Q, f32)
+        T = np.ones(Q, ft)
         steps = np.zeros(Q, np.int64)
         active = np.zeros(Q, np.int64)
         wbits = np.zeros(R ** 3, np.int32)
@@ -72,7 +80,7 @@ def march(sigma, origins, dirs, offset, scaling, step_size=1e-3, sigma_thresh=0.
             assert max_steps is None or n_iter <= max_steps, "the march did not end"
             tt = t[idx]
             pos = o[idx] + tt[:, None] * d[idx]
-            pos = np.fmax(f32(0), np.fmin(CLAMP_HI, pos))                # clamp_coord
+            pos = np.fmax(ft(0), np.fmin(clamp_hi, pos))                 # clamp_coord
             pos = pos * Rf
             fl = np.floor(pos)
             pos = pos - fl
@@ -83,26 +91,27 @@ def march(sigma, origins, dirs, offset, scaling, step_size=1e-3, sigma_thresh=0.
             s = sig[cell]
             m = s > thr                                                  # NaN: no sample
             k = idx[m]
-            att = O.expf(-delta_t[m] * ds[k] * s[m])
-            w = T[k] * (f32(1) - att)
+            att = O.expf((-delta_t[m] * ds[k] * s[m]).astype(f32)).astype(ft)        # expf
+            w = T[k] * (ft(1) - att)
             T[k] = T[k] * att
-            np.maximum.at(wbits, cell[m], np.ascontiguousarray(w).view(np.int32))
+            np.maximum.at(wbits, cell[m], np.ascontiguousarray(w.astype(f32)).view(np.int32))      # fmaxf
             np.add.at(hits, cell[m], 1)
             np.add.at(wsum, cell[m], w.astype(np.float64))
             steps[idx] += 1
             active[k] += 1
             tn = tt + delta_t
-            t[idx] = np.where(tn > tt, tn, INF) if advance_guard else tn
-    return SimpleNamespace(weight=wbits.view(f32).reshape(shape), hits=hits.reshape(shape), hit_cube=hit_cube, steps=steps,
+            t[idx] = np.where(tn > tt, tn, inf) if advance_guard else tn
+    return SimpleNamespace(weight=wbits.view(f32).astype(ft).reshape(shape), hits=hits.reshape(shape), hit_cube=hit_cube, steps=steps,
                            active=active, T=T, weight_sum=wsum.reshape(shape), iterations=n_iter)
 
 
 def march_cameras(sigma, c2w, fx, fy, width, height, offset, scaling, ndc=None, **kw):
     """march() over the pixels of the cameras c2w [V, 3 or 4, 4] (or one matrix): max / sum over all views."""
-    c2w = np.asarray(c2w, f32)
+    ft = kw.get("dtype", f32)
+    c2w = np.asarray(c2w, ft)
     if c2w.ndim == 2:
         c2w = c2w[None]
-    rays = [O.camera_rays(c, fx, fy, width, height, ndc=ndc) for c in c2w]
+    rays = [O.camera_rays(c, fx, fy, width, height, ndc=ndc, dtype=ft) for c in c2w]
     return march(sigma, np.concatenate([r[0] for r in rays]), np.concatenate([r[1] for r in rays]), offset, scaling, **kw)
 
 
