@@ -39,7 +39,7 @@ from ._abi import (ABI_VERSION, EXPORTS, FORMAT_ASG, FORMAT_RGBA, FORMAT_SG, FOR
                    LISTS_TEST_DROP, LISTS_TEST_NOPOLL, LISTS_TEST_STALE, _CLists, _CMotion, _COptions, _CRays, _CTree, _lib)
 from ._marshal import (ACCEL_BRICKS, ACCEL_LOG2, CameraSpec, RaysSpec, RenderOptions, TreeSpec, _ACCEL_CACHE, _accel_for, _accel_log2_for,
                        _call, _check_input, _numel, _pack_camera, _pack_opts, _pack_rays, _pack_tree, _pack_tree_accel, _ptr,
-                       _on, _stream, get_out_data_dim)
+                       _on, _Produced, _raw_stream, _stream, get_out_data_dim)
 
 
 # ---------------------------------------------------------------------------
@@ -147,6 +147,7 @@ def _attach_sigma_mask(tree: TreeSpec, ct: _CTree, thresh: float, keep: bool, ta
         if ent is not None and ent[0]() is f and ent[1] == (f._version, f.data_ptr()) and ent[2] == thresh \
                 and (ent[4] is not None or not table):
             mask, etab = ent[3], (ent[4] if table else None)
+            ent[6].ready_on(_raw_stream(f.device))   # built on another stream: wait for it there (_marshal._Produced)
     if mask is None:
         dev = f.device
         with _on(dev):
@@ -161,8 +162,10 @@ def _attach_sigma_mask(tree: TreeSpec, ct: _CTree, thresh: float, keep: bool, ta
             else:
                 _call("svoxt_sigma_mask_build", ctypes.byref(ct), ctypes.c_float(thresh), _ptr(mask), _stream(dev))
         if keep:
+            with _on(dev):
+                made = _Produced("sigma_mask" if etab is None else "sigma_mask+exp_table", None, (mask, etab), dev)
             _SIGMA_CACHE[key] = (weakref.ref(f, lambda _r, _k=key: _SIGMA_CACHE.pop(_k, None)),
-                                 (f._version, f.data_ptr()), thresh, mask, etab, held)
+                                 (f._version, f.data_ptr()), thresh, mask, etab, held, made)
     ct.sigma_mask = mask.data_ptr()
     ct.sigma_mask_thresh = thresh
     ct._keepalive_mask = mask
@@ -196,7 +199,9 @@ def _grad_scratch(dev, M: int, stride: int):
 def invalidate_caches(*tensors) -> None:
     """Drop what this module derived from the CONTENT of the given tensors (child / data: the acceleration
     grid; features: a cached sigma bitmask) and bump their torch version counters.  For writers that bypass
-    the counters: `t.data[...] = v`, raw-pointer kernels, collectives into `.data`.  No arguments: everything."""
+    the counters: `t.data[...] = v`, raw-pointer kernels, collectives into `.data`.  No arguments: everything.
+    Safe while another stream still reads a dropped product: every stream that consumed it was named to the allocator
+    when it first did (_marshal._Produced), so the memory is not reused under its kernels."""
     if not tensors:
         _ACCEL_CACHE.clear()
         _SIGMA_CACHE.clear()
@@ -714,7 +719,7 @@ def _padded(tree: TreeSpec, rays, lay):
     key = (id(f), f._version, f.data_ptr(), lay)
     ent = getattr(rays, "_svoxt_pad", None)
     if ent is not None and ent[0] == key:
-        return ent[1]
+        return ent[2].ready_on(_raw_stream(f.device))
     Kp, real, dummy, w, sub = lay
     with torch.no_grad():
         fp = torch.cat([f[:, :real], f.new_zeros((f.shape[0], dummy)), f[:, real:]], dim=1)
@@ -724,7 +729,7 @@ def _padded(tree: TreeSpec, rays, lay):
     tp = TreeSpec()
     tp.__dict__.update(tree.__dict__)
     tp.features = fp
-    rays._svoxt_pad = (key, tp)
+    rays._svoxt_pad = (key, tp, _Produced("pad_table", tp, (fp,), f.device))
     return tp
 
 
@@ -789,7 +794,7 @@ def _groups(tree: TreeSpec, rays, lay):
     key = (id(f), f._version, f.data_ptr(), lay)
     ent = getattr(rays, "_svoxt_groups", None)
     if ent is not None and ent[0] == key:
-        return ent[1]
+        return ent[2].ready_on(_raw_stream(f.device))
     bd, C, per = lay
     out = []
     for c0 in range(0, C, per):
@@ -803,7 +808,7 @@ def _groups(tree: TreeSpec, rays, lay):
         rg = type(rays)()
         rg.__dict__.update({k: v for k, v in rays.__dict__.items() if not k.startswith("_svoxt_")})
         out.append((tg, rg, c0, n))
-    rays._svoxt_groups = (key, out)
+    rays._svoxt_groups = (key, out, _Produced("group_tables", out, [g[0].features for g in out], f.device))
     return out
 
 

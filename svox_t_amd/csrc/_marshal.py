@@ -283,6 +283,56 @@ def _stream(device):
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if idx is None else idx))
 
 
+def _raw_stream(device) -> int:
+    """... as a plain integer (0: the null stream): what a cache entry remembers of the stream that built it."""
+    idx = device.index
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if idx is None else idx)
+
+
+class _Produced:
+    """A device-side product that outlives the call that built it (an acceleration grid, a sigma bitmask, a plan), with
+    the stream it was built on and an event recorded behind its last build launch -- made by the builder, on that stream,
+    right after the build was enqueued (the cold path).  Every consumer calls ready_on(handle of ITS stream) before its
+    first launch that reads the product: the builder's own stream -- an integer compare, nothing else -- or a stream that
+    has been through here before (a set lookup) needs nothing; another stream waits for the event, once, and is named
+    to the allocator as a user of the tensors (record_stream), so that dropping the entry cannot hand their memory back
+    to the builder's pool under a kernel of the consumer's.  `what` names the product (tests and messages)."""
+    __slots__ = ("what", "value", "tensors", "device", "handle", "event", "seen")
+
+    def __init__(self, what, value, tensors, device):
+        self.what, self.value, self.device = what, value, device
+        self.tensors = tuple(t for t in tensors if isinstance(t, torch.Tensor) and t.is_cuda)
+        with _on(device):
+            self.handle = _raw_stream(device)
+            self.event = torch.cuda.Event()
+            self.event.record()
+        self.seen = None
+
+    def ready_on(self, handle: int):
+        if handle != self.handle:
+            self._cross(handle)
+        return self.value
+
+    def _cross(self, handle: int) -> None:
+        if self.seen is not None and handle in self.seen:
+            return
+        with _on(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if stream.cuda_stream != handle:
+                raise RuntimeError(f"{self.what}: ready_on() must be given the current stream's handle")
+            stream.wait_event(self.event)
+            for t in self.tensors:
+                t.record_stream(stream)
+        self.seen = (self.seen or set()) | {handle}
+
+    def __reduce__(self):
+        """copy.deepcopy / pickle of whatever holds a product (an N3Tree with its neighbour table, a RaySamples with a row
+        plan): an event is neither, so the copy is a product of its own, built -- by the copy of the tensors -- on the stream
+        that is current where it is made, which reads the original there."""
+        self.ready_on(_raw_stream(self.device))
+        return _Produced, (self.what, self.value, self.tensors, self.device)
+
+
 class _NoContext:
     def __enter__(self):
         return None
@@ -331,6 +381,8 @@ ACCEL_LOG2 = (lambda v: None if v is None else max(0, min(8, int(v))))(os.enviro
 # must call invalidate_caches(); N3Tree.refine / construct_tree / parallel.broadcast_tree do.
 # ACCEL_LOG2 (SVOXT_ACCEL_LOG2) = 0 disables the grid, = g forces a resolution; default: chosen from the tree size.
 # ---------------------------------------------------------------------------
+# The grid is built on the stream current at the time and may be read from any other: an entry carries the _Produced of its
+# cells, and every hit goes through ready_on ("Caches, invalidate_caches and streams").
 _ACCEL_CACHE: dict = {}     # (id(child tensor), bricks) -> (weakref to it, ...); entries are dropped when the tensor dies
 
 
@@ -381,19 +433,20 @@ def _accel_for(tree: TreeSpec, ct: _CTree, bricks: bool = False):
     key = (id(tree.child), bricks)      # (a tree rendered both ways -- training steps and forward-only views -- keeps both grids)
     ent = _ACCEL_CACHE.get(key)
     if ent is not None:
-        cref, cv, dref, dv, n_int, eg, cells = ent
+        cref, cv, dref, dv, n_int, eg, cells, made = ent
         if cref() is tree.child and cv == (tree.child._version, tree.child.data_ptr()) and dref() is tree.data \
                 and dv == (tree.data._version, tree.data.data_ptr()) and n_int == ct.n_internal and eg == g:
-            return cells, g | (SVOXT_ACCEL_BRICKS if bricks else 0)
+            return made.ready_on(_raw_stream(tree.child.device)), g | (SVOXT_ACCEL_BRICKS if bricks else 0)
     dev = tree.child.device
     with _on(dev):
         nbytes = _lib.svoxt_accel_bytes(g, ct.n_internal)       # grid cells + (child, data) pairs
         cells = torch.empty((nbytes // 8, 2), dtype=torch.int32, device=dev)
         _call("svoxt_accel_build", ctypes.byref(ct), g | (SVOXT_ACCEL_BRICKS if bricks else 0), _ptr(cells), _stream(dev))
+        made = _Produced("accel_bricks" if bricks else "accel", cells, (cells,), dev)
     # (versions AND data pointers: `tensor.data = other` swaps the storage without touching the version counter)
     _ACCEL_CACHE[key] = (weakref.ref(tree.child, lambda _r, _k=key: _ACCEL_CACHE.pop(_k, None)),
                          (tree.child._version, tree.child.data_ptr()), weakref.ref(tree.data),
-                         (tree.data._version, tree.data.data_ptr()), ct.n_internal, g, cells)
+                         (tree.data._version, tree.data.data_ptr()), ct.n_internal, g, cells, made)
     return cells, g | (SVOXT_ACCEL_BRICKS if bricks else 0)
 
 

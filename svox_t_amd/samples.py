@@ -85,8 +85,9 @@ class RaySamples:
             raise RuntimeError("row_plan: only the GPU (HIP) path exists; the samples must be on the GPU")
         plans = self.__dict__.setdefault("_row_plans", {})
         if M not in plans:
-            plans[M] = RowPlan(_C.row_plan(self.row.contiguous(), M))
-        return plans[M]
+            arrays = _C.row_plan(self.row.contiguous(), M)
+            plans[M] = _C._Produced("row_plan", RowPlan(arrays), arrays, self.row.device)
+        return plans[M].ready_on(_C._raw_stream(self.row.device))    # (built on another stream: that stream waits for it)
 
     def points(self, rays: Rays, at: str = "mid", *, geometry=None):
         """float32 [T, 3]: a world point per sample, origins[ray] + dirs[ray] * z with z = depth + 0.5 * length ("mid") or

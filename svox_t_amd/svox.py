@@ -174,8 +174,9 @@ class InterpStencil:
             raise RuntimeError("row_plan: only the GPU (HIP) path exists; the stencil must be on the GPU")
         plans = self.__dict__.setdefault("_row_plans", {})
         if M not in plans:
-            plans[M] = RowPlan(_C.row_plan(self.rows.contiguous().reshape(-1), M))
-        return plans[M]
+            arrays = _C.row_plan(self.rows.contiguous().reshape(-1), M)
+            plans[M] = _C._Produced("stencil_plan", RowPlan(arrays), arrays, self.rows.device)
+        return plans[M].ready_on(_C._raw_stream(self.rows.device))   # (built on another stream: that stream waits for it)
 
 
 class _InterpRowsFunction(autograd.Function):
@@ -847,8 +848,9 @@ class N3Tree(nn.Module):
         merge then refuses it).  Cached until the tree changes.  GPU only."""
         self._frontier_guard("frontier")
         if self._last_frontier is None:
-            self._last_frontier = _C.frontier_nodes(self.child, self.filled)
-        return self._last_frontier
+            fr = _C.frontier_nodes(self.child, self.filled)
+            self._last_frontier = _C._Produced("frontier", fr, (fr,), fr.device)
+        return self._last_frontier.ready_on(_C._raw_stream(self.child.device))
 
     def _columns(self, dim, K):
         """`dim` (None, int, slice, list or tensor: what the reference indexes the last axis with) -> (int32 column
@@ -969,8 +971,9 @@ class N3Tree(nn.Module):
                 rows = torch.where((words >= 0) & (words < self.features.shape[0]), words, torch.full_like(words, -1))
                 deepest = int(self.parent_depth[:n, 1].max().item())
                 neighbors = _C.leaf_neighbors(self.child, self.parent_depth, n, leaf_node.shape[0], deepest)
-            self._last_neighbors = (key, LeafNeighbors(leaf_node, depths, rows, neighbors))
-        return self._last_neighbors[1]
+            nb = LeafNeighbors(leaf_node, depths, rows, neighbors)
+            self._last_neighbors = (key, _C._Produced("leaf_neighbors", nb, tuple(nb), neighbors.device))
+        return self._last_neighbors[1].ready_on(_C._raw_stream(self.data.device))
 
     def _tv_plan(self, M):
         """The edge plan of tv() for a feature table of M rows (csrc.TVPlan): every pair of
@@ -984,8 +987,10 @@ class N3Tree(nn.Module):
                     n, N = self.filled, self.N
                     words = self.data[:n].reshape(n, N, N, N)[tuple(nb.leaf_node.T)].long()
                     rows = torch.where((words >= 0) & (words < M), words, torch.full_like(words, -1))
-            self._last_tv_plan = (key, _C.tv_plan(nb.neighbors, nb.depths, rows.contiguous(), M, self.N))
-        return self._last_tv_plan[1]
+            plan = _C.tv_plan(nb.neighbors, nb.depths, rows.contiguous(), M, self.N)
+            self._last_tv_plan = (key, _C._Produced("tv_plan", plan, (plan.row_ptr, plan.other, plan.meta, plan.area_weights),
+                                                    self.data.device))
+        return self._last_tv_plan[1].ready_on(_C._raw_stream(self.data.device))
 
     def _tv_args(self, what, features, dim, p, weight):
         if not self.data.is_cuda:
