@@ -1074,6 +1074,13 @@ typedef struct svoxt_optim_hyper {
 int svoxt_optim_state_count(int32_t kind);
 int svoxt_optim_step(int32_t kind, float* param, const float* grad, float* state1, float* state2, int64_t M, int32_t K,
                      svoxt_optim_hyper hyper, int32_t lazy, void* stream);
+/* The damped Newton step on a diagonal curvature (what svoxt_render_hess_rows_* gives), one launch over the table, in
+ * place.  Per element, float32, one correctly rounded operation at a time: d = hess + damping; where d > 0.f
+ * p = p - lr * (grad / d); otherwise (d <= 0.f, or NaN) the element is not written.  lazy = 1: a row whose grad row is all
+ * zeros (the optimizers' TOUCHED rule) is read no further and not written.  param, grad, hess: device float32 [M, K],
+ * 4-byte aligned, param distinct from both; M, K >= 1, M * K below 2^37.  Entry point added under ABI v22. */
+int svoxt_gauss_newton_step(float* param, const float* grad, const float* hess, int64_t M, int32_t K, float lr, float damping,
+                            int32_t lazy, void* stream);
 
 /* ---- Face neighbours of the leaves and the smoothness loss over them: N3Tree.leaf_neighbors / tv / tv_add_grad (not in
  * the reference) ------------------------------------------------------------------------------------------------------
@@ -1577,6 +1584,51 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
                                   const int64_t* offsets, int64_t T, const float* grad_out, int32_t grad_cols,
                                   int64_t n_long, int64_t n_chunks, float* grad, int32_t grad_stride, void* workspace,
                                   int64_t workspace_bytes, void* stream);
+
+/* ---- se_grad: the gradient and a Gauss-Newton diagonal in one pass (not in the reference) ------
+ * Next to grad [M, K] -- THE BITS svoxt_render_grad_rows_* gives for the same grad_out -- a second table
+ *   hess[m, j] = the sum, over the samples k that name row m and the outputs c, of curv[ray(k), c] * J(k, c, j)^2,
+ * J(k, c, j) the derivative of out[ray(k), c] with respect to entry j of row m THROUGH SAMPLE k ALONE, curv float32
+ * [Q, grad_cols] the second derivative of a per-pixel separable loss in each output (for squared error: the coefficient of
+ * the residual).  The squares are per sample: this is the exact diagonal of the Gauss-Newton Hessian whenever no ray names
+ * a row twice, and the svox family's approximation (the squares of a row's samples on one ray are summed, their cross
+ * terms dropped) where rows are shared -- after refine, merge, quantize.  Entry points added under ABI v22.
+ *   The samples and conventions are the deterministic backward's: crossings with a row and sigma > 0.f; thresholds 0, no
+ *   early stop; att = pexpf(-delta_t * sigma * delta_scale); sig = (float)(1.0 / (1.0 + (double)e)); gsig through double;
+ *   everything float32 without contraction.  Per sample k of ray q, h its entry at column j:
+ *   Colour column j = c * basis_dim + i, min_comp <= i <= max_comp:
+ *     jac = weight * basis[q, i] * gsig[k, c]   (RGBA rows: jac = weight * sig * (1.f - sig)), left to right, the prefix
+ *     of the gradient's contribution; h = (jac * jac) * curv[q, c].  Only channel c depends on that column.
+ *   Sigma column (j = K - 1): h starts at 0.f.  For c = 0 .. C - 1 ascending, a per-channel two-pass walk of the ray's list:
+ *     pass 1: accum_c = the sum of weight_k * sig[k, c] in list order from 0.f (light = 1.f; weight = light * (1.f - att);
+ *             light *= att), then accum_c += light_ray * background_brightness;
+ *     pass 2, from light = 1.f: weight = light * (1.f - att); light *= att; accum_c -= weight * sig[k, c];
+ *             jac = (delta_t * delta_scale) * (sig[k, c] * light - accum_c); h += (jac * jac) * curv[q, c].
+ *     Last, the alpha channel: jac = (delta_t * delta_scale) * light_ray; h += (jac * jac) * curv[q, C].
+ *   Any other column, and columns outside [min_comp, max_comp]: exactly 0.f.  Rows no sample names: exactly 0.f.  Every
+ *   element of hess is written; with a row stride above K the padding is untouched.
+ *   The sum over a row follows svoxt_reduce_rows' order rule: samples in ascending index, chunks of SVOXT_ROW_CHUNK = 256
+ *   from 0.f, the partials in chunk order, rows of more than 256 samples by the long-row path.
+ * The steps: svoxt_render_grad_rows_count, _emit and _plan as they are, over a workspace of
+ * svoxt_render_hess_rows_workspace_bytes(Q, T, M, K, C, basis_dim) bytes (the gradient's, one float a sample for the sigma
+ * entry and a transient [T, C] for sig; -1 and 0 as the gradient's query), then
+ *   svoxt_render_hess_rows_sweep    in the place of svoxt_render_grad_rows_sweep, AFTER the plan and ONCE per emit: the
+ *                                   gradient's kernels, and between its shade and its totals a lane per (sample, channel)
+ *                                   for sig, a lane per (ray, output) for the per-channel walks, a lane per sample for the
+ *                                   sum over the outputs.
+ *   svoxt_render_hess_rows_reduce   svoxt_render_grad_rows_reduce into grad, then the same plan over the squares into
+ *                                   hess (row stride hess_stride floats, 0: K).  T = 0: zeros in both.
+ * Checked: what svoxt_render_grad_rows_* checks (tree.xform NULL; Q, M, T below 2^31; T (C + 1) and M K below 2^38;
+ * grad_cols = 1, C = 0, is served); curv not NULL with Q > 0, 4-byte aligned; hess not NULL, distinct from grad,
+ * hess_stride 0 or >= K; the workspace's size.  No allocation, no synchronisation, no float atomic. */
+int64_t svoxt_render_hess_rows_workspace_bytes(int64_t Q, int64_t T, int64_t M, int32_t K, int32_t C, int32_t basis_dim);
+int svoxt_render_hess_rows_sweep(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                 const int64_t* offsets, int64_t T, const float* grad_out, const float* curv,
+                                 int32_t grad_cols, void* workspace, int64_t workspace_bytes, void* stream);
+int svoxt_render_hess_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt,
+                                  const int64_t* offsets, int64_t T, const float* grad_out, const float* curv,
+                                  int32_t grad_cols, int64_t n_long, int64_t n_chunks, float* grad, int32_t grad_stride,
+                                  float* hess, int32_t hess_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- shade_samples: per-sample colours from feature rows (svoxt_shade.hip; not in the reference) ----
  * The shading step of the per-sample interface: the basis of a sample's ray dotted into its feature row's coefficients,

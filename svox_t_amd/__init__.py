@@ -12,11 +12,11 @@ Importing this package loads libsvoxt_hip.so; build it first with
 from svox_t_amd.helpers import DataFormat, LocalIndex, N3TreeView  # noqa: F401
 from svox_t_amd.svox import (InterpStencil, N3Tree, blend_transformation_matrix, get_transformation_matrix,  # noqa: F401
                             interp_rows, warp_vertices)
-from svox_t_amd.renderer import NDCConfig, Rays, VolumeRenderer  # noqa: F401
+from svox_t_amd.renderer import NDCConfig, Rays, SEGrad, VolumeRenderer  # noqa: F401
 from svox_t_amd.p2v import voxelize  # noqa: F401
 from svox_t_amd.gridw import GridWeights, grid_weights  # noqa: F401
 from svox_t_amd.quant import quantize_median_cut  # noqa: F401
-from svox_t_amd.optim import FeatureAdam, FeatureRMSprop, FeatureSGD  # noqa: F401
+from svox_t_amd.optim import FeatureAdam, FeatureRMSprop, FeatureSGD, gauss_newton_step_  # noqa: F401
 from svox_t_amd.samples import (RaySamples, RowPlan, accumulate, composite, gather_rows, merge_samples,  # noqa: F401
                                 quantile_depth, ray_quantile, ray_scan, reduce_rows, sample_geometry, sample_weights, shade_samples,
                                 take_samples)
@@ -27,4 +27,5 @@ __all__ = ["N3Tree", "N3TreeView", "VolumeRenderer", "Rays", "NDCConfig",
            "blend_transformation_matrix", "voxelize", "grid_weights", "GridWeights", "quantize_median_cut",
            "FeatureSGD", "FeatureRMSprop", "FeatureAdam", "RaySamples", "sample_weights", "accumulate", "composite",
            "RowPlan", "gather_rows", "reduce_rows", "shade_samples", "ray_scan", "ray_quantile", "quantile_depth",
-           "InterpStencil", "interp_rows", "merge_samples", "take_samples", "sample_geometry"]
+           "InterpStencil", "interp_rows", "merge_samples", "take_samples", "sample_geometry", "SEGrad",
+           "gauss_newton_step_"]

@@ -237,6 +237,11 @@ EXPORTS = {
     "svoxt_render_grad_rows_sweep": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
     "svoxt_render_grad_rows_reduce": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32,
                                                      _vp, _i64, _vp]),
+    "svoxt_render_hess_rows_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32]),
+    "svoxt_render_hess_rows_sweep": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_render_hess_rows_reduce": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _i64, _vp, _vp, _i32, _i64, _i64, _vp,
+                                                     _i32, _vp, _i32, _vp, _i64, _vp]),
+    "svoxt_gauss_newton_step": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, ctypes.c_float, ctypes.c_float, _i32, _vp]),
     "svoxt_view_basis": (ctypes.c_int, [_P(_CTree), _P(_CRays), _P(_COptions), _vp, _vp]),
     "svoxt_shade_samples_fwd": (ctypes.c_int, [_vp, _i64, _i32, _P(_COptions), _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "svoxt_shade_samples_bwd_workspace_bytes": (_i64, [_i64, _i32]),

@@ -1047,6 +1047,38 @@ def optim_step(kind: str, param: torch.Tensor, grad: torch.Tensor, state1, state
             torch.autograd.graph.increment_version(x)
 
 
+def gauss_newton_step(param: torch.Tensor, grad: torch.Tensor, hess: torch.Tensor, lr: float = 1.0, damping: float = 0.0,
+                      lazy: bool = True) -> None:
+    """The damped Newton step on a diagonal curvature, IN PLACE, as one launch on torch's current stream
+    (svoxt_gauss_newton_step): per element d = hess + damping, and where d > 0 param = param - lr * (grad / d), float32, one
+    correctly rounded operation at a time; an element with d <= 0 (or NaN) is not written.  lazy: rows whose grad row is
+    all zeros are read no further and not written.  param, grad, hess: float32 [M, K], contiguous, on one GPU, param
+    distinct from both.  param's version counter is bumped.  Bad arguments raise RuntimeError before any GPU work."""
+    tables = [("param", param), ("grad", grad), ("hess", hess)]
+    for name, x in tables:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.layout != torch.strided:
+            raise RuntimeError(f"{name} must be a dense float32 tensor")
+    if param.dim() != 2 or param.shape[0] < 1 or param.shape[1] < 1:
+        raise RuntimeError("param must be [M, K] with M, K >= 1")
+    for name, x in tables[1:]:
+        if tuple(x.shape) != tuple(param.shape):
+            raise RuntimeError(f"{name} must have the shape of param, {tuple(param.shape)}")
+    for name, x in tables:
+        _check_input(x, name)
+        if x.device != param.device:
+            raise RuntimeError(f"{name} must be on the device of param")
+    for name, v in (("lr", lr), ("damping", damping)):
+        if isinstance(v, (torch.Tensor, bool)) or not isinstance(v, (int, float)) or v != v or v < 0:
+            raise RuntimeError(f"{name} must be a Python number >= 0")
+    if param.data_ptr() in (grad.data_ptr(), hess.data_ptr()):
+        raise RuntimeError("param must be distinct from grad and hess")
+    dev = param.device
+    M, K = param.shape
+    with _on(dev), torch.no_grad():
+        _call("svoxt_gauss_newton_step", _ptr(param), _ptr(grad), _ptr(hess), M, K, float(lr), float(damping), int(bool(lazy)), _stream(dev))
+        torch.autograd.graph.increment_version(param)           # written behind torch's back: the counter says so
+
+
 def leaf_neighbors(child: torch.Tensor, parent_depth: torch.Tensor, n_internal: int, L: int, max_depth: int) -> torch.Tensor:
     """int32 [L, 6]: for every leaf slot of the nodes below n_internal (in slot order: row i is leaf index i) the leaf
     index of its face neighbour across -x +x -y +y -z +z, -1 outside the cube, -2 where the face is covered by finer
@@ -1898,6 +1930,93 @@ def volume_render_backward_rows(tree: TreeSpec, rays: RaysSpec, opt: RenderOptio
         tick(None)
     ROWGRAD_LAST.update(Q=Q, T=T, bytes=int(nbytes), n_long=n_long, n_chunks=n_chunks, longest=longest)
     return grad
+
+
+ROWHESS_LAST = {}             # ROWGRAD_LAST's record for the last volume_render_hess_rows
+
+
+def _rows_out_table(t, name, M, K, dev):
+    """(tensor, row stride for the C ABI) of an [M, >= K] output table: a new [M, K] one, or the caller's buffer."""
+    if t is None:
+        return torch.empty((M, K), dtype=torch.float32, device=dev), 0
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != M or t.shape[1] < K \
+            or not t.is_contiguous() or t.device != dev:
+        raise RuntimeError(f"{name} must be a contiguous float32 [M, >= K] tensor on the device of the features")
+    return t, t.shape[1]
+
+
+def volume_render_hess_rows(tree: TreeSpec, rays: RaysSpec, opt: RenderOptions, grad_output: torch.Tensor, curvature: torch.Tensor,
+                            grad=None, hess=None, timers=None):
+    """(grad, hess), both float32 [M, K]: volume_render_backward_rows' gradient for grad_output [Q, C + 1] (or [Q, 1]: the
+    opacity render, C = 0) with its bits, and next to it the Gauss-Newton diagonal of a per-pixel separable loss whose
+    second derivative in each output is curvature [Q, C + 1]:
+
+        hess[m, j] = sum over the samples k naming row m and the outputs c of curvature[ray(k), c] * J(k, c, j)^2
+
+    with J the derivative of out[ray(k), c] in entry j of row m through sample k alone (include/svoxt.h,
+    svoxt_render_hess_rows_*, has the float32 sequence).  The squares are per sample: the exact diagonal whenever no ray
+    names a row twice, the svox family's approximation where rows are shared (after refine, merge, quantize).  One
+    march, one row plan and one shade serve both tables; no float atomic, the same bits in every run and whatever
+    RaysSpec.sort or an image hint say.  Two host reads, as volume_render_backward_rows.  transformation_matrices are not
+    served.  `grad`, `hess`: float32 [M, >= K] buffers to write into (their first K columns).  `timers`: a function
+    called with a step's name before each of the five steps."""
+    import svox_t_amd.csrc as csrc
+    if _numel(tree.transformation_matrices):
+        raise RuntimeError("volume_render_hess_rows: transformation_matrices are not served by the deterministic backward "
+                           "(deterministic=True); use the default backward")
+    _check_input(grad_output, "grad_output")
+    _check_input(curvature, "curvature")
+    Q = _spec_ray_count(rays)
+    if grad_output.dtype != torch.float32 or grad_output.dim() != 2 or grad_output.shape[0] != Q:
+        raise RuntimeError(f"grad_output must be float32 [Q, C + 1] (or [Q, 1]) with Q = {Q} rays")
+    if curvature.dtype != torch.float32 or tuple(curvature.shape) != tuple(grad_output.shape) or curvature.device != grad_output.device:
+        raise RuntimeError("curvature must be float32 with the shape and device of grad_output")
+    cols = grad_output.shape[1]
+    M, K = tree.features.shape
+    want = get_out_data_dim(opt, K)
+    if cols != 1 and cols != want:
+        raise RuntimeError(f"grad_output must have {want} columns (get_out_data_dim), or 1 for the opacity render")
+    C = cols - 1
+    bd = int(opt.basis_dim) if (int(opt.format) != 0 and C > 0) else 0
+    rr = rays if isinstance(rays, CameraSpec) else csrc._in_coherent_order(tree, rays, opt)[0]
+    ct, cr, co = _pack_tree_accel(tree), _pack_rays(rr), _pack_opts(opt)
+    dev = tree.features.device
+    tick = timers if timers is not None else (lambda _name: None)
+    with _on(dev):
+        grad, gstride = _rows_out_table(grad, "grad", M, K, dev)
+        hess, hstride = _rows_out_table(hess, "hess", M, K, dev)
+        if grad.data_ptr() == hess.data_ptr() and M > 0:
+            raise RuntimeError("grad and hess must be distinct tensors")
+        T = 0
+        offsets = None
+        tick("count")
+        if Q > 0:
+            offsets = torch.empty((Q + 1,), dtype=torch.int64, device=dev)
+            cws = _workspace(dev, _lib.svoxt_ray_samples_workspace_bytes(Q), "se_grad: the batch must have fewer than 2^31 rays")
+            _call("svoxt_render_grad_rows_count", ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(offsets), _ptr(cws),
+                  cws.numel(), _stream(dev))
+            T = int(offsets[Q].item())                  # host read 1
+            if T >= 1 << 31:
+                raise RuntimeError(f"se_grad: {T} samples; a batch's lists hold fewer than 2^31 (split the batch)")
+        nbytes = _lib.svoxt_render_hess_rows_workspace_bytes(Q, T, M, K, C, bd)
+        ws = _workspace(dev, nbytes, "se_grad: T * (C + 1) and M * K must be below 2^38") if T > 0 else None
+        lead = (ctypes.byref(ct), ctypes.byref(cr), ctypes.byref(co), _ptr(offsets), T, _ptr(grad_output))
+        n_long = n_chunks = longest = 0
+        if T > 0:
+            tick("emit")
+            _call("svoxt_render_grad_rows_emit", *lead, cols, _ptr(ws), nbytes, _stream(dev))
+            tick("plan")
+            info = torch.empty((4,), dtype=torch.int64, device=dev)
+            _call("svoxt_render_grad_rows_plan", *lead, cols, _ptr(info), _ptr(ws), nbytes, _stream(dev))
+            tick("sweep")
+            _call("svoxt_render_hess_rows_sweep", *lead, _ptr(curvature), cols, _ptr(ws), nbytes, _stream(dev))   # (queued in front of the read)
+            _, longest, n_long, n_chunks = (int(v) for v in info.tolist())        # host read 2
+        tick("reduce")
+        _call("svoxt_render_hess_rows_reduce", *lead, _ptr(curvature), cols, n_long, n_chunks, _ptr(grad), gstride, _ptr(hess), hstride,
+              _ptr(ws), nbytes, _stream(dev))
+        tick(None)
+    ROWHESS_LAST.update(Q=Q, T=T, bytes=int(nbytes), n_long=n_long, n_chunks=n_chunks, longest=longest)
+    return grad, hess
 
 
 # ---------------------------------------------------------------------------

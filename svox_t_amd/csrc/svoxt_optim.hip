@@ -132,6 +132,35 @@ static void optim_launch(float* param, const float* grad, float* state1, float* 
                        reinterpret_cast<V*>(state2), M, E, log2G, h, lazy);
 }
 
+// The damped Newton step on a diagonal curvature (svoxt_gauss_newton_step): lane t is element t & (G - 1) + 64 i of row
+// t >> log2G, the touched test and the lazy exit as in optim_step_kernel.  d = h + damping; where d > 0.f
+// p = p - lr * (g / d), else the element is not written.
+__global__ void __launch_bounds__(kOptimBlock)
+gauss_newton_step_kernel(float* __restrict__ param, const float* __restrict__ grad, const float* __restrict__ hess, int64_t M, int K,
+                         int log2G, float lr, float damping, int lazy) {
+    const int64_t t = (int64_t)blockIdx.x * kOptimBlock + threadIdx.x;
+    const int G = 1 << log2G;
+    const int64_t row = t >> log2G;
+    const int j = (int)(t & (G - 1));
+    const bool in_table = row < M;
+    const int64_t base = row * K;
+    if (lazy != 0) {
+        bool nz = false;
+        if (in_table)
+            for (int i = j; i < K; i += G) nz |= grad[base + i] != 0.f;
+        const uint64_t any = __ballot(nz);         // (lanes that left or hold no element vote 0)
+        const int lane = threadIdx.x & 63;
+        const uint64_t mine = (G == 64 ? ~(uint64_t)0 : (((uint64_t)1 << G) - 1)) << (lane & ~(G - 1));
+        if ((any & mine) == 0) return;             // untouched: p keeps its bits, hess is not read
+    }
+    if (!in_table) return;
+    for (int i = j; i < K; i += G) {
+        const int64_t at = base + i;
+        const float d = hess[at] + damping;
+        if (d > 0.f) param[at] = param[at] - lr * (grad[at] / d);
+    }
+}
+
 static int optim_states(int32_t kind) {
     switch (kind) {
         case OPT_SGD: return 0;
@@ -182,6 +211,25 @@ int svoxt_optim_step(int32_t kind, float* param, const float* grad, float* state
         return true;
     });
     if (!known) return set_error(SVOXT_ERR_INVALID, "%s: kind has no kernel", fn);
+    return check_launch(fn);
+}
+
+int svoxt_gauss_newton_step(float* param, const float* grad, const float* hess, int64_t M, int32_t K, float lr, float damping,
+                            int32_t lazy, void* stream) {
+    const char* fn = "svoxt_gauss_newton_step";
+    if (M < 1 || K < 1) return set_error(SVOXT_ERR_INVALID, "%s: M and K must be >= 1", fn);
+    if ((double)M * (double)K >= 137438953472.0) return set_error(SVOXT_ERR_INVALID, "%s: M * K must be below 2^37", fn);
+    if (param == nullptr || grad == nullptr || hess == nullptr) return set_error(SVOXT_ERR_INVALID, "%s: param / grad / hess is NULL", fn);
+    if (lazy != 0 && lazy != 1) return set_error(SVOXT_ERR_INVALID, "%s: lazy must be 0 or 1", fn);
+    if ((uintptr_t)param % 4 != 0 || (uintptr_t)grad % 4 != 0 || (uintptr_t)hess % 4 != 0)
+        return set_error(SVOXT_ERR_INVALID, "%s: a table is not 4-byte aligned", fn);
+    if (param == grad || param == hess) return set_error(SVOXT_ERR_INVALID, "%s: param must be distinct from grad and hess", fn);
+    const int log2G = optim_log2_group(K);
+    if ((double)M * (double)(1 << log2G) >= 4294967296.0 - kOptimBlock)
+        return set_error(SVOXT_ERR_INVALID, "%s: M * (lanes a row) must be below 2^32 - 256; lanes a row = the power of two >= K, at most 64", fn);
+    const int64_t lanes = M << log2G;
+    hipLaunchKernelGGL(gauss_newton_step_kernel, dim3((unsigned)((lanes + kOptimBlock - 1) / kOptimBlock)), dim3(kOptimBlock), 0,
+                       (hipStream_t)stream, param, grad, hess, M, (int)K, log2G, lr, damping, (int)lazy);
     return check_launch(fn);
 }
 

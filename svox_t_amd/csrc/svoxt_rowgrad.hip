@@ -282,6 +282,142 @@ static int rowgrad_check(const svoxt_tree* tree, const svoxt_rays* rays, const s
     return SVOXT_OK;
 }
 
+// ================================================================================= the Gauss-Newton diagonal (4.34)
+// svoxt_render_hess_rows_*: next to the gradient, hess[m, j] = the sum over the samples k naming row m and the outputs c of
+// curv[ray(k), c] * J(k, c, j)^2 (include/svoxt.h has the sequence).  Count, emit and plan are the gradient's over the
+// larger workspace; the sweep runs the gradient's kernels with three of its own in between:
+//   rowhess_sig_kernel     a lane per (sample, channel), between the shade and the totals (chan = e): sig = (float)(1.0 /
+//                          (1.0 + (double)e)) into the transient [T, C]
+//   rowhess_sweep_kernel   a lane per (ray, output): a channel's lane walks the ray's list twice (accum_c, then the sigma
+//                          Jacobian of that channel alone) and leaves (jac * jac) * curv in the place of sig; the alpha
+//                          lane leaves its term in hsig.  The C + 1 lanes of a ray read a sample's C values side by side.
+//   rowhess_sigma_kernel   a lane per sample: hsig = the channels' terms in ascending order from 0.f, then the alpha's
+// before the gradient's sweep overwrites delta_t and att.  The reduce sums HessValues over the gradient's plan: a colour
+// column squares GradValues' prefix weight * basis * gsig on the fly, the sigma column reads hsig.
+// Workspace: the gradient's, then [hsig f32[T]] (persistent: one float a sample) and [sig f32[T * C]] (transient).
+struct RowHessSpace {
+    RowGradSpace g;
+    float *hsig, *sig;
+    size_t bytes;
+};
+static RowHessSpace rowhess_carve(void* workspace, int64_t Q, int64_t T, int64_t M, int K, int C, int bd) {
+    RowHessSpace sp;
+    sp.g = rowgrad_carve(workspace, Q, T, M, K, C, bd);
+    Carver w(workspace != nullptr ? static_cast<char*>(workspace) + sp.g.bytes : nullptr);
+    sp.hsig = w.take<float>((size_t)T);
+    sp.sig = w.take<float>((size_t)T * (size_t)C);
+    sp.bytes = sp.g.bytes + w.bytes();
+    return sp;
+}
+
+// lane t = k * C + c; in: chan = e
+__global__ void __launch_bounds__(kLaunchBlock)
+rowhess_sig_kernel(int64_t n, const float* __restrict__ chan, float* __restrict__ sig) {
+    const int64_t t = launch_lane();
+    if (t >= n) return;
+    sig[t] = (float)(1.0 / (1.0 + (double)chan[t]));
+}
+
+// lane t = q * (C + 1) + c over the ray's list; in: dt = delta_t, att, sig [T, C].  out: sig[k, c] = channel c's term of
+// the sigma entry of sample k (c < C), hsig[k] = the alpha's (c == C).
+__global__ void __launch_bounds__(kLaunchBlock)
+rowhess_sweep_kernel(Opts opt, int C, const int64_t* __restrict__ offsets, int64_t Q, int64_t T, const float* __restrict__ curv,
+                     const float* __restrict__ dscale, const float* __restrict__ dt, const float* __restrict__ att,
+                     float* __restrict__ sig, float* __restrict__ hsig) {
+    const int64_t t = launch_lane();
+    const int64_t q = t / (C + 1);
+    if (q >= Q) return;
+    const int c = (int)(t - q * (C + 1));
+    const int64_t b = max(offsets[q], (int64_t)0), e = min(offsets[q + 1], T);
+    if (b >= e) return;
+    const float delta_scale = dscale[q];
+    const float cv = curv[q * (C + 1) + c];
+    if (c == C) {                                                // the alpha channel: out[q, C] = 1 - light_ray
+        float light_ray = 1.f;
+        for (int64_t k = b; k < e; ++k) light_ray *= att[k];
+        for (int64_t k = b; k < e; ++k) {
+            const float jac = (dt[k] * delta_scale) * light_ray;
+            hsig[k] = (jac * jac) * cv;
+        }
+        return;
+    }
+    float accum = 0.f;
+    {   // pass 1
+        float light = 1.f;
+        for (int64_t k = b; k < e; ++k) {
+            const float a = att[k];
+            const float weight = light * (1.f - a);
+            light *= a;
+            accum += weight * sig[k * C + c];
+        }
+        accum += light * opt.background_brightness;
+    }
+    {   // pass 2
+        float light = 1.f;
+        for (int64_t k = b; k < e; ++k) {
+            const float a = att[k];
+            const float s = sig[k * C + c];
+            const float weight = light * (1.f - a);
+            light *= a;
+            accum -= weight * s;
+            const float jac = (dt[k] * delta_scale) * (s * light - accum);
+            sig[k * C + c] = (jac * jac) * cv;
+        }
+    }
+}
+
+// a lane per sample; in: hc [T, C] = the channels' terms, hsig = the alpha's.  out: hsig = the sample's sigma entry
+__global__ void __launch_bounds__(kLaunchBlock)
+rowhess_sigma_kernel(int C, int64_t T, const float* __restrict__ hc, float* __restrict__ hsig) {
+    const int64_t k = launch_lane();
+    if (k >= T) return;
+    float h = 0.f;
+    for (int c = 0; c < C; ++c) h += hc[k * C + c];
+    h += hsig[k];
+    hsig[k] = h;
+}
+
+// The entry of sample k at column j of hess: GradValues' columns with sigc = hsig and g = curv.
+struct HessValues {
+    GradValues v;
+    struct Col {
+        GradValues::Col c;
+        __device__ __forceinline__ float at(int64_t k) const {
+            if (c.mode == GradValues::ZERO || k < 0 || k >= c.T) return 0.f;
+            if (c.mode == GradValues::SIGMA) return c.v[k];
+            const int64_t q = c.ray[k];
+            if (q < 0 || q >= c.Q) return 0.f;                   // (the record kernel's own index: never)
+            float jac;
+            if (c.mode == GradValues::BASIS) {
+                jac = c.wgt[k] * c.b[q * c.bd] * c.v[k * c.C];
+            } else {
+                const float sig = c.v[k * c.C];
+                jac = c.wgt[k] * sig * (1.f - sig);
+            }
+            return (jac * jac) * c.g[q * (c.C + 1)];
+        }
+    };
+    __device__ __forceinline__ Col col(int j) const { return Col{v.col(j)}; }
+};
+
+// rowgrad_check's, the curvature beside grad_out, the workspace by the Hessian's query
+static int rowhess_check(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets, int64_t T,
+                         const float* grad_out, const float* curv, int32_t grad_cols, const void* workspace, int64_t workspace_bytes,
+                         const char* fn) {
+    int rc;
+    if ((rc = rowgrad_check(tree, rays, opt, offsets, T, grad_out, grad_cols, workspace, workspace_bytes, false, fn))) return rc;
+    if (rays->Q > 0 && curv == nullptr) return fail(SVOXT_ERR_INVALID, "%s: curv is NULL", fn);
+    if (misaligned(curv, 4)) return fail(SVOXT_ERR_INVALID, "%s: curv (4 bytes) is misaligned", fn);
+    if (T > 0) {
+        if (misaligned(workspace, 8)) return fail(SVOXT_ERR_INVALID, "%s: workspace is not 8-byte aligned", fn);
+        const int C = grad_cols - 1;
+        const int64_t need = svoxt_render_hess_rows_workspace_bytes(rays->Q, T, tree->M, tree->K, C, basis_floats(opt, C));
+        if ((rc = workspace_check(fn, workspace, workspace_bytes, need, "svoxt_render_hess_rows_workspace_bytes(Q, T, M, K, C, basis_dim)")))
+            return rc;
+    }
+    return SVOXT_OK;
+}
+
 }  // namespace svoxt
 
 using namespace svoxt;
@@ -395,6 +531,80 @@ int svoxt_render_grad_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays
     // a lane per (row, column) over all K columns; the row stride stands where reduce_rows has its table's width
     const RowPlanRef plan{sp.row_ptr, sp.perm, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long, T, M, n_long, n_chunks};
     rows_launch<ROWS_SUM, ROWS_SUM>(src, K, plan, nullptr, gs, 0.f, grad, sp.partials, st);
+    return check_launch(fn);
+}
+
+int64_t svoxt_render_hess_rows_workspace_bytes(int64_t Q, int64_t T, int64_t M, int32_t K, int32_t C, int32_t basis_dim) {
+    if (!in31(Q) || !in31(T) || !in31(M)) return -1;
+    if (K < 1 || C < 0 || C >= K || basis_dim < 0 || basis_dim > 25) return -1;
+    if (!elems_fit((double)T, C + 1) || !elems_fit((double)M, K)) return -1;
+    if (T == 0) return 0;
+    return (int64_t)rowhess_carve(nullptr, Q, T, M, K, C, basis_dim).bytes;
+}
+
+int svoxt_render_hess_rows_sweep(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                 int64_t T, const float* grad_out, const float* curv, int32_t grad_cols, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_render_hess_rows_sweep";
+    int rc;
+    if ((rc = rowhess_check(tree, rays, opt, offsets, T, grad_out, curv, grad_cols, workspace, workspace_bytes, fn))) return rc;
+    const int64_t Q = rays->Q;
+    if (Q == 0 || T == 0) return SVOXT_OK;
+    const int C = grad_cols - 1, bd = basis_floats(opt, C);
+    const RowHessSpace hs = rowhess_carve(workspace, Q, T, tree->M, tree->K, C, bd);
+    const RowGradSpace& sp = hs.g;
+    const TreeDev tr = to_dev(tree);
+    const Opts od = to_dev(opt);
+    hipStream_t st = (hipStream_t)stream;
+    float* tc1 = reinterpret_cast<float*>(sp.row);
+    float* tc2 = reinterpret_cast<float*>(row_plan_sort_scratch(sp.plan, T, tree->M));
+    // the launches of svoxt_render_grad_rows_sweep, argument for argument, with the Hessian's three between the shade (which
+    // leaves e, delta_t and att) and the totals / sweep (which overwrite them)
+    hipLaunchKernelGGL(rowgrad_shade_kernel, dim3(launch_blocks(T * (C + 1))), dim3(kLaunchBlock), 0, st, tr.features, tr.M, tr.K, od, C, bd, Q, T,
+                       sp.row, sp.ray, sp.wgt, sp.basis, sp.dscale, sp.sigc, sp.chan);
+    if (C > 0)
+        hipLaunchKernelGGL(rowhess_sig_kernel, launch_grid(T * C), dim3(kLaunchBlock), 0, st, T * C, sp.chan, hs.sig);
+    hipLaunchKernelGGL(rowhess_sweep_kernel, launch_grid(Q * (C + 1)), dim3(kLaunchBlock), 0, st, od, C, offsets, Q, T, curv, sp.dscale, sp.wgt,
+                       sp.sigc, hs.sig, hs.hsig);
+    hipLaunchKernelGGL(rowhess_sigma_kernel, launch_grid(T), dim3(kLaunchBlock), 0, st, C, T, hs.sig, hs.hsig);
+    hipLaunchKernelGGL(rowgrad_totals_kernel, dim3(launch_blocks(T)), dim3(kLaunchBlock), 0, st, od, C, Q, T, sp.ray, grad_out, sp.chan, tc1, tc2);
+    hipLaunchKernelGGL(rowgrad_sweep_kernel, dim3(nblocks(Q)), dim3(kBlock), 0, st, od, C, offsets, Q, T, grad_out, sp.dscale, tc1, tc2, sp.wgt,
+                       sp.sigc);
+    return check_launch(fn);
+}
+
+int svoxt_render_hess_rows_reduce(const svoxt_tree* tree, const svoxt_rays* rays, const svoxt_options* opt, const int64_t* offsets,
+                                  int64_t T, const float* grad_out, const float* curv, int32_t grad_cols, int64_t n_long,
+                                  int64_t n_chunks, float* grad, int32_t grad_stride, float* hess, int32_t hess_stride, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    const char* fn = "svoxt_render_hess_rows_reduce";
+    int rc;
+    if ((rc = rowhess_check(tree, rays, opt, offsets, T, grad_out, curv, grad_cols, workspace, workspace_bytes, fn))) return rc;
+    const int64_t M = tree->M;
+    const int K = tree->K;
+    const int hstride = hess_stride > 0 ? hess_stride : K;
+    if (hstride < K) return fail(SVOXT_ERR_INVALID, "%s: hess_stride smaller than data_dim", fn);
+    if (!elems_fit((double)M, hstride)) return fail(SVOXT_ERR_INVALID, "%s: M * hess_stride must be below 2^38", fn);
+    if (M > 0 && (hess == nullptr || misaligned(hess, 4))) return fail(SVOXT_ERR_INVALID, "%s: hess is NULL or not 4-byte aligned", fn);
+    if (M > 0 && hess == grad) return fail(SVOXT_ERR_INVALID, "%s: grad and hess must be distinct", fn);
+    // the gradient, by its own entry point: its checks of the counts, of grad and its stride, svoxt_row_plan_long, its sums
+    if ((rc = svoxt_render_grad_rows_reduce(tree, rays, opt, offsets, T, grad_out, grad_cols, n_long, n_chunks, grad, grad_stride, workspace,
+                                            workspace_bytes, stream)))
+        return rc;
+    if (M == 0) return SVOXT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (T == 0) {
+        const hipError_t e = hipMemset2DAsync(hess, sizeof(float) * (size_t)hstride, 0, sizeof(float) * (size_t)K, (size_t)M, st);
+        if (e != hipSuccess) return set_error(SVOXT_ERR_HIP, "%s: hipMemset2DAsync: %s", fn, hipGetErrorString(e));
+        return SVOXT_OK;
+    }
+    const int C = grad_cols - 1, bd = basis_floats(opt, C);
+    const RowHessSpace hs = rowhess_carve(workspace, rays->Q, T, M, K, C, bd);
+    const RowGradSpace& sp = hs.g;
+    const HessValues src{GradValues{sp.ray, sp.wgt, hs.hsig, sp.chan, sp.basis, curv, T, rays->Q, K, C, bd, opt->min_comp, opt->max_comp,
+                                    opt->format == SVOXT_FORMAT_RGBA}};
+    const RowPlanRef plan{sp.row_ptr, sp.perm, sp.long_rows, sp.long_chunk_ptr, sp.chunk_long, T, M, n_long, n_chunks};
+    rows_launch<ROWS_SUM, ROWS_SUM>(src, K, plan, nullptr, hstride, 0.f, hess, sp.partials, st);
     return check_launch(fn);
 }
 

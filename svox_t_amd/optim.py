@@ -16,6 +16,9 @@ lazy=False every row is updated, torch.optim's dense semantics: moments decay wh
 decay, Nesterov momentum, dampening, amsgrad, centered RMSprop, RMSprop's momentum and maximize are refused, not ignored.
 
 After tree surgery that replaces `tree.features` (prune, merge, quantize) call `rebind(old, new, row_map)`.
+
+gauss_newton_step_(features, grad, hessdiag, lr=, damping=) is the damped Newton step that consumes
+VolumeRenderer.se_grad's gradient and Gauss-Newton diagonal: one kernel over the table, no state.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ import torch
 
 from svox_t_amd import csrc as _C
 
-__all__ = ["FeatureSGD", "FeatureRMSprop", "FeatureAdam"]
+__all__ = ["FeatureSGD", "FeatureRMSprop", "FeatureAdam", "gauss_newton_step_"]
 
 
 def _check_table(p, what: str) -> None:
@@ -253,3 +256,22 @@ class FeatureAdam(_FeatureOptimizer):
         b1, b2 = (float(b) for b in group["betas"])
         return {"neg_step": -float(group["lr"]) / (1.0 - b1 ** t), "one_minus_beta1": 1.0 - b1, "beta2": b2,
                 "one_minus_beta2": 1.0 - b2, "bias2_sqrt": math.sqrt(1.0 - b2 ** t), "eps": float(group["eps"])}
+
+
+def gauss_newton_step_(features, grad, hessdiag, *, lr: float = 1.0, damping: float = 0.0, lazy: bool = True):
+    """features -= lr * grad / (hessdiag + damping), IN PLACE, as one HIP kernel over the table: the damped Newton step
+    of PlenOctree-style fine-tuning on what VolumeRenderer.se_grad returns.
+
+    Per entry, in float32, each operation correctly rounded: d = hessdiag + damping; where d > 0 the entry becomes
+    p - lr * (grad / d) -- the bits of the same three torch ops -- and otherwise (no curvature and no damping) it is
+    left as it is.  lazy=True (the optimizers' convention): a row whose grad row is all zeros -- no ray of the batch
+    met it -- is read no further and not written.  The version counter of `features` is bumped, as by every operator
+    that writes the table behind torch's back.  Returns `features`."""
+    p = features
+    _check_table(p, "features")
+    for name, x in (("grad", grad), ("hessdiag", hessdiag)):
+        _check_table(x, name)
+        if x.shape != p.shape or x.device != p.device:
+            raise RuntimeError(f"{name} must be float32 {tuple(p.shape)} on {p.device}")
+    _C._extras.gauss_newton_step(p, grad, hessdiag, lr, damping, lazy)
+    return features

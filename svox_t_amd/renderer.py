@@ -24,6 +24,7 @@ from svox_t_amd.helpers import DataFormat, _get_c_extension
 
 NDCConfig = namedtuple("NDCConfig", ["width", "height", "focal"])
 Rays = namedtuple("Rays", ["origins", "dirs", "viewdirs"])
+SEGrad = namedtuple("SEGrad", ["out", "loss", "grad", "hessdiag"])           # what VolumeRenderer.se_grad returns
 
 _C = _get_c_extension()
 
@@ -428,6 +429,99 @@ class VolumeRenderer(nn.Module):
         if reduction == "mean":
             return per_ray.mean()
         return per_ray.sum() if reduction == "sum" else per_ray
+
+    def grad_hess(self, features, rays: Rays, grad_out, curvature, *, fast=False, cuda=True, image_shape=None, sort_rays=None,
+                  transformation_matrices=None):
+        """(grad, hessdiag), both float32 [M, data_dim], for a per-pixel separable loss on forward()'s output: `grad_out`
+        [Q, C+1] is the loss's first derivative in each output, `curvature` [Q, C+1] its second.
+
+        grad is the gradient forward(deterministic=True) + backward(grad_out) gives, with its bits.  hessdiag is the
+        diagonal of the Gauss-Newton Hessian J^T diag(curvature) J, the squares taken PER SAMPLE:
+
+            hessdiag[m, j] = sum over the samples k naming row m and the outputs c of curvature[ray(k), c] * J(k, c, j)^2
+
+        with J(k, c, j) the derivative of out[ray(k), c] in entry j of row m through sample k alone.  That is the exact
+        diagonal whenever no ray names a feature row twice; where rows are shared by several leaves (after refine, merge,
+        quantize) it is the svox family's approximation: a ray's samples on one row add their squares, not the square
+        of their sum.  One march, one row plan and one shade serve both tables; no float atomic, the same bits in every
+        run and whatever sort_rays / image_shape / fast say (the sample set is the backward's: sigma > 0, thresholds 0).
+
+        A plain function: no autograd node is made and `features.grad` is not touched.  Not with
+        transformation_matrices, camera-mode or NDC rays (forward(deterministic=True)'s scope)."""
+        if transformation_matrices is not None:
+            _refuse_deterministic("grad_hess", "transformation_matrices are not served by the deterministic backward")
+        if self.ndc_config is not None and self.ndc_config.width >= 0:
+            _refuse_deterministic("grad_hess", "NDC rays keep the default backward")
+        if not all(isinstance(getattr(rays, n, None), torch.Tensor) for n in ("origins", "dirs", "viewdirs")):
+            _refuse_deterministic("grad_hess", "camera batches keep the default backward: pass Rays(origins, dirs, viewdirs)")
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2:
+            raise RuntimeError("grad_hess: features must be a float32 [M, data_dim] tensor")
+        for name, t in (("grad_out", grad_out), ("curvature", curvature)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rays.origins.shape[0]:
+                raise RuntimeError(f"grad_hess: {name} must be float32 [Q, C+1] with Q = {rays.origins.shape[0]} rays")
+        self._require_gpu(cuda, "grad_hess")
+        rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+        rspec.need_grad = False
+        with torch.no_grad():
+            return _C._extras.volume_render_hess_rows(self.tree._spec(features.detach()), rspec, self._get_options(fast),
+                                                      grad_out.contiguous(), curvature.contiguous())
+
+    def se_grad(self, features, rays: Rays, colors, *, weights=None, reduction="mean", fast=False, cuda=True,
+                image_shape=None, sort_rays=None, transformation_matrices=None):
+        """The svox family's VolumeRenderer.se_grad: render, and return SEGrad(out, loss, grad, hessdiag) for the
+        weighted squared error against `colors` -- what a damped Newton step on the leaf table needs
+        (svox_t_amd.gauss_newton_step_: p -= lr * grad / (hessdiag + damping)).
+
+        :param colors: float32 [Q, C] target colours, or [Q, C+1] to supervise the alpha column as well
+        :param weights: float32 [Q] per-ray weights, or None (ones)
+        :param reduction: "mean": the loss is divided by colors.numel(); "sum": it is not
+        :return: out [Q, C+1]: forward()'s output with its bits (one default-route forward produces it);
+                 loss: sum_q weights[q] * sum_c (out - colors)^2 * scale, scale = 1 / colors.numel() or 1;
+                 grad [M, data_dim]: d loss / d features, the deterministic backward's bits for
+                 grad_out[q, c] = (out[q, c] - colors[q, c]) * coef[q], coef = (2 * scale) * weights;
+                 hessdiag [M, data_dim]: grad_hess's diagonal for curvature[q, c] = coef[q] (see there: exact where no
+                 ray names a row twice, per-sample squares where rows are shared).
+        Both are zero in the alpha column when `colors` has C columns.  Nothing here makes an autograd node.  Refused
+        like forward(deterministic=True): transformation_matrices, camera-mode and NDC rays, cuda=False."""
+        if transformation_matrices is not None:
+            _refuse_deterministic("se_grad", "transformation_matrices are not served by the deterministic backward")
+        if self.ndc_config is not None and self.ndc_config.width >= 0:
+            _refuse_deterministic("se_grad", "NDC rays keep the default backward")
+        if not all(isinstance(getattr(rays, n, None), torch.Tensor) for n in ("origins", "dirs", "viewdirs")):
+            _refuse_deterministic("se_grad", "camera batches keep the default backward: pass Rays(origins, dirs, viewdirs)")
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"reduction must be 'mean' or 'sum', not {reduction!r}")
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() != 2:
+            raise RuntimeError("se_grad: features must be a float32 [M, data_dim] tensor")
+        opt = self._get_options(fast)
+        cols = _C.get_out_data_dim(opt, features.shape[1])
+        Q = rays.origins.shape[0]
+        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or colors.dim() != 2 or colors.shape[0] != Q \
+                or colors.shape[1] not in (cols - 1, cols) or colors.device != features.device:
+            raise RuntimeError(f"se_grad: colors must be float32 [Q, {cols - 1}] (or [Q, {cols}] with alpha) with Q = {Q} rays, "
+                               "on the device of the features")
+        if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32
+                                    or tuple(weights.shape) != (Q,) or weights.device != features.device):
+            raise RuntimeError(f"se_grad: weights must be float32 [Q] with Q = {Q} rays, on the device of the features, or None")
+        self._require_gpu(cuda, "se_grad")
+        with torch.no_grad():
+            f = features.detach()
+            rspec = _rays_spec_from_rays(rays, image_shape, sort_rays)
+            rspec.need_grad = False
+            spec = self.tree._spec(f)
+            out = _C.volume_render(spec, rspec, opt)
+            nc = colors.shape[1]
+            scale = 1.0 / colors.numel() if (reduction == "mean" and colors.numel() > 0) else 1.0
+            w = torch.ones((Q,), dtype=torch.float32, device=f.device) if weights is None else weights
+            coef = (2.0 * scale) * w
+            resid = out[:, :nc] - colors
+            loss = ((resid * resid).sum(dim=1) * w).sum() * scale
+            grad_out = torch.zeros_like(out)
+            curvature = torch.zeros_like(out)
+            grad_out[:, :nc] = resid * coef[:, None]
+            curvature[:, :nc] = coef[:, None]
+            grad, hess = _C._extras.volume_render_hess_rows(spec, rspec, opt, grad_out, curvature)
+        return SEGrad(out, loss, grad, hess)
 
     def _get_options(self, fast=False):
         """RenderOptions for the operator boundary (svox_t/renderer.py:408-439)."""
